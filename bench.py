@@ -18,9 +18,13 @@ The other BASELINE configurations are parity-test cases; `--config` times them w
   4  input_type=PP, 256x256 cube faces, 32 planes, batch 64 faces per step sharded, fp32   (strong scaling)
 A rank's shard (dist.shard_frames) is run as one batch; `value` = frames of ALL ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line with the metric, `roofline` (the CNN's conv kernels, the dominant cost, against
-the MFMA peak of the compute type; per-stage detail under `stages`) and `cpu_baseline` (the CPU oracle timed on
-this box's host cores; config 1 at N=1 only).
+Rank 0 prints ONE JSON line with the metric and `roofline` (the CNN's conv kernels, the dominant cost, against
+the MFMA peak of the compute type, from events inside the timed region).  A plain run does only what that line
+needs: set-up, warm-up, the --steps timed steps, the outputs (--dump-outputs DIR) and the line.  `--full` adds
+every other reading, each of which takes runs of its own: the extra timed regions (`repeats`), the strong-scaling
+reading, the opt-in arithmetic (`alt_arithmetic`), the per-stage pass (`stages`), the sustained matrix-rate probe
+and `cpu_baseline` with its parity (the CPU oracle timed on this box's host cores; config 1 at N=1 only); in a
+plain run those keys are null.
 """
 import argparse
 import json
@@ -176,6 +180,41 @@ def geometry_bytes(h, w, d, psv_bytes=4):
         "assemble": psv + pred + rgba,          # read PSV + pred, write the layer stack
         "render": rgba + 2 * img,               # read every texel once, write rgb + depth
     }
+
+
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: the files of all ranks together stay under 64 MB
+
+
+def dump_outputs(out_dir, result, prefix="", budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the arrays one timed step hands its caller, as out_dir/<prefix><name>.npy in float32.  `result` is what
+    the step returned: a frame's (rgb, depth, rgb_u8, depth_u8, pred dict), or a list of them (--substreams: one per sub-batch,
+    concatenated along the batch).  Every array gets an equal share of `budget` bytes; a larger one is stored as the values
+    at np.random.RandomState(0).randint(0, size, share) (sorted) of its C-ordered flattening -- the same indices in every run of
+    the same arguments, so two builds compare value for value.  Returns {name: [full shape, values written]}."""
+    parts = result if isinstance(result, list) else [result]
+    names = ["rgb", "depth", "rgb_u8", "depth_u8"]
+    arrays = {}
+    for i, name in enumerate(names):
+        if parts[0][i] is not None:
+            arrays[name] = torch.cat([p[i] for p in parts], dim=0)
+    for name in sorted(parts[0][4]):
+        arrays[name] = torch.cat([p[4][name] for p in parts], dim=0)
+    share = budget // 4 // max(1, len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.RandomState(0).randint(0, flat.numel(), size=share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy() if flat.numel() < t.numel() else t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+        written[name] = [list(t.shape), int(a.size)]
+    return written
+
+
+def _round(x, n):
+    return None if x is None else round(x, n)
 
 
 _ORIG_AFFINITY = None
@@ -347,6 +386,13 @@ def main():
     ap.add_argument("--no-sustained-probe", action="store_true",
                     help="skip msi_probe_matrix_rate (roofline.frac_of_sustained / sustained_matrix_rate become null): profiling runs, where the probe's 0.5 s of "
                          "matrix-only kernels would sit in the kernel table")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every reading beyond the headline figure (extra timed regions, strong scaling, the opt-in arithmetic, the "
+                         "per-stage pass, the sustained matrix-rate probe, the CPU oracle leg and its parity); a plain run leaves those keys null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the rendered rgb / depth, their uint8 forms and the "
+                         "network's layer stack) as DIR/<name>.npy in float32 (DIR/rank<r>_<name>.npy with N > 1 ranks); an array larger than "
+                         "its share of %d MB (shared by all ranks) is a fixed, seeded sample of its flattened values (dump_outputs)" % (DUMP_BUDGET_BYTES >> 20))
     ap.add_argument("--dist-check", action="store_true",
                     help="only the N-rank plumbing of this file: launch, rendezvous, weight broadcast, frame ranges, barrier and "
                          "max-over-ranks -- no frame loop, no kernels; runs without a GPU on gloo (tests/test_dist_cpu.py) and "
@@ -506,11 +552,11 @@ def main():
 
     def step(k, cnn_events=None):
         if args.substreams > 1:                                  # the batch as S sub-batches, one per stream (whole step's work)
-            r = None
+            r = []
             for i, sl in enumerate(sub_slices):
                 if sl.stop > sl.start:
                     with torch.cuda.stream(streams[i]):
-                        r = frame(None, models[i], cnn_events=cnn_events, sl=sl)
+                        r.append(frame(None, models[i], cnn_events=cnn_events, sl=sl))
             return r
         if args.streams == 1:
             return frame(None, cnn_events=cnn_events)
@@ -549,29 +595,40 @@ def main():
         step(k); k += 1
         if k % 8 == 0:
             torch.cuda.synchronize()
+    t_warm = time.perf_counter()
     for k in range(max(args.warmup, args.streams)):
         step(k)
+    torch.cuda.synchronize()
+    warm_step_s = (time.perf_counter() - t_warm) / max(args.warmup, args.streams, 1)
     own = []                                                       # this rank's own time of every region
     # settle (untimed, disclosed as `settle_regions_ms`): whole regions of the contract's own form -- no synchronisation inside --
     # until two consecutive ones agree to 3 % (at most four, at most ~3 s).  configs[2] was seen to run its first ~0.8 s of
     # unsynchronised regions 27 % slow on some boxes even after the pre-warm loop above (which synchronises every 8 steps):
     # 13.38, 13.42, 10.54, 10.55, 10.56 ms per step in consecutive regions (profiles/r03_g_config2_transient_bench.json); what is
     # reported is the steady state, and the regions after the contract one (`repeats`) show that it is one
+    # A settle region has at most as many steps as ~0.75 s of warm-up steps took, so that a long --steps does not stretch the
+    # settle phase (the count comes from rank 0's warm-up and is shared: every rank runs regions of the same length)
+    settle_steps = min(args.steps, max(1, int(0.75 / max(warm_step_s, 1e-6))))
+    if use_pg:
+        settle_steps = int(mdist.gather_floats(float(settle_steps), dev)[0])
     settle = []
     if args.settle:
         while len(settle) < 4 and sum(settle) < 3.0:               # (decided on the max-over-ranks region times only: every rank
-            settle.append(timed_region(args.steps)[0])             # takes the same decision -- no rank-local clock in the condition)
+            settle.append(timed_region(settle_steps)[0])           # takes the same decision -- no rank-local clock in the condition)
             if len(settle) >= 2 and abs(settle[-1] - settle[-2]) <= 0.03 * settle[-2]:
                 break
         own.clear()
     elapsed, cnn_ms, result = timed_region(args.steps)             # the contract region: `value` comes from here
-    repeats = [timed_region(args.steps)[0] for _ in range(max(0, args.repeats))]
+    dumped = None
+    if args.dump_outputs and result:
+        dumped = dump_outputs(args.dump_outputs, result, "" if world == 1 else "rank%d_" % rank, DUMP_BUDGET_BYTES // world)
+    repeats = [timed_region(args.steps)[0] for _ in range(max(0, args.repeats))] if args.full else []
     per_rank_ms = mdist.gather_floats(own[0] / args.steps * 1e3, dev) if use_pg else [own[0] / args.steps * 1e3]
 
     # strong-scaling reading of the same path (config 1): a FIXED batch of --strong-frames frames sharded over the ranks,
     # each rank running its shard as consecutive batch-1 frames; barrier + synchronize on both sides, max over ranks
     strong = None
-    if args.config == 1 and args.strong_frames > 0 and args.streams == 1:
+    if args.full and args.config == 1 and args.strong_frames > 0 and args.streams == 1:
         slo, shi = mdist.shard_frames(args.strong_frames, rank, world)
         times = []
         for _ in range(5):
@@ -597,7 +654,7 @@ def main():
     # the opt-in arithmetic, same workload, same region form (N = 1 only: it is a second reading, not part of the contract): the
     # three-product fp16 split is NOT the arithmetic `value` is quoted on (22-bit operands)
     alt, alt_result = None, None
-    if (world == 1 and B > 0 and cfg["dtype"] == "f32" and args.arithmetic is None and not args.net_opt and not args.no_alt_arithmetic
+    if (args.full and world == 1 and B > 0 and cfg["dtype"] == "f32" and args.arithmetic is None and not args.net_opt and not args.no_alt_arithmetic
             and args.streams == 1 and args.substreams == 1):
         alt_model = MSI(weights=weights, coord_net=coord, device=dev, dtype=cfg["dtype"], input_type="PP" if cfg["kind"] == "pp" else "ODS")
         alt_model.net_options[_N.NET_OPT_F32_SPLIT_F16] = 0x3ffff
@@ -626,27 +683,29 @@ def main():
     if rank != 0:
         return
 
-    # per-stage HIP events: a separate, untimed pass (one frame batch at a time on the launch stream)
-    torch.cuda.synchronize()
-    all_events = []
-    for _ in range(5):
-        ev = []
-        frame(ev)
-        all_events.append(ev)
-    torch.cuda.synchronize()
-    stage_ms = {}
-    for si, name in enumerate(stage_names):
-        stage_ms[name] = float(np.mean([ev[si].elapsed_time(ev[si + 1]) for ev in all_events])) if B > 0 else 0.0
+    # per-stage HIP events (--full): a separate, untimed pass (one frame batch at a time on the launch stream)
+    stage_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        all_events = []
+        for _ in range(5):
+            ev = []
+            frame(ev)
+            all_events.append(ev)
+        torch.cuda.synchronize()
+        stage_ms = {}
+        for si, name in enumerate(stage_names):
+            stage_ms[name] = float(np.mean([ev[si].elapsed_time(ev[si + 1]) for ev in all_events])) if B > 0 else 0.0
     ms_per_step = elapsed / args.steps * 1e3
     fps = frames_total * args.steps / elapsed
-    cnn_ms_timed = float(np.mean(cnn_ms)) if cnn_ms else stage_ms["cnn"]   # (streams > 1: from the separate pass)
+    cnn_ms_timed = float(np.mean(cnn_ms)) if cnn_ms else stage_ms and stage_ms["cnn"]   # (streams > 1: from the separate pass, --full only)
 
     bf16 = cfg["dtype"] == "bf16"
     peak = PEAK_BF16_MFMA_TFLOPS if bf16 else PEAK_FP32_MFMA_TFLOPS
     flops = conv_flops(H, W, cin, nout, NGF, coord)                # per frame: the 17 convolutions the interval contains
     gbytes = geometry_bytes(H, W, D, 2 if bf16 else 4)
     nb = max(B, 1)
-    cnn_tflops = flops * nb / (cnn_ms_timed * 1e-3) / 1e12
+    cnn_tflops = flops * nb / (cnn_ms_timed * 1e-3) / 1e12 if cnn_ms_timed else None
     # the peak the convolutions are priced against: per layer the dense MFMA peak of the instruction it runs on -- bf16 plans
     # 2 500 TFLOP/s; fp32 layers 157.3 on v_mfma_f32_32x32x2_f32, or 2 500 / 6 = 416.7 fp32-equivalent TFLOP/s where the plan
     # runs the six-product 3-way bf16 split (conv_halo_x3_kernel) -- blended by the layers' flops: peak = flops / sum(flops_l / peak_l)
@@ -655,20 +714,22 @@ def main():
         kplan = model._plan(B, H, W, cin, nout, NGF)
         layer_peak = [split_peak(kplan.layer_kernel(i)[0]) for i in range(17)]
         peak = sum(layer_fl) / sum(f / pk for f, pk in zip(layer_fl, layer_peak))
-    stages = {k: {"ms": round(v, 4)} for k, v in stage_ms.items()}
-    for k in ("sweep", "assemble", "render"):
-        if stage_ms[k] > 0:
-            gbs = gbytes[k] * nb / (stage_ms[k] * 1e-3) / 1e9
-            stages[k].update({"bound": "hbm", "algorithmic_MB": round(gbytes[k] * nb / 1e6, 1),
-                              "achieved_GBps": round(gbs, 1), "frac": round(gbs / PEAK_HBM_GBS, 4)})
-    stages["cnn"].update({"bound": "mfma", "algorithmic_GFLOP": round(flops * nb / 1e9, 1),
-                          "achieved_TFLOPps": round(flops * nb / (max(stage_ms["cnn"], 1e-9) * 1e-3) / 1e12, 2)})
+    stages = None
+    if stage_ms is not None:
+        stages = {k: {"ms": round(v, 4)} for k, v in stage_ms.items()}
+        for k in ("sweep", "assemble", "render"):
+            if stage_ms[k] > 0:
+                gbs = gbytes[k] * nb / (stage_ms[k] * 1e-3) / 1e9
+                stages[k].update({"bound": "hbm", "algorithmic_MB": round(gbytes[k] * nb / 1e6, 1),
+                                  "achieved_GBps": round(gbs, 1), "frac": round(gbs / PEAK_HBM_GBS, 4)})
+        stages["cnn"].update({"bound": "mfma", "algorithmic_GFLOP": round(flops * nb / 1e9, 1),
+                              "achieved_TFLOPps": round(flops * nb / (max(stage_ms["cnn"], 1e-9) * 1e-3) / 1e12, 2)})
+        if args.substreams > 1:   # the per-stage pass runs the whole batch on one stream: not the configuration that was timed
+            stages["note"] = "per-stage pass = whole batch on ONE stream (substreams only changes the timed region)"
     traffic, traffic_src, traffic_stale = cnn_traffic(args.config, coord)
     conv_bytes = conv_algorithmic_bytes(H, W, cin, NGF, coord, nb, act_bytes=2 if bf16 else 4, w_bytes=2 if bf16 else 4)
-    if args.substreams > 1:   # the per-stage pass runs the whole batch on one stream: not the configuration that was timed
-        stages["note"] = "per-stage pass = whole batch on ONE stream (substreams only changes the timed region)"
 
-    sustained = None if args.no_sustained_probe else sustained_matrix_rate(dev)
+    sustained = None if (args.no_sustained_probe or not args.full) else sustained_matrix_rate(dev)
     unit = "faces/s" if cfg["kind"] == "pp" else "frames/s"
     arithmetic = None
     nx2 = nx3 = 0
@@ -687,7 +748,7 @@ def main():
     line = {
         "metric": metric,
         "value": round(fps, 3), "unit": unit, "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "prewarm_s": args.prewarm, "settle_regions_ms": [round(x / args.steps * 1e3, 4) for x in settle], "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "warmup": args.warmup, "prewarm_s": args.prewarm, "settle_regions_ms": [round(x / settle_steps * 1e3, 4) for x in settle], "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
         "scaling": cfg["scaling"], "vs_baseline": None, "dtype": cfg["dtype"], "data": "synthetic",
         "config": {"workload": cfg["name"] + ", " + ("CoordNet" if coord else "wrap-pad net") + ", infer + "
                                + ("MPI render" if cfg["kind"] == "pp" else "RGB&depth render"),
@@ -704,18 +765,18 @@ def main():
                         "cpu_affinity_rank0": affinity,
                         "weight_broadcast_ms": None if broadcast_ms is None else round(broadcast_ms, 3),
                         "devices_visible": torch.cuda.device_count(), "device_of_rank0": torch.cuda.get_device_name(dev)},
-        "repeats": {"ms_per_step": [round(r / args.steps * 1e3, 4) for r in [elapsed] + repeats],
+        "repeats": None if not args.full else {"ms_per_step": [round(r / args.steps * 1e3, 4) for r in [elapsed] + repeats],
                     "median_ms_per_step": round(float(np.median([elapsed] + repeats)) / args.steps * 1e3, 4),
                     "note": "region 0 is the contract region `value` / `ms_per_step` are computed from"},
         "roofline": {"kernel": "conv_halo*_kernel + conv_igemm_kernel (the 3x3 / 4x4 conv launches of one forward, %s implicit GEMM)" % ("bf16 MFMA" if bf16 else str(arithmetic)),
-                     "bound": "mfma", "achieved": round(cnn_tflops, 3), "peak": round(peak, 2),
+                     "bound": "mfma", "achieved": _round(cnn_tflops, 3), "peak": round(peak, 2),
                      "peak_note": "dense MFMA peak of the instruction each layer runs on, blended by the layers' flops (fp32 MFMA 157.3; six-product bf16 split 2500 / 6 = 416.7, three-product fp16 split 2500 / 3 = 833.3 fp32-equivalent; bf16 2500 TFLOP/s) -- all quoted at the 2.4 GHz peak clock "
                                   "on constant operands.  On operands that change between consecutive MFMAs the part itself clocks 1.76-1.89 GHz and a matrix-only loop sustains 1.72-1.91 PFLOP/s (sustained_matrix_rate below is THIS box's figure; "
                                   "s_memtime counts real shader cycles, the driver's sclk reading is stale on this pool: profiles/r06_clock.txt); the six-product kernels run at that same clock, so what separates `frac_of_sustained` from 1 is skeleton "
                                   "(launch ramp, tile quantisation, prologue / epilogue: profiles/r06_residency.txt), not power",
-                     "unit": "TFLOP/s", "frac": round(cnn_tflops / peak, 4),
-                     "frac_of_fp32_mfma_peak": None if bf16 else round(cnn_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
-                     "frac_of_sustained": round(cnn_tflops / (peak * sustained["changing"]["pflops"] * 1e3 / PEAK_BF16_MFMA_TFLOPS), 4) if (sustained and (bf16 or nx2 + nx3 == 17)) else None,
+                     "unit": "TFLOP/s", "frac": _round(cnn_tflops and cnn_tflops / peak, 4),
+                     "frac_of_fp32_mfma_peak": None if bf16 else _round(cnn_tflops and cnn_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
+                     "frac_of_sustained": round(cnn_tflops / (peak * sustained["changing"]["pflops"] * 1e3 / PEAK_BF16_MFMA_TFLOPS), 4) if (sustained and cnn_tflops and (bf16 or nx2 + nx3 == 17)) else None,
                      "sustained_matrix_rate": None if sustained is None else dict(sustained, note="msi_probe_matrix_rate on THIS box after the timed regions: matrix-only loop (no memory / LDS traffic), bf16 MFMA back to back, on operands that "
                                                    "change between consecutive instructions vs constant ones; dense PFLOP/s and the shader clock (s_memtime cycles per s_memrealtime second). "
                                                    "frac_of_sustained = achieved / (peak x changing.pflops / 2.5): an EXTRA key, `frac` stays on the nominal peak (profiles/r06_clock.txt)"),
@@ -730,15 +791,16 @@ def main():
                      "launches_per_frame": 17, "algorithmic_flops_per_launch_set": flops * nb,
                      "flops_note": "conv1_1 ... conv8_2 only; color_pred (the 1x1 head, %.2f GFLOP per frame) runs in the fused tail "
                                    "after the closing event and is not counted" % (cnn_layer_flops(H, W, cin, nout, NGF, coord)[-1] / 1e9),
-                     "ms_per_forward": round(cnn_ms_timed, 4),
+                     "ms_per_forward": _round(cnn_ms_timed, 4),
                      "timed": "HIP events around msi_net_plan_forward on the launch stream INSIDE the timed region, mean of "
                               "%d forwards (conv launches + the remaining ln_apply launches: conservative for the conv kernels alone)" % max(len(cnn_ms), 1)},
         "stages": stages,
         "strong_scaling": strong,
         "alt_arithmetic": alt,
+        "dumped_outputs": None if dumped is None else {"dir": args.dump_outputs, "arrays": dumped},
     }
 
-    if world == 1 and args.config == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and args.config == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"], parity, alt_parity = cpu_baseline(model, weights, inp, planes, coord, result, D, alt_result)
         line["parity_max_abs_vs_oracle"] = parity
         if alt is not None:

@@ -3,6 +3,8 @@
 build container only -- it reads /root/reference where it lies, copies nothing, and never travels to the GPU box).
 
     python oracle/crosscheck_reference.py [--reference /root/reference]
+    python oracle/crosscheck_reference.py --record tests/golden/reference_crosscheck.json   (also record the reference's outputs)
+    python oracle/crosscheck_reference.py --golden tests/golden/reference_crosscheck.json   (the oracle against the recording)
 
 What it does: imports the reference's geometry/spherical.py, sampling.py, projector.py and homography.py unmodified, with
 `tensorflow` and `tensorflow_graphics` replaced by the ~60-op numpy stand-in below, runs their entry points
@@ -23,11 +25,32 @@ expression trees executed here are the reference's own.
 """
 import argparse
 import contextlib
+import hashlib
+import json
 import os
 import sys
 import types
 
-import numpy as np
+# Every primitive the check runs must give the same bits on every x86-64 host, so that a replay (--golden) reproduces a recording:
+# numpy without its run-time SIMD dispatch (only the compile-time baseline every x86-64 host has), ATen's non-vectorised CPU
+# kernels and MKL's reproducible code path -- read when the libraries start, so set before numpy / torch are imported -- and, in
+# main(), oneDNN off and one thread.  pinning() reports what numpy actually runs with.
+NUMPY_DISPATCH = "SSSE3 SSE41 POPCNT SSE42 AVX F16C FMA3 AVX2 AVX512F AVX512CD AVX512_KNL AVX512_KNM AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL"
+os.environ["NPY_DISABLE_CPU_FEATURES"] = NUMPY_DISPATCH
+os.environ["ATEN_CPU_CAPABILITY"] = "default"
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+import numpy as np  # noqa: E402
+
+
+def pinning():
+    """numpy's compile-time SIMD baseline and the run-time dispatch targets it still uses (a recording is valid where these match
+    and nothing is dispatched)."""
+    try:
+        from numpy._core import _multiarray_umath as mu
+    except ImportError:
+        from numpy.core import _multiarray_umath as mu
+    return {"numpy_baseline": list(mu.__cpu_baseline__),
+            "numpy_dispatched": [k for k in mu.__cpu_dispatch__ if mu.__cpu_features__.get(k)]}
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -317,24 +340,126 @@ def rigid(rng, ang=0.2, tr=0.05):
     return m.astype(F)
 
 
+def digest(a):
+    """SHA-256 of an array's shape and float32 values, -0 folded into +0 and every NaN into one pattern: two arrays have the
+    same digest exactly when same() below calls them identical."""
+    a = np.asarray(a).astype(F) + F(0)
+    a[np.isnan(a)] = np.nan
+    return hashlib.sha256(repr(a.shape).encode() + np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+class Recorded(object):
+    """A recorded reference output that is kept as its digest only (RefOutputs)."""
+
+    def __init__(self, shape, sha256):
+        self.shape, self.sha256 = tuple(shape), sha256
+
+
+def equal(got, want):
+    if isinstance(got, Recorded):
+        return got.shape == np.asarray(want).shape and got.sha256 == digest(want)
+    got, want = np.asarray(got), np.asarray(want)
+    return bool(np.array_equal(got.astype(F).view(np.uint32), want.astype(F).view(np.uint32)) or np.array_equal(got, want, equal_nan=True))
+
+
 def same(name, got, want):
+    if isinstance(got, Recorded):
+        ok = equal(got, want)
+        print("%-46s %-22s %s" % (name, "x".join(str(v) for v in got.shape), "bit-identical" if ok else "MISMATCH (digest of the recording)"))
+        return ok
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, (name, got.shape, want.shape)
-    ok = np.array_equal(got.astype(F).view(np.uint32), want.astype(F).view(np.uint32)) or np.array_equal(got, want, equal_nan=True)
+    ok = equal(got, want)
     n = int((~((got == want) | (np.isnan(got) & np.isnan(want)))).sum())
     print("%-46s %-22s %s" % (name, "x".join(str(v) for v in got.shape), "bit-identical" if ok else "MISMATCH in %d values" % n))
     return ok
 
 
+PINNING_KEY = "__pinning__"
+
+
+class RefOutputs(object):
+    """The reference's outputs: computed live through its function bodies (and recorded, --record), or read back from a
+    recording (--golden without a reference checkout: the check of the oracle then needs nothing outside the repository).  Live
+    with --golden, every output is also compared with the recording (`drift`).  A recording keeps what the replay uses as data --
+    names, and the plane radii -- as values, every other output as its shape and digest(), and the pinning() it was made under."""
+
+    def __init__(self, live, golden=None):
+        self.live = live
+        self.store = {}
+        self.recording = {}
+        self.recorded_pinning = None
+        self.drift = []
+        if golden:
+            with open(golden) as f:
+                for name, e in json.load(f).items():
+                    if name == PINNING_KEY:
+                        self.recorded_pinning = e
+                    else:
+                        self.recording[name] = np.array(e["values"]) if "values" in e else Recorded(e["shape"], e["sha256"])
+        if not live:
+            self.store = self.recording
+
+    def drifted(self):
+        """Live with --golden: the recorded names whose live value differs from the recording, or that were not produced."""
+        return sorted(set(self.drift) | (set(self.recording) - set(self.store))) if self.live and self.recording else []
+
+    def save(self, path):
+        rec = {PINNING_KEY: pinning()}
+        for name, a in sorted(self.store.items()):
+            if a.dtype.kind == "U" or (a.dtype == np.float64 and a.ndim == 1 and a.size <= 64):
+                rec[name] = {"values": a.tolist()}
+            else:
+                rec[name] = {"shape": list(a.shape), "sha256": digest(a)}
+        with open(path, "w") as f:
+            json.dump(rec, f, indent=0, sort_keys=True)
+            f.write("\n")
+
+    def put(self, name, value):
+        if self.live:
+            a = self.store[name] = np.asarray(value)
+            r = self.recording.get(name)
+            if self.recording and (r is None or not (equal(r, a) if isinstance(r, Recorded) else np.array_equal(r, a))):
+                self.drift.append(name)
+
+    def get(self, name):
+        return self.store[name]
+
+    def __call__(self, name, thunk):
+        if self.live:
+            self.put(name, thunk())
+        return self.get(name)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--record", metavar="JSON", help="also record the reference's outputs to JSON (tests/golden/reference_crosscheck.json)")
+    ap.add_argument("--golden", metavar="JSON", help="a recording: replayed where there is no reference checkout, checked against the live "
+                                                     "reference's outputs where there is one")
     args = ap.parse_args()
-    if not os.path.isdir(os.path.join(args.reference, "geometry")):
-        print("no reference checkout at %s (this check runs in the build container only)" % args.reference)
+    live = os.path.isdir(os.path.join(args.reference, "geometry"))
+    if not live and not args.golden:
+        print("no reference checkout at %s (this check runs in the build container only; --golden replays a recording)" % args.reference)
         return 2
+    R = RefOutputs(live, args.golden)
+    here = pinning()
+    if here["numpy_dispatched"] or (R.recorded_pinning is not None and here["numpy_baseline"] != R.recorded_pinning["numpy_baseline"]):
+        print("PINNING: numpy here has baseline %s and still dispatches %s; the recording was made with baseline %s and no dispatch -- "
+              "its digests do not apply to this numpy build (not an oracle mismatch)" % (
+                  here["numpy_baseline"], here["numpy_dispatched"], R.recorded_pinning and R.recorded_pinning["numpy_baseline"]))
+        if not live:
+            return 3
+    print("%s; numpy baseline %s, no run-time dispatch" % ("live reference" + (", checked against the recording" if args.golden else "")
+                                                         if live else "replay of the recording", " ".join(here["numpy_baseline"])))
+    import torch
+    torch.set_num_threads(1)
+    torch.backends.mkldnn.enabled = False
     from oracle import geometry as G
-    projector, sampling, spherical, refnets, slim, refmsi, tf = load_reference(args.reference)
+    if R.live:
+        projector, sampling, spherical, refnets, slim, refmsi, tf = load_reference(args.reference)
+    else:
+        slim = SlimStandIn()
     rng = np.random.RandomState(20260928)
     b, h, w, d = 2, 12, 24, 5
     img = rng.uniform(-1, 1, size=(b, h, w, 3)).astype(F)
@@ -349,8 +474,9 @@ def main():
     # --- K1: ods_sphere_sweep (projector.py:209-211 -> sweep_one :129-170; spherical.py:116-129, 170-233; sampling.py:135-197)
     # (the reference reads intrinsics[0][0][0] of the tiled PER-SAMPLE slice: the sample's own baseline)
     for order in (1, -1):
-        ref = projector.ods_sphere_sweep(_t(img), order, depths, _t(poses), _t(intr))
-        ok &= same("ods_sphere_sweep order %+d" % order, ref, G.ods_sphere_sweep(img, order, depths, poses, intr))
+        name = "ods_sphere_sweep order %+d" % order
+        ref = R(name, lambda: projector.ods_sphere_sweep(_t(img), order, depths, _t(poses), _t(intr)))
+        ok &= same(name, ref, G.ods_sphere_sweep(img, order, depths, poses, intr))
 
     # --- K4: projective_forward_sphere + over_composite(_depth) (projector.py:34-62, 225-265; spherical.py:268-326)
     layers = rng.uniform(-1, 1, size=(d, b, h, w, 4)).astype(F)
@@ -358,53 +484,57 @@ def main():
     tgt_pos = rng.uniform(-0.1, 0.1, size=(b, 3)).astype(F)
     tgt_pose = np.stack([rigid(rng, 0.1, 0.02) for _ in range(b)])
     dep_lb = np.tile(np.asarray(depths, F).reshape(-1, 1), (1, b))
-    ref = projector.projective_forward_sphere(_t(layers), None, _t(tgt_pose), _t(tgt_pos), _t(dep_lb))
+    ref = R("projective_forward_sphere", lambda: projector.projective_forward_sphere(_t(layers), None, _t(tgt_pose), _t(tgt_pos), _t(dep_lb)))
     mine = G.projective_forward_sphere(layers, tgt_pose, tgt_pos, dep_lb)
     ok &= same("projective_forward_sphere", ref, mine)
-    ok &= same("over_composite", projector.over_composite([_t(ref[i]) for i in range(d)]), G.over_composite([mine[i] for i in range(d)]))
-    ok &= same("over_composite_depth", projector.over_composite_depth([_t(ref[i]) for i in range(d)]),
+    ok &= same("over_composite", R("over_composite", lambda: projector.over_composite([_t(ref[i]) for i in range(d)])),
+               G.over_composite([mine[i] for i in range(d)]))
+    ok &= same("over_composite_depth", R("over_composite_depth", lambda: projector.over_composite_depth([_t(ref[i]) for i in range(d)])),
                G.over_composite_depth([mine[i] for i in range(d)]))
 
     # --- msi_render_ods_view (projector.py:100-127; spherical.py:328-365): the reference reads intrinsics[0][0][0] for
     # EVERY sample (the batch's first baseline): compare sample by sample with batch 1, as the oracle documents it
     for order in (1, -1):
         for k in range(b):
-            ref = projector.projective_forward_ods(_t(layers[:, k:k + 1]), order, _t(intr[k:k + 1]), _t(tgt_pose[k:k + 1]),
-                                                   _t(tgt_pos[k:k + 1]), _t(dep_lb[:, k:k + 1]))
+            name = "projective_forward_ods order %+d sample %d" % (order, k)
+            ref = R(name, lambda: projector.projective_forward_ods(_t(layers[:, k:k + 1]), order, _t(intr[k:k + 1]), _t(tgt_pose[k:k + 1]),
+                                                                   _t(tgt_pos[k:k + 1]), _t(dep_lb[:, k:k + 1])))
             mine = G.projective_forward_ods(layers[:, k:k + 1], order, intr[k:k + 1], tgt_pose[k:k + 1], dep_lb[:, k:k + 1])
-            ok &= same("projective_forward_ods order %+d sample %d" % (order, k), ref, mine)
+            ok &= same(name, ref, mine)
 
     # --- msi_render_perspective_view (projector.py:64-98; spherical.py:367-401)
     for vw in (0, 3):
-        ref = projector.projective_forward_sphere_to_perspective(_t(layers), None, _t(tgt_pose), _t(tgt_pos), _t(dep_lb),
-                                                                 viewing_window=vw, tgt_height=9, tgt_width=16)
+        name = "projective_forward_sphere_to_perspective vw=%d" % vw
+        ref = R(name, lambda: projector.projective_forward_sphere_to_perspective(_t(layers), None, _t(tgt_pose), _t(tgt_pos), _t(dep_lb),
+                                                                                 viewing_window=vw, tgt_height=9, tgt_width=16))
         mine = G.projective_forward_sphere_to_perspective(layers, tgt_pos, dep_lb, vw, 9, 16)
-        ok &= same("projective_forward_sphere_to_perspective vw=%d" % vw, ref, mine)
+        ok &= same(name, ref, mine)
 
     # --- PP path: perspective_plane_sweep (projector.py:221-223) and projective_forward_homography (:343-373, homography.py)
     n = 16
     K = np.tile(np.array([[n / 2, 0, n / 2], [0, n / 2, n / 2], [0, 0, 1]], F)[None], (b, 1, 1))
     face = rng.uniform(-1, 1, size=(b, n, n, 3)).astype(F)
     pp_pose = np.stack([rigid(rng, 0.05, 0.05) for _ in range(b)])
-    ref = projector.perspective_plane_sweep(_t(face), 1, depths, _t(pp_pose), _t(K))
+    ref = R("perspective_plane_sweep", lambda: projector.perspective_plane_sweep(_t(face), 1, depths, _t(pp_pose), _t(K)))
     ok &= same("perspective_plane_sweep", ref, G.perspective_plane_sweep(face, depths, pp_pose, K))
     Kinv = np.linalg.inv(K.astype(np.float64)).astype(F)
     _GRAPH_TENSORS["intrinsics_inv:0"] = _t(Kinv)
     players = rng.uniform(-1, 1, size=(d, b, n, n, 4)).astype(F)
-    ref = projector.projective_forward_homography(_t(players), _t(K), _t(pp_pose), _t(dep_lb))
+    ref = R("projective_forward_homography", lambda: projector.projective_forward_homography(_t(players), _t(K), _t(pp_pose), _t(dep_lb)))
     ok &= same("projective_forward_homography", ref, G.projective_forward_homography(players, K, Kinv, pp_pose, dep_lb))
 
     # --- the two networks (matryodshka/nets.py:387-450 msi_train_net, :471-515 msi_coord_train_net): the reference's function
     # bodies drive the stand-in slim ops (the oracle's own primitives), the oracle's forward() is the restatement of the wiring
     from oracle import nets as onets
-    for coord, fn in ((False, refnets.msi_train_net), (True, refnets.msi_coord_train_net)):
+    for coord, fname in ((False, "msi_train_net"), (True, "msi_coord_train_net")):
         cin, nout, ngf = 12, 4, 8
         x = rng.uniform(-1, 1, size=(2, 16, 32, cin)).astype(F)
         slim.weights = onets.init_weights(cin, nout, ngf=ngf, coord_net=coord, seed=77, randomize_affine=True)
         slim.calls = []
-        ref = fn(_t(x), nout, ngf=ngf)
-        ok &= same("%s (%d layers)" % (fn.__name__, len(slim.calls)), ref, onets.forward(slim.weights, x, coord_net=coord))
-        assert [c[0] for c in slim.calls] == [t[0] for t in onets.layer_table(cin, nout, ngf, coord)]
+        ref = R(fname, lambda: getattr(refnets, fname)(_t(x), nout, ngf=ngf))
+        calls = list(R(fname + " layer order", lambda: np.array([c[0] for c in slim.calls])))
+        ok &= same("%s (%d layers)" % (fname, len(calls)), ref, onets.forward(slim.weights, x, coord_net=coord))
+        assert calls == [t[0] for t in onets.layer_table(cin, nout, ngf, coord)]
 
     # --- the MSI class itself (matryodshka/msi.py): inv_depths, preprocess, format_network_input (curr_pose = pose @ ref_pose_inv,
     # order +1 / -1), infer_msi's four colour schemes, the equirect RGB / depth render, deprocess -- one frame (the reference
@@ -418,39 +548,54 @@ def main():
     intr1 = intr[:1]
     ref_pose_inv = np.linalg.inv(ref_pose.astype(np.float64)).astype(F)
     _GRAPH_TENSORS["ref_pose_inv:0"] = _t(ref_pose_inv)
-    m = refmsi.MSI()
-    assert m.inv_depths(1.0, 100.0, 32) == OracleMSI().inv_depths(1.0, 100.0, 32)
-    planes = m.inv_depths(1.0, 100.0, d)
+    m = refmsi.MSI() if R.live else None
+    assert list(R("MSI.inv_depths(1, 100, 32)", lambda: m.inv_depths(1.0, 100.0, 32))) == OracleMSI().inv_depths(1.0, 100.0, 32)
+    planes = [float(p) for p in R("MSI.inv_depths(1, 100, %d)" % d, lambda: m.inv_depths(1.0, 100.0, d))]
     print("%-46s %-22s %s" % ("MSI.inv_depths(1, 100, 32)", "32", "identical (Python floats)"))
     for coord in (True, False):
         for scheme, nout in (("blend_psv", 2 * d), ("blend_bg", 2 * d + 3), ("blend_bg_psv", 3 * d + 3), ("alpha_only", d)):
-            fl = tf.app.flags.FLAGS
-            fl.coord_net, fl.which_color_pred, fl.ngf = coord, scheme, ngf
             slim.weights = onets.init_weights(6 * d, nout, ngf=ngf, coord_net=coord, seed=5, randomize_affine=True)
             # (the reference itself raises UnboundLocalError for blend_bg + 'blend_weights': msi.py:283-284 asks for
             # bg_blend_weights whenever 'bg' is in the scheme's name; the oracle / product return what exists)
             extra = "alphas psv" if scheme == "blend_bg" else "blend_weights alphas psv"
-            pred, net_in = m.infer_msi(_t(src8), _t(ref8), None, None, _t(ref_pose), _t(src_pose), _t(intr1), scheme, d, planes,
-                                       extra_outputs=extra, ngf=ngf)
+            tag = "infer_msi %s %s" % ("coord" if coord else "wrap", scheme)
+            if R.live:
+                fl = tf.app.flags.FLAGS
+                fl.coord_net, fl.which_color_pred, fl.ngf = coord, scheme, ngf
+                pred, net_in = m.infer_msi(_t(src8), _t(ref8), None, None, _t(ref_pose), _t(src_pose), _t(intr1), scheme, d, planes,
+                                           extra_outputs=extra, ngf=ngf)
+                R.put(tag + " net_input", net_in)
+                R.put(tag + " outputs", np.array(sorted(pred)))
+                for k in pred:
+                    R.put(tag + " " + k, pred[k])
+            net_in = R.get(tag + " net_input")
+            pred = {k: R.get(tag + " " + k) for k in R.get(tag + " outputs")}
             o = OracleMSI(weights=slim.weights, coord_net=coord)
             pred_o, net_o = o.infer_msi(src8, ref8, None, None, ref_pose, src_pose, intr1, scheme, d, planes, extra_outputs=extra,
                                         ngf=ngf, ref_pose_inv=ref_pose_inv)
-            tag = "infer_msi %s %s" % ("coord" if coord else "wrap", scheme)
             ok &= same(tag + " net_input", net_in, net_o)
             assert sorted(pred) == sorted(pred_o), (sorted(pred), sorted(pred_o))
             for k in sorted(pred):
                 ok &= same(tag + " " + k, pred[k], pred_o[k])
             if scheme == "blend_psv":
-                rgb = m.msi_render_equirect_view(pred["rgba_layers"], _t(tpose), _t(tpos), planes, _t(intr1))
-                dep = m.msi_render_equirect_depth(pred["rgba_layers"], _t(tpose), _t(tpos), planes, _t(intr1))
+                rgb = R(tag + " render rgb", lambda: m.msi_render_equirect_view(_t(pred["rgba_layers"]), _t(tpose), _t(tpos), planes, _t(intr1)))
+                dep = R(tag + " render depth", lambda: m.msi_render_equirect_depth(_t(pred["rgba_layers"]), _t(tpose), _t(tpos), planes, _t(intr1)))
                 rgb_o = o.msi_render_equirect_view(pred_o["rgba_layers"], tpose, tpos, planes, intr1)
                 dep_o = o.msi_render_equirect_depth(pred_o["rgba_layers"], tpose, tpos, planes, intr1)
                 ok &= same(tag + " render rgb", rgb, rgb_o)
                 ok &= same(tag + " render depth", dep, dep_o)
-                ok &= bool(np.array_equal(np.asarray(m.deprocess_image(rgb)), o.deprocess_image(rgb_o)))
-                ok &= bool(np.array_equal(np.asarray(m.deprocess_depth_image(dep)), o.deprocess_depth_image(dep_o)))
+                ok &= equal(R(tag + " deprocess rgb", lambda: m.deprocess_image(_t(rgb))), o.deprocess_image(rgb_o))
+                ok &= equal(R(tag + " deprocess depth", lambda: m.deprocess_depth_image(_t(dep))), o.deprocess_depth_image(dep_o))
                 print("%-46s %-22s %s" % (tag + " deprocess (uint8)", "1x%dx%dx3 x2" % (h, w), "identical" if ok else "MISMATCH"))
 
+    if args.record:
+        R.save(args.record)
+        print("recorded %d reference outputs to %s" % (len(R.store), args.record))
+    drift = R.drifted()
+    if drift:
+        ok = False
+        print("RECORDING DRIFT: %d output(s) of the live reference differ from %s (first: %s) -- re-record with --record" % (
+            len(drift), args.golden, drift[0]))
     print("RESULT:", "the oracle's geometry, network-wiring and MSI-class restatement is bit-identical to the reference's own expression trees under the stand-in"
           if ok else "MISMATCH -- see above")
     return 0 if ok else 1

@@ -231,7 +231,7 @@ def test_bench_gpus_2_end_to_end_on_one_gpu():
     The line must be the contract's, from a 2-rank process group, with one frame per rank per step."""
     from tests.test_dist_cpu import _run_bench
     j = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--prewarm", "0.2", "--repeats", "0", "--no-settle",
-                    "--strong-frames", "2"], timeout=900)
+                    "--strong-frames", "2", "--full"], timeout=900)
     assert j["n_gpus"] == 2 and j["distributed"]["world_size_process_group"] == 2 and j["distributed"]["backend"] == "gloo"
     assert j["distributed"]["frame_ranges_per_rank"] == [[0, 1], [1, 2]] and j["config"]["frames_per_step"] == 2
     assert j["steps"] == 3 and j["value"] > 0 and abs(j["value"] - 2 * 1e3 / j["ms_per_step"]) <= 0.01 * j["value"]

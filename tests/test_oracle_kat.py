@@ -194,15 +194,15 @@ def test_kat10_wrap_convT_layernorm_runs_before_the_crop():
 
 def test_reference_function_bodies_agree_with_the_oracle():
     """oracle/crosscheck_reference.py: the reference's own geometry / nets / msi function bodies, executed over a numpy
-    stand-in for tensorflow, are bit-identical to the oracle's restatement (build container only: /root/reference does not
-    exist on the GPU box and is never read by a -m gpu test, smoke() or bench.py)."""
+    stand-in for tensorflow, are bit-identical to the oracle's restatement.  Where a reference checkout exists the script runs
+    it live and also checks that tests/golden/reference_crosscheck.json (written by its --record) still holds the same outputs;
+    elsewhere it replays that recording, so the check needs nothing outside the repository.  The script pins numpy, ATen and
+    MKL to code paths that give the same bits on every x86-64 host."""
     import os
     import subprocess
     import sys
-    import pytest
-    if not os.path.isdir("/root/reference/geometry"):
-        pytest.skip("no reference checkout here")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "crosscheck_reference.py")], cwd=root, timeout=600,
+    golden = os.path.join(root, "tests", "golden", "reference_crosscheck.json")
+    p = subprocess.run([sys.executable, os.path.join(root, "oracle", "crosscheck_reference.py"), "--golden", golden], cwd=root, timeout=600,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert p.returncode == 0 and "MISMATCH" not in p.stdout and p.stdout.count("bit-identical") >= 50, p.stdout[-3000:]

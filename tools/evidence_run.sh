@@ -12,11 +12,11 @@ tools/profile_run.sh $TAG/config3 3 $COMMIT
 tools/profile_run.sh $TAG/config4 4 $COMMIT
 # second pass of the bench lines with this call's traffic files installed where bench.py looks for them
 for n in config1 config1_wrapnet config2 config3 config4; do cp gpurun_out/$TAG/$n/hbm_traffic.json profiles/${TAG}_hbm_traffic_$n.json; done
-python bench.py --config 1 > gpurun_out/$TAG/config1/bench.json 2>/dev/null
-python bench.py --config 1 --no-coord-net > gpurun_out/$TAG/config1_wrapnet/bench.json 2>/dev/null
-python bench.py --config 2 > gpurun_out/$TAG/config2/bench.json 2>/dev/null
-python bench.py --config 3 > gpurun_out/$TAG/config3/bench.json 2>/dev/null
-python bench.py --config 4 > gpurun_out/$TAG/config4/bench.json 2>/dev/null
+BENCH_ONLY=1 tools/profile_run.sh $TAG/config1 1 $COMMIT
+BENCH_ONLY=1 tools/profile_run.sh $TAG/config1_wrapnet 1 $COMMIT --no-coord-net
+BENCH_ONLY=1 tools/profile_run.sh $TAG/config2 2 $COMMIT
+BENCH_ONLY=1 tools/profile_run.sh $TAG/config3 3 $COMMIT
+BENCH_ONLY=1 tools/profile_run.sh $TAG/config4 4 $COMMIT
 for n in config1 config1_wrapnet config2 config3 config4; do python -c "
 import json,sys
 j=json.loads(open('gpurun_out/$TAG/$n/bench.json').read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@
 #                        (per-kernel table, per-step totals, per-layer conv table against the MFMA peak)
 #   hbm_traffic.json     HBM bytes per step and kernel: --pmc FETCH_SIZE and --pmc WRITE_SIZE in SEPARATE passes with
 #                        --kernel-trace only (tools/hbm_traffic.py; stamped with the kernel-source hash + COMMIT)
-# Set SKIP_PMC=1 to leave the two counter passes out.
+# Set SKIP_PMC=1 to leave the two counter passes out, BENCH_ONLY=1 to write bench.json alone.
 set -u
 TAG=$1; CONFIG=$2; COMMIT=$3; shift 3
 EXTRA="$*"
@@ -16,7 +16,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout 900 python bench.py --config "$CONFIG" $EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; }
+timeout 900 python bench.py --full --config "$CONFIG" $EXTRA > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; }
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 try:
@@ -26,6 +26,7 @@ try:
 except Exception as e:
     print("bench.json unreadable:", e)
 PY
+[ "${BENCH_ONLY:-0}" = "1" ] && exit 0
 STEPS=20; [ "$CONFIG" != "1" ] && STEPS=6
 timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace -- python bench.py --config "$CONFIG" $EXTRA --steps $STEPS --warmup 3 --repeats 0 \
   --no-cpu-baseline --no-sustained-probe --prewarm 0 --strong-frames 0 --no-settle > "$OUT/prof.log" 2>&1

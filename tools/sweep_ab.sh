@@ -19,7 +19,7 @@ for r in 1 2; do
 for cfg in 2 3; do
   for v in tools/_variants/libmsi_*.so; do
     cp "$v" matryodshka_amd/libmsi_hip.so
-    python bench.py --config $cfg --no-cpu-baseline --no-alt-arithmetic --strong-frames 0 --repeats 0 --steps 10 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg $cfg', '$v', j['value'], j['ms_per_step'], {k:v['ms'] for k,v in j['stages'].items() if isinstance(v, dict)})"
+    python bench.py --full --config $cfg --no-cpu-baseline --no-alt-arithmetic --strong-frames 0 --repeats 0 --steps 10 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg $cfg', '$v', j['value'], j['ms_per_step'], {k:v['ms'] for k,v in j['stages'].items() if isinstance(v, dict)})"
   done
 done
 done
