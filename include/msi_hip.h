@@ -62,8 +62,9 @@ const char *msi_version(void);
  *   5: packed blob carries the fp16-split (x2) block; MSI_NET_OPT_F32_SPLIT_F16, MSI_NET_STATUS_F16_SPLIT_RANGE (round 4)
  *   6: msi_net_plan_calibrate; MSI_NET_OPT_X3_TILE8 (round 5)
  *   7: MSI_NET_OPT_X3_ROWPAR (round 5)
- *   8: msi_probe_matrix_rate (round 6) */
-#define MSI_ABI_VERSION 8
+ *   8: msi_probe_matrix_rate (round 6)
+ *   9: msi_perspective_sweep_volume_bf16 */
+#define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
 /* CRC-32C (Castagnoli) of a host buffer, continuing from `crc` (0 for a new message): the per-tensor checksum of
@@ -236,6 +237,14 @@ int msi_perspective_plane_sweep_f32(const float *image, const float *pose, const
                                     const float *depths, int32_t batch, int32_t height, int32_t width,
                                     int32_t num_depths, float *psv, int32_t psv_channels,
                                     int32_t channel_offset, msi_stream_t stream);
+/* The whole bf16 double volume of MSI.format_network_input for input_type PP (msi.py:1157-1161) in one launch:
+ * pj.perspective_plane_sweep (projector.py:221-223) of ref_image into channels [0,3D) and of src_image into [3D,6D) of
+ * psv_bf16 [B,H,W,6D].  The poses are the two curr_pose = pose @ ref_pose_inv (msi_compose_pose_pair_f32).  Every value
+ * is the round to nearest even of what two msi_perspective_plane_sweep_f32 calls compute, bit for bit. */
+int msi_perspective_sweep_volume_bf16(const float *ref_image, const float *src_image, const float *ref_curr_pose,
+                                      const float *src_curr_pose, const float *intrinsics, const float *depths,
+                                      int32_t batch, int32_t height, int32_t width, int32_t num_depths,
+                                      void *psv_bf16, msi_stream_t stream);
 /* MSI.mpi_render_view (msi.py:527-548): pj.projective_forward_homography (projector.py:343-373) ->
  * homography.planar_transform (homography.py:35-157) -> tf.contrib.resampler (zero padding) ->
  * pj.over_composite.  intrinsics_inv [B,3,3] replaces the hidden graph input `intrinsics_inv:0`

@@ -1392,6 +1392,127 @@ pp_sweep_kernel(const float *__restrict__ image, const float *__restrict__ pose,
   o[2] = blend4(t, pa[2], pb[2], pc[2], pd[2]);
 }
 
+// The whole bf16 PP network input of format_network_input (msi.py:1157-1161) in one launch: ref into channels [0, 3D), src into [3D, 6D)
+// of psv [B,H,W,6D].  Every value is the round-to-nearest-even of what pp_sweep_kernel computes for the same sample, bit for bit: the
+// arithmetic below is pp_sweep_kernel's, op for op.  What changes is what is shared: backproject_planar's (x, y, z) depend on the face's
+// intrinsics, the plane and the pixel, not on the pose, so one thread per (pixel, plane) computes them once for both sources (5 IEEE
+// divides per thread instead of 10 over two launches), and y -- a function of (row, plane) -- once per block into LDS; M = K4 @ pose is
+// computed once per face and source (24 threads, LDS).
+// FAST (64 % D == 0, (W * D) % 64 == 0; the host decides): a wave holds 64 / D complete pixels, whose 6 D channels are one contiguous run,
+// so the wave's 768 bytes leave through a wave-private fp32 strip as 48 16-byte stores of packed pairs (v_cvt_pk_bf16_f32: round to nearest
+// even, what f32_to_bf16 computes for the finite values stored here); non-temporal when the volume exceeds the Infinity Cache (sweep_store16).
+// Generic: one thread per (pixel, plane) stores its six values as bf16 halves.  Corners are 12-byte buffer loads with 32-bit offsets
+// (H * W * 12 < 2^31, checked on the host) in both forms; make_taps' wrapped indices lie inside the image.  The kernel is VALU-bound
+// (DESIGN.md section 4).  NT is a template argument, not sweep_store16's runtime flag: with the packed value computed ahead of the
+// branch, hipcc merges the two stores into one plain store.
+template <int FAST, int NT>
+__global__ void __launch_bounds__(256)
+pp_sweep_volume_bf16_kernel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
+                            const float *__restrict__ pose1, const float *__restrict__ intrinsics, const float *__restrict__ depths,
+                            int height, int width, int nd, int nd_shift, float s0, float sstep, float t0, float tstep,
+                            unsigned short *__restrict__ psv) {
+  // grid = (ceil(W*D / 256), H, B): 32-bit index math only
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int i = blockIdx.y, b = blockIdx.z;
+  const float *Kb = intrinsics + (size_t)b * 9;
+  const float fx = Kb[0], fy = Kb[4], cx = Kb[2], cy = Kb[5];
+  const float T = t0 + tstep * (float)i;
+  __shared__ float s_m[2][12];
+  __shared__ float s_y[64];
+  if (FAST) {
+    // project_perspective's M = K4 @ pose (rows 0..2; the padded column contributes 0 * pose[3][c]) per source, and
+    // backproject_planar's y = depth*T*cy/fy per plane of this row
+    const int tid = threadIdx.x;
+    if (tid < 24) {
+      const int s = tid / 12, e = tid - s * 12, r = e >> 2, c = e & 3;
+      const float *P = (s ? pose1 : pose0) + (size_t)b * 16;
+      s_m[s][e] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
+    } else if (tid >= 64 && tid < 64 + nd) {
+      s_y[tid - 64] = ((depths[tid - 64] * T) * cy) / fy;
+    }
+    __syncthreads();
+    if (idx >= width * nd) return;   // (W * D) % 64 == 0: whole waves
+  } else {
+    if (idx >= width * nd) return;
+  }
+  const int j = FAST ? idx >> nd_shift : idx / nd;
+  const int d = FAST ? idx & (nd - 1) : idx - j * nd;
+  const float S = s0 + sstep * (float)j;
+  const float depth = depths[d];
+  // backproject_planar (spherical.py:146-148), shared by both sources
+  const float x0 = ((depth * S) * cx) / fx;
+  const float y0 = FAST ? s_y[d] : ((depth * T) * cy) / fy;
+  const float z0 = depth * 1.0f;
+  const int img_bytes = height * width * 12;
+  float out[2][3];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const float *P = (s ? pose1 : pose0) + (size_t)b * 16;
+    // apply_pose (projector.py:275-291)
+    const float x = ((P[0] * x0 + P[1] * y0) + P[2] * z0) + P[3] * 1.0f;
+    const float y = ((P[4] * x0 + P[5] * y0) + P[6] * z0) + P[7] * 1.0f;
+    const float z = ((P[8] * x0 + P[9] * y0) + P[10] * z0) + P[11] * 1.0f;
+    float pr[3];
+    if (FAST) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) pr[r] = ((s_m[s][r * 4 + 0] * x + s_m[s][r * 4 + 1] * y) + s_m[s][r * 4 + 2] * z) + s_m[s][r * 4 + 3] * 1.0f;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        float m[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          m[c] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
+        pr[r] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * 1.0f;
+      }
+    }
+    const float u = pr[0] / pr[2], v = pr[1] / pr[2];
+    const Taps t = make_taps(u, v, width, height);
+    const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void *)((s ? image1 : image0) + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
+    const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x0) * 12u, 0, 0));
+    const f32x3_g bq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x1) * 12u, 0, 0));
+    const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x0) * 12u, 0, 0));
+    const f32x3_g dq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x1) * 12u, 0, 0));
+    out[s][0] = blend4(t, a.x, bq.x, c.x, dq.x);
+    out[s][1] = blend4(t, a.y, bq.y, c.y, dq.y);
+    out[s][2] = blend4(t, a.z, bq.z, c.z, dq.z);
+  }
+  const long p = ((long)b * height + i) * width + j;
+  if (FAST) {
+    // the wave's 64 / D pixels are consecutive and each owns 6 D contiguous channels: lane = pl * D + d writes its two triples into the
+    // strip at pl * 6 D + {0, 3 D} + 3 d, then lanes 0..47 each pack 8 of the 384 values into one 16-byte store
+    __shared__ __attribute__((aligned(16))) float s_out[4][384];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pl = lane >> nd_shift;
+    float *w = s_out[wave];
+    __builtin_amdgcn_wave_barrier();
+    const int e0 = pl * 6 * nd + 3 * d;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      w[e0 + c] = out[0][c];
+      w[e0 + 3 * nd + c] = out[1][c];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 48) {
+      const float4 lo = reinterpret_cast<const float4 *>(w)[2 * lane], hi = reinterpret_cast<const float4 *>(w)[2 * lane + 1];
+      uint4 pk;
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.x) : "v"(lo.x), "v"(lo.y));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.y) : "v"(lo.z), "v"(lo.w));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.z) : "v"(hi.x), "v"(hi.y));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.w) : "v"(hi.z), "v"(hi.w));
+      uint4 *dst = reinterpret_cast<uint4 *>(psv + (size_t)(p - pl) * (6 * nd)) + lane;   // (p - pl: the wave's first pixel)
+      sweep_store16(dst, pk, NT);
+    }
+    return;
+  }
+  unsigned short *o = psv + (size_t)p * (6 * nd) + 3 * d;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    o[c] = f32_to_bf16(out[0][c]);
+    o[3 * nd + c] = f32_to_bf16(out[1][c]);
+  }
+}
+
 // MSI.mpi_render_view (msi.py:527-548): pj.projective_forward_homography (projector.py:343-373) ->
 // homography.planar_transform (homography.py:120-157: inv_homography :35-58, transform_points
 // :60-80, normalize_homogeneous :82-94, divide_safe :30-33) -> sampling.bilinear_wrapper =
@@ -1866,6 +1987,40 @@ int msi_perspective_plane_sweep_f32(const float *image, const float *pose, const
                        intrinsics, depths, batch, height, width, num_depths, s0, (s1 - s0) / (float)(width - 1), t0,
                        (t1 - t0) / (float)(height - 1), psv, psv_channels, channel_offset, magic, nt);
   return msi::check_launch("perspective_plane_sweep");
+}
+
+int msi_perspective_sweep_volume_bf16(const float *ref_image, const float *src_image, const float *ref_curr_pose,
+                                      const float *src_curr_pose, const float *intrinsics, const float *depths,
+                                      int32_t batch, int32_t height, int32_t width, int32_t num_depths,
+                                      void *psv_bf16, msi_stream_t stream) {
+  MSI_REQUIRE(ref_image && src_image && ref_curr_pose && src_curr_pose && intrinsics && depths && psv_bf16,
+              "perspective_sweep_volume_bf16: null pointer");
+  MSI_REQUIRE(batch >= 0 && height > 1 && width > 1 && num_depths > 0, "perspective_sweep_volume_bf16: bad dims");
+  if (batch == 0) return MSI_OK;
+  MSI_REQUIRE((long)width * num_depths < 2147483647L && height <= 65535 && batch <= 65535 && (long)height * width * 12 < 2147483647L,
+              "perspective_sweep_volume_bf16: problem too large");
+  const dim3 grid((unsigned)(((long)width * num_depths + 255) / 256), height, batch);
+  // spherical.uv_grid (spherical.py:46-48), tf.linspace fp32 semantics: msi_perspective_plane_sweep_f32's constants
+  const float s0 = (float)(-1.0 + 1.0 / width), s1 = (float)(1.0 - 1.0 / width);
+  const float t0 = (float)(-1.0 + 1.0 / height), t1 = (float)(1.0 - 1.0 / height);
+  const float sstep = (s1 - s0) / (float)(width - 1), tstep = (t1 - t0) / (float)(height - 1);
+  const int nt = (size_t)batch * height * width * 6 * num_depths * 2 > ((size_t)256 << 20) ? 1 : 0;
+  int shift = 0;
+  while ((1 << shift) < num_depths) ++shift;
+  // whole waves of complete pixels (D a power of two up to 64), 16-byte-aligned volume
+  const bool fast = 64 % num_depths == 0 && ((long)width * num_depths) % 64 == 0 && reinterpret_cast<uintptr_t>(psv_bf16) % 16 == 0;
+  unsigned short *psv = static_cast<unsigned short *>(psv_bf16);
+#define MSI_LAUNCH_PPV(FAST_, NT_)                                                                                                        \
+  hipLaunchKernelGGL((pp_sweep_volume_bf16_kernel<FAST_, NT_>), grid, dim3(256), 0, msi::as_stream(stream), ref_image, src_image,       \
+                     ref_curr_pose, src_curr_pose, intrinsics, depths, height, width, num_depths, shift, s0, sstep, t0, tstep, psv)
+  if (fast && nt)
+    MSI_LAUNCH_PPV(1, 1);
+  else if (fast)
+    MSI_LAUNCH_PPV(1, 0);
+  else
+    MSI_LAUNCH_PPV(0, 0);
+#undef MSI_LAUNCH_PPV
+  return msi::check_launch("perspective_sweep_volume_bf16");
 }
 
 int msi_mpi_render_f32(const float *rgba_native, const float *tgt_pose, const float *intrinsics,

@@ -13,7 +13,8 @@ to --height x --width (datasets.py:513-515), runs infer_msi + the equirect RGB /
 Modes (test.py:76-78): `--test_type` concatenates on_video (directory names `video_[<prefix>_]<scene>_...`, :209-217),
 high_res (after the low-res pass, the high-res re-render of :283-394 from the saved blend_weights.npy / alphas.npy and
 `--hres_image_dir`: output_hrestgt_* / output_hresdepth_*), high_res_only (only that); `--input_type PP` takes perspective
-camera lines (`scene ref src tgt input_offset tgt_offset`, datasets.py:427-437) through the plane-sweep / mpi_render_view path.
+camera lines (`scene ref src tgt input_offset tgt_offset`, datasets.py:427-437) through the plane-sweep / mpi_render_view path;
+`--dtype bf16` runs either input type on the bf16 network tier.
 `--checkpoint` reads a TF V2 checkpoint directly (tf_checkpoint.py), `--weights` an .npz of the TF variables
 (see nets.variable_shapes); without either Xavier-initialised
 weights are used (there is no network access for the pretrained checkpoint), step.txt then says 0.
@@ -76,7 +77,7 @@ def write_layer_outputs(outs, jouts, src, ref, num_planes, test_outputs, output_
     if "ref_image" in test_outputs:
         write_image(os.path.join(output_dir, "ref_image_%s.png" % dirname), ref[0].numpy() * 255.0)
     if "psv" in test_outputs:
-        psv = outs["psv"].cpu().numpy()
+        psv = outs["psv"].float().cpu().numpy()       # (a bf16 volume: numpy has no bfloat16)
         for j in range(num_planes):
             write_image(os.path.join(output_dir, "psv_plane_%.3d.png" % j), (psv[0, :, :, j * 3:(j + 1) * 3] + 1.) / 2. * 255)
     if "blend" in which_color_pred and "blend_weights" in test_outputs:      # test.py:262
@@ -252,6 +253,9 @@ def main(argv=None):
     ap.add_argument("--input_type", default="ODS", choices=["ODS", "PP"],
                     help="ODS pairs (camera lines `scene ref src tgt baseline tx ty tz`) or perspective pairs (`scene ref src tgt "
                          "input_offset tgt_offset`, datasets.py:427-437) -- test.py:51")
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
+                    help="f32, or bf16: the bf16 network tier (bf16 sweep volume, weights and activations; fp32 geometry) for "
+                         "either input type")
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--hres_height", type=int, default=2048, help="loader.py:34")
@@ -304,7 +308,7 @@ def main(argv=None):
     else:
         weights = nets.init_weights(6 * d, nout, args.ngf, coord)
     # with weights the network (CoordNet or not) follows from conv1_1/weights' input channels unless the flag insists
-    model = MSI(weights=weights, coord_net=True if coord else None, input_type=args.input_type)
+    model = MSI(weights=weights, coord_net=True if coord else None, input_type=args.input_type, dtype=args.dtype)
     # test.py:112 evaluates tf_random_rotation INSIDE the graph: every sess.run (every sample) draws a new jitter pose;
     # here one seeded generator is advanced per sample
     jitter_rng = np.random.RandomState(args.random_seed) if args.transform_inverse_reg else None

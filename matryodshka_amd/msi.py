@@ -68,12 +68,10 @@ class MSI(object):
         if input_type not in ('ODS', 'PP'):
             raise ValueError("input_type must be 'ODS' or 'PP' (FLAGS.input_type, msi.py:1157-1161)")
         self.input_type = input_type
-        # 'bf16' = BASELINE configs[2]: the sweep volume, the weights and the activations of the network are
-        # bf16 (fp32 accumulate, fp32 LayerNorm statistics, fp32 prediction); geometry stays fp32
+        # 'bf16' = BASELINE configs[2] (and its PP counterpart): the sweep volume, the weights and the activations of the
+        # network are bf16 (fp32 accumulate, fp32 LayerNorm statistics, fp32 prediction); geometry stays fp32
         if dtype not in ('f32', 'bf16'):
             raise ValueError("dtype must be 'f32' or 'bf16'")
-        if dtype == 'bf16' and input_type != 'ODS':
-            raise NotImplementedError("dtype='bf16' is built for the ODS path only")
         self.dtype = dtype
         self._weights = None
         self._blob_cache = {}     # (in_channels, num_outputs, ngf) -> np blob
@@ -318,6 +316,10 @@ class MSI(object):
             N.check(N.lib.msi_ods_sweep_volume(ref_image.data_ptr(), src_image.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(),
                                                intr.data_ptr(), depths.data_ptr(), trig.data_ptr(), b, h, w, nd,
                                                psv.data_ptr(), 1 if bf16 else 0, self._stream()), "msi_ods_sweep_volume")
+        elif bf16:   # sweep_src for perspective inputs (msi.py:1157-1161), the whole bf16 volume in one launch
+            N.check(N.lib.msi_perspective_sweep_volume_bf16(ref_image.data_ptr(), src_image.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(),
+                                                            intr.data_ptr(), depths.data_ptr(), b, h, w, nd, psv.data_ptr(), self._stream()),
+                    "msi_perspective_sweep_volume_bf16")
         else:   # sweep_src for perspective inputs (msi.py:1157-1161); ref_pose_inv = interp_pose_inv (:1113)
             for i, img in enumerate((ref_image, src_image)):
                 N.check(N.lib.msi_perspective_plane_sweep_f32(
