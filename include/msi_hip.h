@@ -205,6 +205,28 @@ int msi_render_equirect_f32(const float *rgba_native, const float *tgt_pose_rt,
                             const float *tgt_pos, const float *depths, const float *trig,
                             int32_t batch, int32_t height, int32_t width, int32_t num_planes,
                             float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
+/* Many views of one MSI per launch (MSI.render_views; no reference counterpart -- the reference's player was not
+ * released): V target cameras per sample, each rendered as msi_render_equirect_f32 renders its one view.
+ *   rgba_native [B,D,H,W,4], depths [D] (far -> near), tgt_pose_rt [B*V,4,4], tgt_pos [B*V,3] (view v of sample b at
+ *   index b*V + v; it samples stack b only).  The ray direction is rotated by pose[:3,:3], the ray origin is
+ *   pose @ (tgt_pos[2], tgt_pos[1], tgt_pos[0], 1) (the x<->z swap of the equirect render).  Rays before the pose:
+ *   MSI_CAMERA_EQUIRECT  the lat-long grid of the OUTPUT size: trig = the msi_build_trig_tables_host table of
+ *                        (out_height, out_width) (required); intrinsics unused.  At out size == (H, W) every view is
+ *                        bit-identical to msi_render_equirect_f32 with that pose.
+ *   MSI_CAMERA_PINHOLE   pixel (i, j) -> (1, (i + 0.5 - cy) / fy, (j + 0.5 - cx) / fx): forward +x, image-down +y,
+ *                        image-right +z, so with an identity pose the centre pixel looks where the centre of an equirect
+ *                        render looks, with the same orientation.  intrinsics [B*V,3,3] row-major in pixels
+ *                        (fx, cx in row 0; fy, cy in row 1) (required); trig unused.  out size >= 2 x 2.
+ *   out_rgb [B,V,out_height,out_width,3], out_depth [B,V,out_height,out_width] (ONE channel: the composited i / D of
+ *   over_composite_depth); either may be NULL, not both.  status_device as above (may be NULL).
+ * The grid runs sample -> view -> row: the views of one stack are rendered one after another. */
+#define MSI_CAMERA_EQUIRECT 0
+#define MSI_CAMERA_PINHOLE 1
+int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, const float *tgt_pos,
+                         const float *intrinsics, const float *depths, const float *trig,
+                         int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                         int32_t camera, int32_t out_height, int32_t out_width,
+                         float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libmsi_hip.so")
 MSI_OK = 0
 MSI_NET_NUM_LAYERS = 18
 RENDER_STATUS_ORIGIN_OUTSIDE = 1
+MSI_CAMERA_EQUIRECT, MSI_CAMERA_PINHOLE = 0, 1   # msi_render_views_f32's camera models
 MSI_ABI_VERSION = 9          # include/msi_hip.h: the version this binding's struct layouts and signatures are written for
 
 
@@ -74,6 +75,7 @@ SIGNATURES = {
     "msi_resize_bilinear_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "msi_assemble_rgba_scaled_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "msi_render_equirect_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "msi_render_views_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_project_layers_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msi_render_ods_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_render_perspective_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),

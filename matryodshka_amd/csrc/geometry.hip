@@ -1251,6 +1251,157 @@ render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt
   }
 }
 
+// Layer d of sample b of a [B,D,H,W,4] stack as a buffer resource: 32-bit texel offsets also for stacks beyond 2 GiB.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t layer_rsrc(const float4 *rgba, int b, int nd, int d, size_t hw, int layer_bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(rgba + ((size_t)b * nd + d) * hw), 0, layer_bytes, 0x00020000);
+}
+
+__device__ __forceinline__ float4 layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
+  typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
+  return __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, texel << 4, 0, 0));
+}
+
+// K4, many views of one stack per launch (msi_render_views_f32): render_kernel's per-layer arithmetic, op for op, for V target
+// cameras per sample.  A workgroup is one (sample, view, target row, 64-pixel block); the 1-D grid runs sample -> view -> row
+// -> block with render_kernel's XCD-aware mapping, so the V views of one stack follow each other (its texels stay in the
+// Infinity Cache while they render) and adjacent rows of one view share an XCD's L2.  The pose, origin and K of a view are
+// wave-uniform (scalar loads).  Rays before the pose:
+//   MSI_CAMERA_EQUIRECT  (cos S cos T, sin T, sin S cos T) on the lat-long grid of the OUTPUT size (trig = its table)
+//   MSI_CAMERA_PINHOLE   (1, (i + 0.5 - cy) / fy, (j + 0.5 - cx) / fx): forward +x, image-down +y, image-right +z -- the
+//                        orientation of the equirect render around its centre pixel
+// and the origin is pose @ (tgt_pos[2], tgt_pos[1], tgt_pos[0], 1) for both.  Outputs rgb [B,V,h,w,3] and depth [B,V,h,w].
+template <int MODE, int CAMERA>
+__global__ void __launch_bounds__(256)
+render_views_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt, const float *__restrict__ tgt_pos,
+                    const float *__restrict__ intrinsics, const float *__restrict__ depths, const float *__restrict__ trig,
+                    int batch, int views, int height, int width, int nd, int out_h, int out_w, float *__restrict__ out_rgb,
+                    float *__restrict__ out_depth, PixConsts K, DepthFrac F, int *__restrict__ status) {
+  const unsigned gx = (unsigned)(out_w + 63) >> 6;
+  const unsigned nblk = gx * (unsigned)out_h * (unsigned)views * (unsigned)batch, per = gridDim.x >> 3;
+  const unsigned lin = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+  if (lin >= nblk) return;
+  const unsigned rowb = lin / gx;
+  const int j_raw = (int)(lin - rowb * gx) * 64 + threadIdx.x;
+  const unsigned bv = rowb / (unsigned)out_h;           // sample * views + view
+  const int i = (int)(rowb - bv * (unsigned)out_h);
+  const int b = (int)(bv / (unsigned)views);
+  const int seg = __builtin_amdgcn_readfirstlane(threadIdx.y);
+  const bool valid = j_raw < out_w;
+  const int j = valid ? j_raw : out_w - 1;
+  __shared__ float s_part[RENDER_SEGS][64][5];
+
+  float rx, ry, rz;
+  if (CAMERA == MSI_CAMERA_PINHOLE) {
+    const float *Kv = intrinsics + (size_t)bv * 9;      // fx . cx / . fy cy
+    rx = 1.0f;
+    ry = (((float)i + 0.5f) - Kv[5]) / Kv[4];            // (IEEE divides: per pixel, not per layer)
+    rz = (((float)j + 0.5f) - Kv[2]) / Kv[0];
+  } else {
+    const float cs = trig[j], ss = trig[out_w + j];
+    const float ct = trig[2 * out_w + i], st = trig[2 * out_w + out_h + i];
+    rx = cs * ct; ry = st; rz = ss * ct;
+  }
+  const float *tp = tgt_pos + (size_t)bv * 3;
+  float cx = tp[2], cy = tp[1], cz = tp[0];
+  const float *P = pose_rt + (size_t)bv * 16;
+  {
+    const float x = (P[0] * rx + P[1] * ry) + P[2] * rz;
+    const float y = (P[4] * rx + P[5] * ry) + P[6] * rz;
+    const float z = (P[8] * rx + P[9] * ry) + P[10] * rz;
+    rx = x; ry = y; rz = z;
+  }
+  {
+    const float x = ((P[0] * cx + P[1] * cy) + P[2] * cz) + P[3] * 1.0f;
+    const float y = ((P[4] * cx + P[5] * cy) + P[6] * cz) + P[7] * 1.0f;
+    const float z = ((P[8] * cx + P[9] * cy) + P[10] * cz) + P[11] * 1.0f;
+    cx = x; cy = y; cz = z;
+  }
+  const float qa = (rx * rx + ry * ry) + rz * rz;
+  const float qb = 2.0f * ((rx * cx + ry * cy) + rz * cz);
+  const float cc = (cx * cx + cy * cy) + cz * cz;
+  const float qb2 = qb * qb;
+  const float fa = 4.0f * qa, ta = 2.0f * qa;
+  const float inv_ta = __builtin_amdgcn_rcpf(ta);
+
+  const size_t hw = (size_t)height * width;
+  const int layer_bytes = (int)(hw * 16);
+  const size_t pix = (size_t)bv * out_h * out_w + (size_t)i * out_w + j;
+  float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f, tr = 1.f;
+  float qc_max = -1.0f;
+  const int d_lo = (seg * nd) / RENDER_SEGS, d_hi = ((seg + 1) * nd) / RENDER_SEGS;
+
+#pragma unroll 4
+  for (int d = d_lo; d < d_hi; ++d) {
+    const float radius = depths[d];
+    const float qc = cc - radius * radius;
+    qc_max = fmaxf(qc_max, qc);
+    const float disc = qb2 - fa * qc;
+#if MSI_FAST_TAIL
+    const float num = t_sqrt(fmaxf(disc, 0.0f)) - qb;
+    const float tq = num * inv_ta;
+    const float t = __builtin_fmaf(__builtin_fmaf(-tq, ta, num), inv_ta, tq);
+#else
+    const float t = t_div(-qb + t_sqrt(fmaxf(disc, 0.0f)), ta);
+#endif
+    const float x = cx + t * rx;
+    const float y = cy + t * ry;
+    const float z = cz + t * rz;
+    float theta, phi;
+    t_angles(x, y, z, radius, theta, phi);
+#if MSI_FAST_TAIL
+    const float u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
+    const float v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
+#else
+    const float u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
+    const float v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
+#endif
+    const TapsR tp4 = make_taps_ranged(u, v, width, height);
+    const __amdgpu_buffer_rsrc_t L = layer_rsrc(rgba, b, nd, d, hw, layer_bytes);
+    const float4 A = layer_tap(L, tp4.oa), Bv = layer_tap(L, tp4.ob), C = layer_tap(L, tp4.oc), Dv = layer_tap(L, tp4.od);
+    const float al = blend4(tp4, A.w, Bv.w, C.w, Dv.w);
+    if (MODE & RENDER_RGB) {
+      const float r = blend4(tp4, A.x, Bv.x, C.x, Dv.x);
+      const float g = blend4(tp4, A.y, Bv.y, C.y, Dv.y);
+      const float bl = blend4(tp4, A.z, Bv.z, C.z, Dv.z);
+      if (d == 0) {
+        o0 = r; o1 = g; o2 = bl;
+      } else {
+        const float om = 1.0f - al;
+        o0 = r * al + o0 * om;
+        o1 = g * al + o1 * om;
+        o2 = bl * al + o2 * om;
+      }
+    }
+    if (MODE & RENDER_DEPTH) {
+      if (d == 0) {
+        od = 0.0f;
+      } else {
+        const float frac = nd <= DEPTH_FRAC_MAX ? F.f[d] : (float)((double)d / (double)nd);
+        od = frac * al + od * (1.0f - al);
+      }
+    }
+    tr = tr * (1.0f - al);
+  }
+  // (as render_kernel: the origin of this view is not inside every sphere, or is NaN)
+  if (status != nullptr && threadIdx.x == 0 && (!(qc_max < 0.0f) || cc != cc)) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+  s_part[seg][threadIdx.x][0] = o0; s_part[seg][threadIdx.x][1] = o1; s_part[seg][threadIdx.x][2] = o2;
+  s_part[seg][threadIdx.x][3] = od; s_part[seg][threadIdx.x][4] = tr;
+  __syncthreads();
+  if (seg != 0 || !valid) return;
+#pragma unroll
+  for (int sg = 1; sg < RENDER_SEGS; ++sg) {    // back to front: segment 0 holds the farthest layers
+    const float *q = s_part[sg][threadIdx.x];
+    o0 = q[0] + q[4] * o0; o1 = q[1] + q[4] * o1; o2 = q[2] + q[4] * o2;
+    od = q[3] + q[4] * od;
+  }
+  // (a wave's 64 pixels are one contiguous 768-byte rgb run and one 256-byte depth run)
+  if (MODE & RENDER_RGB) {
+    float *o = out_rgb + pix * 3;
+    o[0] = o0; o[1] = o1; o[2] = o2;
+  }
+  if (MODE & RENDER_DEPTH) out_depth[pix] = od;
+}
+
 // tf.image.resize(..., BILINEAR, align_corners=True) [TF-knowledge: resize_bilinear_op]:
 // src = dst * (in-1)/(out-1); lower = floor(src), upper = min(ceil(src), in-1), lerp = src - lower;
 // top = tl + (tr - tl)*xl; bottom = bl + (br - bl)*xl; out = top + (bottom - top)*yl.
@@ -1947,6 +2098,55 @@ int msi_render_equirect_f32(const float *rgba_native, const float *tgt_pose_rt,
   const int mode = (out_rgb ? RENDER_RGB : 0) | (out_depth ? RENDER_DEPTH : 0);
   return render_common(mode, RAY_EQUIRECT, rgba_native, tgt_pose_rt, tgt_pos, nullptr, depths, trig, batch, height,
                        width, num_planes, same_size(height, width), out_rgb, out_depth, nullptr, status_device, stream);
+}
+
+int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, const float *tgt_pos,
+                         const float *intrinsics, const float *depths, const float *trig,
+                         int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                         int32_t camera, int32_t out_height, int32_t out_width,
+                         float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream) {
+  MSI_REQUIRE(out_rgb || out_depth, "render_views: both outputs are NULL");
+  MSI_REQUIRE(rgba_native && tgt_pose_rt && tgt_pos && depths, "render_views: null pointer");
+  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || camera == MSI_CAMERA_PINHOLE, "render_views: unknown camera %d", camera);
+  MSI_REQUIRE(camera != MSI_CAMERA_EQUIRECT || trig, "render_views: null pointer (equirect camera needs trig)");
+  MSI_REQUIRE(camera != MSI_CAMERA_PINHOLE || intrinsics, "render_views: null pointer (pinhole camera needs intrinsics)");
+  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "render_views: bad dims");
+  MSI_REQUIRE(views >= 1, "render_views: views must be >= 1 (got %d)", views);
+  const int min_out = camera == MSI_CAMERA_PINHOLE ? 2 : 1;
+  MSI_REQUIRE(out_height >= min_out && out_width >= min_out, "render_views: bad output size %d x %d", out_height, out_width);
+  MSI_REQUIRE((long)height * width < (1L << 24), "render_views: layers of more than 2^24 texels (24-bit texel offsets)");
+  const long lim = (1L << 31) - 8;
+  long nblk = (long)((out_width + 63) / 64) * out_height;     // (each factor < 2^31: checked before every product)
+  MSI_REQUIRE(nblk < lim, "render_views: too many target pixels for one launch");
+  nblk *= views;
+  MSI_REQUIRE(nblk < lim, "render_views: too many target pixels for one launch");
+  nblk *= batch;
+  MSI_REQUIRE(nblk < lim, "render_views: too many target pixels for one launch");
+  if (batch == 0) return MSI_OK;
+  const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(64, RENDER_SEGS);
+  const PixConsts K = make_consts(height, width);
+  DepthFrac F;
+  for (int d = 0; d < DEPTH_FRAC_MAX; ++d) F.f[d] = d < num_planes ? (float)((double)d / (double)num_planes) : 0.0f;
+  const int mode = (out_rgb ? RENDER_RGB : 0) | (out_depth ? RENDER_DEPTH : 0);
+  hipStream_t s = msi::as_stream(stream);
+#define MSI_LAUNCH_VIEWS(M, CAM)                                                                                        \
+  hipLaunchKernelGGL((render_views_kernel<M, CAM>), grid, block, 0, s, reinterpret_cast<const float4 *>(rgba_native), \
+                     tgt_pose_rt, tgt_pos, intrinsics, depths, trig, batch, views, height, width, num_planes,         \
+                     out_height, out_width, out_rgb, out_depth, K, F, status_device)
+#define MSI_LAUNCH_VIEWS_M(CAM)                                                     \
+  switch (mode) {                                                                   \
+    case RENDER_RGB: MSI_LAUNCH_VIEWS(RENDER_RGB, CAM); break;                      \
+    case RENDER_DEPTH: MSI_LAUNCH_VIEWS(RENDER_DEPTH, CAM); break;                  \
+    default: MSI_LAUNCH_VIEWS(RENDER_RGB | RENDER_DEPTH, CAM); break;               \
+  }
+  if (camera == MSI_CAMERA_PINHOLE) {
+    MSI_LAUNCH_VIEWS_M(MSI_CAMERA_PINHOLE)
+  } else {
+    MSI_LAUNCH_VIEWS_M(MSI_CAMERA_EQUIRECT)
+  }
+#undef MSI_LAUNCH_VIEWS_M
+#undef MSI_LAUNCH_VIEWS
+  return msi::check_launch("render_views");
 }
 
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

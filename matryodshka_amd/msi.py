@@ -567,6 +567,66 @@ class MSI(object):
                 "msi_render_perspective_f32")
         return out
 
+    # ------------------------------------------------------------------ viewer: many views of one MSI per launch
+    CAMERAS = {'equirect': N.MSI_CAMERA_EQUIRECT, 'pinhole': N.MSI_CAMERA_PINHOLE}
+
+    def render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes, camera='equirect', intrinsics=None, size=None,
+                     want_rgb=True, want_depth=True):
+        """V views of each MSI in ONE launch (msi_render_views_f32; no reference counterpart) -> (rgb, depth):
+        rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w] (one channel: msi_render_equirect_depth(...)[..., 0]); either is None
+        when switched off.
+
+        rgba_layers [B,H,W,D,4] (a permuted view of the native [B,D,H,W,4] stack goes through without a copy);
+        tgt_pose_rt [B,V,4,4], tgt_pos [B,V,3] ([V,4,4] / [V,3] when B = 1).  Each view has the meaning of the pair of
+        msi_render_equirect_view: the ray direction is rotated by pose[:3,:3], the ray origin is
+        pose @ (tgt_pos[2], tgt_pos[1], tgt_pos[0], 1), and view v of sample b samples stack b only.
+        size = (h, w), shared by every view: default (H, W) for 'equirect', required for 'pinhole'.
+          'equirect': pixel (i, j) takes its ray from the lat-long grid of the OUTPUT size (at (H, W) each view is
+                      bit-identical to msi_render_equirect_view_and_depth with its pose).
+          'pinhole':  intrinsics [B,V,3,3] or one [3,3] for every view, in pixels (fx, fy, cx, cy); pixel (i, j) looks
+                      along (1, (i + 0.5 - cy) / fy, (j + 0.5 - cx) / fx) before the pose: forward +x, image-down +y,
+                      image-right +z -- with an identity pose the centre pixel looks where the centre of an equirect
+                      render looks, with the same orientation.
+        Host-side poses and positions are checked for every view before the launch (ValueError when an origin is not
+        inside the innermost sphere); device-side ones are flagged through render_status()."""
+        if camera not in self.CAMERAS:
+            raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
+        if not (want_rgb or want_depth):
+            raise ValueError("render_views: want_rgb and want_depth are both False")
+        native = self._native_layers(rgba_layers)
+        b, d, h, w, _ = native.shape
+        self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
+        pose, pos = self._f32(tgt_pose_rt), self._f32(tgt_pos)
+        if b == 1 and pose.dim() == 3 and pos.dim() == 2:
+            pose, pos = pose[None], pos[None]
+        if pose.dim() != 4 or pose.shape[0] != b or tuple(pose.shape[2:]) != (4, 4):
+            raise ValueError("tgt_pose_rt must be [B,V,4,4] with B = %d (or [V,4,4] for B = 1), got %s" % (b, tuple(pose.shape)))
+        v = pose.shape[1]
+        if tuple(pos.shape) != (b, v, 3):
+            raise ValueError("tgt_pos must be [B,V,3] = %s, got %s" % ((b, v, 3), tuple(pos.shape)))
+        depths = self._planes(planes)
+        if depths.numel() != d:
+            raise ValueError("len(planes) != number of layers")
+        intr, trig = None, None
+        if camera == 'equirect':
+            oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
+            trig = self._trig(oh, ow)
+        else:
+            if size is None or intrinsics is None:
+                raise ValueError("camera='pinhole' needs size=(h, w) and intrinsics")
+            oh, ow = int(size[0]), int(size[1])
+            intr = self._f32(intrinsics).reshape(-1, 3, 3)
+            if intr.shape[0] == 1:
+                intr = intr.expand(b * v, 3, 3).contiguous()
+            if intr.shape[0] != b * v:
+                raise ValueError("intrinsics must be [B,V,3,3] or [3,3]")
+        rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
+        dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
+        N.check(N.lib.msi_render_views_f32(native.data_ptr(), pose.data_ptr(), pos.data_ptr(), _ptr(intr), depths.data_ptr(),
+                                           _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep),
+                                           self._render_status.data_ptr(), self._stream()), "msi_render_views_f32")
+        return rgb, dep
+
     # ------------------------------------------------------------------ test.py:283-394
     def msi_render_equirect_hres(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image,
                                  ref_pose, src_pose, tgt_pose_rt, tgt_pos, planes, intrinsics,
