@@ -227,6 +227,38 @@ int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, con
                          int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
                          int32_t camera, int32_t out_height, int32_t out_width,
                          float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
+
+/* Compact layer stacks (MSI.pack_layers / unpack_layers / render_views on a PackedLayers; no reference counterpart beyond
+ * test.py:271-276, which stores an MSI as 8-bit colour and alpha PNGs -- the 256 levels of MSI_LAYERS_RGBA8).  The layout
+ * is the native one, [B,D,H,W] texels, with a smaller texel:
+ *   MSI_LAYERS_F32      16 bytes: four floats (rgba_native itself; not a format of pack / unpack)
+ *   MSI_LAYERS_RGBA8     4 bytes: r, g, b, a in this byte order.  fp32 arithmetic, one rounding per operation, no fused
+ *                        multiply-add; rint = round half to even:
+ *                          encode colour  q = rint((min(max(x, -1), 1) + 1) * 127.5)
+ *                          encode alpha   q = rint(min(max(x, 0), 1) * 255)
+ *                          decode colour  x = (float(q) - 127.5) * kc,  kc = fl32(1 / 127.5) = 0x1.010102p-7
+ *                          decode alpha   x = float(q) * ka,            ka = fl32(1 / 255)   = 0x1.010102p-8
+ *                        Codes 0 / 255 decode to exactly -1 / +1 (colour) and 0 / 1 (alpha); decode(255 - q) = -decode(q)
+ *                        for colour; both tables increase strictly and encode(decode(q)) = q.  Round-trip error <= half a
+ *                        step: 1/255 (colour), 1/510 (alpha).  A NaN input is outside the contract: it does not fault and
+ *                        encodes as code 0 (max / min return their other operand).
+ *   MSI_LAYERS_RGBA16F   8 bytes: four IEEE halves, r, g, b, a.  Encode = round-to-nearest-even of the fp32 value, no
+ *                        clamp; decode is exact.
+ * msi_pack_layers / msi_unpack_layers convert `texels` (= B*D*H*W) texels between rgba_native and `packed`; the two buffers
+ * must not overlap and are 16-byte aligned.  msi_render_views_packed is msi_render_views_f32 reading a stack of `format`
+ * (MSI_LAYERS_F32 forwards to msi_render_views_f32): every tap is decoded by the rule above and composited with the fp32
+ * kernel's arithmetic, so the outputs are bit-identical to msi_render_views_f32 on the msi_unpack_layers of the stack.
+ * texels = 0 and batch = 0 return MSI_OK without a launch. */
+#define MSI_LAYERS_F32 0
+#define MSI_LAYERS_RGBA8 1
+#define MSI_LAYERS_RGBA16F 2
+int msi_pack_layers(const float *rgba_native, int32_t format, void *packed, int64_t texels, msi_stream_t stream);
+int msi_unpack_layers(const void *packed, int32_t format, float *rgba_native, int64_t texels, msi_stream_t stream);
+int msi_render_views_packed(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                            const float *intrinsics, const float *depths, const float *trig,
+                            int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                            int32_t camera, int32_t out_height, int32_t out_width,
+                            float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "MSI":
         from .msi import MSI
         return MSI
+    if name == "PackedLayers":      # (packed.py does not load the library: a saved stack can be read on a host without a GPU)
+        from .packed import PackedLayers
+        return PackedLayers
     raise AttributeError(name)

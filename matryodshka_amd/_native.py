@@ -15,7 +15,8 @@ MSI_OK = 0
 MSI_NET_NUM_LAYERS = 18
 RENDER_STATUS_ORIGIN_OUTSIDE = 1
 MSI_CAMERA_EQUIRECT, MSI_CAMERA_PINHOLE = 0, 1   # msi_render_views_f32's camera models
-MSI_ABI_VERSION = 9          # include/msi_hip.h: the version this binding's struct layouts and signatures are written for
+MSI_LAYERS_F32, MSI_LAYERS_RGBA8, MSI_LAYERS_RGBA16F = 0, 1, 2   # texel formats of msi_pack_layers / msi_render_views_packed
+MSI_ABI_VERSION = 9         # include/msi_hip.h: the version this binding's struct layouts and signatures are written for
 
 
 class MsiError(RuntimeError):
@@ -76,6 +77,9 @@ SIGNATURES = {
     "msi_assemble_rgba_scaled_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "msi_render_equirect_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_render_views_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "msi_pack_layers": (_I, [_P, _I, _P, ctypes.c_int64, _P]),
+    "msi_unpack_layers": (_I, [_P, _I, _P, ctypes.c_int64, _P]),
+    "msi_render_views_packed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_project_layers_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msi_render_ods_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_render_perspective_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),

@@ -1402,6 +1402,258 @@ render_views_kernel(const float4 *__restrict__ rgba, const float *__restrict__ p
   if (MODE & RENDER_DEPTH) out_depth[pix] = od;
 }
 
+// K4 from a compact stack (msi_render_views_packed; the formats and their exact rule are in msi_hip.h): a sibling of
+// render_views_kernel with the texel format of the stack as FMT (MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F; the fp32 kernel above
+// stays as it is, instruction for instruction).  A tap is ONE 4-byte (rgba8: buffer_load_dword) or 8-byte (rgba16f:
+// buffer_load_dwordx2) load through the same per-layer descriptor, with layer_bytes and the texel shift scaled to the format,
+// decoded to the four fp32 values msi_unpack_layers writes for that texel (rgba8: 11 VALU per tap -- four v_cvt_f32_ubyte, three
+// subtracts, four multiplies; rgba16f: four v_cvt_f32_f16).  Everything after the decode is render_views_kernel's arithmetic,
+// op for op, so a render from a packed stack is bit-identical to msi_render_views_f32 on the unpacked one.
+constexpr float RGBA8_KC = 0x1.010102p-7f;   // fl32(1 / 127.5)
+constexpr float RGBA8_KA = 0x1.010102p-8f;   // fl32(1 / 255)
+typedef _Float16 half4_g __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2_g __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float4 rgba8_decode(unsigned q) {   // (the byte picks compile to v_cvt_f32_ubyte0..3)
+  float4 t;
+  t.x = ((float)(q & 0xffu) - 127.5f) * RGBA8_KC;
+  t.y = ((float)((q >> 8) & 0xffu) - 127.5f) * RGBA8_KC;
+  t.z = ((float)((q >> 16) & 0xffu) - 127.5f) * RGBA8_KC;
+  t.w = (float)(q >> 24) * RGBA8_KA;
+  return t;
+}
+
+__device__ __forceinline__ float4 rgba16f_decode(u32x2_g q) {
+  const half4_g h = __builtin_bit_cast(half4_g, q);
+  float4 t;
+  t.x = (float)h.x; t.y = (float)h.y; t.z = (float)h.z; t.w = (float)h.w;
+  return t;
+}
+
+template <int FMT> struct TexelShift {   // log2 of the bytes per texel
+  static_assert(FMT == MSI_LAYERS_RGBA8 || FMT == MSI_LAYERS_RGBA16F, "a packed texel format");
+  static constexpr int value = FMT == MSI_LAYERS_RGBA8 ? 2 : 3;
+};
+
+// layer_rsrc / layer_tap for a packed stack
+template <int FMT>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t packed_layer_rsrc(const void *layers, int b, int nd, int d, size_t hw, int layer_bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + ((((size_t)b * nd + d) * hw) << TexelShift<FMT>::value)),
+                                           0, layer_bytes, 0x00020000);
+}
+
+template <int FMT>
+__device__ __forceinline__ float4 packed_layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
+  if constexpr (FMT == MSI_LAYERS_RGBA8)
+    return rgba8_decode(__builtin_amdgcn_raw_buffer_load_b32(L, texel << 2, 0, 0));
+  else
+    return rgba16f_decode((u32x2_g)__builtin_amdgcn_raw_buffer_load_b64(L, texel << 3, 0, 0));
+}
+
+template <int MODE, int CAMERA, int FMT>
+__global__ void __launch_bounds__(256)
+render_views_packed_kernel(const void *__restrict__ layers, const float *__restrict__ pose_rt, const float *__restrict__ tgt_pos,
+                           const float *__restrict__ intrinsics, const float *__restrict__ depths, const float *__restrict__ trig,
+                           int batch, int views, int height, int width, int nd, int out_h, int out_w, float *__restrict__ out_rgb,
+                           float *__restrict__ out_depth, PixConsts K, DepthFrac F, int *__restrict__ status) {
+  const unsigned gx = (unsigned)(out_w + 63) >> 6;
+  const unsigned nblk = gx * (unsigned)out_h * (unsigned)views * (unsigned)batch, per = gridDim.x >> 3;
+  const unsigned lin = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+  if (lin >= nblk) return;
+  const unsigned rowb = lin / gx;
+  const int j_raw = (int)(lin - rowb * gx) * 64 + threadIdx.x;
+  const unsigned bv = rowb / (unsigned)out_h;           // sample * views + view
+  const int i = (int)(rowb - bv * (unsigned)out_h);
+  const int b = (int)(bv / (unsigned)views);
+  const int seg = __builtin_amdgcn_readfirstlane(threadIdx.y);
+  const bool valid = j_raw < out_w;
+  const int j = valid ? j_raw : out_w - 1;
+  __shared__ float s_part[RENDER_SEGS][64][5];
+
+  float rx, ry, rz;
+  if (CAMERA == MSI_CAMERA_PINHOLE) {
+    const float *Kv = intrinsics + (size_t)bv * 9;      // fx . cx / . fy cy
+    rx = 1.0f;
+    ry = (((float)i + 0.5f) - Kv[5]) / Kv[4];            // (IEEE divides: per pixel, not per layer)
+    rz = (((float)j + 0.5f) - Kv[2]) / Kv[0];
+  } else {
+    const float cs = trig[j], ss = trig[out_w + j];
+    const float ct = trig[2 * out_w + i], st = trig[2 * out_w + out_h + i];
+    rx = cs * ct; ry = st; rz = ss * ct;
+  }
+  const float *tp = tgt_pos + (size_t)bv * 3;
+  float cx = tp[2], cy = tp[1], cz = tp[0];
+  const float *P = pose_rt + (size_t)bv * 16;
+  {
+    const float x = (P[0] * rx + P[1] * ry) + P[2] * rz;
+    const float y = (P[4] * rx + P[5] * ry) + P[6] * rz;
+    const float z = (P[8] * rx + P[9] * ry) + P[10] * rz;
+    rx = x; ry = y; rz = z;
+  }
+  {
+    const float x = ((P[0] * cx + P[1] * cy) + P[2] * cz) + P[3] * 1.0f;
+    const float y = ((P[4] * cx + P[5] * cy) + P[6] * cz) + P[7] * 1.0f;
+    const float z = ((P[8] * cx + P[9] * cy) + P[10] * cz) + P[11] * 1.0f;
+    cx = x; cy = y; cz = z;
+  }
+  const float qa = (rx * rx + ry * ry) + rz * rz;
+  const float qb = 2.0f * ((rx * cx + ry * cy) + rz * cz);
+  const float cc = (cx * cx + cy * cy) + cz * cz;
+  const float qb2 = qb * qb;
+  const float fa = 4.0f * qa, ta = 2.0f * qa;
+  const float inv_ta = __builtin_amdgcn_rcpf(ta);
+
+  const size_t hw = (size_t)height * width;
+  const int layer_bytes = (int)(hw << TexelShift<FMT>::value);
+  const size_t pix = (size_t)bv * out_h * out_w + (size_t)i * out_w + j;
+  float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f, tr = 1.f;
+  float qc_max = -1.0f;
+  const int d_lo = (seg * nd) / RENDER_SEGS, d_hi = ((seg + 1) * nd) / RENDER_SEGS;
+
+#pragma unroll 4
+  for (int d = d_lo; d < d_hi; ++d) {
+    const float radius = depths[d];
+    const float qc = cc - radius * radius;
+    qc_max = fmaxf(qc_max, qc);
+    const float disc = qb2 - fa * qc;
+#if MSI_FAST_TAIL
+    const float num = t_sqrt(fmaxf(disc, 0.0f)) - qb;
+    const float tq = num * inv_ta;
+    const float t = __builtin_fmaf(__builtin_fmaf(-tq, ta, num), inv_ta, tq);
+#else
+    const float t = t_div(-qb + t_sqrt(fmaxf(disc, 0.0f)), ta);
+#endif
+    const float x = cx + t * rx;
+    const float y = cy + t * ry;
+    const float z = cz + t * rz;
+    float theta, phi;
+    t_angles(x, y, z, radius, theta, phi);
+#if MSI_FAST_TAIL
+    const float u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
+    const float v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
+#else
+    const float u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
+    const float v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
+#endif
+    const TapsR tp4 = make_taps_ranged(u, v, width, height);
+    const __amdgpu_buffer_rsrc_t L = packed_layer_rsrc<FMT>(layers, b, nd, d, hw, layer_bytes);
+    const float4 A = packed_layer_tap<FMT>(L, tp4.oa), Bv = packed_layer_tap<FMT>(L, tp4.ob), C = packed_layer_tap<FMT>(L, tp4.oc), Dv = packed_layer_tap<FMT>(L, tp4.od);
+    const float al = blend4(tp4, A.w, Bv.w, C.w, Dv.w);
+    if (MODE & RENDER_RGB) {
+      const float r = blend4(tp4, A.x, Bv.x, C.x, Dv.x);
+      const float g = blend4(tp4, A.y, Bv.y, C.y, Dv.y);
+      const float bl = blend4(tp4, A.z, Bv.z, C.z, Dv.z);
+      if (d == 0) {
+        o0 = r; o1 = g; o2 = bl;
+      } else {
+        const float om = 1.0f - al;
+        o0 = r * al + o0 * om;
+        o1 = g * al + o1 * om;
+        o2 = bl * al + o2 * om;
+      }
+    }
+    if (MODE & RENDER_DEPTH) {
+      if (d == 0) {
+        od = 0.0f;
+      } else {
+        const float frac = nd <= DEPTH_FRAC_MAX ? F.f[d] : (float)((double)d / (double)nd);
+        od = frac * al + od * (1.0f - al);
+      }
+    }
+    tr = tr * (1.0f - al);
+  }
+  // (as render_kernel: the origin of this view is not inside every sphere, or is NaN)
+  if (status != nullptr && threadIdx.x == 0 && (!(qc_max < 0.0f) || cc != cc)) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+  s_part[seg][threadIdx.x][0] = o0; s_part[seg][threadIdx.x][1] = o1; s_part[seg][threadIdx.x][2] = o2;
+  s_part[seg][threadIdx.x][3] = od; s_part[seg][threadIdx.x][4] = tr;
+  __syncthreads();
+  if (seg != 0 || !valid) return;
+#pragma unroll
+  for (int sg = 1; sg < RENDER_SEGS; ++sg) {    // back to front: segment 0 holds the farthest layers
+    const float *q = s_part[sg][threadIdx.x];
+    o0 = q[0] + q[4] * o0; o1 = q[1] + q[4] * o1; o2 = q[2] + q[4] * o2;
+    od = q[3] + q[4] * od;
+  }
+  // (a wave's 64 pixels are one contiguous 768-byte rgb run and one 256-byte depth run)
+  if (MODE & RENDER_RGB) {
+    float *o = out_rgb + pix * 3;
+    o[0] = o0; o[1] = o1; o[2] = o2;
+  }
+  if (MODE & RENDER_DEPTH) out_depth[pix] = od;
+}
+
+// msi_pack_layers / msi_unpack_layers: streaming conversions of the native stack, 16-byte loads and stores on both sides.  One
+// thread takes the texels of one 16-byte piece of the packed stack -- four rgba8 texels (four float4 loads, one store) or two
+// rgba16f texels -- and the < 4 texels that do not fill a piece go one at a time through the first threads of the grid.
+// NT = 1 (the host picks it when the destination is larger than the 256-MiB Infinity Cache): non-temporal stores, as in the sweep
+// (a template argument: behind a runtime flag hipcc merges the two stores into one plain store).
+// NaN inputs of the rgba8 encoder (outside the contract): fmaxf returns its other operand, so a NaN channel encodes as code 0.
+__device__ __forceinline__ unsigned rgba8_encode(const float4 &t) {
+  const unsigned r = (unsigned)rintf((fminf(fmaxf(t.x, -1.0f), 1.0f) + 1.0f) * 127.5f);
+  const unsigned g = (unsigned)rintf((fminf(fmaxf(t.y, -1.0f), 1.0f) + 1.0f) * 127.5f);
+  const unsigned b = (unsigned)rintf((fminf(fmaxf(t.z, -1.0f), 1.0f) + 1.0f) * 127.5f);
+  const unsigned a = (unsigned)rintf(fminf(fmaxf(t.w, 0.0f), 1.0f) * 255.0f);
+  return r | (g << 8) | (b << 16) | (a << 24);
+}
+
+__device__ __forceinline__ u32x2_g rgba16f_encode(const float4 &t) {
+  half4_g h;
+  h.x = (_Float16)t.x; h.y = (_Float16)t.y; h.z = (_Float16)t.z; h.w = (_Float16)t.w;
+  return __builtin_bit_cast(u32x2_g, h);
+}
+
+template <int FMT, int NT>
+__global__ void __launch_bounds__(256)
+pack_layers_kernel(const float4 *__restrict__ in, void *__restrict__ out, size_t texels) {
+  constexpr int TPP = FMT == MSI_LAYERS_RGBA8 ? 4 : 2;   // texels per 16-byte piece
+  const size_t pieces = texels / TPP;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t p = tid; p < pieces; p += stride) {
+    float4 t[TPP];
+#pragma unroll
+    for (int k = 0; k < TPP; ++k) t[k] = in[p * TPP + k];
+    uint4 v;
+    if constexpr (FMT == MSI_LAYERS_RGBA8) {
+      v.x = rgba8_encode(t[0]); v.y = rgba8_encode(t[1]); v.z = rgba8_encode(t[2]); v.w = rgba8_encode(t[3]);
+    } else {
+      const u32x2_g lo = rgba16f_encode(t[0]), hi = rgba16f_encode(t[1]);
+      v.x = lo.x; v.y = lo.y; v.z = hi.x; v.w = hi.y;
+    }
+    sweep_store16(static_cast<uint4 *>(out) + p, v, NT);
+  }
+  const size_t tail = pieces * TPP + tid;
+  if (tid < (size_t)TPP && tail < texels) {
+    if (FMT == MSI_LAYERS_RGBA8) static_cast<unsigned *>(out)[tail] = rgba8_encode(in[tail]);
+    else static_cast<u32x2_g *>(out)[tail] = rgba16f_encode(in[tail]);
+  }
+}
+
+template <int FMT, int NT>
+__global__ void __launch_bounds__(256)
+unpack_layers_kernel(const void *__restrict__ in, float4 *__restrict__ out, size_t texels) {
+  constexpr int TPP = FMT == MSI_LAYERS_RGBA8 ? 4 : 2;
+  const size_t pieces = texels / TPP;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t p = tid; p < pieces; p += stride) {
+    const uint4 v = static_cast<const uint4 *>(in)[p];
+    float4 t[TPP];
+    if constexpr (FMT == MSI_LAYERS_RGBA8) {
+      t[0] = rgba8_decode(v.x); t[1] = rgba8_decode(v.y); t[2] = rgba8_decode(v.z); t[3] = rgba8_decode(v.w);
+    } else {
+      u32x2_g lo, hi;
+      lo.x = v.x; lo.y = v.y; hi.x = v.z; hi.y = v.w;
+      t[0] = rgba16f_decode(lo); t[1] = rgba16f_decode(hi);
+    }
+#pragma unroll
+    for (int k = 0; k < TPP; ++k) sweep_store16(reinterpret_cast<uint4 *>(out + p * TPP + k), __builtin_bit_cast(uint4, t[k]), NT);
+  }
+  const size_t tail = pieces * TPP + tid;
+  if (tid < (size_t)TPP && tail < texels) {
+    if (FMT == MSI_LAYERS_RGBA8) out[tail] = rgba8_decode(static_cast<const unsigned *>(in)[tail]);
+    else out[tail] = rgba16f_decode(static_cast<const u32x2_g *>(in)[tail]);
+  }
+}
+
 // tf.image.resize(..., BILINEAR, align_corners=True) [TF-knowledge: resize_bilinear_op]:
 // src = dst * (in-1)/(out-1); lower = floor(src), upper = min(ceil(src), in-1), lerp = src - lower;
 // top = tl + (tr - tl)*xl; bottom = bl + (br - bl)*xl; out = top + (bottom - top)*yl.
@@ -2100,28 +2352,30 @@ int msi_render_equirect_f32(const float *rgba_native, const float *tgt_pose_rt,
                        width, num_planes, same_size(height, width), out_rgb, out_depth, nullptr, status_device, stream);
 }
 
-int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, const float *tgt_pos,
-                         const float *intrinsics, const float *depths, const float *trig,
-                         int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
-                         int32_t camera, int32_t out_height, int32_t out_width,
-                         float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream) {
-  MSI_REQUIRE(out_rgb || out_depth, "render_views: both outputs are NULL");
-  MSI_REQUIRE(rgba_native && tgt_pose_rt && tgt_pos && depths, "render_views: null pointer");
-  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || camera == MSI_CAMERA_PINHOLE, "render_views: unknown camera %d", camera);
-  MSI_REQUIRE(camera != MSI_CAMERA_EQUIRECT || trig, "render_views: null pointer (equirect camera needs trig)");
-  MSI_REQUIRE(camera != MSI_CAMERA_PINHOLE || intrinsics, "render_views: null pointer (pinhole camera needs intrinsics)");
-  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "render_views: bad dims");
-  MSI_REQUIRE(views >= 1, "render_views: views must be >= 1 (got %d)", views);
+// msi_render_views_f32 and msi_render_views_packed: one set of checks and one launch table (`who` names the entry point in the
+// error text; `format` is one of MSI_LAYERS_*, already validated by the caller).
+static int render_views_launch(const char *who, const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                               const float *intrinsics, const float *depths, const float *trig,
+                               int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                               int32_t camera, int32_t out_height, int32_t out_width,
+                               float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream) {
+  MSI_REQUIRE(out_rgb || out_depth, "%s: both outputs are NULL", who);
+  MSI_REQUIRE(layers && tgt_pose_rt && tgt_pos && depths, "%s: null pointer", who);
+  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || camera == MSI_CAMERA_PINHOLE, "%s: unknown camera %d", who, camera);
+  MSI_REQUIRE(camera != MSI_CAMERA_EQUIRECT || trig, "%s: null pointer (equirect camera needs trig)", who);
+  MSI_REQUIRE(camera != MSI_CAMERA_PINHOLE || intrinsics, "%s: null pointer (pinhole camera needs intrinsics)", who);
+  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "%s: bad dims", who);
+  MSI_REQUIRE(views >= 1, "%s: views must be >= 1 (got %d)", who, views);
   const int min_out = camera == MSI_CAMERA_PINHOLE ? 2 : 1;
-  MSI_REQUIRE(out_height >= min_out && out_width >= min_out, "render_views: bad output size %d x %d", out_height, out_width);
-  MSI_REQUIRE((long)height * width < (1L << 24), "render_views: layers of more than 2^24 texels (24-bit texel offsets)");
+  MSI_REQUIRE(out_height >= min_out && out_width >= min_out, "%s: bad output size %d x %d", who, out_height, out_width);
+  MSI_REQUIRE((long)height * width < (1L << 24), "%s: layers of more than 2^24 texels (24-bit texel offsets)", who);
   const long lim = (1L << 31) - 8;
   long nblk = (long)((out_width + 63) / 64) * out_height;     // (each factor < 2^31: checked before every product)
-  MSI_REQUIRE(nblk < lim, "render_views: too many target pixels for one launch");
+  MSI_REQUIRE(nblk < lim, "%s: too many target pixels for one launch", who);
   nblk *= views;
-  MSI_REQUIRE(nblk < lim, "render_views: too many target pixels for one launch");
+  MSI_REQUIRE(nblk < lim, "%s: too many target pixels for one launch", who);
   nblk *= batch;
-  MSI_REQUIRE(nblk < lim, "render_views: too many target pixels for one launch");
+  MSI_REQUIRE(nblk < lim, "%s: too many target pixels for one launch", who);
   if (batch == 0) return MSI_OK;
   const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(64, RENDER_SEGS);
   const PixConsts K = make_consts(height, width);
@@ -2129,10 +2383,17 @@ int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, con
   for (int d = 0; d < DEPTH_FRAC_MAX; ++d) F.f[d] = d < num_planes ? (float)((double)d / (double)num_planes) : 0.0f;
   const int mode = (out_rgb ? RENDER_RGB : 0) | (out_depth ? RENDER_DEPTH : 0);
   hipStream_t s = msi::as_stream(stream);
-#define MSI_LAUNCH_VIEWS(M, CAM)                                                                                        \
-  hipLaunchKernelGGL((render_views_kernel<M, CAM>), grid, block, 0, s, reinterpret_cast<const float4 *>(rgba_native), \
-                     tgt_pose_rt, tgt_pos, intrinsics, depths, trig, batch, views, height, width, num_planes,         \
-                     out_height, out_width, out_rgb, out_depth, K, F, status_device)
+#define MSI_VIEWS_ARGS tgt_pose_rt, tgt_pos, intrinsics, depths, trig, batch, views, height, width, num_planes, out_height, out_width, \
+                       out_rgb, out_depth, K, F, status_device
+#define MSI_LAUNCH_VIEWS(M, CAM)                                                                                                        \
+  switch (format) {                                                                                                                     \
+    case MSI_LAYERS_RGBA8:                                                                                                              \
+      hipLaunchKernelGGL((render_views_packed_kernel<M, CAM, MSI_LAYERS_RGBA8>), grid, block, 0, s, layers, MSI_VIEWS_ARGS); break;     \
+    case MSI_LAYERS_RGBA16F:                                                                                                            \
+      hipLaunchKernelGGL((render_views_packed_kernel<M, CAM, MSI_LAYERS_RGBA16F>), grid, block, 0, s, layers, MSI_VIEWS_ARGS); break;   \
+    default:                                                                                                                            \
+      hipLaunchKernelGGL((render_views_kernel<M, CAM>), grid, block, 0, s, static_cast<const float4 *>(layers), MSI_VIEWS_ARGS); break; \
+  }
 #define MSI_LAUNCH_VIEWS_M(CAM)                                                     \
   switch (mode) {                                                                   \
     case RENDER_RGB: MSI_LAUNCH_VIEWS(RENDER_RGB, CAM); break;                      \
@@ -2146,7 +2407,74 @@ int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, con
   }
 #undef MSI_LAUNCH_VIEWS_M
 #undef MSI_LAUNCH_VIEWS
-  return msi::check_launch("render_views");
+#undef MSI_VIEWS_ARGS
+  return msi::check_launch(who);
+}
+
+int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, const float *tgt_pos,
+                         const float *intrinsics, const float *depths, const float *trig,
+                         int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                         int32_t camera, int32_t out_height, int32_t out_width,
+                         float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream) {
+  return render_views_launch("render_views", rgba_native, MSI_LAYERS_F32, tgt_pose_rt, tgt_pos, intrinsics, depths, trig, batch, views,
+                             height, width, num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
+}
+
+int msi_render_views_packed(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                            const float *intrinsics, const float *depths, const float *trig,
+                            int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                            int32_t camera, int32_t out_height, int32_t out_width,
+                            float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream) {
+  MSI_REQUIRE(format == MSI_LAYERS_F32 || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F,
+              "render_views_packed: unknown format %d", format);
+  return render_views_launch("render_views_packed", layers, format, tgt_pose_rt, tgt_pos, intrinsics, depths, trig, batch, views,
+                             height, width, num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
+}
+
+// grid of the pack / unpack kernels: one thread per 16-byte piece of the packed stack (grid-stride beyond 2^20 workgroups)
+static unsigned pack_grid(int64_t texels, int per_piece) {
+  const int64_t pieces = texels / per_piece, blocks = (pieces + 255) / 256;
+  return (unsigned)(blocks < 1 ? 1 : blocks > (1 << 20) ? (1 << 20) : blocks);
+}
+
+int msi_pack_layers(const float *rgba_native, int32_t format, void *packed, int64_t texels, msi_stream_t stream) {
+  MSI_REQUIRE(rgba_native && packed, "pack_layers: null pointer");
+  MSI_REQUIRE(format != MSI_LAYERS_F32, "pack_layers: MSI_LAYERS_F32 is the unpacked format (nothing to pack)");
+  MSI_REQUIRE(format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F, "pack_layers: unknown format %d", format);
+  MSI_REQUIRE(texels >= 0, "pack_layers: negative texel count");
+  if (texels == 0) return MSI_OK;
+  const float4 *in = reinterpret_cast<const float4 *>(rgba_native);
+  hipStream_t s = msi::as_stream(stream);
+  const bool nt = (size_t)texels * (format == MSI_LAYERS_RGBA8 ? 4 : 8) > ((size_t)256 << 20);
+#define MSI_LAUNCH_PACK(FMT, TPP, NT) \
+  hipLaunchKernelGGL((pack_layers_kernel<FMT, NT>), dim3(pack_grid(texels, TPP)), dim3(256), 0, s, in, packed, (size_t)texels)
+  if (format == MSI_LAYERS_RGBA8) {
+    if (nt) MSI_LAUNCH_PACK(MSI_LAYERS_RGBA8, 4, 1); else MSI_LAUNCH_PACK(MSI_LAYERS_RGBA8, 4, 0);
+  } else {
+    if (nt) MSI_LAUNCH_PACK(MSI_LAYERS_RGBA16F, 2, 1); else MSI_LAUNCH_PACK(MSI_LAYERS_RGBA16F, 2, 0);
+  }
+#undef MSI_LAUNCH_PACK
+  return msi::check_launch("pack_layers");
+}
+
+int msi_unpack_layers(const void *packed, int32_t format, float *rgba_native, int64_t texels, msi_stream_t stream) {
+  MSI_REQUIRE(rgba_native && packed, "unpack_layers: null pointer");
+  MSI_REQUIRE(format != MSI_LAYERS_F32, "unpack_layers: MSI_LAYERS_F32 is the unpacked format (nothing to unpack)");
+  MSI_REQUIRE(format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F, "unpack_layers: unknown format %d", format);
+  MSI_REQUIRE(texels >= 0, "unpack_layers: negative texel count");
+  if (texels == 0) return MSI_OK;
+  float4 *out = reinterpret_cast<float4 *>(rgba_native);
+  hipStream_t s = msi::as_stream(stream);
+  const bool nt = (size_t)texels * 16 > ((size_t)256 << 20);
+#define MSI_LAUNCH_UNPACK(FMT, TPP, NT) \
+  hipLaunchKernelGGL((unpack_layers_kernel<FMT, NT>), dim3(pack_grid(texels, TPP)), dim3(256), 0, s, packed, out, (size_t)texels)
+  if (format == MSI_LAYERS_RGBA8) {
+    if (nt) MSI_LAUNCH_UNPACK(MSI_LAYERS_RGBA8, 4, 1); else MSI_LAUNCH_UNPACK(MSI_LAYERS_RGBA8, 4, 0);
+  } else {
+    if (nt) MSI_LAUNCH_UNPACK(MSI_LAYERS_RGBA16F, 2, 1); else MSI_LAUNCH_UNPACK(MSI_LAYERS_RGBA16F, 2, 0);
+  }
+#undef MSI_LAUNCH_UNPACK
+  return msi::check_launch("unpack_layers");
 }
 
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

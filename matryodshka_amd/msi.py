@@ -20,6 +20,7 @@ import torch
 
 from . import _native as N
 from . import nets
+from .packed import FORMATS as PACKED_FORMATS, PackedLayers
 
 
 def _ptr(t):
@@ -428,6 +429,9 @@ class MSI(object):
 
     # ------------------------------------------------------------------ msi.py:384-452
     def _native_layers(self, rgba_layers):
+        if isinstance(rgba_layers, PackedLayers):
+            raise TypeError("this method reads fp32 layer stacks only: render a PackedLayers with render_views, or expand it "
+                            "with unpack_layers first")
         rgba_layers = rgba_layers.to(device=self.device, dtype=torch.float32) if torch.is_tensor(rgba_layers) \
             else self._f32(rgba_layers)
         if rgba_layers.dim() != 5 or rgba_layers.shape[-1] != 4:
@@ -570,7 +574,7 @@ class MSI(object):
     # ------------------------------------------------------------------ viewer: many views of one MSI per launch
     CAMERAS = {'equirect': N.MSI_CAMERA_EQUIRECT, 'pinhole': N.MSI_CAMERA_PINHOLE}
 
-    def render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes, camera='equirect', intrinsics=None, size=None,
+    def render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, camera='equirect', intrinsics=None, size=None,
                      want_rgb=True, want_depth=True):
         """V views of each MSI in ONE launch (msi_render_views_f32; no reference counterpart) -> (rgb, depth):
         rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w] (one channel: msi_render_equirect_depth(...)[..., 0]); either is None
@@ -588,12 +592,23 @@ class MSI(object):
                       image-right +z -- with an identity pose the centre pixel looks where the centre of an equirect
                       render looks, with the same orientation.
         Host-side poses and positions are checked for every view before the launch (ValueError when an origin is not
-        inside the innermost sphere); device-side ones are flagged through render_status()."""
+        inside the innermost sphere); device-side ones are flagged through render_status().
+        rgba_layers may be a PackedLayers (pack_layers; msi_render_views_packed): the kernel gathers from the compact stack
+        itself and the outputs are bit-identical to rendering unpack_layers(rgba_layers).  planes=None then takes the planes
+        the PackedLayers carries (ValueError when it carries none); for an fp32 stack planes is required."""
         if camera not in self.CAMERAS:
             raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
         if not (want_rgb or want_depth):
             raise ValueError("render_views: want_rgb and want_depth are both False")
-        native = self._native_layers(rgba_layers)
+        packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
+        if packed is not None:
+            native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
+            if planes is None:
+                planes = packed.planes
+        else:
+            native = self._native_layers(rgba_layers)
+        if planes is None:
+            raise ValueError("render_views: planes is required (only a PackedLayers that carries its planes may leave it out)")
         b, d, h, w, _ = native.shape
         self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
         pose, pos = self._f32(tgt_pose_rt), self._f32(tgt_pos)
@@ -622,10 +637,45 @@ class MSI(object):
                 raise ValueError("intrinsics must be [B,V,3,3] or [3,3]")
         rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
         dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
+        if packed is not None:
+            N.check(N.lib.msi_render_views_packed(native.data_ptr(), self.LAYER_FORMATS[packed.format], pose.data_ptr(), pos.data_ptr(),
+                                                  _ptr(intr), depths.data_ptr(), _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow,
+                                                  _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream()),
+                    "msi_render_views_packed")
+            return rgb, dep
         N.check(N.lib.msi_render_views_f32(native.data_ptr(), pose.data_ptr(), pos.data_ptr(), _ptr(intr), depths.data_ptr(),
                                            _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep),
                                            self._render_status.data_ptr(), self._stream()), "msi_render_views_f32")
         return rgb, dep
+
+    # ------------------------------------------------------------------ compact stacks (matryodshka_amd/packed.py)
+    LAYER_FORMATS = {'rgba8': N.MSI_LAYERS_RGBA8, 'rgba16f': N.MSI_LAYERS_RGBA16F}
+
+    def pack_layers(self, rgba_layers, format='rgba8', planes=None):
+        """fp32 stack [B,H,W,D,4] -> PackedLayers in `format` ('rgba8': 4 bytes per texel, 'rgba16f': 8; the rule is in
+        packed.py / msi_hip.h), one streaming kernel (msi_pack_layers).  A permuted view of the native [B,D,H,W,4] stack goes
+        through without a copy, as in render_views.  `planes`, when given, travel with the stack."""
+        if format not in PACKED_FORMATS:
+            raise ValueError("format must be one of %s, not %r" % (PACKED_FORMATS, format))
+        native = self._native_layers(rgba_layers)
+        b, d, h, w, _ = native.shape
+        if planes is not None and len(planes) != d:
+            raise ValueError("len(planes) != number of layers")
+        data = torch.empty((b, d, h, w, 4), dtype=torch.uint8 if format == 'rgba8' else torch.float16, device=self.device)
+        N.check(N.lib.msi_pack_layers(native.data_ptr(), self.LAYER_FORMATS[format], data.data_ptr(), b * d * h * w, self._stream()),
+                "msi_pack_layers")
+        return PackedLayers(data, format, planes)
+
+    def unpack_layers(self, packed):
+        """PackedLayers -> fp32 [B,H,W,D,4], a permuted view of a new native [B,D,H,W,4] stack (msi_unpack_layers)."""
+        if not isinstance(packed, PackedLayers):
+            raise TypeError("unpack_layers takes a PackedLayers")
+        data = packed.data if packed.data.device == self.device else packed.data.to(self.device)
+        b, d, h, w, _ = data.shape
+        native = torch.empty((b, d, h, w, 4), dtype=torch.float32, device=self.device)
+        N.check(N.lib.msi_unpack_layers(data.data_ptr(), self.LAYER_FORMATS[packed.format], native.data_ptr(), b * d * h * w,
+                                        self._stream()), "msi_unpack_layers")
+        return native.permute(0, 2, 3, 1, 4)
 
     # ------------------------------------------------------------------ test.py:283-394
     def msi_render_equirect_hres(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image,

@@ -8,10 +8,11 @@ from matryodshka_amd import isa_lint
 
 def snapshot(lib):
     out = {}
+    objdump = isa_lint.OBJDUMP or isa_lint._find_objdump()   # (the lint resolves it on its first use only)
     for triple, blob in isa_lint.code_objects(lib):
         with tempfile.NamedTemporaryFile(suffix=".hsaco") as f:
             f.write(blob); f.flush()
-            txt = subprocess.run([isa_lint.OBJDUMP, "-d", "--no-show-raw-insn", f.name], check=True, stdout=subprocess.PIPE).stdout.decode()
+            txt = subprocess.run([objdump, "-d", "--no-show-raw-insn", f.name], check=True, stdout=subprocess.PIPE).stdout.decode()
         cur = None
         for line in txt.splitlines():
             m = re.match(r"^[0-9a-f]+ <(.+)>:", line)
