@@ -487,6 +487,28 @@ int msi_net_plan_forward_rgba(const msi_net_plan *plan, const float *packed, con
                               float *blend_weights, float *alphas, float *pred, void *workspace, size_t workspace_bytes,
                               msi_stream_t stream, void *event_after_convs);
 
+/* msi_net_plan_forward_rgba with the layer stack emitted in a compact format (MSI_LAYERS_RGBA8 / MSI_LAYERS_RGBA16F, see
+ * msi_pack_layers) straight from the fused tail: the kernel encodes the fp32 texel it has just blended and stores 4 or 8
+ * bytes instead of 16, so a consumer that keeps, stores or renders packed stacks (msi_render_views_packed) never has an
+ * fp32 stack in memory and runs no msi_pack_layers pass.
+ *   layers_out   [B,D,H,W] texels of `format`, 16-byte aligned, or NULL.  `format` must be MSI_LAYERS_RGBA8 or
+ *                MSI_LAYERS_RGBA16F when layers_out is non-NULL and is ignored when it is NULL.
+ *   rgba_native  [B,D,H,W,4] fp32, or NULL.  At least one of rgba_native and layers_out is non-NULL; with both, ONE launch
+ *                writes both stacks.
+ *   every other argument as in msi_net_plan_forward_rgba.
+ * CONTRACT: layers_out is bit-identical to msi_pack_layers(format) applied to the rgba_native that
+ * msi_net_plan_forward_rgba writes for the same plan and input, for fp32 plans and for bf16 plans; rgba_native,
+ * blend_weights, alphas and pred, when requested, are bit-identical to msi_net_plan_forward_rgba's.
+ * Argument checks, in this order: unknown format with a non-NULL layers_out -> MSI_E_BADARG ("unknown format"); both
+ * outputs NULL -> MSI_E_BADARG ("null pointer") -- neither needs a plan or a device; then the checks of
+ * msi_net_plan_forward_rgba (NULL plan -> MSI_E_BADARG, MSI_E_UNSUPPORTED under exactly its conditions: assemble the fp32
+ * stack with msi_assemble_rgba_color_f32 and pack it with msi_pack_layers there).  Error texts name net_forward_layers.
+ * A plan of batch 0 returns MSI_OK without a launch.  With layers_out = NULL the call IS msi_net_plan_forward_rgba (the
+ * same kernel, head_assemble_kernel); with a layers_out the tail runs as head_assemble_packed_kernel<BF16, format>. */
+int msi_net_plan_forward_layers(const msi_net_plan *plan, const float *packed, const void *net_input, float *rgba_native,
+                                void *layers_out, int32_t format, float *blend_weights, float *alphas, float *pred,
+                                void *workspace, size_t workspace_bytes, msi_stream_t stream, void *event_after_convs);
+
 /* Descriptor-level convenience: the two calls below build a transient plan per call (set-up time, tests); the
  * frame loop uses msi_net_plan_forward.
  * net_input [B,H,W,in_channels] -> pred [B,H,W,num_outputs]. */

@@ -101,6 +101,7 @@ SIGNATURES = {
     "msi_net_plan_calibrate": (_I, [_P, _P, _P, _P, c_size_t, _P, POINTER(c_int32)]),
     "msi_net_plan_forward": (_I, [_P, _P, _P, _P, _P, c_size_t, _P]),
     "msi_net_plan_forward_rgba": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P, _P]),
+    "msi_net_plan_forward_layers": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, c_size_t, _P, _P]),
     "msi_net_forward_f32": (_I, [POINTER(NetDesc), _P, _P, _P, _P, c_size_t, _P]),
     "msi_net_forward_bf16": (_I, [POINTER(NetDesc), _P, _P, _P, _P, c_size_t, _P]),
 }

@@ -46,7 +46,8 @@ def _newer(target, deps):
 def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(INCLUDE, "msi_hip.h"), os.path.join(CSRC, "msi_common.h"), os.path.join(CSRC, "cnn_device.h"), __file__]
+    headers = [os.path.join(INCLUDE, "msi_hip.h"), os.path.join(CSRC, "msi_common.h"), os.path.join(CSRC, "cnn_device.h"),
+               os.path.join(CSRC, "cnn_tail_head_assemble.inc"), __file__]
     objs = []
     jobs = []
     for src, extra in SOURCES:

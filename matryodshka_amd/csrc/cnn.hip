@@ -1046,10 +1046,12 @@ int msi_net_plan_forward(const msi_net_plan *plan, const float *packed, const vo
   return run_layers(plan, packed, net_input, pred, workspace, workspace_bytes, stream_, MSI_NET_NUM_LAYERS);
 }
 
-int msi_net_plan_forward_rgba(const msi_net_plan *plan, const float *packed, const void *net_input, float *rgba_native,
-                              float *blend_weights, float *alphas, float *pred, void *workspace, size_t workspace_bytes,
-                              msi_stream_t stream_, void *event_after_convs) {
-  MSI_REQUIRE(plan, "net_forward_rgba: null plan");
+// The fused tail behind msi_net_plan_forward_rgba (format = MSI_LAYERS_F32, layers_out = null: head_assemble_kernel) and
+// msi_net_plan_forward_layers (a packed layers_out: head_assemble_packed_kernel, rgba_native optional); `who` names the caller in error texts.
+static int forward_fused_tail(const char *who, const msi_net_plan *plan, const float *packed, const void *net_input, float *rgba_native,
+                              void *layers_out, int32_t format, float *blend_weights, float *alphas, float *pred, void *workspace,
+                              size_t workspace_bytes, msi_stream_t stream_, void *event_after_convs) {
+  MSI_REQUIRE(plan, "%s: null plan", who);
   const msi_net_desc *desc = &plan->desc;
   const Net &net = plan->net;
   const Layer &H = net.layers[MSI_NET_NUM_LAYERS - 1];
@@ -1058,19 +1060,20 @@ int msi_net_plan_forward_rgba(const msi_net_plan *plan, const float *packed, con
   if ((!bf16 && !plan->launch[MSI_NET_NUM_LAYERS - 1].fuse_ln) || (bf16 && !plan->opt[MSI_NET_OPT_HEAD_FUSE_LN]) ||
       H.c0 > 64 || H.c0 % 4 != 0 || desc->num_outputs != 2 * nd || nd % 4 != 0 || nd > 64 || desc->in_channels != 6 * nd ||
       ((long)desc->height * desc->width) % HA_TP != 0)
-    return msi::fail(MSI_E_UNSUPPORTED, "net_forward_rgba: fused tail needs a blend_psv network (in = 6 D, out = 2 D, "
-                     "D %% 4 == 0, D <= 64, ngf <= 64, HEAD_FUSE_LN on)");
-  MSI_REQUIRE(rgba_native, "net_forward_rgba: null pointer");
+    return msi::fail(MSI_E_UNSUPPORTED, "%s: fused tail needs a blend_psv network (in = 6 D, out = 2 D, "
+                     "D %% 4 == 0, D <= 64, ngf <= 64, HEAD_FUSE_LN on)", who);
+  MSI_REQUIRE(rgba_native || layers_out, "%s: null pointer", who);
+  MSI_REQUIRE(!layers_out || (reinterpret_cast<uintptr_t>(layers_out) & 15) == 0, "%s: layers_out is not 16-byte aligned", who);
   const int ng = (nd + HA_LG - 1) / HA_LG;   // layer groups (grid.y of the fused tail): D = 64 -> 2 x 32 layers
   if (nd % ng != 0 || (nd / ng) % 4 != 0 || (ng > 1 && bf16 && (nd / ng) % 8 != 0))
-    return msi::fail(MSI_E_UNSUPPORTED, "net_forward_rgba: D = %d does not split into layer groups of a multiple of %d", nd, bf16 ? 8 : 4);
+    return msi::fail(MSI_E_UNSUPPORTED, "%s: D = %d does not split into layer groups of a multiple of %d", who, nd, bf16 ? 8 : 4);
   // (bf16: the head's source stays raw fp32 -- no ln_apply launch, no bf16 copy: this kernel normalises and rounds it)
   int rc = run_layers(plan, packed, net_input, nullptr, workspace, workspace_bytes, stream_, MSI_NET_NUM_LAYERS - 1);
   if (rc || desc->batch == 0) return rc;
   hipStream_t stream = msi::as_stream(stream_);
   if (event_after_convs) {
     hipError_t e = hipEventRecord(static_cast<hipEvent_t>(event_after_convs), stream);
-    if (e != hipSuccess) return msi::fail(MSI_E_LAUNCH, "net_forward_rgba: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return msi::fail(MSI_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
   }
   char *ws = static_cast<char *>(workspace);
   const Layer &S = net.layers[H.src0];
@@ -1086,6 +1089,7 @@ int msi_net_plan_forward_rgba(const msi_net_plan *plan, const float *packed, con
   q.aff = aff;
   q.psv = net_input;
   q.rgba = reinterpret_cast<float4 *>(rgba_native);
+  q.layers = layers_out;
   q.bw_out = blend_weights;
   q.al_out = alphas;
   q.pred_out = pred;
@@ -1101,7 +1105,7 @@ int msi_net_plan_forward_rgba(const msi_net_plan *plan, const float *packed, con
     q.mg_vpp = magic(vpp);
     q.mg_nchunk = magic((unsigned)(q.ksteps * 8));
     q.mg_hw = magic((unsigned)q.hw);
-    if (q.npix_total >= (1L << 32)) return msi::fail(MSI_E_UNSUPPORTED, "net_forward_rgba: more than 2^32 pixels per batch");
+    if (q.npix_total >= (1L << 32)) return msi::fail(MSI_E_UNSUPPORTED, "%s: more than 2^32 pixels per batch", who);
   }
   constexpr int BN = 64;
   size_t r_bytes = (size_t)q.ksteps * (HA_TP + BN) * ROW_BYTES;
@@ -1112,9 +1116,27 @@ int msi_net_plan_forward_rgba(const msi_net_plan *plan, const float *packed, con
   }
   const size_t lds = 2 * 64 * 4 + 64 + ((r_bytes + 15) & ~(size_t)15) + (size_t)HA_TP * (2 * q.lg + 1) * sizeof(float);
   const long ntile = q.npix_total / HA_TP;
-  if (((ntile + 7) / 8) * 8 * ng >= (1L << 31)) return msi::fail(MSI_E_UNSUPPORTED, "net_forward_rgba: too many pixel tiles for one launch");
+  if (((ntile + 7) / 8) * 8 * ng >= (1L << 31)) return msi::fail(MSI_E_UNSUPPORTED, "%s: too many pixel tiles for one launch", who);
   // (see the kernel: XCD x takes tiles x, x + 8, ...; the layer groups of a tile are neighbours there)
-  return launch_head_assemble(bf16, (unsigned)(((ntile + 7) / 8) * 8 * ng), lds, stream, q);
+  return launch_head_assemble(bf16, layers_out ? format : MSI_LAYERS_F32, (unsigned)(((ntile + 7) / 8) * 8 * ng), lds, stream, q);
+}
+
+int msi_net_plan_forward_rgba(const msi_net_plan *plan, const float *packed, const void *net_input, float *rgba_native,
+                              float *blend_weights, float *alphas, float *pred, void *workspace, size_t workspace_bytes,
+                              msi_stream_t stream_, void *event_after_convs) {
+  return forward_fused_tail("net_forward_rgba", plan, packed, net_input, rgba_native, nullptr, MSI_LAYERS_F32, blend_weights, alphas, pred,
+                            workspace, workspace_bytes, stream_, event_after_convs);
+}
+
+int msi_net_plan_forward_layers(const msi_net_plan *plan, const float *packed, const void *net_input, float *rgba_native,
+                                void *layers_out, int32_t format, float *blend_weights, float *alphas, float *pred, void *workspace,
+                                size_t workspace_bytes, msi_stream_t stream_, void *event_after_convs) {
+  // (the first two checks need no plan, hence no device)
+  MSI_REQUIRE(!layers_out || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F,
+              "net_forward_layers: unknown format %d (layers_out is MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F)", format);
+  MSI_REQUIRE(rgba_native || layers_out, "net_forward_layers: null pointer");
+  return forward_fused_tail("net_forward_layers", plan, packed, net_input, rgba_native, layers_out, format, blend_weights, alphas, pred,
+                            workspace, workspace_bytes, stream_, event_after_convs);
 }
 
 static int run_layers(const msi_net_plan *plan, const float *packed, const void *net_input, float *pred,

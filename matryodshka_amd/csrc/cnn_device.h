@@ -4,7 +4,7 @@
 //   cnn_halo.hip   the native fp32 halo-patch kernels (stride 1 / 2, conv-transpose)
 //   cnn_x3.hip     fp32 through the six-product bf16 / three-product fp16 split (stride 1 incl. the 8-row tile, stride 2, conv-transpose)
 //   cnn_bf16.hip   the bf16 halo-patch kernels (stride 1 / 2, conv-transpose)
-//   cnn_tail.hip   fused tail (head + RGBA assembly), LayerNorm finish / apply, zero
+//   cnn_tail.hip   fused tail (head + RGBA assembly; its body is cnn_tail_head_assemble.inc, shared by the fp32 and the packed kernels), LayerNorm finish / apply, zero
 // Here: constants, ConvParams, the per-layer launch record (namespace msi_cnn: shared TYPES need one identity across translation units), the device helpers
 // of the k-loops and the epilogue (anonymous namespace: every unit inlines its own), and the launch entry points each family exports.
 #pragma once
@@ -153,7 +153,7 @@ struct HeadAsmParams {
   const float *bias;
   const float *aff;          // affine of the source layer's LayerNorm [B][scale[C0] | shift[C0]] (ln_finish_kernel)
   const void *psv;           // [B,H,W,6D] fp32, or bf16 (BF16IN)
-  float4 *rgba;              // [B,D,H,W] float4
+  float4 *rgba;              // [B,D,H,W] float4 (the packed instantiations: optional, null = no fp32 stack)
   float *bw_out, *al_out;    // optional [B,H,W,D]
   float *pred_out;           // optional [B,H,W,2D] (tanh output)
   int C0, ksteps, npad, nd, hw;
@@ -161,6 +161,7 @@ struct HeadAsmParams {
   unsigned mg_vpp, mg_nchunk, mg_hw;   // udiv_magic multipliers of the 16-byte vectors per pixel of the sweep-volume tile, of the
                              // 16-byte chunks per pixel of the activation tile, of H * W (run-time integer divisions are ~25 VALU each)
   long npix_total;
+  void *layers;              // (last: the members above keep their kernel-argument offsets) packed instantiations only: [B,D,H,W] texels of their format (MSI_LAYERS_RGBA8: 4 bytes, MSI_LAYERS_RGBA16F: 8)
 };
 
 // ---- launch entry points of the kernel families (each returns an MSI_* code; p carries every pointer) ----
@@ -174,7 +175,7 @@ int launch_ln_finish(int batch, hipStream_t stream, const long long *sums, doubl
                      float *aff, int raw16);
 int launch_ln_apply(int bf16out, unsigned blocks, int batch, size_t lds, hipStream_t stream, float *x, const long long *sums, double inv_n, const double *scl, int *status,
                     const float *gamma, const float *beta, size_t per_sample, int C, float *aff, unsigned short *yb);
-int launch_head_assemble(int bf16in, unsigned grid_x, size_t lds, hipStream_t stream, const HeadAsmParams &q);
+int launch_head_assemble(int bf16in, int format, unsigned grid_x, size_t lds, hipStream_t stream, const HeadAsmParams &q);   // format = MSI_LAYERS_F32: head_assemble_kernel, else the packed form writing q.layers
 int debug_conv_occupancy(int lds_bytes);                                                                          // cnn_igemm.hip (tools/conv_timing.py)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the function ON A DEVICE: set once per (instantiation,

@@ -1411,8 +1411,7 @@ render_views_kernel(const float4 *__restrict__ rgba, const float *__restrict__ p
 // op for op, so a render from a packed stack is bit-identical to msi_render_views_f32 on the unpacked one.
 constexpr float RGBA8_KC = 0x1.010102p-7f;   // fl32(1 / 127.5)
 constexpr float RGBA8_KA = 0x1.010102p-8f;   // fl32(1 / 255)
-typedef _Float16 half4_g __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_g __attribute__((ext_vector_type(2)));
+// (half4_g, u32x2_g and the encoders rgba8_encode / rgba16f_encode: msi_common.h, shared with the fused tail of cnn_tail.hip)
 
 __device__ __forceinline__ float4 rgba8_decode(unsigned q) {   // (the byte picks compile to v_cvt_f32_ubyte0..3)
   float4 t;
@@ -1587,21 +1586,7 @@ render_views_packed_kernel(const void *__restrict__ layers, const float *__restr
 // rgba16f texels -- and the < 4 texels that do not fill a piece go one at a time through the first threads of the grid.
 // NT = 1 (the host picks it when the destination is larger than the 256-MiB Infinity Cache): non-temporal stores, as in the sweep
 // (a template argument: behind a runtime flag hipcc merges the two stores into one plain store).
-// NaN inputs of the rgba8 encoder (outside the contract): fmaxf returns its other operand, so a NaN channel encodes as code 0.
-__device__ __forceinline__ unsigned rgba8_encode(const float4 &t) {
-  const unsigned r = (unsigned)rintf((fminf(fmaxf(t.x, -1.0f), 1.0f) + 1.0f) * 127.5f);
-  const unsigned g = (unsigned)rintf((fminf(fmaxf(t.y, -1.0f), 1.0f) + 1.0f) * 127.5f);
-  const unsigned b = (unsigned)rintf((fminf(fmaxf(t.z, -1.0f), 1.0f) + 1.0f) * 127.5f);
-  const unsigned a = (unsigned)rintf(fminf(fmaxf(t.w, 0.0f), 1.0f) * 255.0f);
-  return r | (g << 8) | (b << 16) | (a << 24);
-}
-
-__device__ __forceinline__ u32x2_g rgba16f_encode(const float4 &t) {
-  half4_g h;
-  h.x = (_Float16)t.x; h.y = (_Float16)t.y; h.z = (_Float16)t.z; h.w = (_Float16)t.w;
-  return __builtin_bit_cast(u32x2_g, h);
-}
-
+// The encoders (rgba8_encode, rgba16f_encode) are in msi_common.h.
 template <int FMT, int NT>
 __global__ void __launch_bounds__(256)
 pack_layers_kernel(const float4 *__restrict__ in, void *__restrict__ out, size_t texels) {

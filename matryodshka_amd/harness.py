@@ -15,6 +15,9 @@ high_res (after the low-res pass, the high-res re-render of :283-394 from the sa
 `--hres_image_dir`: output_hrestgt_* / output_hresdepth_*), high_res_only (only that); `--input_type PP` takes perspective
 camera lines (`scene ref src tgt input_offset tgt_offset`, datasets.py:427-437) through the plane-sweep / mpi_render_view path;
 `--dtype bf16` runs either input type on the bf16 network tier.
+`--msi_format rgba8|rgba16f` also keeps each sample's MSI as a compact stack: the inference launch that writes the fp32 layers
+emits the packed ones as well, saved with their planes as `msi_<dir>.npz` (PackedLayers.save) -- the stored-frame feed of
+MSI.render_views.
 `--checkpoint` reads a TF V2 checkpoint directly (tf_checkpoint.py), `--weights` an .npz of the TF variables
 (see nets.variable_shapes); without either Xavier-initialised
 weights are used (there is no network access for the pretrained checkpoint), step.txt then says 0.
@@ -99,17 +102,25 @@ def write_layer_outputs(outs, jouts, src, ref, num_planes, test_outputs, output_
                 write_image(os.path.join(output_dir, "jitter_msi_rgb_%.2d.png" % i), (jr[0, :, :, i, :3] + 1.) / 2. * 255)
 
 
+def save_packed_msi(outs, output_dir, dirname):
+    """--msi_format: the sample's packed stack (with its planes) as msi_<dirname>.npz next to its other files."""
+    if "packed_layers" in outs:
+        outs["packed_layers"].save(os.path.join(output_dir, "msi_%s.npz" % dirname))
+
+
 def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_outputs, output_dir, dirname,
-               which_color_pred="blend_psv", jitter_pose=None):
+               which_color_pred="blend_psv", jitter_pose=None, msi_format=None):
     """One iteration of the loop at test.py:199-281.  images = (ref, src, tgt) float [H,W,3] in [0,1]
-    (image order ref, src, tgt: data_loader.py:134-136)."""
+    (image order ref, src, tgt: data_loader.py:134-136).  msi_format ('rgba8' | 'rgba16f'): the sample's inference also
+    emits the packed stack, saved as msi_<dirname>.npz; every other output is unchanged."""
     import torch
     ref, src, tgt = (torch.from_numpy(np.ascontiguousarray(x[None])) for x in images)
     eye = np.eye(4, dtype=np.float32)[None]
     intr = np.array([[[baseline, 0, 0], [0, 1, 0], [0, 0, 1]]], dtype=np.float32)       # data_loader.py:160
     pos = np.asarray(tgt_pos, dtype=np.float32)[None]
+    layer_format = "f32" if msi_format is None else ("f32", msi_format)
     outs, net_input = model.infer_msi(src, ref, None, None, eye, eye, intr, which_color_pred, num_planes, planes,
-                                      extra_outputs="blend_weights alphas psv", ngf=ngf)
+                                      extra_outputs="blend_weights alphas psv", ngf=ngf, layer_format=layer_format)
     # (after EVERY forward: the status word is reset by the next one -- ADVICE r03.  A flagged forward does not stop the sample: its
     # files are written first and the error is raised at the end, so that main()'s "flag and continue" finds them on disk -- ADVICE r04)
     from ._native import MsiError
@@ -134,7 +145,7 @@ def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_o
             print("LayerNorm windows calibrated on %s: %d layers moved" % (dirname, moved))
             del deferred[:]
             outs, net_input = model.infer_msi(src, ref, None, None, eye, eye, intr, which_color_pred, num_planes, planes,
-                                              extra_outputs="blend_weights alphas psv", ngf=ngf)
+                                              extra_outputs="blend_weights alphas psv", ngf=ngf, layer_format=layer_format)
             check_status()
         except MsiError as e:
             if cstate.get(ckey, 0) != "ok":
@@ -174,6 +185,7 @@ def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_o
             write_image(os.path.join(output_dir, "output_ptgt%d_%s.png" % (vw, dirname)),
                         model.deprocess_image(o)[0].cpu().numpy())
     write_layer_outputs(outs, jouts, src, ref, num_planes, test_outputs, output_dir, dirname, which_color_pred)
+    save_packed_msi(outs, output_dir, dirname)
     if deferred:
         raise deferred[0]
     return outs
@@ -189,11 +201,11 @@ def sample_dirname(scene, ids, test_type="", prefix=""):
 
 
 def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, ngf, test_outputs, output_dir, dirname,
-                  which_color_pred="blend_psv"):
+                  which_color_pred="blend_psv", msi_format=None):
     """input_type=PP (test.py:51; data_loader.py:205-226): perspective pair, source camera shifted by -input_offset along
     x, target by -tgt_offset, intrinsics fx = cx = W/2, fy = cy = H/2; plane-sweep volume at the slerp mid-point pose
     (train.py:118-121), target view by mpi_render_view through tgt_pose @ interp_pose_inv (msi.py:644-646).  The MPI path
-    has no depth render (the reference has none either)."""
+    has no depth render (the reference has none either).  msi_format: as in run_sample."""
     import torch
     from . import poses
     ref, src, tgt = (torch.from_numpy(np.ascontiguousarray(x[None])) for x in images)
@@ -205,13 +217,15 @@ def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, n
     K = np.array([[[0.5 * w, 0, 0.5 * w], [0, 0.5 * h, 0.5 * h], [0, 0, 1]]], dtype=np.float32)
     interp_inv = np.linalg.inv(poses.interpolate_pose(eye, src_pose).astype(np.float64)).astype(np.float32)
     outs, net_input = model.infer_msi(src, ref, None, None, eye, src_pose, K, which_color_pred, num_planes, planes,
-                                      extra_outputs="blend_weights alphas psv", ngf=ngf, ref_pose_inv=interp_inv)
+                                      extra_outputs="blend_weights alphas psv", ngf=ngf, ref_pose_inv=interp_inv,
+                                      layer_format="f32" if msi_format is None else ("f32", msi_format))
     os.makedirs(output_dir, exist_ok=True)
     if "tgt_image" in test_outputs:
         rgb = model.mpi_render_view(outs["rgba_layers"], np.matmul(tgt_pose, interp_inv).astype(np.float32), planes, K)
         write_image(os.path.join(output_dir, "tgt_image_%s.png" % dirname), tgt[0].numpy() * 255.0)
         write_image(os.path.join(output_dir, "output_tgt_%s.png" % dirname), model.deprocess_image(rgb)[0].cpu().numpy())
     write_layer_outputs(outs, None, src, ref, num_planes, test_outputs, output_dir, dirname, which_color_pred)
+    save_packed_msi(outs, output_dir, dirname)
     return outs
 
 
@@ -256,6 +270,9 @@ def main(argv=None):
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="f32, or bf16: the bf16 network tier (bf16 sweep volume, weights and activations; fp32 geometry) for "
                          "either input type")
+    ap.add_argument("--msi_format", default=None, choices=["rgba8", "rgba16f"],
+                    help="also save each sample's MSI as a compact layer stack msi_<dir>.npz (PackedLayers.save, planes included), "
+                         "emitted by the same launch that writes the fp32 layers; default: off")
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--hres_height", type=int, default=2048, help="loader.py:34")
@@ -332,7 +349,7 @@ def main(argv=None):
             try:
                 if args.input_type == "PP":
                     run_sample_pp(model, images, cam[0], cam[1], planes, d, args.ngf, args.test_outputs, out_dir, dirname,
-                                  which_color_pred=args.which_color_pred)
+                                  which_color_pred=args.which_color_pred, msi_format=args.msi_format)
                     model.network_status()   # raises if a LayerNorm statistic left the range the kernels resolve
                 else:
                     jitter = None
@@ -340,7 +357,7 @@ def main(argv=None):
                         from . import poses
                         jitter = poses.random_rotation(args.rot_factor, args.tr_factor, jitter_rng)
                     run_sample(model, images, cam[0], cam[1:4], planes, d, args.ngf, args.test_outputs, out_dir, dirname,
-                               which_color_pred=args.which_color_pred, jitter_pose=jitter)
+                               which_color_pred=args.which_color_pred, jitter_pose=jitter, msi_format=args.msi_format)
                 model.render_status()        # raises if a render's ray origin was outside the innermost sphere
             except (MsiError, ValueError) as e:
                 # a sample whose statistics leave the LayerNorm window (a heuristic built from the weights) or whose target lies

@@ -332,10 +332,11 @@ class MSI(object):
     # ------------------------------------------------------------------ msi.py:40-289
     def infer_msi(self, raw_src_image, raw_ref_image, raw_hres_src_image, raw_hres_ref_image,
                   ref_pose, src_pose, intrinsics, which_color_pred, num_msi_planes, psv_planes,
-                  extra_outputs='', ngf=64, ref_pose_inv=None, jitter_pose_inv=None):
+                  extra_outputs='', ngf=64, ref_pose_inv=None, jitter_pose_inv=None, layer_format='f32'):
         """Construct and run the MSI inference path.  Returns (pred dict, net_input).
         Note the reference's argument order: src before ref (msi.py:40-46).
-        which_color_pred: blend_psv (2D outputs) | blend_bg (2D+3) | blend_bg_psv (3D+3) | alpha_only (D), msi.py:119-275."""
+        which_color_pred: blend_psv (2D outputs) | blend_bg (2D+3) | blend_bg_psv (3D+3) | alpha_only (D), msi.py:119-275.
+        layer_format: see infer_layers; a packed stack (pred['packed_layers']) carries psv_planes as its planes."""
         if which_color_pred not in self.COLOR_SCHEMES:
             raise ValueError("which_color_pred=%r (blend_psv, blend_bg, blend_bg_psv, alpha_only)" % which_color_pred)
         if len(psv_planes) != num_msi_planes:
@@ -344,7 +345,10 @@ class MSI(object):
         src_image, ref_image = self.preprocess_image_pair(raw_src_image, raw_ref_image)
         net_input = self.format_network_input(ref_image, src_image, ref_pose, src_pose, psv_planes,
                                               intrinsics, ref_pose_inv=ref_pose_inv, jitter_pose_inv=jitter_pose_inv)
-        pred = self.infer_layers(net_input, num_msi_planes, ngf, extra_outputs, which_color_pred)
+        pred = self.infer_layers(net_input, num_msi_planes, ngf, extra_outputs, which_color_pred, layer_format=layer_format)
+        if 'packed_layers' in pred:
+            pk = pred['packed_layers']
+            pred['packed_layers'] = PackedLayers(pk.data, pk.format, psv_planes)
         return pred, net_input
 
     def run_net(self, net_input, num_outputs, ngf=64):
@@ -361,14 +365,33 @@ class MSI(object):
         self._last_forward = (plan, ws)
         return pred
 
+    @staticmethod
+    def _layer_formats(layer_format):
+        """layer_format of infer_layers -> (want the fp32 stack, packed format or None)."""
+        allowed = ('f32',) + PACKED_FORMATS
+        req = (layer_format,) if isinstance(layer_format, str) else tuple(layer_format) if isinstance(layer_format, (tuple, list)) else None
+        if not req or any(not isinstance(f, str) or f not in allowed for f in req):
+            raise ValueError("layer_format must be one of %s or a tuple of them, not %r" % (allowed, layer_format))
+        packed = sorted(set(f for f in req if f != 'f32'))
+        if len(packed) > 1:
+            raise ValueError("layer_format takes at most one packed format per call (%s: 'f32' plus one of %s), not %r"
+                             % (allowed, PACKED_FORMATS, layer_format))
+        return 'f32' in req, (packed[0] if packed else None)
+
     def infer_layers(self, net_input, num_msi_planes, ngf=64, extra_outputs='', which_color_pred='blend_psv',
-                     event_after_convs=None):
+                     event_after_convs=None, layer_format='f32'):
         """msi_net + layer_prediction of infer_msi (msi.py:95-147): net_input -> pred dict.  For the reference's default
         colour scheme the 1x1 head, conv8_2's LayerNorm and the RGBA assembly run as ONE fused kernel
         (msi_net_plan_forward_rgba: the tanh prediction never goes to HBM; fp32: bit-identical to the two-step path,
         bf16: the same bf16 operands, fp32 summation order of the head differs);
         everything else takes run_net + assemble_layers.  event_after_convs: torch.cuda.Event (already recorded once, so
-        that its handle exists) recorded between the convolutions and the fused tail."""
+        that its handle exists) recorded between the convolutions and the fused tail.
+        layer_format: 'f32' (default), 'rgba8', 'rgba16f', or a tuple of them with at most one packed format.  'f32' in the
+        request -> pred['rgba_layers']; a packed format -> pred['packed_layers'], a PackedLayers (native layout, no planes
+        attached) that the fused kernel writes itself (msi_net_plan_forward_layers: bit-identical to pack_layers of the fp32
+        stack, which a packed-only request never allocates).  Where the fused tail does not apply the packed stack is
+        pack_layers of the assembled fp32 one: the same bits for every configuration."""
+        want_f32, pfmt = self._layer_formats(layer_format)
         b, h, w, cin = net_input.shape
         d = num_msi_planes
         fused = (which_color_pred == 'blend_psv' and
@@ -381,19 +404,34 @@ class MSI(object):
             msi_pred = self.run_net(net_input, num_outputs, ngf)
             if event_after_convs is not None:
                 event_after_convs.record()
-            return self.assemble_layers(net_input, msi_pred, d, extra_outputs, which_color_pred)
+            pred = self.assemble_layers(net_input, msi_pred, d, extra_outputs, which_color_pred)
+            if pfmt is not None:
+                pred['packed_layers'] = self.pack_layers(pred['rgba_layers'], pfmt)
+                if not want_f32:
+                    del pred['rgba_layers']
+            return pred
         desc, packed, ws = self._net(b, h, w, cin, 2 * d, ngf)
         plan = self._plan(b, h, w, cin, 2 * d, ngf)
         new = lambda: torch.empty((b, h, w, d), dtype=torch.float32, device=self.device)
-        rgba = torch.empty((b, d, h, w, 4), dtype=torch.float32, device=self.device)
+        rgba = torch.empty((b, d, h, w, 4), dtype=torch.float32, device=self.device) if want_f32 else None
         bw = new() if 'blend_weights' in extra_outputs else None
         al = new() if 'alpha' in extra_outputs else None
         ev = 0 if event_after_convs is None else event_after_convs.cuda_event
-        N.check(N.lib.msi_net_plan_forward_rgba(plan.handle, packed.data_ptr(), net_input.data_ptr(), rgba.data_ptr(),
-                                                _ptr(bw), _ptr(al), 0, ws.data_ptr(), ws.numel(), self._stream(), ev),
-                "msi_net_plan_forward_rgba")
+        if pfmt is None:
+            N.check(N.lib.msi_net_plan_forward_rgba(plan.handle, packed.data_ptr(), net_input.data_ptr(), rgba.data_ptr(),
+                                                    _ptr(bw), _ptr(al), 0, ws.data_ptr(), ws.numel(), self._stream(), ev),
+                    "msi_net_plan_forward_rgba")
+        else:
+            codes = torch.empty((b, d, h, w, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+            N.check(N.lib.msi_net_plan_forward_layers(plan.handle, packed.data_ptr(), net_input.data_ptr(), _ptr(rgba), codes.data_ptr(),
+                                                      self.LAYER_FORMATS[pfmt], _ptr(bw), _ptr(al), 0, ws.data_ptr(), ws.numel(),
+                                                      self._stream(), ev), "msi_net_plan_forward_layers")
         self._last_forward = (plan, ws)
-        pred = {'rgba_layers': rgba.permute(0, 2, 3, 1, 4)}
+        pred = {}
+        if rgba is not None:
+            pred['rgba_layers'] = rgba.permute(0, 2, 3, 1, 4)
+        if pfmt is not None:
+            pred['packed_layers'] = PackedLayers(codes, pfmt)
         if bw is not None:
             pred['blend_weights'] = bw
         if al is not None:
