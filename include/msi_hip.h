@@ -184,6 +184,30 @@ int msi_resize_bilinear_f32(const float *in, float *out, int32_t batch, int32_t 
 int msi_assemble_rgba_scaled_f32(const float *psv, const float *weights_alphas, float *rgba_native,
                                  int32_t batch, int32_t height, int32_t width, int32_t num_planes,
                                  msi_stream_t stream);
+/* (a) + (b) + (c) in ONE launch (MSI.hres_layers): the high-res layer stack straight from the two high-res images and the
+ * low-res blend weights / alphas, as fp32, in a compact format (see msi_pack_layers), or both.  Neither the [B,Hh,Wh,6D] sweep
+ * volume nor the [B,Hh,Wh,2D] upsampled tensor exists: a texel is computed from two image gathers, eight low-res taps and one
+ * blend, and stored once.
+ *   ref_image, src_image   [B,Hh,Wh,3] preprocessed; ref_curr_pose, src_curr_pose [B,4,4], intrinsics [B,3,3], depths [D] and
+ *                          trig (the table of (Hh, Wh) = (height, width)) as msi_ods_sweep_volume takes them
+ *   blend_weights, alphas  [B,h,w,D] each ((h, w) = (low_height, low_width)), already in (0,1), 16-byte aligned
+ *   rgba_native            [B,D,Hh,Wh,4] fp32, 16-byte aligned, or NULL
+ *   layers_out             [B,D,Hh,Wh] texels of `format`, 16-byte aligned, or NULL.  `format` must be MSI_LAYERS_RGBA8 or
+ *                          MSI_LAYERS_RGBA16F when layers_out is non-NULL and is ignored when it is NULL.
+ * At least one output is non-NULL; with both, one launch writes both.
+ * CONTRACT: rgba_native is bit-identical to msi_ods_sweep_volume (fp32) -> msi_resize_bilinear_f32 of [blend_weights | alphas]
+ * (concatenated along the channels) -> msi_assemble_rgba_scaled_f32, and layers_out is bit-identical to
+ * msi_pack_layers(format) of that stack (the kernel runs the same device functions in the same order; geometry.hip is
+ * compiled without contraction).
+ * Argument checks, in this order: unknown format with a non-NULL layers_out -> MSI_E_BADARG ("unknown format"); both outputs
+ * NULL -> MSI_E_BADARG ("null pointer"); any other NULL pointer; non-positive dims (batch < 0) -> MSI_E_BADARG ("bad dims");
+ * num_planes % 4 != 0 -> MSI_E_UNSUPPORTED; then the size limits of the kernels it replaces, MSI_E_BADARG: Hh * Wh < 2^24
+ * (24-bit pixel offsets), Hh <= 65535 and B <= 65535 (grid dimensions), h * w * D < 2^31.  Error texts name hres_layers.
+ * batch = 0 returns MSI_OK without a launch.  Batch rides on the grid (no frame loop): high-res is a batch-1 workload. */
+int msi_hres_layers(const float *ref_image, const float *src_image, const float *ref_curr_pose, const float *src_curr_pose,
+                    const float *intrinsics, const float *depths, const float *trig, const float *blend_weights,
+                    const float *alphas, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
+                    int32_t num_planes, float *rgba_native, void *layers_out, int32_t format, msi_stream_t stream);
 
 /* ---- K4: target-view reprojection + over-composite -------------------------------
  * MSI.msi_render_equirect_view / _depth (msi.py:407-429, 384-405):

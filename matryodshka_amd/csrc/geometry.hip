@@ -1674,6 +1674,122 @@ __global__ void resize_bilinear_kernel(const float4 *__restrict__ in, float4 *__
   }
 }
 
+// ---- msi_hres_layers: the high-res layer stack of test.py:283-394 in ONE pass -----------------------------------------------
+// A texel of that stack is a function of two image gathers (the ODS sweep samples of the ref / src image), eight low-res taps (the
+// bilinear resize of its blend weight and alpha) and one blend; the three-launch form (ods_sweep_kernel<float, NS, 2, 0> ->
+// resize_bilinear_kernel -> assemble_kernel<0, COLOR_BLEND_PSV>) writes and re-reads a [B,Hh,Wh,6D] volume and a [B,Hh,Wh,2D] tensor
+// to get there.  This kernel calls the SAME device functions (ods_quad, ods_tail, make_taps_bytes, gather3 / blend4), the resize's
+// expressions and the assembly's blend in the same order -- the file is compiled without contraction, so every texel has the bits of
+// the three launches -- and stores it as 16 (fp32), 8 (rgba16f) or 4 (rgba8) bytes, or as fp32 and one packed format at once.
+// Mapping: the output is D-major, so unlike the sweep (depth in the fastest lanes, NHWC) a lane is one PIXEL of a 256-column run of
+// row blockIdx.y and walks the layers: trigonometry, the resize corners and the pose comparison are per-pixel work done once, each
+// layer's store is one contiguous run per wave (64 x 16 / 8 / 4 bytes; a lane's fp32 texel is one 16-byte piece), and neighbouring
+// lanes gather neighbouring texels of the images.  Weights and alphas are [B,h,w,D] (layer fastest): one float4 per corner covers
+// four layers, so the eight taps of a texel cost two 16-byte loads; a row of blocks shares two low-res rows, which stay in L1 / L2.
+// FMT: MSI_LAYERS_F32 (no packed output), MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F; WITH_F32: the fp32 stack is written (too);
+// NT: bit 0 / bit 1 = non-temporal stores of the fp32 / the packed stack (the host sets a bit when that destination is larger
+// than the 256-MiB Infinity Cache; a template argument, as in pack_layers_kernel).
+// Layers per group (one G-float vector per low-res corner; the group is unrolled) and the waves per SIMD the register allocation aims at.  What hides the gathers'
+// latency is the independent samples a lane has in flight, not the wave count (same-box A/B, DESIGN.md section 4, profiles/hres_layers_variants.txt): G = 4 at four waves
+// (101-103 VGPRs) 2.3 ms at 4096x2048x32, G = 2 at five waves the same there and 1.9 x slower at 1280x640, G = 1 at six waves 1.7 x / 2.8 x slower; G = 4 at five waves spills.
+#ifndef MSI_HRES_GROUP   // (tuning: -DMSI_HRES_GROUP=1 / 2 / 4)
+#define MSI_HRES_GROUP 4
+#endif
+constexpr int HRES_G = MSI_HRES_GROUP;
+typedef float hres_vec __attribute__((ext_vector_type(HRES_G)));
+__device__ __forceinline__ hres_vec hres_lerp(const float *__restrict__ p, unsigned tl, unsigned tr, unsigned bl, unsigned br, float xl, float yl) {
+  const hres_vec a = *reinterpret_cast<const hres_vec *>(p + tl), b = *reinterpret_cast<const hres_vec *>(p + tr);
+  const hres_vec c = *reinterpret_cast<const hres_vec *>(p + bl), d = *reinterpret_cast<const hres_vec *>(p + br);
+  const hres_vec top = a + (b - a) * xl;        // (elementwise; resize_bilinear_kernel's MSI_LERP2)
+  const hres_vec bot = c + (d - c) * xl;
+  return top + (bot - top) * yl;
+}
+
+template <int FMT, int NT>
+__device__ __forceinline__ void hres_store_packed(void *__restrict__ base, size_t texel, const float4 &t) {
+  if constexpr (FMT == MSI_LAYERS_RGBA8) {
+    unsigned *p = static_cast<unsigned *>(base) + texel;
+    const unsigned q = rgba8_encode(t);
+    if (NT) __builtin_nontemporal_store(q, p); else *p = q;
+  } else {
+    u32x2_g *p = static_cast<u32x2_g *>(base) + texel;
+    const u32x2_g q = rgba16f_encode(t);
+    if (NT) __builtin_nontemporal_store(q, p); else *p = q;
+  }
+}
+
+#ifndef MSI_HRES_WAVES   // (tuning: -DMSI_HRES_WAVES=4 / 5)
+#define MSI_HRES_WAVES 4
+#endif
+template <int FMT, int WITH_F32, int NT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSI_HRES_WAVES, 8)))
+hres_layers_kernel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
+                   const float *__restrict__ pose1, const float *__restrict__ intrinsics, const float *__restrict__ depths,
+                   const float *__restrict__ trig, const float *__restrict__ blend_weights, const float *__restrict__ alphas,
+                   int low_h, int low_w, int height, int width, int nd, float sy, float sx, PixConsts K,
+                   float4 *__restrict__ rgba, void *__restrict__ packed) {
+  // grid = (ceil(W / 256), H, B): one thread per pixel, all layers
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= width) return;
+  const int i = blockIdx.y, b = blockIdx.z;
+
+  // the sweep's per-pixel constants (ods_sweep_kernel)
+  const float cs = trig[j], ss = trig[width + j];
+  const float ct = trig[2 * width + i], st = trig[2 * width + height + i];
+  const float csct = cs * ct, ssct = ss * ct;
+  const int img_bytes = height * width * 12;
+  const float *P0 = pose0 + (size_t)b * 16, *P1 = pose1 + (size_t)b * 16;
+  const __amdgpu_buffer_rsrc_t img0 = __builtin_amdgcn_make_buffer_rsrc((void *)(image0 + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t img1 = __builtin_amdgcn_make_buffer_rsrc((void *)(image1 + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
+  const float r = intrinsics[(size_t)b * 9];
+  bool same = true;                             // both sources share the quadratic when their poses are equal
+#pragma unroll
+  for (int k = 0; k < 12; ++k) same = same && (P0[k] == P1[k]);
+
+  // the resize's corners and fractions (resize_bilinear_kernel; sy, sx from the host as in msi_resize_bilinear_f32)
+  const float fy = (float)i * sy, fx = (float)j * sx;
+  const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
+  const int y1 = min((int)ceilf(fy), low_h - 1), x1 = min((int)ceilf(fx), low_w - 1);
+  const float yl = fy - (float)y0, xl = fx - (float)x0;
+  const size_t low_base = (size_t)b * low_h * low_w * nd;          // (h * w * D < 2^31: checked on the host)
+  const float *bw = blend_weights + low_base, *al = alphas + low_base;
+  const unsigned o_tl = (unsigned)(y0 * low_w + x0) * (unsigned)nd, o_tr = (unsigned)(y0 * low_w + x1) * (unsigned)nd;
+  const unsigned o_bl = (unsigned)(y1 * low_w + x0) * (unsigned)nd, o_br = (unsigned)(y1 * low_w + x1) * (unsigned)nd;
+
+  const size_t hw = (size_t)height * width;
+  size_t texel = (size_t)b * nd * hw + (size_t)i * width + j;      // layer 0 of this pixel in the [B,D,H,W] stack
+  for (int d0 = 0; d0 < nd; d0 += HRES_G) {                        // (nd % 4 == 0: checked on the host)
+    const hres_vec wv = hres_lerp(bw + d0, o_tl, o_tr, o_bl, o_br, xl, yl);
+    const hres_vec av = hres_lerp(al + d0, o_tl, o_tr, o_bl, o_br, xl, yl);
+#pragma unroll
+    for (int q = 0; q < HRES_G; ++q) {
+      const float depth = depths[d0 + q];
+      float u, v, fg[3], bg[3];
+      const OdsQuad q0 = ods_quad(P0, r, depth, csct, st, ssct);
+      ods_tail(q0, 1.0f, K, u, v);
+      gather3(img0, make_taps_bytes(u, v, width, height), fg);
+      if (same) {
+        ods_tail(q0, -1.0f, K, u, v);
+      } else {
+        const OdsQuad q1 = ods_quad(P1, r, depth, csct, st, ssct);
+        ods_tail(q1, -1.0f, K, u, v);
+      }
+      gather3(img1, make_taps_bytes(u, v, width, height), bg);
+      // assemble_kernel, COLOR_BLEND_PSV with pred_scaled
+      const float w = wv[q];
+      const float omw = 1.0f - w;
+      float4 o;
+      o.x = w * fg[0] + omw * bg[0];
+      o.y = w * fg[1] + omw * bg[1];
+      o.z = w * fg[2] + omw * bg[2];
+      o.w = av[q];
+      if (WITH_F32) sweep_store16(reinterpret_cast<uint4 *>(rgba + texel), __builtin_bit_cast(uint4, o), NT & 1);
+      if constexpr (FMT != MSI_LAYERS_F32) hres_store_packed<FMT, (NT >> 1) & 1>(packed, texel, o);
+      texel += hw;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------ PP path (config 5)
 // pj.perspective_plane_sweep (projector.py:221-223) = sweep_one with spherical.uv_grid (:46-48),
 // backproject_planar (:131-149), apply_pose, project_perspective (:248-266) and the SAME
@@ -2279,6 +2395,62 @@ int msi_resize_bilinear_f32(const float *in, float *out, int32_t batch, int32_t 
                      reinterpret_cast<const float4 *>(in), reinterpret_cast<float4 *>(out), n, in_h, in_w,
                      channels / 4, out_h, out_w, sy, sx);
   return msi::check_launch("resize_bilinear");
+}
+
+int msi_hres_layers(const float *ref_image, const float *src_image, const float *ref_curr_pose, const float *src_curr_pose,
+                    const float *intrinsics, const float *depths, const float *trig, const float *blend_weights,
+                    const float *alphas, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
+                    int32_t num_planes, float *rgba_native, void *layers_out, int32_t format, msi_stream_t stream) {
+  MSI_REQUIRE(!layers_out || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F, "hres_layers: unknown format %d", format);
+  MSI_REQUIRE(rgba_native || layers_out, "hres_layers: null pointer (both outputs are NULL)");
+  MSI_REQUIRE(ref_image && src_image && ref_curr_pose && src_curr_pose && intrinsics && depths && trig && blend_weights && alphas,
+              "hres_layers: null pointer");
+  MSI_REQUIRE(batch >= 0 && low_height > 0 && low_width > 0 && height > 0 && width > 0 && num_planes > 0, "hres_layers: bad dims");
+  if (num_planes % 4 != 0)
+    return msi::fail(MSI_E_UNSUPPORTED, "hres_layers: num_planes=%d must be a multiple of 4", num_planes);
+  MSI_REQUIRE(height <= 65535 && batch <= 65535 && (long)height * width < (1L << 24),
+              "hres_layers: problem too large (24-bit pixel offsets: H * W < 2^24, H <= 65535)");
+  MSI_REQUIRE((long)low_height * low_width * num_planes < (1L << 31), "hres_layers: low-res tensors too large (h * w * D < 2^31)");
+  if (batch == 0) return MSI_OK;
+  // the scales of msi_resize_bilinear_f32
+  const float sy = height > 1 ? (float)(low_height - 1) / (float)(height - 1) : 0.0f;
+  const float sx = width > 1 ? (float)(low_width - 1) / (float)(width - 1) : 0.0f;
+  const int fmt = layers_out ? format : MSI_LAYERS_F32;
+  // non-temporal stores for a destination that cannot stay in the 256-MiB Infinity Cache (as msi_pack_layers)
+  const size_t texels = (size_t)batch * num_planes * height * width, cache = (size_t)256 << 20;
+  const int nt = (rgba_native && texels * 16 > cache ? 1 : 0) | (layers_out && texels * (fmt == MSI_LAYERS_RGBA8 ? 4 : 8) > cache ? 2 : 0);
+  const dim3 grid((unsigned)((width + 255) / 256), height, batch);
+#define MSI_LAUNCH_HRES(FMT, F32_, NT_)                                                                                              \
+  hipLaunchKernelGGL((hres_layers_kernel<FMT, F32_, NT_>), grid, dim3(256), 0, msi::as_stream(stream), ref_image, src_image,           \
+                     ref_curr_pose, src_curr_pose, intrinsics, depths, trig, blend_weights, alphas, low_height, low_width, height,   \
+                     width, num_planes, sy, sx, make_consts(height, width), reinterpret_cast<float4 *>(rgba_native), layers_out)
+#define MSI_LAUNCH_HRES_P(FMT)                                                                                             \
+  {                                                                                                                        \
+    if (rgba_native) {                                                                                                     \
+      switch (nt) {                                                                                                        \
+        case 0: MSI_LAUNCH_HRES(FMT, 1, 0); break;                                                                         \
+        case 1: MSI_LAUNCH_HRES(FMT, 1, 1); break;                                                                         \
+        case 2: MSI_LAUNCH_HRES(FMT, 1, 2); break;                                                                         \
+        default: MSI_LAUNCH_HRES(FMT, 1, 3); break;                                                                        \
+      }                                                                                                                    \
+    } else if (nt) {                                                                                                       \
+      MSI_LAUNCH_HRES(FMT, 0, 2);                                                                                          \
+    } else {                                                                                                               \
+      MSI_LAUNCH_HRES(FMT, 0, 0);                                                                                          \
+    }                                                                                                                      \
+  }
+  if (fmt == MSI_LAYERS_RGBA8) {
+    MSI_LAUNCH_HRES_P(MSI_LAYERS_RGBA8)
+  } else if (fmt == MSI_LAYERS_RGBA16F) {
+    MSI_LAUNCH_HRES_P(MSI_LAYERS_RGBA16F)
+  } else if (nt) {
+    MSI_LAUNCH_HRES(MSI_LAYERS_F32, 1, 1);
+  } else {
+    MSI_LAUNCH_HRES(MSI_LAYERS_F32, 1, 0);
+  }
+#undef MSI_LAUNCH_HRES_P
+#undef MSI_LAUNCH_HRES
+  return msi::check_launch("hres_layers");
 }
 
 static int render_common(int mode, int ray, const float *rgba_native, const float *pose, const float *tgt_pos,

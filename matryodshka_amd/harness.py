@@ -17,7 +17,7 @@ camera lines (`scene ref src tgt input_offset tgt_offset`, datasets.py:427-437) 
 `--dtype bf16` runs either input type on the bf16 network tier.
 `--msi_format rgba8|rgba16f` also keeps each sample's MSI as a compact stack: the inference launch that writes the fp32 layers
 emits the packed ones as well, saved with their planes as `msi_<dir>.npz` (PackedLayers.save) -- the stored-frame feed of
-MSI.render_views.
+MSI.render_views; in the high_res modes the high-res stack is kept the same way, as `msi_hres_<dir>.npz` (MSI.hres_layers).
 `--checkpoint` reads a TF V2 checkpoint directly (tf_checkpoint.py), `--weights` an .npz of the TF variables
 (see nets.variable_shapes); without either Xavier-initialised
 weights are used (there is no network access for the pretrained checkpoint), step.txt then says 0.
@@ -229,12 +229,14 @@ def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, n
     return outs
 
 
-def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, dirname):
+def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, dirname, msi_format=None):
     """The high-res pass of test.py:283-394 for one sample: the low-res blend weights / alphas the first pass saved
     (blend_weights.npy, alphas.npy, test.py:264-271) are upsampled (align_corners), the layers re-assembled from the
     high-res sweep volume and rendered -- one fused device pass (MSI.msi_render_equirect_hres) instead of the
     reference's per-plane sess.run + numpy composite -- and written as test.py:383-394 does: (x + 1) / 2 * 255 and
-    depth * 255, clipped and truncated to uint8 by write_image."""
+    depth * 255, clipped and truncated to uint8 by write_image.  msi_format ('rgba8' | 'rgba16f'): the launch that builds the
+    high-res stack (MSI.hres_layers) also emits it packed, saved with its planes as msi_hres_<dirname>.npz; the images are
+    the same bytes either way."""
     import torch
     bw_path, al_path = os.path.join(output_dir, "blend_weights.npy"), os.path.join(output_dir, "alphas.npy")
     if not (os.path.exists(bw_path) and os.path.exists(al_path)):
@@ -245,11 +247,19 @@ def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, d
     eye = np.eye(4, dtype=np.float32)[None]
     intr = np.array([[[baseline, 0, 0], [0, 1, 0], [0, 0, 1]]], dtype=np.float32)
     pos = np.asarray(tgt_pos, dtype=np.float32)[None]
-    rgb, dep = model.msi_render_equirect_hres(bw, al, ref, src, eye, eye, eye, pos, planes, intr)
+    packed = None
+    if msi_format is None:
+        rgb, dep = model.msi_render_equirect_hres(bw, al, ref, src, eye, eye, eye, pos, planes, intr)
+    else:
+        layers = model.hres_layers(bw, al, ref, src, eye, eye, planes, intr, layer_format=("f32", msi_format))
+        rgb, dep = model.msi_render_equirect_view_and_depth(layers["rgba_layers"], eye, pos, planes, intr)
+        packed = layers["packed_layers"]
     os.makedirs(output_dir, exist_ok=True)
     print("Saving high-res output to %s" % output_dir)
     write_image(os.path.join(output_dir, "output_hrestgt_%s.png" % dirname), ((rgb[0].cpu().numpy() + 1.) / 2.) * 255.)
     write_image(os.path.join(output_dir, "output_hresdepth_%s.png" % dirname), dep[0].cpu().numpy() * 255.)
+    if packed is not None:
+        packed.save(os.path.join(output_dir, "msi_hres_%s.npz" % dirname))
     return rgb, dep
 
 
@@ -272,7 +282,8 @@ def main(argv=None):
                          "either input type")
     ap.add_argument("--msi_format", default=None, choices=["rgba8", "rgba16f"],
                     help="also save each sample's MSI as a compact layer stack msi_<dir>.npz (PackedLayers.save, planes included), "
-                         "emitted by the same launch that writes the fp32 layers; default: off")
+                         "emitted by the same launch that writes the fp32 layers (with --test_type high_res also the high-res "
+                         "stack, msi_hres_<dir>.npz); default: off")
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--hres_height", type=int, default=2048, help="loader.py:34")
@@ -376,7 +387,7 @@ def main(argv=None):
             hres = [load_image(os.path.join(args.hres_image_dir, "%s_pos%s.jpeg" % (scene, i)), args.hres_height, args.hres_width)
                     for i in ids[:2]]
             dirname = sample_dirname(scene, ids, args.test_type, args.prefix)
-            run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname)
+            run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname, msi_format=args.msi_format)
             n += "high_res_only" in args.test_type
     print("processed %d samples%s" % (n, " (%d flagged UNRELIABLE: %s)" % (len(failed), ", ".join(failed)) if failed else ""))
     return n

@@ -716,15 +716,72 @@ class MSI(object):
         return native.permute(0, 2, 3, 1, 4)
 
     # ------------------------------------------------------------------ test.py:283-394
+    def hres_layers(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
+                    intrinsics, ref_pose_inv=None, layer_format='f32'):
+        """The high-res layer stack of test.py:283-394 in ONE launch (msi_hres_layers): the high-res ODS sweep of both images,
+        the align_corners bilinear resize of the low-res blend_weights / alphas ([B,H,W,D], in (0,1): infer_msi's
+        extra_outputs) and the blend, without the [B,Hh,Wh,6D] sweep volume or the upsampled tensor in memory.
+        layer_format as in infer_layers: 'f32' in the request -> result['rgba_layers'] ([B,Hh,Wh,D,4], a permuted view of the
+        native stack); 'rgba8' / 'rgba16f' -> result['packed_layers'], a PackedLayers that carries `planes` and goes straight
+        into render_views; ('f32', packed) writes both in the same launch.  The fp32 stack has the bits of format_network_input
+        -> msi_resize_bilinear_f32 -> msi_assemble_rgba_scaled_f32, the packed one those of pack_layers of it; a packed-only
+        request allocates nothing but the packed stack.  ODS models only (fp32 or bf16: the high-res colours are fp32 either
+        way).  Poses as in format_network_input (ref_pose_inv computed on the host when absent)."""
+        want_f32, pfmt = self._layer_formats(layer_format)
+        if self.input_type != 'ODS':
+            raise ValueError("hres_layers: the fused high-res assembly is built for input_type='ODS' models")
+        bw, al = self._f32(blend_weights), self._f32(alphas)
+        if bw.dim() != 4 or bw.shape != al.shape:
+            raise ValueError("hres_layers: blend_weights and alphas must be [B,H,W,D] and agree")
+        b, h, w, d = bw.shape
+        depths = self._planes(planes)
+        if depths.numel() != d:
+            raise ValueError("len(planes) != number of layers")
+        hres_ref = self.preprocess_image(raw_hres_ref_image)
+        hres_src = self.preprocess_image(raw_hres_src_image)
+        if hres_ref.shape[0] != b or hres_ref.shape[3] != 3 or hres_src.shape != hres_ref.shape:
+            raise ValueError("hres_layers: images must be [B,Hh,Wh,3], agree, and have the batch of blend_weights")
+        hh, hw = hres_ref.shape[1], hres_ref.shape[2]
+        if ref_pose_inv is None:
+            ref_pose_inv = torch.linalg.inv(torch.as_tensor(ref_pose, dtype=torch.float32).cpu().double()).float()   # test.py:111
+        ref_pose, src_pose, ref_pose_inv = self._f32(ref_pose), self._f32(src_pose), self._f32(ref_pose_inv)
+        if ref_pose_inv.shape[0] != b:
+            ref_pose_inv = ref_pose_inv.reshape(-1, 4, 4).expand(b, 4, 4).contiguous()
+        cur = torch.empty((2, b, 4, 4), dtype=torch.float32, device=self.device)
+        N.check(N.lib.msi_compose_pose_pair_f32(ref_pose.data_ptr(), src_pose.data_ptr(), ref_pose_inv.data_ptr(),
+                                                cur[0].data_ptr(), cur[1].data_ptr(), b, self._stream()),
+                "msi_compose_pose_pair_f32")
+        intr, trig = self._f32(intrinsics), self._trig(hh, hw)
+        rgba = torch.empty((b, d, hh, hw, 4), dtype=torch.float32, device=self.device) if want_f32 else None
+        codes = None
+        if pfmt is not None:
+            codes = torch.empty((b, d, hh, hw, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+        N.check(N.lib.msi_hres_layers(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(),
+                                      intr.data_ptr(), depths.data_ptr(), trig.data_ptr(), bw.data_ptr(), al.data_ptr(),
+                                      b, h, w, hh, hw, d, _ptr(rgba), _ptr(codes), self.LAYER_FORMATS.get(pfmt, N.MSI_LAYERS_F32),
+                                      self._stream()), "msi_hres_layers")
+        out = {}
+        if rgba is not None:
+            out['rgba_layers'] = rgba.permute(0, 2, 3, 1, 4)
+        if codes is not None:
+            out['packed_layers'] = PackedLayers(codes, pfmt, planes)
+        return out
+
     def msi_render_equirect_hres(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image,
                                  ref_pose, src_pose, tgt_pose_rt, tgt_pos, planes, intrinsics,
                                  ref_pose_inv=None):
-        """High-res re-render of test.py:283-394 as ONE fused device pass: the reference loops over
-        the planes on the host (one sess.run + numpy composite per plane, to fit its GPU memory); with
-        288 GB of HBM the whole high-res sweep volume and layer stack stay resident.
+        """High-res re-render of test.py:283-394 as two launches: the reference loops over the planes
+        on the host (one sess.run + numpy composite per plane, to fit its GPU memory); here hres_layers
+        builds the whole fp32 high-res stack in one kernel (no sweep volume in memory) and one render
+        composites it.  To keep the stack, or to get it packed, call hres_layers itself.
         blend_weights / alphas: the low-res [B,H,W,D] outputs of infer_msi(extra_outputs=
         'blend_weights alphas') (test.py:264-271 saves them as .npy).  Returns (rgb, depth), both
         [B,Hh,Wh,3] float (rgb in [-1,1], depth = composited plane index / D as test.py:374-382)."""
+        if self.input_type == 'ODS':
+            rgba_layers = self.hres_layers(blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose,
+                                           planes, intrinsics, ref_pose_inv=ref_pose_inv, layer_format='f32')['rgba_layers']
+            return self.msi_render_equirect_view_and_depth(rgba_layers, tgt_pose_rt, tgt_pos, planes, intrinsics)
+        # perspective inputs: sweep, resize and assembly as three launches
         bw = self._f32(blend_weights)
         al = self._f32(alphas)
         b, h, w, d = bw.shape
