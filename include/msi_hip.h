@@ -197,7 +197,7 @@ int msi_assemble_rgba_scaled_f32(const float *psv, const float *weights_alphas, 
  * At least one output is non-NULL; with both, one launch writes both.
  * CONTRACT: rgba_native is bit-identical to msi_ods_sweep_volume (fp32) -> msi_resize_bilinear_f32 of [blend_weights | alphas]
  * (concatenated along the channels) -> msi_assemble_rgba_scaled_f32, and layers_out is bit-identical to
- * msi_pack_layers(format) of that stack (the kernel runs the same device functions in the same order; geometry.hip is
+ * msi_pack_layers(format) of that stack (the kernel runs the same device functions in the same order; the geometry units are
  * compiled without contraction).
  * Argument checks, in this order: unknown format with a non-NULL layers_out -> MSI_E_BADARG ("unknown format"); both outputs
  * NULL -> MSI_E_BADARG ("null pointer"); any other NULL pointer; non-positive dims (batch < 0) -> MSI_E_BADARG ("bad dims");

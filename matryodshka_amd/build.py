@@ -14,16 +14,19 @@ OBJ_DIR = os.path.join(HERE, "csrc", "_obj")
 ARCH = "gfx950"
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC,
           "-Wall", "-Wno-unused-function"]
-# (source, extra flags).  geometry.hip must not contract a*b+c into fma: see its header.
+# (source, extra flags).
 # -fno-slp-vectorize (r05): the SLP vectorizer packs scalar fp32 code into v_pk_*_f32 with cross-half operand selects; one such instruction of the
 # conv epilogue was the source of a rare wrong LayerNorm statistic (matryodshka_amd/isa_lint.py, DESIGN.md section 4 "the wobble").  Packed math
 # that pays is written by hand as two-float vectors; the lint below refuses a library that contains the operand routing again.
 NO_SLP = ["-fno-slp-vectorize"]
 SOURCES = [
     ("common.cpp", ["-x", "hip"]),
-    ("probe.hip", []),                                                     # msi_probe_matrix_rate (measurement aid of bench.py)
-    ("geometry.hip", ["-ffp-contract=off"] + NO_SLP + os.environ.get("MSI_GEO_DEFINES", "").split()),   # e.g. MSI_GEO_DEFINES="-DMSI_SWEEP_WAVES=5" (tuning)
+    ("probe.hip", NO_SLP),                                                 # msi_probe_matrix_rate (measurement aid of bench.py)
 ]
+# the geometry side: one translation unit per kernel family (csrc/geometry_device.h holds what they share and says why none of them may contract
+# a*b+c into fma), compiled in parallel.  The flags are attached here, to the whole list: a unit cannot join without them.
+GEO_UNITS = ["geo_prep.hip", "geo_sweep.hip", "geo_layers.hip", "geo_render.hip", "geo_planar.hip"]
+SOURCES += [(u, ["-ffp-contract=off"] + NO_SLP + os.environ.get("MSI_GEO_DEFINES", "").split()) for u in GEO_UNITS]   # e.g. MSI_GEO_DEFINES="-DMSI_SWEEP_WAVES=5" (tuning)
 # the K2 convolution path: one translation unit per kernel family (r05; cnn_device.h holds what they share), compiled in parallel
 CNN_UNITS = ["cnn.hip", "cnn_igemm.hip", "cnn_halo.hip", "cnn_x3.hip", "cnn_bf16.hip", "cnn_tail.hip"]
 SOURCES += [(u, NO_SLP + os.environ.get("MSI_CNN_DEFINES", "").split()) for u in CNN_UNITS]   # e.g. MSI_CNN_DEFINES="-DMSI_NSTAGE=2" (tuning)
@@ -43,18 +46,25 @@ def _newer(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _side(path):
+    """"cnn" / "geo" for a file named for one side of the library (cnn_device.h, geometry_device.h, geo_sweep.hip): such a header is a dependency
+    of that side's units only; "" for everything else, which every unit depends on."""
+    name = os.path.basename(path)
+    return name[:3] if name[:3] in ("cnn", "geo") else ""
+
+
 def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(INCLUDE, "msi_hip.h"), os.path.join(CSRC, "msi_common.h"), os.path.join(CSRC, "cnn_device.h"),
-               os.path.join(CSRC, "cnn_tail_head_assemble.inc"), __file__]
+    # every header and .inc of csrc/ (a hand-written list left stale objects behind a "successful" build when one was forgotten), the public header and this file
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(INCLUDE, "msi_hip.h"), __file__]
     objs = []
     jobs = []
     for src, extra in SOURCES:
         spath = os.path.join(CSRC, src)
         opath = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
         objs.append(opath)
-        if force or _newer(opath, [spath] + headers):
+        if force or _newer(opath, [spath] + [h for h in headers if _side(h) in ("", _side(src))]):
             cmd = [hipcc] + COMMON + extra + ["-c", spath, "-o", opath]
             if verbose:
                 print("[build]", " ".join(cmd), flush=True)

@@ -10,7 +10,7 @@ namespace {
 // flight while the 32 x C0 activations (conv8_2 raw, normalised + ReLU'd on the way like the stand-alone head does)
 // and the 2D x C0 weights go to LDS and 2 D / 32 waves run the k-steps on the fp32 MFMA -- the SAME instruction
 // sequence as the stand-alone head (k ascending, transposed accumulators), so the prediction is bit-identical --
-// then bias + tanh + (x+1)/2 land in an LDS tile and the assembly of K3 (geometry.hip, same expressions, no
+// then bias + tanh + (x+1)/2 land in an LDS tile and the assembly of K3 (geo_layers.hip, same expressions, no
 // contraction) writes float4 texels of the D-major stack.  HBM-bound: reads C0 + 6D floats, writes 4D per pixel.
 
 // A workgroup owns 32 pixels x lg layers (layer group g = blockIdx.y: blend weights g lg .. + lg, the alphas behind

@@ -239,7 +239,7 @@
     }
   }
   __syncthreads();
-  // 7. assembly (assemble_kernel, COLOR_BLEND_PSV; no contraction, like geometry.hip): thread -> (pixel, every 8th layer)
+  // 7. assembly (assemble_kernel, COLOR_BLEND_PSV; no contraction, like geo_layers.hip): thread -> (pixel, every 8th layer)
   {
 #pragma clang fp contract(off)
     const int px = tid & (HA_TP - 1);

@@ -1,0 +1,409 @@
+// The planar (PP) path of the geometry side: pp_sweep_kernel, pp_sweep_volume_bf16_kernel and mpi_render_kernel; kernels first, their C ABI
+// entry points below.
+#include "geometry_device.h"
+
+namespace {
+
+// ------------------------------------------------------------------------ PP path (config 5)
+// pj.perspective_plane_sweep (projector.py:221-223) = sweep_one with spherical.uv_grid (:46-48),
+// backproject_planar (:131-149), apply_pose, project_perspective (:248-266) and the SAME
+// wrap-around sampler as the ODS sweep.  Faithful to the reference, the pose is applied twice:
+// once by apply_pose (projector.py:155) and once inside project_perspective through
+// intrinsics @ pose (spherical.py:258-259); the 3x3 intrinsics are zero-padded to 4x4
+// (projector.py:145-148), so only rows 0..2 of the product are used.
+// FAST (round 6): the form for full waves of complete pixels (64 % D == 0, (W * D) % 256 == 0, 16-byte-aligned runs; the host decides).  Same arithmetic, same bits;
+// what changes is the plumbing the ODS sweep went through in rounds 1-2: (a) M = K4 @ pose -- 60 multiply-adds that depend on the FACE only -- is computed by twelve
+// threads and broadcast through LDS instead of by every thread; (b) a corner is ONE 12-byte buffer load, not three dword loads behind 64-bit address arithmetic;
+// (c) a wave's 64 / D complete pixels leave through a wave-private LDS strip as 16-byte-per-lane stores of whole 3 D-float runs instead of 3 dword stores at a
+// 12-byte stride per lane; non-temporal when the volume exceeds the Infinity Cache (sweep_store16).  Measured at configs[4] (64 faces, two sweeps each): DESIGN.md section 4.
+template <int FAST>
+__global__ void __launch_bounds__(256)
+pp_sweep_kernel(const float *__restrict__ image, const float *__restrict__ pose,
+                const float *__restrict__ intrinsics, const float *__restrict__ depths, int batch,
+                int height, int width, int nd, float s0, float sstep, float t0, float tstep,
+                float *__restrict__ psv, int channels, int coff, unsigned nd_magic, int nt) {
+  // grid = (ceil(W*D / 256), H, B): 32-bit index math only (64-bit div/mod are emulated in ~100
+  // VALU instructions each and used to dominate this kernel)
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (!FAST && idx >= width * nd) return;
+  int j, d;
+  if (FAST) {
+    unsigned jq = __umulhi((unsigned)idx, nd_magic);   // idx / nd by multiply-high (+ one correction)
+    if ((unsigned)idx - jq * (unsigned)nd >= (unsigned)nd) ++jq;
+    j = (int)jq; d = idx - j * nd;
+  } else {
+    j = idx / nd; d = idx - j * nd;
+  }
+  const int i = blockIdx.y, b = blockIdx.z;
+  const long p = ((long)b * height + i) * width + j;
+  const float S = s0 + sstep * (float)j, T = t0 + tstep * (float)i;
+  const float depth = depths[d];
+  const float *Kb = intrinsics + (size_t)b * 9;
+  const float fx = Kb[0], fy = Kb[4], cx = Kb[2], cy = Kb[5];
+  // backproject_planar (spherical.py:146-148): x = depth*S*cx/fx, y = depth*T*cy/fy, z = depth*1
+  float x = ((depth * S) * cx) / fx;
+  float y = ((depth * T) * cy) / fy;
+  float z = depth * 1.0f;
+  const float *P = pose + (size_t)b * 16;
+  {  // apply_pose (projector.py:275-291)
+    const float ax = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
+    const float ay = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
+    const float az = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
+    x = ax; y = ay; z = az;
+  }
+  // project_perspective: M = K4 @ pose, rows 0..2; the padded column contributes 0 * pose[3][c]
+  float pr[3];
+  __shared__ float s_m[12];
+  if (FAST) {
+    if (threadIdx.x < 12) {
+      const int r = threadIdx.x >> 2, c = threadIdx.x & 3;
+      s_m[threadIdx.x] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 3; ++r) pr[r] = ((s_m[r * 4 + 0] * x + s_m[r * 4 + 1] * y) + s_m[r * 4 + 2] * z) + s_m[r * 4 + 3] * 1.0f;
+  } else {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    float m[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      m[c] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
+    pr[r] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * 1.0f;
+  }
+  }
+  const float u = pr[0] / pr[2], v = pr[1] / pr[2];
+  const Taps t = make_taps(u, v, width, height);
+  if (FAST) {
+    const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void *)(image + (size_t)b * height * width * 3), 0, height * width * 12, 0x00020000);
+    const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x0) * 12u, 0, 0));
+    const f32x3_g bq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x1) * 12u, 0, 0));
+    const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x0) * 12u, 0, 0));
+    const f32x3_g dq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x1) * 12u, 0, 0));
+    const float o0 = blend4(t, a.x, bq.x, c.x, dq.x), o1 = blend4(t, a.y, bq.y, c.y, dq.y), o2 = blend4(t, a.z, bq.z, c.z, dq.z);
+    // whole-pixel runs through the wave's strip: lane = (pixel of the wave, depth); the wave's 64 / D pixels are consecutive, each owns 3 D contiguous floats at + coff
+    __shared__ __attribute__((aligned(16))) float s_out[4][192];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float *w = s_out[wave];
+    __builtin_amdgcn_wave_barrier();
+    w[lane * 3 + 0] = o0; w[lane * 3 + 1] = o1; w[lane * 3 + 2] = o2;      // (lane = pl * D + d: the strip IS the pixels' runs back to back)
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 48) {
+      const int vpp = (3 * nd) >> 2;                                         // 16-byte vectors per pixel run
+      unsigned plq = __umulhi((unsigned)lane, 0xffffffffu / (unsigned)vpp + 1u);
+      if ((unsigned)lane - plq * (unsigned)vpp >= (unsigned)vpp) --plq;      // (lane < 48, vpp >= 3: the estimate is exact or one too large)
+      const int pl = (int)plq, k = lane - pl * vpp;
+      const long pw0 = ((long)b * height + i) * width + (long)((blockIdx.x * 256 + wave * 64) / nd);
+      uint4 *dst = reinterpret_cast<uint4 *>(psv + (size_t)(pw0 + pl) * channels + coff) + k;
+      sweep_store16(dst, reinterpret_cast<const uint4 *>(w)[lane], nt);
+    }
+    return;
+  }
+  const float *img = image + (size_t)b * height * width * 3;
+  const float *pa = img + ((size_t)t.y0 * width + t.x0) * 3;
+  const float *pb = img + ((size_t)t.y0 * width + t.x1) * 3;
+  const float *pc = img + ((size_t)t.y1 * width + t.x0) * 3;
+  const float *pd = img + ((size_t)t.y1 * width + t.x1) * 3;
+  float *o = psv + (size_t)p * channels + coff + d * 3;
+  o[0] = blend4(t, pa[0], pb[0], pc[0], pd[0]);
+  o[1] = blend4(t, pa[1], pb[1], pc[1], pd[1]);
+  o[2] = blend4(t, pa[2], pb[2], pc[2], pd[2]);
+}
+
+// The whole bf16 PP network input of format_network_input (msi.py:1157-1161) in one launch: ref into channels [0, 3D), src into [3D, 6D)
+// of psv [B,H,W,6D].  Every value is the round-to-nearest-even of what pp_sweep_kernel computes for the same sample, bit for bit: the
+// arithmetic below is pp_sweep_kernel's, op for op.  What changes is what is shared: backproject_planar's (x, y, z) depend on the face's
+// intrinsics, the plane and the pixel, not on the pose, so one thread per (pixel, plane) computes them once for both sources (5 IEEE
+// divides per thread instead of 10 over two launches), and y -- a function of (row, plane) -- once per block into LDS; M = K4 @ pose is
+// computed once per face and source (24 threads, LDS).
+// FAST (64 % D == 0, (W * D) % 64 == 0; the host decides): a wave holds 64 / D complete pixels, whose 6 D channels are one contiguous run,
+// so the wave's 768 bytes leave through a wave-private fp32 strip as 48 16-byte stores of packed pairs (v_cvt_pk_bf16_f32: round to nearest
+// even, what f32_to_bf16 computes for the finite values stored here); non-temporal when the volume exceeds the Infinity Cache (sweep_store16).
+// Generic: one thread per (pixel, plane) stores its six values as bf16 halves.  Corners are 12-byte buffer loads with 32-bit offsets
+// (H * W * 12 < 2^31, checked on the host) in both forms; make_taps' wrapped indices lie inside the image.  The kernel is VALU-bound
+// (DESIGN.md section 4).  NT is a template argument, not sweep_store16's runtime flag: with the packed value computed ahead of the
+// branch, hipcc merges the two stores into one plain store.
+template <int FAST, int NT>
+__global__ void __launch_bounds__(256)
+pp_sweep_volume_bf16_kernel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
+                            const float *__restrict__ pose1, const float *__restrict__ intrinsics, const float *__restrict__ depths,
+                            int height, int width, int nd, int nd_shift, float s0, float sstep, float t0, float tstep,
+                            unsigned short *__restrict__ psv) {
+  // grid = (ceil(W*D / 256), H, B): 32-bit index math only
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int i = blockIdx.y, b = blockIdx.z;
+  const float *Kb = intrinsics + (size_t)b * 9;
+  const float fx = Kb[0], fy = Kb[4], cx = Kb[2], cy = Kb[5];
+  const float T = t0 + tstep * (float)i;
+  __shared__ float s_m[2][12];
+  __shared__ float s_y[64];
+  if (FAST) {
+    // project_perspective's M = K4 @ pose (rows 0..2; the padded column contributes 0 * pose[3][c]) per source, and
+    // backproject_planar's y = depth*T*cy/fy per plane of this row
+    const int tid = threadIdx.x;
+    if (tid < 24) {
+      const int s = tid / 12, e = tid - s * 12, r = e >> 2, c = e & 3;
+      const float *P = (s ? pose1 : pose0) + (size_t)b * 16;
+      s_m[s][e] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
+    } else if (tid >= 64 && tid < 64 + nd) {
+      s_y[tid - 64] = ((depths[tid - 64] * T) * cy) / fy;
+    }
+    __syncthreads();
+    if (idx >= width * nd) return;   // (W * D) % 64 == 0: whole waves
+  } else {
+    if (idx >= width * nd) return;
+  }
+  const int j = FAST ? idx >> nd_shift : idx / nd;
+  const int d = FAST ? idx & (nd - 1) : idx - j * nd;
+  const float S = s0 + sstep * (float)j;
+  const float depth = depths[d];
+  // backproject_planar (spherical.py:146-148), shared by both sources
+  const float x0 = ((depth * S) * cx) / fx;
+  const float y0 = FAST ? s_y[d] : ((depth * T) * cy) / fy;
+  const float z0 = depth * 1.0f;
+  const int img_bytes = height * width * 12;
+  float out[2][3];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const float *P = (s ? pose1 : pose0) + (size_t)b * 16;
+    // apply_pose (projector.py:275-291)
+    const float x = ((P[0] * x0 + P[1] * y0) + P[2] * z0) + P[3] * 1.0f;
+    const float y = ((P[4] * x0 + P[5] * y0) + P[6] * z0) + P[7] * 1.0f;
+    const float z = ((P[8] * x0 + P[9] * y0) + P[10] * z0) + P[11] * 1.0f;
+    float pr[3];
+    if (FAST) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) pr[r] = ((s_m[s][r * 4 + 0] * x + s_m[s][r * 4 + 1] * y) + s_m[s][r * 4 + 2] * z) + s_m[s][r * 4 + 3] * 1.0f;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        float m[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          m[c] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
+        pr[r] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * 1.0f;
+      }
+    }
+    const float u = pr[0] / pr[2], v = pr[1] / pr[2];
+    const Taps t = make_taps(u, v, width, height);
+    const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void *)((s ? image1 : image0) + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
+    const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x0) * 12u, 0, 0));
+    const f32x3_g bq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x1) * 12u, 0, 0));
+    const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x0) * 12u, 0, 0));
+    const f32x3_g dq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x1) * 12u, 0, 0));
+    out[s][0] = blend4(t, a.x, bq.x, c.x, dq.x);
+    out[s][1] = blend4(t, a.y, bq.y, c.y, dq.y);
+    out[s][2] = blend4(t, a.z, bq.z, c.z, dq.z);
+  }
+  const long p = ((long)b * height + i) * width + j;
+  if (FAST) {
+    // the wave's 64 / D pixels are consecutive and each owns 6 D contiguous channels: lane = pl * D + d writes its two triples into the
+    // strip at pl * 6 D + {0, 3 D} + 3 d, then lanes 0..47 each pack 8 of the 384 values into one 16-byte store
+    __shared__ __attribute__((aligned(16))) float s_out[4][384];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pl = lane >> nd_shift;
+    float *w = s_out[wave];
+    __builtin_amdgcn_wave_barrier();
+    const int e0 = pl * 6 * nd + 3 * d;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      w[e0 + c] = out[0][c];
+      w[e0 + 3 * nd + c] = out[1][c];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 48) {
+      const float4 lo = reinterpret_cast<const float4 *>(w)[2 * lane], hi = reinterpret_cast<const float4 *>(w)[2 * lane + 1];
+      uint4 pk;
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.x) : "v"(lo.x), "v"(lo.y));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.y) : "v"(lo.z), "v"(lo.w));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.z) : "v"(hi.x), "v"(hi.y));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.w) : "v"(hi.z), "v"(hi.w));
+      uint4 *dst = reinterpret_cast<uint4 *>(psv + (size_t)(p - pl) * (6 * nd)) + lane;   // (p - pl: the wave's first pixel)
+      sweep_store16(dst, pk, NT);
+    }
+    return;
+  }
+  unsigned short *o = psv + (size_t)p * (6 * nd) + 3 * d;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    o[c] = f32_to_bf16(out[0][c]);
+    o[3 * nd + c] = f32_to_bf16(out[1][c]);
+  }
+}
+
+// MSI.mpi_render_view (msi.py:527-548): pj.projective_forward_homography (projector.py:343-373) ->
+// homography.planar_transform (homography.py:120-157: inv_homography :35-58, transform_points
+// :60-80, normalize_homogeneous :82-94, divide_safe :30-33) -> sampling.bilinear_wrapper =
+// tf.contrib.resampler (zero padding) -> pj.over_composite, fused.  The per-(layer, sample)
+// inverse homographies (a few dozen flops each) are computed once per workgroup into LDS.
+constexpr int MPI_MAX_PLANES = 128;
+
+__device__ __forceinline__ float4 fetch_or_zero(const float4 *L, int x, int y, int width, int height) {
+  if (x >= 0 && y >= 0 && x < width && y < height) return L[(size_t)y * width + x];
+  return make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+__global__ void __launch_bounds__(256)
+mpi_render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ tgt_pose,
+                  const float *__restrict__ intrinsics, const float *__restrict__ intrinsics_inv,
+                  const float *__restrict__ depths, int batch, int height, int width, int nd,
+                  float *__restrict__ out_rgb) {
+  __shared__ float hom[MPI_MAX_PLANES][9];
+  const int b = blockIdx.z;
+  const int tid = threadIdx.y * 64 + threadIdx.x;
+  if (tid < nd) {
+    const float *P = tgt_pose + (size_t)b * 16;
+    const float *Ks = intrinsics + (size_t)b * 9, *Ki = intrinsics_inv + (size_t)b * 9;
+    float rt[3][3], t[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rt[r][c] = P[c * 4 + r];  // rot_t = transpose(pose[:3,:3])
+      t[r] = P[r * 4 + 3];
+    }
+    const float a = -depths[tid];
+    // n_hat = [0,0,1]: n_hat @ rot_t = row 2 of rot_t
+    const float nrt_t = (rt[2][0] * t[0] + rt[2][1] * t[1]) + rt[2][2] * t[2];
+    float den = a - nrt_t;
+    den += 1e-8f * (den == 0.0f ? 1.0f : 0.0f);  // divide_safe
+    float m1[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const float q = (rt[r][0] * t[0] + rt[r][1] * t[1]) + rt[r][2] * t[2];  // (rot_t @ t)[r]
+#pragma unroll
+      for (int c = 0; c < 3; ++c) m1[r][c] = rt[r][c] + (q * rt[2][c]) / den;
+    }
+    float m2[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        m2[r][c] = (Ks[r * 3 + 0] * m1[0][c] + Ks[r * 3 + 1] * m1[1][c]) + Ks[r * 3 + 2] * m1[2][c];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        hom[tid][r * 3 + c] = (m2[r][0] * Ki[0 * 3 + c] + m2[r][1] * Ki[1 * 3 + c]) + m2[r][2] * Ki[2 * 3 + c];
+  }
+  __syncthreads();
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  const int i = blockIdx.y * 4 + threadIdx.y;
+  if (j >= width || i >= height) return;
+  const float uu = (float)j, vv = (float)i;  // meshgrid_abs (projector.py:478-499)
+  const size_t hw = (size_t)height * width;
+  float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+  for (int d = 0; d < nd; ++d) {
+    const float *h = hom[d];
+    const float xs = (uu * h[0] + vv * h[1]) + 1.0f * h[2];
+    const float ys = (uu * h[3] + vv * h[4]) + 1.0f * h[5];
+    float ws = (uu * h[6] + vv * h[7]) + 1.0f * h[8];
+    ws += 1e-8f * (ws == 0.0f ? 1.0f : 0.0f);
+    const float x = xs / ws, y = ys / ws;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    // tf.contrib.resampler [TF-knowledge]: zero outside (-1, W) x (-1, H); missing corners are 0
+    if (x > -1.0f && y > -1.0f && x < (float)width && y < (float)height) {
+      const float fxf = floorf(x), fyf = floorf(y);
+      const int fx = (int)fxf, fy = (int)fyf, cx = fx + 1, cy = fy + 1;
+      const float dx = (float)cx - x, dy = (float)cy - y;
+      const float4 *L = rgba + ((size_t)b * nd + d) * hw;
+      const float4 a00 = fetch_or_zero(L, fx, fy, width, height), a11 = fetch_or_zero(L, cx, cy, width, height);
+      const float4 a01 = fetch_or_zero(L, fx, cy, width, height), a10 = fetch_or_zero(L, cx, fy, width, height);
+      const float w00 = dx * dy, w11 = (1.0f - dx) * (1.0f - dy), w01 = dx * (1.0f - dy), w10 = (1.0f - dx) * dy;
+      v.x = ((w00 * a00.x + w11 * a11.x) + w01 * a01.x) + w10 * a10.x;
+      v.y = ((w00 * a00.y + w11 * a11.y) + w01 * a01.y) + w10 * a10.y;
+      v.z = ((w00 * a00.z + w11 * a11.z) + w01 * a01.z) + w10 * a10.z;
+      v.w = ((w00 * a00.w + w11 * a11.w) + w01 * a01.w) + w10 * a10.w;
+    }
+    if (d == 0) {
+      o0 = v.x; o1 = v.y; o2 = v.z;
+    } else {
+      const float om = 1.0f - v.w;
+      o0 = v.x * v.w + o0 * om;
+      o1 = v.y * v.w + o1 * om;
+      o2 = v.z * v.w + o2 * om;
+    }
+  }
+  float *o = out_rgb + ((size_t)b * hw + (size_t)i * width + j) * 3;
+  o[0] = o0; o[1] = o1; o[2] = o2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msi_perspective_plane_sweep_f32(const float *image, const float *pose, const float *intrinsics,
+                                    const float *depths, int32_t batch, int32_t height, int32_t width,
+                                    int32_t num_depths, float *psv, int32_t psv_channels,
+                                    int32_t channel_offset, msi_stream_t stream) {
+  MSI_REQUIRE(image && pose && intrinsics && depths && psv, "perspective_plane_sweep: null pointer");
+  MSI_REQUIRE(batch >= 0 && height > 1 && width > 1 && num_depths > 0, "perspective_plane_sweep: bad dims");
+  MSI_REQUIRE(channel_offset >= 0 && channel_offset + 3 * num_depths <= psv_channels,
+              "perspective_plane_sweep: channel window outside %d channels", psv_channels);
+  if (batch == 0) return MSI_OK;
+  MSI_REQUIRE((long)width * num_depths < 2147483647L && height <= 65535 && batch <= 65535,
+              "perspective_plane_sweep: problem too large");
+  const dim3 grid((unsigned)(((long)width * num_depths + 255) / 256), height, batch);
+  const UvGrid gs = uv_grid(width), gt = uv_grid(height);
+  const unsigned magic = udiv_magic32(num_depths);
+  const int nt = beyond_infinity_cache((size_t)batch * height * width * psv_channels * 4) ? 1 : 0;
+  // full waves of complete pixels whose 3 D-float runs are 16-byte aligned, 32-bit byte offsets into one face
+  const bool fast = 64 % num_depths == 0 && ((long)width * num_depths) % 256 == 0 && (3 * num_depths) % 4 == 0 && psv_channels % 4 == 0 && channel_offset % 4 == 0 &&
+                    (long)height * width * 12 < 2147483647L && num_depths >= 4;
+  if (fast)
+    hipLaunchKernelGGL(pp_sweep_kernel<1>, grid, dim3(256), 0, msi::as_stream(stream), image, pose,
+                       intrinsics, depths, batch, height, width, num_depths, gs.start, gs.step, gt.start, gt.step,
+                       psv, psv_channels, channel_offset, magic, nt);
+  else
+    hipLaunchKernelGGL(pp_sweep_kernel<0>, grid, dim3(256), 0, msi::as_stream(stream), image, pose,
+                       intrinsics, depths, batch, height, width, num_depths, gs.start, gs.step, gt.start, gt.step,
+                       psv, psv_channels, channel_offset, magic, nt);
+  return msi::check_launch("perspective_plane_sweep");
+}
+
+int msi_perspective_sweep_volume_bf16(const float *ref_image, const float *src_image, const float *ref_curr_pose,
+                                      const float *src_curr_pose, const float *intrinsics, const float *depths,
+                                      int32_t batch, int32_t height, int32_t width, int32_t num_depths,
+                                      void *psv_bf16, msi_stream_t stream) {
+  MSI_REQUIRE(ref_image && src_image && ref_curr_pose && src_curr_pose && intrinsics && depths && psv_bf16,
+              "perspective_sweep_volume_bf16: null pointer");
+  MSI_REQUIRE(batch >= 0 && height > 1 && width > 1 && num_depths > 0, "perspective_sweep_volume_bf16: bad dims");
+  if (batch == 0) return MSI_OK;
+  MSI_REQUIRE((long)width * num_depths < 2147483647L && height <= 65535 && batch <= 65535 && (long)height * width * 12 < 2147483647L,
+              "perspective_sweep_volume_bf16: problem too large");
+  const dim3 grid((unsigned)(((long)width * num_depths + 255) / 256), height, batch);
+  const UvGrid gs = uv_grid(width), gt = uv_grid(height);
+  const int nt = beyond_infinity_cache((size_t)batch * height * width * 6 * num_depths * 2) ? 1 : 0;
+  int shift = 0;
+  while ((1 << shift) < num_depths) ++shift;
+  // whole waves of complete pixels (D a power of two up to 64), 16-byte-aligned volume
+  const bool fast = 64 % num_depths == 0 && ((long)width * num_depths) % 64 == 0 && reinterpret_cast<uintptr_t>(psv_bf16) % 16 == 0;
+  unsigned short *psv = static_cast<unsigned short *>(psv_bf16);
+#define MSI_LAUNCH_PPV(FAST_, NT_)                                                                                                        \
+  hipLaunchKernelGGL((pp_sweep_volume_bf16_kernel<FAST_, NT_>), grid, dim3(256), 0, msi::as_stream(stream), ref_image, src_image,       \
+                     ref_curr_pose, src_curr_pose, intrinsics, depths, height, width, num_depths, shift, gs.start, gs.step, gt.start, gt.step, psv)
+  if (fast && nt)
+    MSI_LAUNCH_PPV(1, 1);
+  else if (fast)
+    MSI_LAUNCH_PPV(1, 0);
+  else
+    MSI_LAUNCH_PPV(0, 0);
+#undef MSI_LAUNCH_PPV
+  return msi::check_launch("perspective_sweep_volume_bf16");
+}
+
+int msi_mpi_render_f32(const float *rgba_native, const float *tgt_pose, const float *intrinsics,
+                       const float *intrinsics_inv, const float *depths, int32_t batch, int32_t height,
+                       int32_t width, int32_t num_planes, float *out_rgb, msi_stream_t stream) {
+  MSI_REQUIRE(rgba_native && tgt_pose && intrinsics && intrinsics_inv && depths && out_rgb, "mpi_render: null pointer");
+  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "mpi_render: bad dims");
+  if (num_planes > MPI_MAX_PLANES)
+    return msi::fail(MSI_E_UNSUPPORTED, "mpi_render: at most %d planes", MPI_MAX_PLANES);
+  if (batch == 0) return MSI_OK;
+  const dim3 grid((width + 63) / 64, (height + 3) / 4, batch), block(64, 4);
+  hipLaunchKernelGGL(mpi_render_kernel, grid, block, 0, msi::as_stream(stream),
+                     reinterpret_cast<const float4 *>(rgba_native), tgt_pose, intrinsics, intrinsics_inv, depths, batch,
+                     height, width, num_planes, out_rgb);
+  return msi::check_launch("mpi_render");
+}
+
+}  // extern "C"

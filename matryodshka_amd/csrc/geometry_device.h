@@ -1,0 +1,408 @@
+// Shared by the translation units of the geometry-side kernels of the MSI infer->render path for gfx950 (HBM-bound), one unit per kernel family:
+//   geo_prep.hip    K5 pre/deprocess (single and pair), pose composition, the host-built trig tables
+//   geo_sweep.hip   K1 ODS sphere sweep: ods_sweep_kernel, ods_sweep_lds_kernel
+//   geo_layers.hip  K3 RGBA assembly, bilinear resize, the fused high-res layer stack, pack / unpack of the compact stacks
+//   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed sibling
+//   geo_planar.hip  the PP path: perspective plane sweeps and the MPI render
+// Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
+// sharing is a contract.  What a single family uses lives in that family's unit.
+//
+// Every unit that includes this header is compiled with -ffp-contract=off (build.py GEO_UNITS): the reference evaluates every
+// elementwise TF op separately in fp32 (no FMA contraction), and project_ods'
+// discriminant is ill-conditioned enough that a contracted
+// multiply-add flips the `disc >= 0` branch on ~1% of far-plane pixels.  With the
+// reference's operation order, IEEE sqrt/div (hipcc default) and the host-built
+// trig tables, every branch below is bit-reproducible against the CPU oracle.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+
+#include "msi_common.h"
+
+namespace {
+
+// ---- sweep, layers (hres_layers_kernel), render, planar: the pixel-coordinate constants, the wrap-around bilinear taps and the fast continuous tail.
+// Contract: a sample position and its four corner weights have the same bits in every kernel that resamples an image or a layer.
+// fp32 constants the reference folds from Python doubles (spherical.py:54-68,
+// :222-223), rounded once on the host.
+struct PixConsts {
+  float pi, pi_over_w, u_den, wm1;          // u = ((theta + pi) - pi/W) / (2pi - 2pi/W) * (W-1)
+  float half_pi, half_pi_over_h, v_den, hm1;  // v = ((phi + pi/2) - (pi/2)/H) / (pi - pi/H) * (H-1)
+  float u_scale, v_scale;                   // (W-1) / u_den, (H-1) / v_den, rounded once from fp64 (fast tail)
+};
+
+PixConsts make_consts(int height, int width) {
+  const double PI = 3.14159265358979323846;
+  PixConsts k;
+  k.pi = (float)PI;
+  k.pi_over_w = (float)(PI / width);
+  k.u_den = (float)(2 * PI - 2 * PI / width);
+  k.wm1 = (float)(width - 1);
+  k.half_pi = (float)(0.5 * PI);
+  k.half_pi_over_h = (float)(0.5 * PI / height);
+  k.v_den = (float)(PI - PI / height);
+  k.hm1 = (float)(height - 1);
+  k.u_scale = (float)((double)(width - 1) / (2 * PI - 2 * PI / width));
+  k.v_scale = (float)((double)(height - 1) / (PI - PI / height));
+  return k;
+}
+
+// tf.mod on int32 = floor-mod.  Pixel coordinates that come out of the angle formulas lie in
+// [-1, n], so the index (a = x + n) is in [n-1, 2n]: one conditional subtract; anything else (only
+// reachable through NaN/inf garbage) takes the generic integer-division path (~20 instructions,
+// which used to be paid 4x per bilinear lookup).
+__device__ __forceinline__ int floor_mod(int a, int n) {
+  if (a >= 0 && a < 2 * n) return a >= n ? a - n : a;
+  int m = a % n;
+  return m < 0 ? m + n : m;
+}
+
+// Corner indices and area weights of sampling.resample (sampling.py:150-165,
+// 187-190): weights from the UNWRAPPED corners, indices wrapped in both axes.
+struct Taps {
+  int x0, x1, y0, y1;
+  float wa, wb, wc, wd;
+};
+
+__device__ __forceinline__ Taps make_taps(float x, float y, int width, int height) {
+  Taps t;
+  const float fx0 = floorf(x), fy0 = floorf(y);
+  const int x0 = (int)fx0, y0 = (int)fy0;
+  const int x1 = x0 + 1, y1 = y0 + 1;
+  const float dx0 = x - (float)x0, dy0 = y - (float)y0;
+  const float dx1 = (float)x1 - x, dy1 = (float)y1 - y;
+  t.x0 = floor_mod(x0 + width, width);
+  t.y0 = floor_mod(y0 + height, height);
+  t.x1 = floor_mod(x1 + width, width);
+  t.y1 = floor_mod(y1 + height, height);
+  t.wa = dy1 * dx1;
+  t.wb = dy1 * dx0;
+  t.wc = dy0 * dx1;
+  t.wd = dy0 * dx0;
+  return t;
+}
+
+// make_taps for coordinates that lie in [-1, n] by construction -- the sweep and the render derive them from angles
+// (theta in [-pi, pi], phi clamped / in [-pi/2, pi/2]  =>  u in [-0.5, W-0.5], v in [-0.5, H-0.5]) -- so the floor-mod
+// is one unsigned min per corner, nothing branches, and the corner positions are 24-bit pixel offsets (row * W + col,
+// full-rate v_mul_u32_u24; the host checks H * W < 2^24) for 32-bit buffer addressing: the generic form above spent
+// a quarter of these VALU-bound kernels in 64-bit address multiplies and exec-masked division fall-backs.
+// Weights as above (unwrapped corners; (float)(int)floor(x) == floor(x) in this range); garbage inputs (NaN -> 0, inf)
+// are clamped into the image instead of taking the reference's undefined int cast.
+struct TapsR {
+  unsigned oa, ob, oc, od;   // pixel offsets of (y0,x0) (y0,x1) (y1,x0) (y1,x1)
+  float wa, wb, wc, wd;
+};
+
+__device__ __forceinline__ TapsR make_taps_ranged(float x, float y, int width, int height) {
+  TapsR t;
+  const float fx0 = floorf(x), fy0 = floorf(y);
+  const float dx0 = x - fx0, dy0 = y - fy0;
+  const float dx1 = (fx0 + 1.0f) - x, dy1 = (fy0 + 1.0f) - y;
+  t.wa = dy1 * dx1;
+  t.wb = dy1 * dx0;
+  t.wc = dy0 * dx1;
+  t.wd = dy0 * dx0;
+  const int x0 = max(-1, min((int)fx0, width - 1)), y0 = max(-1, min((int)fy0, height - 1));
+  const unsigned ax = (unsigned)(x0 + width), ay = (unsigned)(y0 + height);
+  const unsigned x0w = min(ax, ax - (unsigned)width), y0w = min(ay, ay - (unsigned)height);   // -1 -> n-1
+  const unsigned bx = (unsigned)(x0 + 1), by = (unsigned)(y0 + 1);
+  const unsigned x1w = min(bx, bx - (unsigned)width), y1w = min(by, by - (unsigned)height);   // n -> 0
+  const unsigned r0 = __umul24(y0w, (unsigned)width), r1 = __umul24(y1w, (unsigned)width);
+  t.oa = r0 + x0w; t.ob = r0 + x1w; t.oc = r1 + x0w; t.od = r1 + x1w;
+  return t;
+}
+
+__device__ __forceinline__ float blend4(const TapsR &t, float a, float b, float c, float d) {
+  return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;
+}
+
+__device__ __forceinline__ float blend4(const Taps &t, float a, float b, float c, float d) {
+  // tf.add_n([area_a*A, area_b*B, area_c*C, area_d*D]) summed in list order.
+  return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;
+}
+
+// ---- the CONTINUOUS tail of the angle math ----------------------------------------------------------
+// Everything that feeds a branch of the reference (|z| > |x|, sign(pz), disc >= 0: the quadratic of project_ods up
+// to `disc`) is evaluated op for op in IEEE fp32 above / below.  What follows the branches -- the root, the direction,
+// the two angles and the pixel coordinates -- is a continuous function of its inputs, so 1-ulp primitives
+// (v_rcp_f32 + one Newton step, v_sqrt_f32, a degree-7 odd minimax atan, 1.3e-7 rad) move a sample by <= 2e-5 px,
+// i.e. the bilinear result by ~1e-5 of the image range (tolerance 1e-3), and cost a third of the IEEE sequences
+// (the sweep and the render are VALU-bound: ~470 / ~260 instructions per sample with libm atan2f and IEEE
+// divide / sqrt, profiles/r01_*).  -DMSI_FAST_TAIL=0 restores the IEEE / libm tail.
+#ifndef MSI_FAST_TAIL
+#define MSI_FAST_TAIL 1
+#endif
+
+__device__ __forceinline__ float t_sqrt(float x) {
+#if MSI_FAST_TAIL
+  return __builtin_amdgcn_sqrtf(x);
+#else
+  return sqrtf(x);
+#endif
+}
+
+__device__ __forceinline__ float t_div(float a, float b) {
+#if MSI_FAST_TAIL
+  const float r = __builtin_amdgcn_rcpf(b);
+  const float q = a * r;
+  return __builtin_fmaf(__builtin_fmaf(-q, b, a), r, q);   // one correction step: <= 1 ulp for normal operands
+#else
+  return a / b;
+#endif
+}
+
+__device__ __forceinline__ float t_atan2(float y, float x) {
+#if MSI_FAST_TAIL
+  const float ax = fabsf(x), ay = fabsf(y);
+  const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
+  float a = mn * __builtin_amdgcn_rcpf(mx);
+  a = (mx == 0.0f) ? 0.0f : a;                                // atan2(+-0, +-0) = +-0 / +-pi like libm
+  const float s = a * a;
+  float p = -0.0040545277297496796f;
+  p = __builtin_fmaf(p, s, 0.021862812340259552f);
+  p = __builtin_fmaf(p, s, -0.05591211095452309f);
+  p = __builtin_fmaf(p, s, 0.09642180800437927f);
+  p = __builtin_fmaf(p, s, -0.13908623158931732f);
+  p = __builtin_fmaf(p, s, 0.19946564733982086f);
+  p = __builtin_fmaf(p, s, -0.33329859375953674f);
+  p = __builtin_fmaf(p, s, 0.9999993443489075f);
+  float r = p * a;
+  r = (ay > ax) ? 1.57079632679489662f - r : r;
+  r = (x < 0.0f || (x == 0.0f && __builtin_signbitf(x))) ? 3.14159265358979324f - r : r;
+  r = (mx != mx || mn != mn) ? __builtin_nanf("") : r;        // NaN in -> NaN out (the callers test for it)
+  return __builtin_copysignf(r, y);
+#else
+  return atan2f(y, x);
+#endif
+}
+
+// atan on [-1, 1] (the polynomial of t_atan2 without its range reduction) and the two angles of a point (x, y, z) with
+// horizontal distance h = sqrt(x^2 + z^2) and norm R through half-angle forms, tan(a / 2) = sin a / (1 + cos a):
+//   atan2(y, h) = 2 atan(y / (h + R))                       (|phi| <= pi/2: the argument is in [-1, 1] as it is)
+//   atan2(z, x) = 2 atan(z / (h + x))            for x >= 0,
+//               = copysign(pi, z) - 2 atan(z / (h - x))  for x < 0   (both arguments in [-1, 1])
+// -- no min / max / swap range reduction, no quadrant fix-ups, one shared square root: ~14 instead of ~30 instructions
+// per angle in the render kernel, which is bound by its VALU stream.  Same 1.3e-7 rad polynomial (doubled: 2.6e-7 rad =
+// 3e-5 px at W = 640); atan2(+-0, +-0) = +-0 like libm's for (+0, +0).  Used by the render kernel (no data-dependent reference
+// branch in its chain, finite inputs) and, since r04, by the sweep's continuous tail (ods_tail): there the angles feed floor() of
+// the pixel coordinates, so a sample within 3e-5 px of an integer may take the neighbouring tap pair -- with weights (1 - eps, eps)
+// against (eps', 1 - eps') on the same two texels, i.e. the bilinear value moves by <= 3e-5 of a texel difference (the resample is
+// continuous across tap boundaries); the reference's branch-deciding values (disc, |z| > |x|, sign(pz)) are computed before this,
+// IEEE op for op.  NaN inputs (disc < 0 pixels) produce NaN / garbage angles that ods_tail overrides as the reference does.
+__device__ __forceinline__ float t_atan_unit(float a) {
+  const float s = a * a;
+  float p = -0.0040545277297496796f;
+  p = __builtin_fmaf(p, s, 0.021862812340259552f);
+  p = __builtin_fmaf(p, s, -0.05591211095452309f);
+  p = __builtin_fmaf(p, s, 0.09642180800437927f);
+  p = __builtin_fmaf(p, s, -0.13908623158931732f);
+  p = __builtin_fmaf(p, s, 0.19946564733982086f);
+  p = __builtin_fmaf(p, s, -0.33329859375953674f);
+  p = __builtin_fmaf(p, s, 0.9999993443489075f);
+  return p * a;
+}
+
+__device__ __forceinline__ void t_angles(float x, float y, float z, float R, float &theta_neg, float &phi) {
+#if defined(MSI_RENDER_OLD_ANGLES)   // (A/B: the r03 form, two range-reduced atan2)
+  theta_neg = -t_atan2(z, x);
+  phi = t_atan2(y, t_sqrt(x * x + z * z));
+#elif MSI_FAST_TAIL
+  const float h = __builtin_amdgcn_sqrtf(x * x + z * z);
+  const float den = fmaxf(h + fabsf(x), 1.17549435e-38f);               // (x = z = 0: 0 / tiny = 0)
+  const float a2 = 2.0f * t_atan_unit(z * __builtin_amdgcn_rcpf(den));
+  const float th = __builtin_signbitf(x) ? __builtin_copysignf(3.14159265358979324f, z) - a2 : a2;
+  theta_neg = -th;
+  phi = 2.0f * t_atan_unit(y * __builtin_amdgcn_rcpf(h + R));
+#else
+  theta_neg = -atan2f(z, x);
+  phi = atan2f(y, sqrtf(x * x + z * z));
+#endif
+}
+
+// ---- sweep, layers (assemble_kernel reads the bf16 volume), planar: ONE bf16 rounding for every kernel that writes or reads a bf16 volume.
+// fp32 <-> bf16 (round to nearest even; the values stored here are finite)
+__device__ __forceinline__ unsigned short f32_to_bf16(float f) {
+  const unsigned u = __builtin_bit_cast(unsigned, f);
+  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ float bf16_to_f32(unsigned short h) {
+  return __builtin_bit_cast(float, (unsigned)h << 16);
+}
+__device__ __forceinline__ void store_elem(float *p, size_t i, float v) { p[i] = v; }
+__device__ __forceinline__ void store_elem(unsigned short *p, size_t i, float v) { p[i] = f32_to_bf16(v); }
+
+// ---- sweep and layers: hres_layers_kernel must produce the bits of ods_sweep_kernel -> resize -> assemble, so it runs THESE functions, op for op.
+// ------------------------------------------------------------------------ K1
+// project_ods (spherical.py:181-229) in two parts.
+// (1) ods_quad: everything up to the discriminant, op for op in IEEE fp32 (no contraction: every unit that includes this header is compiled with
+//     -ffp-contract=off) -- it decides the reference's three branches (|z| > |x|, sign(pz), disc >= 0), and `disc` is
+//     ill conditioned, so not one rounding may differ from the oracle here.
+// (2) ods_tail: root, ray direction, angles, pixel coordinates -- continuous in (a, bq, f, px, pz, disc), evaluated
+//     with the 1-ulp primitives above.  It is the only part that depends on `order`, so when both sources of the sweep
+//     volume have the same pose (the test path: identity poses, msi.py:1125) they share (1).
+struct OdsQuad {
+  float f, px, pz, a, bq, disc, y;
+  bool zlx;
+};
+
+__device__ __forceinline__ OdsQuad ods_quad(const float *__restrict__ P, float r, float depth, float csct, float st, float ssct) {
+  OdsQuad q;
+  // backproject_spherical (spherical.py:125-128)
+  float x = depth * csct;
+  float y = depth * st;
+  float z = depth * ssct;
+  // apply_pose (projector.py:275-291): pose @ [x,y,z,1], terms summed left to right
+  const float px_ = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
+  const float py_ = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
+  const float pz_ = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
+  x = px_;
+  y = py_;
+  z = pz_;
+  // project_ods (spherical.py:181-192)
+  q.f = r * r - (x * x + z * z);
+  q.zlx = fabsf(z) > fabsf(x);
+  q.px = q.zlx ? x : z;
+  q.pz = q.zlx ? z : x;
+  const float pz2 = q.pz * q.pz;
+  q.a = 1.0f + (q.px * q.px) / pz2;
+  q.bq = ((-2.0f * q.f) * q.px) / pz2;
+  const float c = q.f + (q.f * q.f) / pz2;
+  q.disc = q.bq * q.bq - (4.0f * q.a) * c;
+  q.y = y;
+  return q;
+}
+
+// (spherical.py:195-229) -> pixel coordinates (u, v); (1, 1) where disc < 0 or NaN
+__device__ __forceinline__ void ods_tail(const OdsQuad &q, float order, const PixConsts &K, float &u, float &v) {
+  const float sgn = (q.pz > 0.0f) ? 1.0f : ((q.pz < 0.0f) ? -1.0f : q.pz);
+  float s = ((-order) * sgn) * t_sqrt(q.disc);
+  s = q.zlx ? s : -s;
+  float dx = t_div(-q.bq + s, 2.0f * q.a);
+  float dz = t_div(q.f - q.px * dx, q.pz);
+  const float dxf = q.zlx ? -dx : -dz;
+  const float dzf = q.zlx ? -dz : -dx;
+  dx = dxf;
+  dz = dzf;
+#if MSI_FAST_TAIL && !defined(MSI_SWEEP_OLD_ANGLES)
+  // (r04: the render kernel's half-angle forms -- one square root more, two range reductions less; where disc < 0 everything
+  // here is NaN or garbage and the override below applies, as before)
+  float theta, phi;
+  t_angles(dx, q.y, dz, t_sqrt((dx * dx + dz * dz) + q.y * q.y), theta, phi);
+#else
+  const float theta = -t_atan2(dz, dx);
+  float phi = t_atan2(q.y, t_sqrt(dx * dx + dz * dz));
+#endif
+  if (phi != phi) phi = 1.0f;
+  phi = (phi <= K.half_pi) ? phi : K.half_pi;
+  phi = (phi >= -K.half_pi) ? phi : -K.half_pi;
+#if MSI_FAST_TAIL
+  u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
+  v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
+#else
+  u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
+  v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
+#endif
+  if (!(q.disc >= 0.0f)) {
+    u = 1.0f;
+    v = 1.0f;
+  }
+}
+
+// resample (sampling.py:135-197) of one RGB texel; `img` = buffer descriptor of one sample's [H,W,3] image.
+// The four corners as BYTE offsets (pixel offset x 12, 24-bit multiply) + area weights: everything of a sample that does
+// not depend on the image -- kept in registers while the frames of a batch that share (pose, baseline) are gathered.
+typedef unsigned u32x3_g __attribute__((ext_vector_type(3)));
+typedef float f32x3_g __attribute__((ext_vector_type(3)));
+struct TapsB {
+  unsigned oa, ob, oc, od;
+  float wa, wb, wc, wd;
+};
+__device__ __forceinline__ TapsB make_taps_bytes(float u, float v, int width, int height) {
+  const TapsR t = make_taps_ranged(u, v, width, height);
+  TapsB r;
+  r.oa = __umul24(t.oa, 12u); r.ob = __umul24(t.ob, 12u); r.oc = __umul24(t.oc, 12u); r.od = __umul24(t.od, 12u);
+  r.wa = t.wa; r.wb = t.wb; r.wc = t.wc; r.wd = t.wd;
+  return r;
+}
+__device__ __forceinline__ float blend4(const TapsB &t, float a, float b, float c, float d) {
+  return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;   // tf.add_n order (sampling.py:187-190)
+}
+__device__ __forceinline__ void gather3(__amdgpu_buffer_rsrc_t img, const TapsB &t, float *out) {
+  const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oa, 0, 0));
+#ifdef MSI_SWEEP_ABLATE_TAPS   // timing experiment only (wrong volume): two of the four corner loads
+  const f32x3_g b = a;
+  const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oc, 0, 0));
+  const f32x3_g d = c;
+#else
+  const f32x3_g b = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.ob, 0, 0));
+  const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oc, 0, 0));
+  const f32x3_g d = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.od, 0, 0));
+#endif
+  out[0] = blend4(t, a.x, b.x, c.x, d.x);
+  out[1] = blend4(t, a.y, b.y, c.y, d.y);
+  out[2] = blend4(t, a.z, b.z, c.z, d.z);
+}
+
+// ---- sweep, layers (pack / unpack / hres) and planar: the 16-byte store of every streaming kernel; its host side is beyond_infinity_cache below.
+// The 16-byte pieces of a wave's whole-pixel strip.  nt != 0 (block-uniform; the host sets it when the volume is larger than the 256-MB Infinity Cache): non-temporal
+// stores -- a volume that cannot stay cached until conv1_1 reads it should not evict what can (r06, same-box A/B at configs[2]: sweep 1.07 -> 0.98 ms per 16 frames;
+// configs[3] -1 %; at batch 1 the 157-MB volume stays cached and keeps plain stores).  -DMSI_SWEEP_ABLATE_STORE: timing experiment only (no stores at all).
+__device__ __forceinline__ void sweep_store16(uint4 *dst, const uint4 &v, int nt) {
+#ifdef MSI_SWEEP_ABLATE_STORE
+  if (nt < 0) *dst = v;
+#else
+  if (nt) {
+    __builtin_nontemporal_store(v.x, &dst->x); __builtin_nontemporal_store(v.y, &dst->y); __builtin_nontemporal_store(v.z, &dst->z); __builtin_nontemporal_store(v.w, &dst->w);
+  } else {
+    *dst = v;
+  }
+#endif
+}
+
+// ---- render (render_views_packed_kernel) and layers (unpack_layers_kernel): ONE decode rule, so a render from a packed stack is bit-identical to
+// msi_render_views_f32 on the unpacked one.
+constexpr float RGBA8_KC = 0x1.010102p-7f;   // fl32(1 / 127.5)
+constexpr float RGBA8_KA = 0x1.010102p-8f;   // fl32(1 / 255)
+// (half4_g, u32x2_g and the encoders rgba8_encode / rgba16f_encode: msi_common.h, shared with the fused tail of cnn_tail.hip)
+
+__device__ __forceinline__ float4 rgba8_decode(unsigned q) {   // (the byte picks compile to v_cvt_f32_ubyte0..3)
+  float4 t;
+  t.x = ((float)(q & 0xffu) - 127.5f) * RGBA8_KC;
+  t.y = ((float)((q >> 8) & 0xffu) - 127.5f) * RGBA8_KC;
+  t.z = ((float)((q >> 16) & 0xffu) - 127.5f) * RGBA8_KC;
+  t.w = (float)(q >> 24) * RGBA8_KA;
+  return t;
+}
+
+__device__ __forceinline__ float4 rgba16f_decode(u32x2_g q) {
+  const half4_g h = __builtin_bit_cast(half4_g, q);
+  float4 t;
+  t.x = (float)h.x; t.y = (float)h.y; t.z = (float)h.z; t.w = (float)h.w;
+  return t;
+}
+
+// ---- host helpers -------------------------------------------------------------------------------------------------------------
+// every family with a 1-D grid-stride kernel (prep, layers)
+int grid_1d(size_t n) {
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride the rest
+  if (blocks == 0) blocks = 1;
+  return (int)blocks;
+}
+
+// sweep, layers, planar: non-temporal stores (sweep_store16 and its siblings) for a destination that cannot stay in the 256-MiB Infinity Cache anyway
+bool beyond_infinity_cache(size_t bytes) { return bytes > ((size_t)256 << 20); }
+
+// render (RAY_PERSPECTIVE) and planar: spherical.uv_grid (spherical.py:46-48) = tf.linspace(-1 + 1/n, 1 - 1/n, n) with its fp32 semantics; v[i] = start + step * i
+struct UvGrid { float start, step; };
+UvGrid uv_grid(int n) {
+  const float s0 = (float)(-1.0 + 1.0 / n), s1 = (float)(1.0 - 1.0 / n);
+  return UvGrid{s0, (s1 - s0) / (float)(n - 1)};
+}
+
+// sweep and planar: x / n = __umulhi(x, magic) (+ one correction in the kernel), see cnn.hip udiv_magic
+unsigned udiv_magic32(int n) { return n == 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)n); }
+
+}  // namespace

@@ -23,7 +23,7 @@ inline int check_launch(const char *what) {
 }  // namespace msi
 
 // ---- the texel encoders of the compact layer formats (MSI_LAYERS_RGBA8 / MSI_LAYERS_RGBA16F; the rule is stated in msi_hip.h) ----
-// ONE definition for every kernel that writes a packed texel: pack_layers_kernel (geometry.hip) and the packed forms of the fused
+// ONE definition for every kernel that writes a packed texel: pack_layers_kernel (geo_layers.hip) and the packed forms of the fused
 // tail (cnn_tail.hip).  fp32 arithmetic with one rounding per operation: the bodies switch contraction off themselves, so that a
 // unit compiled without -ffp-contract=off inlines the same operations.
 // NaN inputs of the rgba8 encoder (outside the contract): fmaxf returns its other operand, so a NaN channel encodes as code 0.

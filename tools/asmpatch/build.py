@@ -5,6 +5,8 @@ new fat binary into the host assembly and link tools/_variants/libmsi_<name>.so.
 Patches are functions in tools/asmpatch/patches.py: name(lines_of_the_kernel) -> new lines."""
 import argparse, os, re, subprocess, sys, importlib.util
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from matryodshka_amd import build
 W = "/tmp/asmpatch"
 LLVM = "/opt/rocm/lib/llvm/bin"
 ap = argparse.ArgumentParser()
@@ -56,6 +58,6 @@ for name in a.names:
     run([LLVM + "/clang", "-cc1as", "-triple", "x86_64-unknown-linux-gnu", "-filetype", "obj", "-main-file-name", "cnn.hip", "-target-cpu", "x86-64", "-mrelocation-model", "pic", "-o", "%s/cnn_%s.o" % (W, name), hp])
     os.makedirs(ROOT + "/tools/_variants", exist_ok=True)
     run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", "%s/tools/_variants/libmsi_%s.so" % (ROOT, name),
-         ROOT + "/matryodshka_amd/csrc/_obj/common.o", ROOT + "/matryodshka_amd/csrc/_obj/geometry.o", "%s/cnn_%s.o" % (W, name)] +
-        [ROOT + "/matryodshka_amd/csrc/_obj/" + u[:-4] + ".o" for u in ("cnn.hip", "cnn_igemm.hip", "cnn_halo.hip", "cnn_x3.hip", "cnn_bf16.hip", "cnn_tail.hip") if u != a.unit])
+         "%s/cnn_%s.o" % (W, name)] +
+        [os.path.join(build.OBJ_DIR, os.path.splitext(u)[0] + ".o") for u, _ in build.SOURCES if u != a.unit])   # (every other unit: the objects of the installed build)
     print("built", name, "(%d -> %d lines)" % (k1 - k0, len(body)))

@@ -19,7 +19,8 @@ def snapshot(lib):
             if m:
                 cur = m.group(1); out.setdefault(cur, []); continue
             ins = line.split("//")[0].strip()
-            if cur and ins and not ins.startswith("s_nop") and not ins.startswith("s_code_end"):
+            # ("...": objdump's line for the zero padding behind the last kernel of a code object -- not an instruction of whichever kernel comes last in its unit)
+            if cur and ins and ins != "..." and not ins.startswith("s_nop") and not ins.startswith("s_code_end"):
                 ins = re.sub(r"\b(s_cbranch_\w+|s_branch)\s+\S+", r"\1 L", ins)
                 out[cur].append(ins)
     return out

@@ -1,4 +1,4 @@
-// Bit-equality of the shared-reciprocal division of geometry.hip (div3_shared) with the compiler's IEEE fp32 `/` on the device:
+// Bit-equality of the shared-reciprocal division once tried in the geometry kernels (div3_shared; today csrc/geo_*.hip) with the compiler's IEEE fp32 `/` on the device:
 //   (a) 2^33 pseudo-random operand pairs with the denominator in [2^-30, 2^30] and the numerator zero or in [2^-60, 2^60] (either sign),
 //   (b) every denominator significand (2^23) x 16 exponents x 8 numerators.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off div_shared.hip -o div_shared && ./div_shared
