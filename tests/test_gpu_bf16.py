@@ -12,6 +12,7 @@ Tolerances (stated here because north_star's 1e-3 is the fp32 gate):
 import numpy as np
 import pytest
 
+from tests.util import make_inputs, poison_workspace, read_raw_output
 pytestmark = pytest.mark.gpu
 
 
@@ -33,14 +34,15 @@ def test_bf16_net_matches_bf16_oracle(env, coord, b, h, w, cin, nout, ngf):
     rng = np.random.RandomState(4)
     x = onets.bf16_round(rng.uniform(-1, 1, size=(b, h, w, cin)).astype(np.float32))
     m = MSI(weights=weights, coord_net=coord, dtype='bf16')
+    poison_workspace(m, b, h, w, cin, nout, ngf)
     pred = m.run_net(torch.from_numpy(x).cuda().bfloat16(), nout, ngf).cpu().numpy()
     ref, acts = onets.forward(weights, x, coord_net=coord, return_activations=True, bf16=True)
     ref32 = onets.forward(weights, x, coord_net=coord)
-    from tests.util import read_raw_output
     desc, packed, ws = m._net(b, h, w, cin, nout, ngf)
     infos = nets.layer_infos(desc)
     raw = read_raw_output(ws, packed, infos[0], b, "bf16")
     o = acts["conv1_1/raw"]
+    assert np.isfinite(raw).all() and np.isfinite(pred).all()
     # the raw output is stored as fp16 (11 significand bits): 2^-11 relative to each value, i.e. <= 5e-4 of the layer scale
     assert np.abs(raw - o).max() <= 5e-4 * np.abs(o).max()
     err = np.abs(pred - ref)
@@ -58,9 +60,12 @@ def test_bf16_big_tile_matches_small_tile(env):
     from matryodshka_amd import _native as N
     m = MSI(weights=weights, coord_net=True, dtype='bf16')
     m.net_options[N.NET_OPT_BIGTILE] = 0
+    poison_workspace(m, b, h, w, cin, nout, ngf)
     small = m.run_net(x, nout, ngf).cpu().numpy()
     m.net_options[N.NET_OPT_BIGTILE] = 2
+    poison_workspace(m, b, h, w, cin, nout, ngf)
     big = m.run_net(x, nout, ngf).cpu().numpy()
+    assert np.isfinite(small).all() and np.isfinite(big).all()
     ref = onets.forward(weights, x.float().cpu().numpy(), coord_net=True, bf16=True)
     d = np.abs(big - small)
     assert d.max() <= 4e-2 and d.mean() <= 3e-3, (d.max(), d.mean())
@@ -70,7 +75,6 @@ def test_bf16_big_tile_matches_small_tile(env):
 
 def test_bf16_sweep_is_rounded_fp32_sweep(env):
     torch, MSI, nets, onets, OracleMSI = env
-    from tests.util import make_inputs
     b, h, w, d = 1, 32, 64, 8
     inp = make_inputs(11, b, h, w)
     m = MSI(dtype='bf16')
@@ -90,7 +94,6 @@ def test_bf16_sweep_is_rounded_fp32_sweep(env):
 def test_bf16_pipeline_config3_shapes(env):
     """D = 64 (Cin = 384, 128 head channels), batch 2, reduced image: infer + render through the bf16 path."""
     torch, MSI, nets, onets, OracleMSI = env
-    from tests.util import make_inputs
     b, h, w, d, ngf = 2, 32, 64, 64, 16
     inp = make_inputs(21, b, h, w)
     weights = onets.init_weights(6 * d, 2 * d, ngf=ngf, coord_net=True, seed=2, randomize_affine=True)
@@ -155,9 +158,9 @@ def test_bf16_every_layer_tracks_the_bf16_oracle(env):
     weights = onets.init_weights(cin, nout, ngf=ngf, coord_net=True, seed=17, randomize_affine=True)
     x = onets.bf16_round(np.random.RandomState(8).uniform(-1, 1, size=(b, h, w, cin)).astype(np.float32))
     m = MSI(weights=weights, coord_net=True, dtype="bf16")
+    poison_workspace(m, b, h, w, cin, nout, ngf)
     pred = m.run_net(torch.from_numpy(x).cuda().bfloat16(), nout, ngf).cpu().numpy()
     ref, acts = onets.forward(weights, x, coord_net=True, return_activations=True, bf16=True)
-    from tests.util import read_raw_output
     desc, packed, ws = m._net(b, h, w, cin, nout, ngf)
     report = {}
     for info in nets.layer_infos(desc):
@@ -165,6 +168,7 @@ def test_bf16_every_layer_tracks_the_bf16_oracle(env):
             continue
         name = info.name.decode()
         raw = read_raw_output(ws, packed, info, b, "bf16")
+        assert np.isfinite(raw).all(), name
         o = acts[name + "/raw"]
         scale = np.abs(o).max()
         err = np.abs(raw - o) / scale
@@ -192,7 +196,10 @@ def test_bf16_halo_patch_kernel_matches_tap_kernel_and_oracle(env, coord, b, h, 
     halo = MSI(weights=weights, coord_net=coord, dtype="bf16")
     tap = MSI(weights=weights, coord_net=coord, dtype="bf16")
     tap.net_options[N.NET_OPT_HALO] = 0
+    poison_workspace(halo, b, h, w, cin, nout, ngf)
+    poison_workspace(tap, b, h, w, cin, nout, ngf)
     p1, p0 = halo.run_net(xg, nout, ngf), tap.run_net(xg, nout, ngf)
+    assert bool(torch.isfinite(p1).all()) and bool(torch.isfinite(p0).all())
     plan = halo._plan(b, h, w, cin, nout, ngf)
     raw_layers = [i for i in range(17) if N.lib.msi_net_plan_layer_is_normalized(plan.handle, i) == 0]
     if ngf == 64 and h % 64 == 0:
@@ -222,7 +229,10 @@ def test_bf16_halo_kernel_eight_and_four_waves_agree(env, coord, b, h, w, cin, n
     w8 = MSI(weights=weights, coord_net=coord, dtype="bf16")
     w4 = MSI(weights=weights, coord_net=coord, dtype="bf16")
     w4.net_options[N.NET_OPT_BF16_WAVES] = 4
+    poison_workspace(w8, b, h, w, cin, nout, ngf)
+    poison_workspace(w4, b, h, w, cin, nout, ngf)
     p8, p4 = w8.run_net(xg, nout, ngf), w4.run_net(xg, nout, ngf)
+    assert bool(torch.isfinite(p8).all()) and bool(torch.isfinite(p4).all())
     d = (p8 - p4).abs()
     assert float(d.max()) <= 4e-2 and float(d.mean()) <= 3e-3, (float(d.max()), float(d.mean()))
     for _ in range(3):

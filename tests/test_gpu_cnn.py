@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests.util import poison_workspace
 pytestmark = pytest.mark.gpu
 _HEAD_FUSED = True   # default plan: the fp32 head applies conv8_2's LayerNorm itself (conv8_2's buffer stays raw)
 
@@ -28,6 +29,7 @@ def _run(env, b, h, w, cin, nout, ngf, coord, seed=0, options=None):
     x = rng.uniform(-1, 1, size=(b, h, w, cin)).astype(np.float32)
     m = MSI(weights=weights, coord_net=coord)
     m.net_options.update(options or {})
+    poison_workspace(m, b, h, w, cin, nout, ngf)     # (a tile nobody computes must not read back as an earlier model's output)
     pred = m.run_net(torch.from_numpy(x).cuda(), nout, ngf)
     torch.cuda.synchronize()
     ref, acts = onets.forward(weights, x, coord_net=coord, return_activations=True)
@@ -41,9 +43,11 @@ def _run(env, b, h, w, cin, nout, ngf, coord, seed=0, options=None):
         raw = ws[info.raw_offset:info.raw_offset + 4 * n].view(torch.float32).reshape(b, info.out_h, info.out_w, info.cout)
         name = info.name.decode()
         raws[name] = raw.cpu().numpy()
+        assert np.isfinite(raws[name]).all(), "%s: %d non-finite raw outputs" % (name, int((~np.isfinite(raws[name])).sum()))
         # a layer whose every consumer applies its LayerNorm while loading (the head, halo-patch layers) stays RAW in memory
         if N.lib.msi_net_plan_layer_is_normalized(plan.handle, li) == 0:
             acts[name] = acts[name + "/raw"]
+    assert bool(torch.isfinite(pred).all())
     return pred.cpu().numpy(), ref, raws, acts
 
 
@@ -143,15 +147,18 @@ def test_full_size_split_k_handoff_is_deterministic(env, dtype, batch):
     x = torch.rand((batch, 320, 640, 192), device="cuda") * 2 - 1
     if dtype == "bf16":
         x = x.bfloat16()
+    poison_workspace(m, batch, 320, 640, 192, 64, 64)
     ref = m.run_net(x, 64, 64).clone()
     assert bool(torch.isfinite(ref).all())
     for _ in range(20):
         assert torch.equal(m.run_net(x, 64, 64), ref)
     alt = MSI(weights=weights, coord_net=True, dtype=dtype)
     alt.net_options[N.NET_OPT_FIXUP_KERNEL] = 1
+    poison_workspace(alt, batch, 320, 640, 192, 64, 64)
     assert torch.equal(alt.run_net(x, 64, 64), ref)
     nosplit = MSI(weights=weights, coord_net=True, dtype=dtype)
     nosplit.net_options[N.NET_OPT_TAILSPLIT] = 0
+    poison_workspace(nosplit, batch, 320, 640, 192, 64, 64)
     tol = 2e-5 if dtype == "f32" else 4e-2      # unsplit tiles: another fp32 summation order only
     assert float((nosplit.run_net(x, 64, 64) - ref).abs().max()) <= tol
 
@@ -245,7 +252,10 @@ def test_halo_patch_kernel_matches_tap_kernel_and_oracle(env, coord, b, h, w, ci
     halo.net_options[N.NET_OPT_HALO] = halo_opt      # 5: the default; bit 1: + convt_halo_kernel on the conv-transposes (measured slower: opt-in)
     tap = MSI(weights=weights, coord_net=coord)
     tap.net_options[N.NET_OPT_HALO] = 0
+    poison_workspace(halo, b, h, w, cin, nout, ngf)
+    poison_workspace(tap, b, h, w, cin, nout, ngf)
     p1, p0 = halo.run_net(x, nout, ngf), tap.run_net(x, nout, ngf)
+    assert bool(torch.isfinite(p1).all()) and bool(torch.isfinite(p0).all())
     plan = halo._plan(b, h, w, cin, nout, ngf)
     raw_layers = [i for i in range(17) if N.lib.msi_net_plan_layer_is_normalized(plan.handle, i) == 0]
     if h % 32 == 0 and w % 128 == 0:                 # every level tiles into 4 x 16 patches:
@@ -261,6 +271,7 @@ def test_halo_patch_kernel_matches_tap_kernel_and_oracle(env, coord, b, h, w, ci
     fix = MSI(weights=weights, coord_net=coord)
     fix.net_options[N.NET_OPT_FIXUP_KERNEL] = 1
     fix.net_options[N.NET_OPT_HALO] = halo_opt
+    poison_workspace(fix, b, h, w, cin, nout, ngf)
     assert torch.equal(fix.run_net(x, nout, ngf), p1)
     if h * w <= 160 * 320:
         ref = onets.forward(weights, x.cpu().numpy(), coord_net=coord)

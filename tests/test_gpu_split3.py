@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.test_gpu_cnn import _run, env  # noqa: F401
+from tests.util import poison_workspace
 
 pytestmark = pytest.mark.gpu
 ALL = 0x3ffff
@@ -49,7 +50,9 @@ def test_split3_is_deterministic_and_fixup_launch_agrees(env, f16):
     m = MSI(weights=weights, coord_net=True)
     m.net_options[N.NET_OPT_F32_SPLIT3] = ALL
     m.net_options[N.NET_OPT_F32_SPLIT_F16] = f16
+    poison_workspace(m, b, h, w, cin, nout, ngf)
     first = m.run_net(x, nout, ngf).clone()
+    assert bool(torch.isfinite(first).all())
     for _ in range(10):
         assert torch.equal(m.run_net(x, nout, ngf), first)
     assert m.network_status() == 0
@@ -59,6 +62,7 @@ def test_split3_is_deterministic_and_fixup_launch_agrees(env, f16):
     f.net_options[N.NET_OPT_F32_SPLIT3] = ALL
     f.net_options[N.NET_OPT_F32_SPLIT_F16] = f16
     f.net_options[N.NET_OPT_FIXUP_KERNEL] = 1
+    poison_workspace(f, b, h, w, cin, nout, ngf)
     assert torch.equal(f.run_net(x, nout, ngf), first)
 
 

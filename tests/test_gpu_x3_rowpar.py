@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests.test_gpu_cnn import _run, env  # noqa: F401
+from tests.util import poison_workspace
 
 pytestmark = pytest.mark.gpu
 ALL = 0x3ffff
@@ -49,7 +50,9 @@ def test_row_parity_is_deterministic_and_fixup_launch_agrees(env):
     weights = onets.init_weights(cin, nout, ngf=ngf, coord_net=True, seed=9, randomize_affine=True)
     x = torch.rand((b, h, w, cin), device="cuda") * 2 - 1
     m = MSI(weights=weights, coord_net=True)
+    poison_workspace(m, b, h, w, cin, nout, ngf)
     first = m.run_net(x, nout, ngf).clone()
+    assert bool(torch.isfinite(first).all())
     for _ in range(20):
         assert torch.equal(m.run_net(x, nout, ngf), first)
     assert m.network_status() == 0
@@ -57,6 +60,7 @@ def test_row_parity_is_deterministic_and_fixup_launch_agrees(env):
     assert any(plan.layer_kernel(i)[2] > 0 and "conv_halo_x3_kernel<3," in plan.layer_kernel(i)[0] for i in range(17)), plan.kernels()
     f = MSI(weights=weights, coord_net=True)
     f.net_options[N.NET_OPT_FIXUP_KERNEL] = 1
+    poison_workspace(f, b, h, w, cin, nout, ngf)
     assert torch.equal(f.run_net(x, nout, ngf), first)
     # a height whose eighth is NOT a multiple of 8 rows keeps the plain tile (the option is a request, the plan decides)
     g = MSI(weights=weights, coord_net=True)

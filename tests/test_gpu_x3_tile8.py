@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests.test_gpu_cnn import _run, env  # noqa: F401
+from tests.util import poison_workspace
 
 pytestmark = pytest.mark.gpu
 ALL = 0x3ffff | (1 << 30)   # every eligible layer, whatever its grid size
@@ -41,7 +42,9 @@ def test_tile8_is_deterministic_and_fixup_launch_agrees(env):
     x = torch.rand((b, h, w, cin), device="cuda") * 2 - 1
     m = MSI(weights=weights, coord_net=True)
     m.net_options[N.NET_OPT_X3_TILE8] = ALL
+    poison_workspace(m, b, h, w, cin, nout, ngf)
     first = m.run_net(x, nout, ngf).clone()
+    assert bool(torch.isfinite(first).all())
     for _ in range(20):
         assert torch.equal(m.run_net(x, nout, ngf), first)
     assert m.network_status() == 0
@@ -50,4 +53,5 @@ def test_tile8_is_deterministic_and_fixup_launch_agrees(env):
     f = MSI(weights=weights, coord_net=True)
     f.net_options[N.NET_OPT_X3_TILE8] = ALL
     f.net_options[N.NET_OPT_FIXUP_KERNEL] = 1
+    poison_workspace(f, b, h, w, cin, nout, ngf)
     assert torch.equal(f.run_net(x, nout, ngf), first)

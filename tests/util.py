@@ -72,3 +72,22 @@ def read_raw_output(ws, packed, info, batch, dtype):
     scl = packed[info.ln_scale_offset:info.ln_scale_offset + 8].cpu().numpy().view(np.float64)
     up = np.float32(16777216.0 / scl[0])
     return ws[info.raw_offset:info.raw_offset + 2 * n].view(torch.float16).reshape(shape).float().cpu().numpy() * up
+
+
+def poison_workspace(m, b, h, w, cin, nout, ngf):
+    """Fill the network workspace of model `m` (matryodshka_amd.MSI, with its current net_options) for this shape with
+    0xFF bytes -- NaN as fp32, fp16 and bf16 -- and return it.  Call it BEFORE the first forward of a plan.
+
+    MSI._net allocates the workspace with torch.empty, and the caching allocator likes to hand a new plan the block a
+    dropped model has just released: a same-input A/B test (tile8 vs 4-row, halo vs tap, fix-up vs in-launch) can then
+    read the OTHER variant's correct raw outputs where its own variant computed no tile or lost a store.  On a poisoned
+    workspace such an element stays NaN, and so does everything downstream of it.
+
+    The whole workspace is poisoned: nothing in it is written once and kept.  Its regions are (cnn.hip: build_net) the
+    layers' raw outputs / published affines / bf16 activation copies, the K-range slabs, and the zero region (arrival
+    tickets, LayerNorm sums, apply-ahead flags, status word) -- the first three are written by the forward that reads
+    them, the last is cleared by every forward's first launch.  What IS written once outside the forward (packed weights,
+    LayerNorm windows, msi_net_plan_calibrate's result) lives in the packed blob, which this does not touch."""
+    _, _, ws = m._net(b, h, w, cin, nout, ngf)
+    ws.fill_(0xFF)
+    return ws

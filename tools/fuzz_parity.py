@@ -7,7 +7,7 @@ dtype) within the supported set, small enough for the CPU oracle.  Exercises M-t
 
 --halo: shapes that reach the halo-patch kernels (ngf 32 / 64, maps in multiples of 4 x 16 / 8 x 16 / 16 x 16, channel
 counts in multiples of 32 / 64) with a random MSI_NET_OPT_HALO in {0, 1, 3, 5, 7}, a random FIXUP_KERNEL and a random NUM_CUS
-(8 / 16 CUs in the plan: the stride-2 halo kernels and the K splits are then reached by small grids).
+(8 .. 104 CUs in the plan, odd counts among them, or the default part's 256: the stride-2 halo kernels and the K splits are then reached by small grids).
 """
 import argparse
 import os
@@ -26,6 +26,7 @@ ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--halo", action="store_true")
 a = ap.parse_args()
 from matryodshka_amd import _native as N
+NUM_CUS_SET = (8, 9, 12, 20, 24, 56, 104, 256)   # small, odd and the device's: tests/test_gpu_fuzz.py draws from the same set
 rng = np.random.RandomState(a.seed)
 worst = {"f32": 0.0, "bf16": 0.0}
 fails = 0
@@ -49,7 +50,7 @@ for it in range(a.n):
         cq = 64 if dtype == "bf16" else 32
         cin = cq * int(rng.randint(1, 4)) if rng.rand() < 0.7 else q * int(rng.randint(1, 13))
         opts = {N.NET_OPT_HALO: int(rng.choice([0, 1, 3, 5, 5, 7])), N.NET_OPT_FIXUP_KERNEL: int(rng.rand() < 0.3),
-                N.NET_OPT_BIGTILE: int(rng.choice([1, 1, 2])), N.NET_OPT_NUM_CUS: int(rng.choice([256, 8, 16]))}
+                N.NET_OPT_BIGTILE: int(rng.choice([1, 1, 2])), N.NET_OPT_NUM_CUS: int(rng.choice(NUM_CUS_SET))}
     if not coord:          # wrap_pad(x, 2, 2) at 1/8 resolution needs at least two columns / rows (the reference fails below that too)
         h, w = max(h, 16), max(w, 16)
     weights = onets.init_weights(cin, nout, ngf=ngf, coord_net=coord, seed=int(rng.randint(1 << 30)), randomize_affine=True)
