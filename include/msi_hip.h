@@ -330,6 +330,35 @@ int msi_perspective_sweep_volume_bf16(const float *ref_image, const float *src_i
 int msi_mpi_render_f32(const float *rgba_native, const float *tgt_pose, const float *intrinsics,
                        const float *intrinsics_inv, const float *depths, int32_t batch, int32_t height,
                        int32_t width, int32_t num_planes, float *out_rgb, msi_stream_t stream);
+/* Many views of one MPI per launch (MSI.mpi_render_views; no reference counterpart): V target cameras per stack, each rendered
+ * as msi_mpi_render_f32 renders its one view, at any output size, from an fp32 or a packed stack.
+ *   layers             [B,D,H,W] texels of `format`: MSI_LAYERS_F32 (rgba_native), MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F
+ *   tgt_pose           [B*V,4,4]  view v of sample b at index b*V + v; it samples stack b only
+ *   intrinsics         [B,3,3]    the SOURCE camera K of stack b
+ *   tgt_intrinsics_inv [B*V,3,3]  the inverse of the TARGET camera of view (b, v), in pixels of the output size
+ *   depths             [D] (far -> near), D <= 128
+ *   out_rgb [B,V,out_height,out_width,3], out_depth [B,V,out_height,out_width]; either may be NULL, not both.
+ * Contract:
+ *   rgb    Pixel (i, j) of the output is the point (j, i, 1) of meshgrid_abs at the OUTPUT size, taken through the inverse
+ *          homography K_s (R^T + R^T t n^T R^T / (-depth - n^T R^T t)) K_t^-1 of each plane, sampled with the zero-padding
+ *          bilinear resampler and over-composited far to near, with msi_mpi_render_f32's operations in its order.  With
+ *          (out_height, out_width) = (H, W) and tgt_intrinsics_inv = its intrinsics_inv, every view is BIT-IDENTICAL to
+ *          msi_mpi_render_f32 with that view's pose.
+ *   depth  pj.over_composite_depth (projector.py:225-244) of the same warped layers, ONE channel: 0 at the farthest layer,
+ *          then (d / D) * alpha + out * (1 - alpha) with d / D the fp32 rounding of the fp64 quotient -- the composited plane
+ *          index / D as in msi_render_views_f32, not a physical depth.
+ *   zero padding  A sample outside (-1, W) x (-1, H) contributes (0, 0, 0, 0) for that layer, a corner outside the layer
+ *          contributes zeros with its weight (no wrap-around): where every layer samples outside, rgb and depth are 0.
+ *   packed stacks  Every tap is decoded by the rule of msi_unpack_layers, so the outputs are bit-identical to the same call
+ *          on the msi_unpack_layers of the stack with MSI_LAYERS_F32.
+ * Argument checks before any launch, MSI_E_BADARG unless noted: both outputs NULL; a NULL input; batch < 0 or a
+ * non-positive height / width / num_planes ("bad dims"); views < 1; an output size below 1 x 1; an unknown format;
+ * num_planes > 128 -> MSI_E_UNSUPPORTED; H * W >= 2^24 (24-bit texel offsets); more than 2^31 - 8 workgroups (64 x 4
+ * output pixels each).  batch = 0 then returns MSI_OK without a launch. */
+int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_pose, const float *intrinsics,
+                         const float *tgt_intrinsics_inv, const float *depths, int32_t batch, int32_t views, int32_t height,
+                         int32_t width, int32_t num_planes, int32_t out_height, int32_t out_width, float *out_rgb,
+                         float *out_depth, msi_stream_t stream);
 
 /* ---- K2: encoder-decoder CNN -------------------------------------------------------
  * nets.msi_coord_train_net (nets.py:471-515; coord_net=1) and nets.msi_train_net

@@ -1,5 +1,5 @@
-// The planar (PP) path of the geometry side: pp_sweep_kernel, pp_sweep_volume_bf16_kernel and mpi_render_kernel; kernels first, their C ABI
-// entry points below.
+// The planar (PP) path of the geometry side: pp_sweep_kernel, pp_sweep_volume_bf16_kernel, mpi_render_kernel and mpi_render_views_kernel (many
+// views of one MPI per launch, from an fp32 or a packed stack); kernels first, their C ABI entry points below.
 #include "geometry_device.h"
 
 namespace {
@@ -327,6 +327,151 @@ mpi_render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ tgt
   o[0] = o0; o[1] = o1; o[2] = o2;
 }
 
+// The MPI render for a viewer (msi_mpi_render_views; no reference counterpart): V target cameras per stack in one launch, any output size,
+// rgb and / or the one-channel depth of over_composite_depth, from an fp32, rgba8 or rgba16f stack.  mpi_render_kernel above stays as it is;
+// this kernel repeats its arithmetic op for op -- the homography (rot_t, divide_safe, m1, K_s @ m1, @ K_t_inv), the three dot products,
+// divide_safe on ws, the two IEEE divides, the (-1, W) x (-1, H) test, floor, the four weights, the sum order w00 a00 + w11 a11 + w01 a01 +
+// w10 a10 and the strictly sequential composite in one thread -- so at the stack's own size its rgb has the bits of msi_mpi_render_f32.
+// What changes is the plumbing:
+//   grid    1-D, sample -> view -> 4-row group -> 64-pixel block with render_views_kernel's XCD-aware mapping: the views of one stack follow
+//           each other through the Infinity Cache and adjacent row groups share an XCD's L2.  A workgroup is 64 x 4 pixels of one (sample,
+//           view), a wave one row; its D inverse homographies (source K of sample b, pose and inverse target K of view (b, v)) are computed
+//           once in the prologue into LDS.
+//   taps    buffer loads through a per-layer descriptor (the layer index is wave-uniform: scalar), one 16-, 8- or 4-byte load per tap.  A
+//           tap outside the layer is given an offset beyond the descriptor's range and comes back as zeros: no branch.  The mask covers
+//           columns AND rows: a column outside [0, W) would alias the neighbouring row, and a row outside [0, H) would leave the range by
+//           itself, but at byte offsets within 16 bytes of 2^32 -- the explicit mask keeps every offset that is sent either inside the layer
+//           or at 2^31.  fp32 and rgba16f zeros decode to the (0, 0, 0, 0) of fetch_or_zero; an rgba8 zero decodes to colour -1, so its three
+//           colour channels are selected to zero by the same mask.  Decoders: geometry_device.h, the rule of msi_unpack_layers.
+//   pixels  that sample outside (-1, W) x (-1, H) (or NaN) run the same instructions on the coordinate (0, 0) with every tap masked, and
+//           their layer value is selected to zero: no divergent branch around the loads, same bits for the pixels inside.
+//   loop    unrolled by 4: the warp of a layer does not depend on the running composite, so the taps of several layers are in flight under
+//           the sequential blend.
+template <int FMT>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mpi_layer_rsrc(const void *layers, int b, int nd, int d, size_t hw) {
+  if constexpr (FMT == MSI_LAYERS_F32)
+    return layer_rsrc(static_cast<const float4 *>(layers), b, nd, d, hw, (int)(hw << 4));   // (H * W < 2^24, checked on the host)
+  else
+    return packed_layer_rsrc<FMT>(layers, b, nd, d, hw, (int)(hw << TexelShift<FMT>::value));
+}
+
+// the texel at offset `texel` of layer L when ok, else the zeros of fetch_or_zero
+template <int FMT>
+__device__ __forceinline__ float4 mpi_tap(__amdgpu_buffer_rsrc_t L, int texel, bool ok) {
+  if constexpr (FMT == MSI_LAYERS_F32) {
+    return layer_tap(L, ok ? (unsigned)texel : 0x80000000u >> 4);
+  } else {
+    float4 t = packed_layer_tap<FMT>(L, ok ? (unsigned)texel : 0x80000000u >> TexelShift<FMT>::value);
+    if constexpr (FMT == MSI_LAYERS_RGBA8) {   // (code 0 is colour -1; alpha 0 and the rgba16f zeros are 0 already)
+      t.x = ok ? t.x : 0.0f; t.y = ok ? t.y : 0.0f; t.z = ok ? t.z : 0.0f;
+    }
+    return t;
+  }
+}
+
+template <int MODE, int FMT>
+__global__ void __launch_bounds__(256)
+mpi_render_views_kernel(const void *__restrict__ layers, const float *__restrict__ tgt_pose, const float *__restrict__ intrinsics,
+                        const float *__restrict__ tgt_intrinsics_inv, const float *__restrict__ depths, int batch, int views,
+                        int height, int width, int nd, int out_h, int out_w, float *__restrict__ out_rgb,
+                        float *__restrict__ out_depth, DepthFrac F) {
+  __shared__ float hom[MPI_MAX_PLANES][9];
+  const unsigned gx = (unsigned)(out_w + 63) >> 6, gy = (unsigned)(out_h + 3) >> 2;
+  const unsigned nblk = gx * gy * (unsigned)views * (unsigned)batch, per = gridDim.x >> 3;
+  const unsigned lin = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+  if (lin >= nblk) return;                              // (grid rounded up to a multiple of 8; whole workgroups leave)
+  const unsigned rowb = lin / gx;
+  const int j = (int)(lin - rowb * gx) * 64 + threadIdx.x;
+  const unsigned bv = rowb / gy;                        // sample * views + view
+  const int i = (int)(rowb - bv * gy) * 4 + threadIdx.y;
+  const int b = (int)(bv / (unsigned)views);
+  const int tid = threadIdx.y * 64 + threadIdx.x;
+  if (tid < nd) {   // mpi_render_kernel's prologue, op for op
+    const float *P = tgt_pose + (size_t)bv * 16;
+    const float *Ks = intrinsics + (size_t)b * 9, *Ki = tgt_intrinsics_inv + (size_t)bv * 9;
+    float rt[3][3], t[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rt[r][c] = P[c * 4 + r];  // rot_t = transpose(pose[:3,:3])
+      t[r] = P[r * 4 + 3];
+    }
+    const float a = -depths[tid];
+    const float nrt_t = (rt[2][0] * t[0] + rt[2][1] * t[1]) + rt[2][2] * t[2];
+    float den = a - nrt_t;
+    den += 1e-8f * (den == 0.0f ? 1.0f : 0.0f);  // divide_safe
+    float m1[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const float q = (rt[r][0] * t[0] + rt[r][1] * t[1]) + rt[r][2] * t[2];  // (rot_t @ t)[r]
+#pragma unroll
+      for (int c = 0; c < 3; ++c) m1[r][c] = rt[r][c] + (q * rt[2][c]) / den;
+    }
+    float m2[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        m2[r][c] = (Ks[r * 3 + 0] * m1[0][c] + Ks[r * 3 + 1] * m1[1][c]) + Ks[r * 3 + 2] * m1[2][c];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        hom[tid][r * 3 + c] = (m2[r][0] * Ki[0 * 3 + c] + m2[r][1] * Ki[1 * 3 + c]) + m2[r][2] * Ki[2 * 3 + c];
+  }
+  __syncthreads();
+  if (j >= out_w || i >= out_h) return;
+  const float uu = (float)j, vv = (float)i;  // meshgrid_abs of the OUTPUT size
+  const size_t hw = (size_t)height * width;
+  const float wf = (float)width, hf = (float)height;
+  float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f;
+#pragma unroll 4
+  for (int d = 0; d < nd; ++d) {
+    const float *h = hom[d];
+    const float xs = (uu * h[0] + vv * h[1]) + 1.0f * h[2];
+    const float ys = (uu * h[3] + vv * h[4]) + 1.0f * h[5];
+    float ws = (uu * h[6] + vv * h[7]) + 1.0f * h[8];
+    ws += 1e-8f * (ws == 0.0f ? 1.0f : 0.0f);
+    const float xq = xs / ws, yq = ys / ws;
+    // tf.contrib.resampler: zero outside (-1, W) x (-1, H); missing corners are 0
+    const bool inside = xq > -1.0f && yq > -1.0f && xq < wf && yq < hf;
+    const float x = inside ? xq : 0.0f, y = inside ? yq : 0.0f;
+    const float fxf = floorf(x), fyf = floorf(y);
+    const int fx = (int)fxf, fy = (int)fyf, cx = fx + 1, cy = fy + 1;   // fx in [-1, W-1], fy in [-1, H-1]
+    const float dx = (float)cx - x, dy = (float)cy - y;
+    const bool x0 = inside && fx >= 0, x1 = inside && cx < width, y0 = fy >= 0, y1 = cy < height;
+    const int r0 = fy * width, r1 = r0 + width;
+    const __amdgpu_buffer_rsrc_t L = mpi_layer_rsrc<FMT>(layers, b, nd, d, hw);
+    const float4 a00 = mpi_tap<FMT>(L, r0 + fx, x0 && y0), a11 = mpi_tap<FMT>(L, r1 + cx, x1 && y1);
+    const float4 a01 = mpi_tap<FMT>(L, r1 + fx, x0 && y1), a10 = mpi_tap<FMT>(L, r0 + cx, x1 && y0);
+    const float w00 = dx * dy, w11 = (1.0f - dx) * (1.0f - dy), w01 = dx * (1.0f - dy), w10 = (1.0f - dx) * dy;
+    const float al = inside ? ((w00 * a00.w + w11 * a11.w) + w01 * a01.w) + w10 * a10.w : 0.0f;
+    if (MODE & RENDER_RGB) {
+      const float r = inside ? ((w00 * a00.x + w11 * a11.x) + w01 * a01.x) + w10 * a10.x : 0.0f;
+      const float g = inside ? ((w00 * a00.y + w11 * a11.y) + w01 * a01.y) + w10 * a10.y : 0.0f;
+      const float bl = inside ? ((w00 * a00.z + w11 * a11.z) + w01 * a01.z) + w10 * a10.z : 0.0f;
+      if (d == 0) {
+        o0 = r; o1 = g; o2 = bl;
+      } else {
+        const float om = 1.0f - al;
+        o0 = r * al + o0 * om;
+        o1 = g * al + o1 * om;
+        o2 = bl * al + o2 * om;
+      }
+    }
+    if (MODE & RENDER_DEPTH) {   // over_composite_depth (projector.py:225-244): 0 at layer 0, then (d / D) a + out (1 - a)
+      if (d == 0) od = 0.0f;
+      else od = F.f[d] * al + od * (1.0f - al);
+    }
+  }
+  const size_t pix = ((size_t)bv * out_h + i) * out_w + j;
+  if (MODE & RENDER_RGB) {
+    float *o = out_rgb + pix * 3;
+    o[0] = o0; o[1] = o1; o[2] = o2;
+  }
+  if (MODE & RENDER_DEPTH) out_depth[pix] = od;
+}
+
 }  // namespace
 
 extern "C" {
@@ -404,6 +549,52 @@ int msi_mpi_render_f32(const float *rgba_native, const float *tgt_pose, const fl
                      reinterpret_cast<const float4 *>(rgba_native), tgt_pose, intrinsics, intrinsics_inv, depths, batch,
                      height, width, num_planes, out_rgb);
   return msi::check_launch("mpi_render");
+}
+
+int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_pose, const float *intrinsics,
+                         const float *tgt_intrinsics_inv, const float *depths, int32_t batch, int32_t views, int32_t height,
+                         int32_t width, int32_t num_planes, int32_t out_height, int32_t out_width, float *out_rgb,
+                         float *out_depth, msi_stream_t stream) {
+  MSI_REQUIRE(out_rgb || out_depth, "mpi_render_views: both outputs are NULL");
+  MSI_REQUIRE(layers && tgt_pose && intrinsics && tgt_intrinsics_inv && depths, "mpi_render_views: null pointer");
+  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "mpi_render_views: bad dims");
+  MSI_REQUIRE(views >= 1, "mpi_render_views: views must be >= 1 (got %d)", views);
+  MSI_REQUIRE(out_height >= 1 && out_width >= 1, "mpi_render_views: bad output size %d x %d", out_height, out_width);
+  MSI_REQUIRE(format == MSI_LAYERS_F32 || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F,
+              "mpi_render_views: unknown format %d", format);
+  if (num_planes > MPI_MAX_PLANES)
+    return msi::fail(MSI_E_UNSUPPORTED, "mpi_render_views: at most %d planes", MPI_MAX_PLANES);
+  MSI_REQUIRE((long)height * width < (1L << 24), "mpi_render_views: layers of more than 2^24 texels (24-bit texel offsets)");
+  const long lim = (1L << 31) - 8;
+  long nblk = (long)((out_width + 63) / 64) * ((out_height + 3) / 4);     // (each factor < 2^31: checked before every product)
+  MSI_REQUIRE(nblk < lim, "mpi_render_views: too many target pixels for one launch");
+  nblk *= views;
+  MSI_REQUIRE(nblk < lim, "mpi_render_views: too many target pixels for one launch");
+  nblk *= batch;
+  MSI_REQUIRE(nblk < lim, "mpi_render_views: too many target pixels for one launch");
+  if (batch == 0) return MSI_OK;
+  const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(64, 4);
+  DepthFrac F;
+  for (int d = 0; d < DEPTH_FRAC_MAX; ++d) F.f[d] = d < num_planes ? (float)((double)d / (double)num_planes) : 0.0f;
+  const int mode = (out_rgb ? RENDER_RGB : 0) | (out_depth ? RENDER_DEPTH : 0);
+  hipStream_t s = msi::as_stream(stream);
+#define MSI_LAUNCH_MPI_VIEWS(M, FMT_)                                                                                             \
+  hipLaunchKernelGGL((mpi_render_views_kernel<M, FMT_>), grid, block, 0, s, layers, tgt_pose, intrinsics, tgt_intrinsics_inv, depths, \
+                     batch, views, height, width, num_planes, out_height, out_width, out_rgb, out_depth, F)
+#define MSI_LAUNCH_MPI_VIEWS_M(FMT_)                                                \
+  switch (mode) {                                                                   \
+    case RENDER_RGB: MSI_LAUNCH_MPI_VIEWS(RENDER_RGB, FMT_); break;                 \
+    case RENDER_DEPTH: MSI_LAUNCH_MPI_VIEWS(RENDER_DEPTH, FMT_); break;             \
+    default: MSI_LAUNCH_MPI_VIEWS(RENDER_RGB | RENDER_DEPTH, FMT_); break;          \
+  }
+  switch (format) {
+    case MSI_LAYERS_RGBA8: MSI_LAUNCH_MPI_VIEWS_M(MSI_LAYERS_RGBA8) break;
+    case MSI_LAYERS_RGBA16F: MSI_LAUNCH_MPI_VIEWS_M(MSI_LAYERS_RGBA16F) break;
+    default: MSI_LAUNCH_MPI_VIEWS_M(MSI_LAYERS_F32) break;
+  }
+#undef MSI_LAUNCH_MPI_VIEWS_M
+#undef MSI_LAUNCH_MPI_VIEWS
+  return msi::check_launch("mpi_render_views");
 }
 
 }  // extern "C"

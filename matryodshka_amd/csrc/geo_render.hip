@@ -11,18 +11,11 @@ namespace {
 // adjacent waves share tap rows in L1).  The ray/sphere quadratic's a and b do
 // not depend on the layer, so per layer only sqrt, one divide and the two atan2
 // remain; the running composite lives in registers and every texel of the
-// D x H x W x 4 stack is fetched from HBM once.
-enum RenderMode { RENDER_RGB = 1, RENDER_DEPTH = 2, RENDER_LAYERS = 4 };
+// D x H x W x 4 stack is fetched from HBM once.  (RenderMode, DepthFrac and the layer descriptors / taps: geometry_device.h, shared with the MPI render.)
 constexpr int RENDER_SEGS = 4;   // layer segments per pixel (threads in y)
 // ray model of the TARGET view: equirect (spherical.intersect_sphere, spherical.py:268-326),
 // ODS eye (intersect_ods, :328-365) or the hard-coded perspective crop (intersect_perspective, :367-401)
 enum RayModel { RAY_EQUIRECT = 0, RAY_ODS = 1, RAY_PERSPECTIVE = 2 };
-
-// (i / len) of projector.py:242 per layer: a Python double division converted to an fp32 tensor constant.  Tabulated on the
-// host (kernel argument, read with a scalar load: the layer index is wave-uniform) -- as an expression in the kernel it was an
-// emulated fp64 division, ~25 half-rate instructions per (thread, layer), a fifth of the render kernel's VALU time.
-constexpr int DEPTH_FRAC_MAX = 128;
-struct DepthFrac { float f[DEPTH_FRAC_MAX]; };
 
 struct RayParams {
   int out_h, out_w;        // target image size (== layer size except for RAY_PERSPECTIVE)
@@ -223,16 +216,6 @@ render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt
   }
 }
 
-// Layer d of sample b of a [B,D,H,W,4] stack as a buffer resource: 32-bit texel offsets also for stacks beyond 2 GiB.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t layer_rsrc(const float4 *rgba, int b, int nd, int d, size_t hw, int layer_bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(rgba + ((size_t)b * nd + d) * hw), 0, layer_bytes, 0x00020000);
-}
-
-__device__ __forceinline__ float4 layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
-  typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
-  return __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, texel << 4, 0, 0));
-}
-
 // K4, many views of one stack per launch (msi_render_views_f32): render_kernel's per-layer arithmetic, op for op, for V target
 // cameras per sample.  A workgroup is one (sample, view, target row, 64-pixel block); the 1-D grid runs sample -> view -> row
 // -> block with render_kernel's XCD-aware mapping, so the V views of one stack follow each other (its texels stay in the
@@ -381,26 +364,6 @@ render_views_kernel(const float4 *__restrict__ rgba, const float *__restrict__ p
 // decoded to the four fp32 values msi_unpack_layers writes for that texel (rgba8: 11 VALU per tap -- four v_cvt_f32_ubyte, three
 // subtracts, four multiplies; rgba16f: four v_cvt_f32_f16).  Everything after the decode is render_views_kernel's arithmetic,
 // op for op, so a render from a packed stack is bit-identical to msi_render_views_f32 on the unpacked one.
-template <int FMT> struct TexelShift {   // log2 of the bytes per texel
-  static_assert(FMT == MSI_LAYERS_RGBA8 || FMT == MSI_LAYERS_RGBA16F, "a packed texel format");
-  static constexpr int value = FMT == MSI_LAYERS_RGBA8 ? 2 : 3;
-};
-
-// layer_rsrc / layer_tap for a packed stack
-template <int FMT>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t packed_layer_rsrc(const void *layers, int b, int nd, int d, size_t hw, int layer_bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + ((((size_t)b * nd + d) * hw) << TexelShift<FMT>::value)),
-                                           0, layer_bytes, 0x00020000);
-}
-
-template <int FMT>
-__device__ __forceinline__ float4 packed_layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
-  if constexpr (FMT == MSI_LAYERS_RGBA8)
-    return rgba8_decode(__builtin_amdgcn_raw_buffer_load_b32(L, texel << 2, 0, 0));
-  else
-    return rgba16f_decode((u32x2_g)__builtin_amdgcn_raw_buffer_load_b64(L, texel << 3, 0, 0));
-}
-
 template <int MODE, int CAMERA, int FMT>
 __global__ void __launch_bounds__(256)
 render_views_packed_kernel(const void *__restrict__ layers, const float *__restrict__ pose_rt, const float *__restrict__ tgt_pos,

@@ -3,7 +3,7 @@
 //   geo_sweep.hip   K1 ODS sphere sweep: ods_sweep_kernel, ods_sweep_lds_kernel
 //   geo_layers.hip  K3 RGBA assembly, bilinear resize, the fused high-res layer stack, pack / unpack of the compact stacks
 //   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed sibling
-//   geo_planar.hip  the PP path: perspective plane sweeps and the MPI render
+//   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
 // sharing is a contract.  What a single family uses lives in that family's unit.
 //
@@ -381,6 +381,47 @@ __device__ __forceinline__ float4 rgba16f_decode(u32x2_g q) {
   float4 t;
   t.x = (float)h.x; t.y = (float)h.y; t.z = (float)h.z; t.w = (float)h.w;
   return t;
+}
+
+// ---- render (render_kernel, render_views_kernel and its packed sibling) and planar (mpi_render_views_kernel): the output modes, the layer fraction of
+// over_composite_depth and ONE way to address and load a texel of a layer stack, fp32 or packed, so the many-views renders of both families read the
+// same bits from the same stack.
+enum RenderMode { RENDER_RGB = 1, RENDER_DEPTH = 2, RENDER_LAYERS = 4 };
+
+// (i / len) of projector.py:242 per layer: a Python double division converted to an fp32 tensor constant.  Tabulated on the
+// host (kernel argument, read with a scalar load: the layer index is wave-uniform) -- as an expression in the kernel it was an
+// emulated fp64 division, ~25 half-rate instructions per (thread, layer), a fifth of the render kernel's VALU time.
+constexpr int DEPTH_FRAC_MAX = 128;
+struct DepthFrac { float f[DEPTH_FRAC_MAX]; };
+
+// Layer d of sample b of a [B,D,H,W,4] stack as a buffer resource: 32-bit texel offsets also for stacks beyond 2 GiB.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t layer_rsrc(const float4 *rgba, int b, int nd, int d, size_t hw, int layer_bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(rgba + ((size_t)b * nd + d) * hw), 0, layer_bytes, 0x00020000);
+}
+
+__device__ __forceinline__ float4 layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
+  typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
+  return __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, texel << 4, 0, 0));
+}
+
+template <int FMT> struct TexelShift {   // log2 of the bytes per texel
+  static_assert(FMT == MSI_LAYERS_RGBA8 || FMT == MSI_LAYERS_RGBA16F, "a packed texel format");
+  static constexpr int value = FMT == MSI_LAYERS_RGBA8 ? 2 : 3;
+};
+
+// layer_rsrc / layer_tap for a packed stack
+template <int FMT>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t packed_layer_rsrc(const void *layers, int b, int nd, int d, size_t hw, int layer_bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + ((((size_t)b * nd + d) * hw) << TexelShift<FMT>::value)),
+                                           0, layer_bytes, 0x00020000);
+}
+
+template <int FMT>
+__device__ __forceinline__ float4 packed_layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
+  if constexpr (FMT == MSI_LAYERS_RGBA8)
+    return rgba8_decode(__builtin_amdgcn_raw_buffer_load_b32(L, texel << 2, 0, 0));
+  else
+    return rgba16f_decode((u32x2_g)__builtin_amdgcn_raw_buffer_load_b64(L, texel << 3, 0, 0));
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------------------------------

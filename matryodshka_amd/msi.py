@@ -468,8 +468,8 @@ class MSI(object):
     # ------------------------------------------------------------------ msi.py:384-452
     def _native_layers(self, rgba_layers):
         if isinstance(rgba_layers, PackedLayers):
-            raise TypeError("this method reads fp32 layer stacks only: render a PackedLayers with render_views, or expand it "
-                            "with unpack_layers first")
+            raise TypeError("this method reads fp32 layer stacks only: render a PackedLayers with render_views (MSI) or "
+                            "mpi_render_views (MPI), or expand it with unpack_layers first")
         rgba_layers = rgba_layers.to(device=self.device, dtype=torch.float32) if torch.is_tensor(rgba_layers) \
             else self._f32(rgba_layers)
         if rgba_layers.dim() != 5 or rgba_layers.shape[-1] != 4:
@@ -823,3 +823,77 @@ class MSI(object):
                                          depths.data_ptr(), b, h, w, d, out.data_ptr(), self._stream()),
                 "msi_mpi_render_f32")
         return out
+
+    def _view_intrinsics(self, k, b, v, what):
+        """[B,V,3,3], [B,3,3] or [3,3] -> fp32 [B*V,3,3] (one camera per view), on the device it came from."""
+        k = k.float() if torch.is_tensor(k) else torch.as_tensor(np.asarray(k, dtype=np.float32))
+        if k.dim() == 2:
+            k = k[None, None]
+        elif k.dim() == 3:
+            k = k[:, None]
+        if k.dim() != 4 or tuple(k.shape[2:]) != (3, 3) or k.shape[0] not in (1, b) or k.shape[1] not in (1, v):
+            raise ValueError("%s must be [B,V,3,3], [B,3,3] or [3,3] with B = %d, V = %d, got %s" % (what, b, v, tuple(k.shape)))
+        return k.expand(b, v, 3, 3).reshape(b * v, 3, 3)
+
+    def mpi_render_views(self, rgba_layers, tgt_pose, planes=None, intrinsics=None, tgt_intrinsics=None, intrinsics_inv=None,
+                         size=None, want_rgb=True, want_depth=True):
+        """V views of each MPI in ONE launch (msi_mpi_render_views; no reference counterpart) -> (rgb, depth): rgb
+        [B,V,h,w,3] in [-1,1], depth [B,V,h,w] (the composited plane index / D of over_composite_depth, one channel); either
+        is None when switched off.  Works on any model (ODS or PP, f32 or bf16): the stack is what matters.
+
+        rgba_layers [B,H,W,D,4] (a permuted view of the native [B,D,H,W,4] stack goes through without a copy) or a
+        PackedLayers, which the kernel gathers from directly: the outputs are bit-identical to rendering
+        unpack_layers(rgba_layers).  planes=None takes the planes a PackedLayers carries (ValueError when it carries none);
+        for an fp32 stack planes is required.
+        tgt_pose [B,V,4,4] ([V,4,4] when B = 1): each has the meaning of mpi_render_view's tgt_pose, and view v of sample b
+        samples stack b only.  intrinsics: the stack's camera, [B,3,3] or [3,3].  The target camera is EITHER
+        tgt_intrinsics ([B,V,3,3], [B,3,3] or [3,3]; inverted on the host in fp64 and rounded to fp32, as mpi_render_view
+        does) OR intrinsics_inv (same shapes, used as given); neither means inverse(intrinsics), both is a ValueError.
+        size = (h, w), shared by every view, default (H, W); the target camera is in pixels of that size.  At size (H, W)
+        with the same intrinsics_inv, rgb[:, v] is bit-identical to mpi_render_view with tgt_pose[:, v]."""
+        if not (want_rgb or want_depth):
+            raise ValueError("mpi_render_views: want_rgb and want_depth are both False")
+        if tgt_intrinsics is not None and intrinsics_inv is not None:
+            raise ValueError("mpi_render_views: pass tgt_intrinsics or intrinsics_inv, not both")
+        if intrinsics is None:
+            raise ValueError("mpi_render_views: intrinsics (the stack's camera) is required")
+        packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
+        if packed is not None:
+            native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
+            if planes is None:
+                planes = packed.planes
+        else:
+            native = self._native_layers(rgba_layers)
+        if planes is None:
+            raise ValueError("mpi_render_views: planes is required (only a PackedLayers that carries its planes may leave it out)")
+        b, d, h, w, _ = native.shape
+        pose = self._f32(tgt_pose)
+        if b == 1 and pose.dim() == 3:
+            pose = pose[None]
+        if pose.dim() != 4 or pose.shape[0] != b or tuple(pose.shape[2:]) != (4, 4):
+            raise ValueError("tgt_pose must be [B,V,4,4] with B = %d (or [V,4,4] for B = 1), got %s" % (b, tuple(pose.shape)))
+        pose = pose.contiguous()
+        v = pose.shape[1]
+        intr = self._f32(intrinsics).reshape(-1, 3, 3)
+        if intr.shape[0] == 1 and b > 1:
+            intr = intr.expand(b, 3, 3)
+        if intr.shape[0] != b:
+            raise ValueError("intrinsics must be [B,3,3] with B = %d or [3,3], got %s" % (b, tuple(intr.shape)))
+        intr = intr.contiguous()
+        if intrinsics_inv is not None:
+            k_inv = self._view_intrinsics(intrinsics_inv, b, v, "intrinsics_inv")
+        else:
+            k_t = self._view_intrinsics(intrinsics if tgt_intrinsics is None else tgt_intrinsics, b, v, "tgt_intrinsics")
+            k_inv = torch.linalg.inv(k_t.cpu().double()).float()
+        k_inv = self._f32(k_inv.contiguous())
+        depths = self._planes(planes)
+        if depths.numel() != d:
+            raise ValueError("len(planes) != number of layers")
+        oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
+        rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
+        dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
+        fmt = self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+        N.check(N.lib.msi_mpi_render_views(native.data_ptr(), fmt, pose.data_ptr(), intr.data_ptr(), k_inv.data_ptr(),
+                                           depths.data_ptr(), b, v, h, w, d, oh, ow, _ptr(rgb), _ptr(dep), self._stream()),
+                "msi_mpi_render_views")
+        return rgb, dep
