@@ -63,7 +63,8 @@ const char *msi_version(void);
  *   6: msi_net_plan_calibrate; MSI_NET_OPT_X3_TILE8 (round 5)
  *   7: MSI_NET_OPT_X3_ROWPAR (round 5)
  *   8: msi_probe_matrix_rate (round 6)
- *   9: msi_perspective_sweep_volume_bf16 */
+ *   9: msi_perspective_sweep_volume_bf16
+ *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -359,6 +360,47 @@ int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_po
                          const float *tgt_intrinsics_inv, const float *depths, int32_t batch, int32_t views, int32_t height,
                          int32_t width, int32_t num_planes, int32_t out_height, int32_t out_width, float *out_rgb,
                          float *out_depth, msi_stream_t stream);
+
+/* ---- image scores --------------------------------------------------------------------
+ * eval.py:127-174 (tf.image.ssim, tf.image.psnr with max_val 255; the mean absolute difference of consecutive frames) for
+ * images that are already on the device; matryodshka_amd/evaluate.py is the host statement of the same numbers.  Per pair p
+ * of n_pairs: pred image p against target image p / group (group = 1: one to one; group = V: [B,V,...] renders against
+ * [B,...] ground truth; group = n_pairs: everything against one image).
+ *   pred    [n_pairs, H, W, C]          C in 1..4; both fp32 (MSI_SCORE_F32) or both uint8 (MSI_SCORE_U8)
+ *   target  [n_pairs / group, H, W, C]
+ *   transform, applied to both images as a pixel is read (fp64 from there on):
+ *     MSI_SCORE_RAW    the value as it is (the only transform of uint8 images)
+ *     MSI_SCORE_IMAGE  ((double)x + 1) / 2 * 255;  MSI_SCORE_DEPTH  (double)x * 255
+ *     quantize = 1 (IMAGE or DEPTH, fp32 only): the 8-bit level msi_deprocess_f32_u8 stores, op for op in fp32 (NaN -> 0)
+ *   row_weights  [H] doubles on the device or NULL (all ones): one weight per image row, e.g. the solid angle of an
+ *     equirectangular row (WS-PSNR)
+ *   metrics  MSI_SCORE_MSE | MSI_SCORE_MAE | MSI_SCORE_SSIM
+ *   out  [n_pairs][4] doubles = mse, mae, ssim, psnr; NaN where not requested (psnr comes with MSI_SCORE_MSE):
+ *     mse  = sum_r w_r sum_{c,ch} d^2 / (sum_r w_r * W * C), mae the same with |d|
+ *     psnr = 20 log10(max_val) - 10 log10(mse), +inf when mse = 0
+ *     ssim = tf.image.ssim: 11 x 11 softmax-normalised Gaussian (sigma 1.5) applied separably at VALID positions, k1 = 0.01,
+ *            k2 = 0.03, the mean of the lum * cs map, a map row weighted with the weight of its window's centre row:
+ *            sum_i w_{i+5} sum_{j,ch} map / (sum_i w_{i+5} * (W - 10) * C)
+ *   workspace  msi_score_workspace_bytes(n_pairs, H, W, C) bytes (0 and an error text for dims it refuses); it may arrive
+ *     uninitialised.
+ * fp64 arithmetic, no atomics: a pair's four numbers are bit-reproducible from call to call and do not depend on how many other
+ * pairs share the call.  Sums of integer levels (uint8 or quantised images, no weights) are exact.
+ * Argument checks before any HIP call: MSI_E_BADARG for a NULL pred / target / out / workspace, n_pairs < 1, group < 1 or not a
+ * divisor of n_pairs, a non-positive height / width, C outside 1..4, an unknown dtype / transform, quantize or a non-RAW
+ * transform with uint8, quantize with RAW, an empty or unknown metrics mask, SSIM with min(H, W) < 11, max_val <= 0;
+ * MSI_E_UNSUPPORTED for more than 2^31 - 1 workgroups (16 x 32 map positions each); MSI_E_WORKSPACE for a workspace that is too small. */
+#define MSI_SCORE_F32 0
+#define MSI_SCORE_U8 1
+#define MSI_SCORE_RAW 0
+#define MSI_SCORE_IMAGE 1
+#define MSI_SCORE_DEPTH 2
+#define MSI_SCORE_MSE 1u
+#define MSI_SCORE_MAE 2u
+#define MSI_SCORE_SSIM 4u
+size_t msi_score_workspace_bytes(int32_t n_pairs, int32_t height, int32_t width, int32_t channels);
+int msi_score_images(const void *pred, const void *target, int32_t dtype, int32_t transform, int32_t quantize, int32_t n_pairs,
+                     int32_t group, int32_t height, int32_t width, int32_t channels, const double *row_weights, double max_val,
+                     uint32_t metrics, double *out, void *workspace, size_t workspace_bytes, msi_stream_t stream);
 
 /* ---- K2: encoder-decoder CNN -------------------------------------------------------
  * nets.msi_coord_train_net (nets.py:471-515; coord_net=1) and nets.msi_train_net

@@ -16,7 +16,10 @@ MSI_NET_NUM_LAYERS = 18
 RENDER_STATUS_ORIGIN_OUTSIDE = 1
 MSI_CAMERA_EQUIRECT, MSI_CAMERA_PINHOLE = 0, 1   # msi_render_views_f32's camera models
 MSI_LAYERS_F32, MSI_LAYERS_RGBA8, MSI_LAYERS_RGBA16F = 0, 1, 2   # texel formats of msi_pack_layers / msi_render_views_packed
-MSI_ABI_VERSION = 9         # include/msi_hip.h: the version this binding's struct layouts and signatures are written for
+MSI_SCORE_F32, MSI_SCORE_U8 = 0, 1                             # msi_score_images: dtype
+MSI_SCORE_RAW, MSI_SCORE_IMAGE, MSI_SCORE_DEPTH = 0, 1, 2      # ... transform
+MSI_SCORE_MSE, MSI_SCORE_MAE, MSI_SCORE_SSIM = 1, 2, 4         # ... metrics mask (PSNR comes with MSE)
+MSI_ABI_VERSION = 9       # include/msi_hip.h: the version this binding's struct layouts and signatures are written for
 
 
 class MsiError(RuntimeError):
@@ -88,6 +91,8 @@ SIGNATURES = {
     "msi_perspective_sweep_volume_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "msi_mpi_render_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "msi_mpi_render_views": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "msi_score_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),
+    "msi_score_images": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, ctypes.c_double, ctypes.c_uint32, _P, _P, c_size_t, _P]),
     "msi_net_layer_info": (_I, [POINTER(NetDesc), _I, POINTER(LayerInfo)]),
     "msi_net_param_floats": (c_size_t, [POINTER(NetDesc)]),
     "msi_net_packed_floats": (c_size_t, [POINTER(NetDesc)]),

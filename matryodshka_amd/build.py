@@ -22,6 +22,9 @@ NO_SLP = ["-fno-slp-vectorize"]
 SOURCES = [
     ("common.cpp", ["-x", "hip"]),
     ("probe.hip", NO_SLP),                                                 # msi_probe_matrix_rate (measurement aid of bench.py)
+    # msi_score_images (fp64 PSNR / SSIM / frame differences): no contraction -- its 8-bit quantisation restates deprocess_kernel op for op, and the
+    # SSIM map of two identical images must be exactly 1; the filter taps ask for fma explicitly
+    ("score.hip", ["-ffp-contract=off"] + NO_SLP),
 ]
 # the geometry side: one translation unit per kernel family (csrc/geometry_device.h holds what they share and says why none of them may contract
 # a*b+c into fma), compiled in parallel.  The flags are attached here, to the whole list: a unit cannot join without them.

@@ -2,6 +2,10 @@
 
     python -m matryodshka_amd.evaluate --result_root results --model_names msi-hip --output_table eval.json
 
+`--on_device` scores the same PNG pairs with MSI.score_views (msi_score_images: the fp64 device statement of the functions below)
+instead; the table has the same keys.  Everything else here stays host numpy and is the metric of record the device scorer is
+tested against.
+
 eval.py:127-145 `evaluate_one`: per example directory, `tgt_image_*` (ground truth) against `output_tgt_*` (render):
   tf.image.ssim(pred, tgt, max_val=255) and tf.image.psnr(pred, tgt, max_val=255)
 eval.py:147-174 `evaluate_consecutive_one`: mean absolute frame-to-frame difference of `output_tgt_*` / `output_depth_*`
@@ -44,8 +48,24 @@ def _filter_valid(x, win):
     return out
 
 
-def ssim(img1, img2, max_val=255.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03):
-    """tf.image.ssim for one image pair [H,W,C] (eval.py:139)."""
+def solid_angle_row_weights(h):
+    """cos((i + 0.5 - h/2) pi / h), i = 0..h-1: the solid angle of a pixel of row i of an equirectangular image, up to a
+    constant -- the weighting of WS-PSNR.  It is NOT the reference's create_spherical_weights, which is an attention term of
+    its training loss and out of scope here."""
+    return np.cos((np.arange(h, dtype=np.float64) + 0.5 - h / 2.0) * (np.pi / h))
+
+
+def _row_weights(row_weights, h):
+    w = np.asarray(row_weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != h:
+        raise ValueError("row_weights: %d weights for %d rows" % (w.shape[0], h))
+    return w
+
+
+def ssim(img1, img2, max_val=255.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, row_weights=None):
+    """tf.image.ssim for one image pair [H,W,C] (eval.py:139).  row_weights [H] (default None: the plain mean): a row of the
+    lum * cs map counts with the weight of its window's centre row,
+    sum_i w[i+r] sum_{j,ch} map[i,j,ch] / (sum_i w[i+r] * (W - 2r) * C), r = filter_size // 2."""
     x = np.asarray(img1, dtype=np.float64)
     y = np.asarray(img2, dtype=np.float64)
     if x.shape != y.shape or x.ndim != 3:
@@ -60,17 +80,39 @@ def ssim(img1, img2, max_val=255.0, filter_size=11, filter_sigma=1.5, k1=0.01, k
     num1 = _filter_valid(x * y, win) * 2.0
     den1 = _filter_valid(x * x + y * y, win)
     cs = (num1 - num0 + c2) / (den1 - den0 + c2)
-    return float((lum * cs).mean(axis=(0, 1)).mean())
+    if row_weights is None:
+        return float((lum * cs).mean(axis=(0, 1)).mean())
+    r = filter_size // 2
+    w = _row_weights(row_weights, x.shape[0])[r:x.shape[0] - r]
+    m = lum * cs
+    return float((w * m.sum(axis=(1, 2))).sum() / (w.sum() * m.shape[1] * m.shape[2]))
 
 
-def psnr(img1, img2, max_val=255.0):
-    """tf.image.psnr (eval.py:140); inf for identical images."""
+def _weighted_mean(v, row_weights):
+    """sum_r w_r sum_{c,ch} v / (sum_r w_r * W * C) of v [H,W,C]."""
+    w = _row_weights(row_weights, v.shape[0])
+    return float((w * v.sum(axis=(1, 2))).sum() / (w.sum() * v.shape[1] * v.shape[2]))
+
+
+def psnr(img1, img2, max_val=255.0, row_weights=None):
+    """tf.image.psnr (eval.py:140); inf for identical images.  row_weights [H]: the squared error of row r counts with
+    w_r (with solid_angle_row_weights: WS-PSNR)."""
     x = np.asarray(img1, dtype=np.float64)
     y = np.asarray(img2, dtype=np.float64)
-    mse = float(((x - y) ** 2).mean())
+    mse = float(((x - y) ** 2).mean()) if row_weights is None else _weighted_mean((x - y) ** 2, row_weights)
     if mse == 0.0:
         return float("inf")
     return float(20.0 * np.log10(max_val) - 10.0 * np.log10(mse))
+
+
+def mae(img1, img2, row_weights=None):
+    """Mean absolute difference of two images [H,W,C] in fp64 (eval.py:147-174 takes it of consecutive frames), optionally
+    with one weight per row."""
+    x = np.asarray(img1, dtype=np.float64)
+    y = np.asarray(img2, dtype=np.float64)
+    if x.shape != y.shape or x.ndim != 3:
+        raise ValueError("mae: images must be [H,W,C] and agree")
+    return float(np.abs(x - y).mean()) if row_weights is None else _weighted_mean(np.abs(x - y), row_weights)
 
 
 def load_image(path):
@@ -143,6 +185,45 @@ def collect_video_consecutive_examples(result_root, model_names, scene_names):
     return out
 
 
+def _device_scores(result_root, models, examples, pairs):
+    """--on_device: what evaluate_one / evaluate_consecutive_one return for every (model, example) and (model, frame pair),
+    from MSI.score_views on the uint8 levels of the same PNG files; one read-back after the last launch."""
+    import torch
+    from . import MSI
+    model = MSI()
+
+    def up(path):
+        return torch.from_numpy(load_image(path).astype(np.uint8)).to(model.device)
+
+    def first(d, pattern, pick=lambda f: sorted(f)[0]):
+        files = glob.glob(os.path.join(d, pattern))
+        if not files:
+            raise FileNotFoundError("%s: no %s (run the harness with 'tgt_image' in --test_outputs)" % (d, pattern))
+        return up(pick(files))
+
+    one, cons = [], []
+    for e in examples:
+        row = []
+        for m in models:
+            d = os.path.join(result_root, m, e)
+            row.append(model.score_views(first(d, "output_tgt_*"), first(d, "tgt_image_*"), metrics=("ssim", "psnr")))
+        one.append(row)
+    for scene_pairs in pairs:
+        rows = []
+        for pr in scene_pairs:
+            row = []
+            for m in models:
+                d1, d2 = (os.path.join(result_root, m, e) for e in pr)
+                row.append([model.score_views(first(d1, pat, _pick), first(d2, pat, _pick), metrics=("mae",))["mae"]
+                            for pat in ("output_tgt_*", "output_depth_*")])
+            rows.append(row)
+        cons.append(rows)
+    ssim_t = [[float(s["ssim"]) for s in row] for row in one]
+    psnr_t = [[float(s["psnr"]) for s in row] for row in one]
+    cons_t = [[[[float(v) for v in md] for md in row] for row in rows] for rows in cons]
+    return ssim_t, psnr_t, cons_t
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--result_root", default="results")
@@ -151,22 +232,31 @@ def main(argv=None):
     ap.add_argument("--video", action="store_true",
                     help="eval_type on_video (eval.py:185-215): frame-to-frame differences of the 'video' examples, per scene")
     ap.add_argument("--videos", default="room_0 room_2 office_0 apartment_0", help="scene names of the video examples (eval.py:43)")
+    ap.add_argument("--on_device", action="store_true",
+                    help="score the PNG pairs on the GPU (MSI.score_views on their uint8 levels) instead of in host numpy; same table")
     a = ap.parse_args(argv)
     models = [m for m in a.model_names.split(",") if m]
     examples = collect_examples(a.result_root, models)
     table = {"model_names": models, "examples": examples, "ssim": [], "psnr": []}
-    for e in examples:
-        scores = [evaluate_one(a.result_root, m, e) for m in models]
-        table["ssim"].append([s[0] for s in scores])
-        table["psnr"].append([s[1] for s in scores])
+    scenes = [s for s in a.videos.split(" ") if s] if a.video else []
+    pairs = collect_video_consecutive_examples(a.result_root, models, scenes) if a.video else []
+    if a.on_device:
+        table["ssim"], table["psnr"], device_diffs = _device_scores(a.result_root, models, examples, pairs)
+    else:
+        for e in examples:
+            scores = [evaluate_one(a.result_root, m, e) for m in models]
+            table["ssim"].append([s[0] for s in scores])
+            table["psnr"].append([s[1] for s in scores])
     table["mean_ssim"] = [float(np.mean([r[i] for r in table["ssim"]])) for i in range(len(models))] if examples else []
     table["mean_psnr"] = [float(np.mean([r[i] for r in table["psnr"]])) for i in range(len(models))] if examples else []
     if a.video:
-        scenes = [s for s in a.videos.split(" ") if s]
-        pairs = collect_video_consecutive_examples(a.result_root, models, scenes)
         table["video_scenes"] = scenes
-        table["consecutive"] = [[{"frames": list(pr), "diffs": [list(evaluate_consecutive_one(a.result_root, m, pr)) for m in models]}
-                                 for pr in scene_pairs] for scene_pairs in pairs]
+        if a.on_device:
+            table["consecutive"] = [[{"frames": list(pr), "diffs": device_diffs[i][j]} for j, pr in enumerate(scene_pairs)]
+                                    for i, scene_pairs in enumerate(pairs)]
+        else:
+            table["consecutive"] = [[{"frames": list(pr), "diffs": [list(evaluate_consecutive_one(a.result_root, m, pr)) for m in models]}
+                                     for pr in scene_pairs] for scene_pairs in pairs]
     with open(a.output_table, "w") as f:
         json.dump(table, f)
     print("Output written to %s" % a.output_table)

@@ -21,10 +21,15 @@ MSI.render_views; in the high_res modes the high-res stack is kept the same way,
 `--checkpoint` reads a TF V2 checkpoint directly (tf_checkpoint.py), `--weights` an .npz of the TF variables
 (see nets.variable_shapes); without either Xavier-initialised
 weights are used (there is no network access for the pretrained checkpoint), step.txt then says 0.
+`--score` also scores every sample that renders output_tgt against its tgt_image on the device (MSI.score_views on the 8-bit
+levels the PNG files hold) and writes <output_root>/<experiment>/scores.json: example names, ssim and psnr per example, their means,
+and with on_video the mean absolute difference of consecutive output_tgt / output_depth frames per scene -- the numbers of
+matryodshka_amd.evaluate without reading the files back.
 Host I/O only: all arithmetic is in libmsi_hip.so.
 """
 import argparse
 import glob
+import json
 import os
 
 import numpy as np
@@ -108,8 +113,44 @@ def save_packed_msi(outs, output_dir, dirname):
         outs["packed_layers"].save(os.path.join(output_dir, "msi_%s.npz" % dirname))
 
 
+class DeviceScores(object):
+    """--score: SSIM / PSNR of each sample's output_tgt against its tgt_image, and for video runs the frame-to-frame differences
+    of output_tgt / output_depth per scene, from MSI.score_views on the uint8 levels write_image stores (so they are
+    evaluate.evaluate_one / evaluate_consecutive_one of the written files).  Nothing is read back before table()."""
+
+    def __init__(self, model, keep_frames=False):
+        self.model, self.keep_frames = model, keep_frames
+        self.names, self.scores, self.frames = [], [], {}
+
+    def add(self, dirname, scene, tgt_image, output_tgt, output_depth=None):
+        """tgt_image: the float image handed to write_image; output_tgt / output_depth: the uint8 device images written."""
+        import torch
+        tgt = torch.from_numpy(np.clip(np.asarray(tgt_image), 0, 255).astype("uint8")).to(self.model.device)
+        self.names.append(dirname)
+        self.scores.append(self.model.score_views(output_tgt, tgt, metrics=("ssim", "psnr")))
+        if self.keep_frames:
+            self.frames.setdefault(scene, []).append((dirname, output_tgt, output_depth))
+
+    def table(self):
+        import torch
+        ssim, psnr = ([float(s[k]) for s in self.scores] for k in ("ssim", "psnr"))
+        table = {"examples": self.names, "ssim": ssim, "psnr": psnr,
+                 "mean_ssim": float(np.mean(ssim)) if ssim else None, "mean_psnr": float(np.mean(psnr)) if psnr else None}
+        if self.keep_frames:
+            table["consecutive"] = []
+            for scene in sorted(self.frames):
+                frames = sorted(self.frames[scene], key=lambda f: f[0])
+                entry = {"scene": scene, "frames": [f[0] for f in frames], "output_tgt": [], "output_depth": []}
+                for key, col in (("output_tgt", 1), ("output_depth", 2)):
+                    if len(frames) > 1 and all(f[col] is not None for f in frames):
+                        stack = torch.stack([f[col].reshape(f[col].shape[0], f[col].shape[1], -1) for f in frames])
+                        entry[key] = [float(v) for v in self.model.score_consecutive(stack).cpu()]
+                table["consecutive"].append(entry)
+        return table
+
+
 def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_outputs, output_dir, dirname,
-               which_color_pred="blend_psv", jitter_pose=None, msi_format=None):
+               which_color_pred="blend_psv", jitter_pose=None, msi_format=None, scorer=None, scene=None):
     """One iteration of the loop at test.py:199-281.  images = (ref, src, tgt) float [H,W,3] in [0,1]
     (image order ref, src, tgt: data_loader.py:134-136).  msi_format ('rgba8' | 'rgba16f'): the sample's inference also
     emits the packed stack, saved as msi_<dirname>.npz; every other output is unchanged."""
@@ -162,9 +203,11 @@ def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_o
     if "tgt_image" in test_outputs:
         rgb, dep = model.msi_render_equirect_view_and_depth(outs["rgba_layers"], eye, pos, planes, intr)
         write_image(os.path.join(output_dir, "tgt_image_%s.png" % dirname), tgt[0].numpy() * 255.0)
-        write_image(os.path.join(output_dir, "output_tgt_%s.png" % dirname), model.deprocess_image(rgb)[0].cpu().numpy())
-        write_image(os.path.join(output_dir, "output_depth_%s.png" % dirname),
-                    model.deprocess_depth_image(dep)[0].cpu().numpy())
+        rgb8, dep8 = model.deprocess_image(rgb)[0], model.deprocess_depth_image(dep)[0]
+        write_image(os.path.join(output_dir, "output_tgt_%s.png" % dirname), rgb8.cpu().numpy())
+        write_image(os.path.join(output_dir, "output_depth_%s.png" % dirname), dep8.cpu().numpy())
+        if scorer is not None:
+            scorer.add(dirname, scene, tgt[0].numpy() * 255.0, rgb8, dep8)
         if jouts is not None:        # test.py:160-165 renders through the jitter pose; :237-240 (the reference reads a
             # 'jitter_output_depth' it never produces -- here the depth is rendered the same way)
             jrgb, jdep = model.msi_render_equirect_view_and_depth(jouts["rgba_layers"], np.asarray(jitter_pose, np.float32),
@@ -201,7 +244,7 @@ def sample_dirname(scene, ids, test_type="", prefix=""):
 
 
 def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, ngf, test_outputs, output_dir, dirname,
-                  which_color_pred="blend_psv", msi_format=None):
+                  which_color_pred="blend_psv", msi_format=None, scorer=None, scene=None):
     """input_type=PP (test.py:51; data_loader.py:205-226): perspective pair, source camera shifted by -input_offset along
     x, target by -tgt_offset, intrinsics fx = cx = W/2, fy = cy = H/2; plane-sweep volume at the slerp mid-point pose
     (train.py:118-121), target view by mpi_render_view through tgt_pose @ interp_pose_inv (msi.py:644-646).  The MPI path
@@ -223,7 +266,10 @@ def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, n
     if "tgt_image" in test_outputs:
         rgb = model.mpi_render_view(outs["rgba_layers"], np.matmul(tgt_pose, interp_inv).astype(np.float32), planes, K)
         write_image(os.path.join(output_dir, "tgt_image_%s.png" % dirname), tgt[0].numpy() * 255.0)
-        write_image(os.path.join(output_dir, "output_tgt_%s.png" % dirname), model.deprocess_image(rgb)[0].cpu().numpy())
+        rgb8 = model.deprocess_image(rgb)[0]
+        write_image(os.path.join(output_dir, "output_tgt_%s.png" % dirname), rgb8.cpu().numpy())
+        if scorer is not None:
+            scorer.add(dirname, scene, tgt[0].numpy() * 255.0, rgb8)
     write_layer_outputs(outs, None, src, ref, num_planes, test_outputs, output_dir, dirname, which_color_pred)
     save_packed_msi(outs, output_dir, dirname)
     return outs
@@ -313,6 +359,9 @@ def main(argv=None):
     ap.add_argument("--test_outputs", default="rgba_layers_src_image_ref_image_tgt_image_blend_weights_alphas",
                     help="test.py:79-82")
     ap.add_argument("--num_runs", type=int, default=-1)
+    ap.add_argument("--score", action="store_true",
+                    help="score output_tgt against tgt_image on the device (MSI.score_views) and write <experiment>/scores.json: ssim and "
+                         "psnr per example and their means; with on_video also the consecutive-frame differences per scene; default: off")
     ap.add_argument("--strict", action="store_true",
                     help="abort at the first sample whose LayerNorm statistics leave the kernels' fixed-point window or whose target "
                          "position lies outside the innermost sphere (default: write UNRELIABLE.txt next to its files and go on)")
@@ -343,6 +392,7 @@ def main(argv=None):
     planes = model.inv_depths(args.min_depth, args.max_depth, d)
     exp_dir = os.path.join(args.output_root, args.experiment_name)
     os.makedirs(exp_dir, exist_ok=True)
+    scorer = DeviceScores(model, keep_frames="on_video" in args.test_type) if args.score else None
     samples = list(parse_camera_files(args.cameras_glob, args.input_type))
     if args.num_runs >= 0:
         samples = samples[:args.num_runs]
@@ -360,7 +410,7 @@ def main(argv=None):
             try:
                 if args.input_type == "PP":
                     run_sample_pp(model, images, cam[0], cam[1], planes, d, args.ngf, args.test_outputs, out_dir, dirname,
-                                  which_color_pred=args.which_color_pred, msi_format=args.msi_format)
+                                  which_color_pred=args.which_color_pred, msi_format=args.msi_format, scorer=scorer, scene=scene)
                     model.network_status()   # raises if a LayerNorm statistic left the range the kernels resolve
                 else:
                     jitter = None
@@ -368,7 +418,8 @@ def main(argv=None):
                         from . import poses
                         jitter = poses.random_rotation(args.rot_factor, args.tr_factor, jitter_rng)
                     run_sample(model, images, cam[0], cam[1:4], planes, d, args.ngf, args.test_outputs, out_dir, dirname,
-                               which_color_pred=args.which_color_pred, jitter_pose=jitter, msi_format=args.msi_format)
+                               which_color_pred=args.which_color_pred, jitter_pose=jitter, msi_format=args.msi_format,
+                               scorer=scorer, scene=scene)
                 model.render_status()        # raises if a render's ray origin was outside the innermost sphere
             except (MsiError, ValueError) as e:
                 # a sample whose statistics leave the LayerNorm window (a heuristic built from the weights) or whose target lies
@@ -389,6 +440,10 @@ def main(argv=None):
             dirname = sample_dirname(scene, ids, args.test_type, args.prefix)
             run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname, msi_format=args.msi_format)
             n += "high_res_only" in args.test_type
+    if scorer is not None:
+        with open(os.path.join(exp_dir, "scores.json"), "w") as f:
+            json.dump(scorer.table(), f)
+        print("Scores written to %s" % os.path.join(exp_dir, "scores.json"))
     print("processed %d samples%s" % (n, " (%d flagged UNRELIABLE: %s)" % (len(failed), ", ".join(failed)) if failed else ""))
     return n
 

@@ -897,3 +897,86 @@ class MSI(object):
                                            depths.data_ptr(), b, v, h, w, d, oh, ow, _ptr(rgb), _ptr(dep), self._stream()),
                 "msi_mpi_render_views")
         return rgb, dep
+
+    # ------------------------------------------------------------------ image scores (eval.py:127-174 on the device)
+    SCORE_TRANSFORMS = {'raw': N.MSI_SCORE_RAW, 'image': N.MSI_SCORE_IMAGE, 'depth': N.MSI_SCORE_DEPTH}
+    SCORE_METRICS = {'mse': N.MSI_SCORE_MSE, 'psnr': N.MSI_SCORE_MSE, 'mae': N.MSI_SCORE_MAE, 'ssim': N.MSI_SCORE_SSIM}
+
+    def score_views(self, pred, target, metrics=('psnr', 'ssim', 'mae'), transform='image', quantize=True, row_weights=None,
+                    max_val=255.0):
+        """PSNR / SSIM / mean absolute difference of images that are on the device (msi_score_images; evaluate.py states the
+        same numbers on the host) -> dict of float64 device tensors of shape L, one entry per requested metric and always 'mse'.
+
+        pred [*L,h,w,C] and target [*P,h,w,C], C in 1..4, both fp32 or both uint8, both on this model's device; P is a prefix
+        of L, and every pred image is scored against the target image of its leading P indices: [B,V,h,w,C] renders against
+        [B,h,w,C] ground truth, or any batch against one [h,w,C] image.
+        transform: what a stored value means -- 'image' ([-1,1] -> 0..255, deprocess_image's range), 'depth' ([0,1] -> 0..255)
+        or 'raw' (the value as it is); quantize=True scores the 8-bit level deprocess_image / deprocess_depth_image would
+        store (what the harness writes to PNG), False the unrounded value; 'raw' values have no level, quantize is ignored
+        for them.  uint8 images are levels already: 'raw', no quantisation, whatever these two arguments say.
+        row_weights: None, 'solid_angle' (evaluate.solid_angle_row_weights(h): WS-PSNR and its SSIM / MAE counterparts for
+        equirectangular images) or h weights; msi_hip.h gives the weighted formulas.
+        fp64 on the device, bit-reproducible; the workspace is allocated per call and nothing synchronises."""
+        if not (torch.is_tensor(pred) and torch.is_tensor(target)):
+            raise TypeError("score_views: pred and target must be torch tensors on %s" % (self.device,))
+        if pred.device != self.device or target.device != self.device:
+            raise ValueError("score_views: pred is on %s and target on %s, the model on %s" % (pred.device, target.device, self.device))
+        if pred.dtype != target.dtype or pred.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("score_views: pred and target must both be float32 or both uint8, got %s and %s" % (pred.dtype, target.dtype))
+        ps, ts = tuple(pred.shape), tuple(target.shape)
+        if len(ps) < 3 or len(ts) < 3 or len(ts) > len(ps) or ps[-3:] != ts[-3:] or ts[:-3] != ps[:len(ts) - 3]:
+            raise ValueError("score_views: pred %s and target %s must be [*L,h,w,C] and [*P,h,w,C] with P a prefix of L" % (ps, ts))
+        h, w, c = ps[-3:]
+        lead = ps[:-3]
+        n_pairs = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        n_targets = int(np.prod(ts[:-3], dtype=np.int64)) if len(ts) > 3 else 1
+        if n_pairs < 1 or min(h, w) < 1 or not 1 <= c <= 4:
+            raise ValueError("score_views: empty batch or image, or C outside 1..4: pred %s, target %s" % (ps, ts))
+        metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+        unknown = [m for m in metrics if m not in self.SCORE_METRICS]
+        if unknown:
+            raise ValueError("score_views: unknown metrics %s (of %s)" % (unknown, sorted(self.SCORE_METRICS)))
+        mask = N.MSI_SCORE_MSE
+        for m in metrics:
+            mask |= self.SCORE_METRICS[m]
+        if (mask & N.MSI_SCORE_SSIM) and min(h, w) < 11:
+            raise ValueError("score_views: SSIM needs images of at least 11 x 11, got %d x %d (pred %s)" % (h, w, ps))
+        if pred.dtype == torch.uint8:
+            dtype, tcode, q = N.MSI_SCORE_U8, N.MSI_SCORE_RAW, 0
+        else:
+            if transform not in self.SCORE_TRANSFORMS:
+                raise ValueError("score_views: transform must be one of %s" % sorted(self.SCORE_TRANSFORMS))
+            dtype, tcode = N.MSI_SCORE_F32, self.SCORE_TRANSFORMS[transform]
+            q = int(bool(quantize) and tcode != N.MSI_SCORE_RAW)
+        weights = None
+        if row_weights is not None:
+            if isinstance(row_weights, str):
+                if row_weights != 'solid_angle':
+                    raise ValueError("score_views: row_weights must be None, 'solid_angle' or %d weights" % h)
+                from .evaluate import solid_angle_row_weights
+                row_weights = solid_angle_row_weights(h)
+            if not torch.is_tensor(row_weights):
+                row_weights = torch.as_tensor(np.asarray(row_weights, dtype=np.float64))
+            weights = row_weights.to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
+            if weights.numel() != h:
+                raise ValueError("score_views: %d row weights for images of %d rows (pred %s)" % (weights.numel(), h, ps))
+        pred, target = pred.contiguous(), target.contiguous()
+        out = torch.empty((n_pairs, 4), dtype=torch.float64, device=self.device)
+        ws_bytes = N.lib.msi_score_workspace_bytes(n_pairs, h, w, c)
+        if ws_bytes == 0:
+            raise N.MsiError("msi_score_workspace_bytes failed: %s" % N.last_error())
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        N.check(N.lib.msi_score_images(pred.data_ptr(), target.data_ptr(), dtype, tcode, q, n_pairs, n_pairs // n_targets, h, w, c,
+                                       _ptr(weights), float(max_val), mask, out.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()),
+                "msi_score_images")
+        cols = {'mse': 0, 'mae': 1, 'ssim': 2, 'psnr': 3}
+        return {m: out[:, cols[m]].reshape(lead) for m in ('mse',) + tuple(m for m in metrics if m != 'mse')}
+
+    def score_consecutive(self, frames, transform='image', quantize=True):
+        """Mean absolute difference of neighbouring frames, [N,h,w,C] -> [N-1] float64 on the device: the quantity of
+        evaluate.evaluate_consecutive_one (eval.py:147-174) without the files.  transform / quantize as in score_views."""
+        if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[0] < 2:
+            raise ValueError("score_consecutive: frames must be a [N,h,w,C] tensor with N >= 2, got %s" %
+                             (tuple(frames.shape) if torch.is_tensor(frames) else type(frames),))
+        frames = frames.contiguous()
+        return self.score_views(frames[:-1], frames[1:], metrics=('mae',), transform=transform, quantize=quantize)['mae']
