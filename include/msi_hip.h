@@ -542,6 +542,11 @@ int32_t msi_net_plan_layer_is_normalized(const msi_net_plan *plan, int32_t layer
  * (color_pred reports the stand-alone head; msi_net_plan_forward_rgba replaces it by head_assemble_kernel). */
 int32_t msi_net_plan_layer_kernel(const msi_net_plan *plan, int32_t layer, char *name, size_t name_bytes, int32_t *nblocks,
                                   int32_t *nsplit_tiles);
+/* The launch parameters the plan holds for `layer`, as opaque bytes (tests of the planner hash them: a refactor of the planner
+ * must leave them unchanged): the kernel argument with its pointers null, then inlaunch, fuse_ln, skip_apply, ln_blocks as four
+ * int32.  *needed = their size (optional); out may be NULL to ask for it, else out[bytes] must hold them.  The layout is the
+ * library's own and may change between builds. */
+int32_t msi_net_plan_layer_params(const msi_net_plan *plan, int32_t layer, void *out, size_t bytes, size_t *needed);
 /* Health of the LAST forward that ran with `workspace` on `stream` (synchronises the stream: call it after a frame,
  * not inside the frame loop's hot path): MSI_OK, or MSI_E_RANGE with the reason in msi_last_error_string when a
  * LayerNorm sum overflowed its fixed-point window (bit 1 of *status_bits: raw outputs > ~3000x the scale the weights

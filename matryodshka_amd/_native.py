@@ -104,6 +104,7 @@ SIGNATURES = {
     "msi_net_plan_workspace_bytes": (c_size_t, [_P]),
     "msi_net_plan_layer_is_normalized": (_I, [_P, _I]),
     "msi_net_plan_layer_kernel": (_I, [_P, _I, _P, c_size_t, POINTER(c_int32), POINTER(c_int32)]),
+    "msi_net_plan_layer_params": (_I, [_P, _I, _P, c_size_t, POINTER(c_size_t)]),
     "msi_net_plan_status": (_I, [_P, _P, _P, POINTER(c_int32)]),
     "msi_net_plan_calibrate": (_I, [_P, _P, _P, _P, c_size_t, _P, POINTER(c_int32)]),
     "msi_net_plan_forward": (_I, [_P, _P, _P, _P, _P, c_size_t, _P]),
@@ -168,6 +169,14 @@ class NetPlan(object):
         check(lib.msi_net_plan_layer_kernel(self.handle, int(layer), ctypes.cast(buf, c_void_p), 96, ctypes.byref(nb), ctypes.byref(ns)),
               "msi_net_plan_layer_kernel")
         return buf.value.decode(), int(nb.value), int(ns.value)
+
+    def layer_params(self, layer):
+        """The launch parameters planned for `layer`, as bytes (msi_net_plan_layer_params: what tools/plan_golden.py hashes)."""
+        n = c_size_t(0)
+        check(lib.msi_net_plan_layer_params(self.handle, int(layer), None, 0, ctypes.byref(n)), "msi_net_plan_layer_params")
+        buf = ctypes.create_string_buffer(n.value)
+        check(lib.msi_net_plan_layer_params(self.handle, int(layer), ctypes.cast(buf, c_void_p), n.value, None), "msi_net_plan_layer_params")
+        return buf.raw
 
     def kernels(self):
         """[(layer name-less index, kernel, workgroups, split tiles)] for the 18 layers in graph order."""

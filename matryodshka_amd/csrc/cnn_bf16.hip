@@ -878,11 +878,7 @@ int launch_halo_bf16(const LayerLaunch &Q, const ConvParams &p, hipStream_t stre
 #endif
   static_assert(lds >= EPI_STAGE_BYTES, "the epilogue's staging strips");
   if (APPLY && p.C0 > 512) return msi::fail(MSI_E_UNSUPPORTED, "conv_halo_bf16: APPLY with more than 512 input channels");
-  static thread_local unsigned long long done = 0;
-  int rc0 = set_max_lds(reinterpret_cast<const void *>(conv_halo_bf16_kernel<BM, BN, RATE, APPLY, NW>), lds, done, "conv_halo_bf16");
-  if (rc0) return rc0;
-  hipLaunchKernelGGL((conv_halo_bf16_kernel<BM, BN, RATE, APPLY, NW>), dim3(Q.nblocks), dim3(64 * NW), lds, stream, p);
-  return msi::check_launch("conv_halo_bf16");
+  return launch_kernel<conv_halo_bf16_kernel<BM, BN, RATE, APPLY, NW>, lds, 64 * NW>(Q.nblocks, p, stream, "conv_halo_bf16");
 }
 
 template <int APPLY, int NW>
@@ -890,45 +886,44 @@ int launch_halo_bf16_s2(const LayerLaunch &Q, const ConvParams &p, hipStream_t s
   constexpr int lds = HaloGeomBS2::LDS_BYTES + (APPLY ? 8 * 512 : 0);
   static_assert(lds >= EPI_STAGE_BYTES && 2 * lds <= 160 * 1024, "staging strips; two workgroups per CU");
   if (APPLY && p.C0 > 512) return msi::fail(MSI_E_UNSUPPORTED, "conv_halo_bf16_s2: APPLY with more than 512 input channels");
-  static thread_local unsigned long long done = 0;
-  int rc0 = set_max_lds(reinterpret_cast<const void *>(conv_halo_bf16_s2_kernel<APPLY, NW>), lds, done, "conv_halo_bf16_s2");
-  if (rc0) return rc0;
-  hipLaunchKernelGGL((conv_halo_bf16_s2_kernel<APPLY, NW>), dim3(Q.nblocks), dim3(64 * NW), lds, stream, p);
-  return msi::check_launch("conv_halo_bf16_s2");
+  return launch_kernel<conv_halo_bf16_s2_kernel<APPLY, NW>, lds, 64 * NW>(Q.nblocks, p, stream, "conv_halo_bf16_s2");
 }
 
 template <int BM, int BN, int APPLY>
 int launch_convt_halo_bf16(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
   constexpr int lds = HaloGeomB<BM, BN, 1>::LDS_BYTES;
-  static thread_local unsigned long long done = 0;
-  int rc0 = set_max_lds(reinterpret_cast<const void *>(convt_halo_bf16_kernel<BM, BN, APPLY>), lds, done, "convt_halo_bf16");
-  if (rc0) return rc0;
-  hipLaunchKernelGGL((convt_halo_bf16_kernel<BM, BN, APPLY>), dim3(Q.nblocks), dim3(256), lds, stream, p);
-  return msi::check_launch("convt_halo_bf16");
+  return launch_kernel<convt_halo_bf16_kernel<BM, BN, APPLY>, lds>(Q.nblocks, p, stream, "convt_halo_bf16");
 }
 
 }  // namespace
 
 namespace msi_cnn {
-int launch_bf16_halo(const LayerLaunch &Q, const ConvParams &p, int rate, bool w8, hipStream_t stream) {
-  if (Q.halo_tb) {
+int launch_bf16_halo(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
+  const ConvVariant &V = Q.variant;
+  switch (vkey(V.family, V.bm / 64, V.bn / 64, V.rate, V.apply, V.waves)) {   // <BM, BN (in 64s), RATE, APPLY, waves>
+    case vkey(CONV_HALO_BF16, 2, 2, 1, 0, 4): return launch_halo_bf16<128, 128, 1, 0, 4>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 2, 2, 1, 0, 8): return launch_halo_bf16<128, 128, 1, 0, 8>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 2, 2, 1, 1, 4): return launch_halo_bf16<128, 128, 1, 1, 4>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 2, 2, 1, 1, 8): return launch_halo_bf16<128, 128, 1, 1, 8>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 2, 2, 2, 0, 4): return launch_halo_bf16<128, 128, 2, 0, 4>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 2, 2, 2, 0, 8): return launch_halo_bf16<128, 128, 2, 0, 8>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 2, 2, 2, 1, 4): return launch_halo_bf16<128, 128, 2, 1, 4>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 2, 2, 2, 1, 8): return launch_halo_bf16<128, 128, 2, 1, 8>(Q, p, stream);
+    // (the 256 x 64 tile stays at four waves: eight do not fit their 128 registers -- 44-64 bytes of scratch -- and were
+    // measured slower, conv8_2 27.8 k -> 32.9 k cycles per workgroup)
+    case vkey(CONV_HALO_BF16, 4, 1, 1, 0, 4): return launch_halo_bf16<256, 64, 1, 0, 4>(Q, p, stream);
+    case vkey(CONV_HALO_BF16, 4, 1, 1, 1, 4): return launch_halo_bf16<256, 64, 1, 1, 4>(Q, p, stream);
+    // (four waves: with eight the staging path does not fit 128 registers -- 48 bytes of scratch -- and was measured
+    // 0.8 % of the network slower, three interleaved repeats)
+    case vkey(CONV_HALO_BF16_S2, 2, 2, 0, 0, 4): return launch_halo_bf16_s2<0, 4>(Q, p, stream);
+    case vkey(CONV_HALO_BF16_S2, 2, 2, 0, 1, 4): return launch_halo_bf16_s2<1, 4>(Q, p, stream);
+    case vkey(CONVT_HALO_BF16, 2, 2, 0, 0): return launch_convt_halo_bf16<128, 128, 0>(Q, p, stream);
+    case vkey(CONVT_HALO_BF16, 2, 1, 0, 0): return launch_convt_halo_bf16<128, 64, 0>(Q, p, stream);
+    case vkey(CONVT_HALO_BF16, 2, 1, 0, 1): return launch_convt_halo_bf16<128, 64, 1>(Q, p, stream);
     // (the 128 x 128 tile with APPLY needs more than the 256 registers of two waves per SIMD -- 120 bytes of scratch inside
     // the chunk loop -- and is not built: the plan only marks sources of the 128 x 64 tile as raw)
-    if (p.halo_apply) return Q.hbn == 128 ? msi::fail(MSI_E_UNSUPPORTED, "convt_halo_bf16: APPLY is built for the 128x64 tile")
-                                          : launch_convt_halo_bf16<128, 64, 1>(Q, p, stream);
-    return Q.hbn == 128 ? launch_convt_halo_bf16<128, 128, 0>(Q, p, stream) : launch_convt_halo_bf16<128, 64, 0>(Q, p, stream);
+    case vkey(CONVT_HALO_BF16, 2, 2, 0, 1): return msi::fail(MSI_E_UNSUPPORTED, "convt_halo_bf16: APPLY is built for the 128x64 tile");
   }
-  if (Q.halo_s2)   // (four waves: with eight the staging path does not fit 128 registers -- 48 bytes of scratch -- and was measured
-                   // 0.8 % of the network slower, three interleaved repeats)
-    return Q.halo_apply ? launch_halo_bf16_s2<1, 4>(Q, p, stream) : launch_halo_bf16_s2<0, 4>(Q, p, stream);
-#define MSI_HB(BM_, BN_, R_, A_) (w8 ? launch_halo_bf16<BM_, BN_, R_, A_, 8>(Q, p, stream) : launch_halo_bf16<BM_, BN_, R_, A_, 4>(Q, p, stream))
-  if (Q.hbm == 128) {
-    if (rate == 1) return Q.halo_apply ? MSI_HB(128, 128, 1, 1) : MSI_HB(128, 128, 1, 0);
-    return Q.halo_apply ? MSI_HB(128, 128, 2, 1) : MSI_HB(128, 128, 2, 0);
-  }
-#undef MSI_HB
-  // (the 256 x 64 tile stays at four waves: eight do not fit their 128 registers -- 44-64 bytes of scratch -- and were
-  // measured slower, conv8_2 27.8 k -> 32.9 k cycles per workgroup)
-  return Q.halo_apply ? launch_halo_bf16<256, 64, 1, 1, 4>(Q, p, stream) : launch_halo_bf16<256, 64, 1, 0, 4>(Q, p, stream);
+  return msi::fail(MSI_E_UNSUPPORTED, "conv_halo_bf16: no bf16 halo kernel of family %d with tile %d x %d, rate %d, APPLY %d, %d waves", V.family, V.bm, V.bn, V.rate, V.apply, V.waves);
 }
 }  // namespace msi_cnn

@@ -1,5 +1,7 @@
 // Shared by the translation units of the K2 convolution kernels (r05: cnn.hip used to be ONE 400 KB translation unit -- VERDICT r04 item 8):
-//   cnn.hip        host side: layer table, packing, plan, forward, C ABI
+//   cnn_net.hip    host side: the network description and the weight packer (cnn_plan.h holds the host types)
+//   cnn_plan.hip   host side: tile planner, the choice of each layer's kernel (ConvVariant), plan entry points
+//   cnn.hip        host side: forward loop (launch_conv), fused tail, status, calibration, descriptor-level conveniences
 //   cnn_igemm.hip  conv_igemm_kernel (tap-DMA implicit GEMM, fp32 / bf16), conv_fixup_kernel
 //   cnn_halo.hip   the native fp32 halo-patch kernels (stride 1 / 2, conv-transpose)
 //   cnn_x3.hip     fp32 through the six-product bf16 / three-product fp16 split (stride 1 incl. the 8-row tile, stride 2, conv-transpose)
@@ -118,28 +120,40 @@ struct ConvParams {
 #endif
 };
 
-enum { TILE_64x64 = 0, TILE_128x128 = 1, TILE_128x64 = 2, TILE_64x128 = 3 };
+// Which kernel a layer runs: one family per __global__ template and that template's arguments as plain ints.  Chosen once, at plan time
+// (choose_variant, cnn_plan.hip); the launchers, launch_conv's fix-up and msi_net_plan_layer_kernel's name all read this record and nothing else.
+enum ConvFamily {
+  CONV_IGEMM = 0,                                                                                    // cnn_igemm.hip: conv_igemm_kernel<BM, BN, MODE, BF16> (the tap kernel)
+  CONV_HALO, CONV_HALO_S2, CONVT_HALO,                                                               // cnn_halo.hip: the native fp32 halo-patch kernels
+  CONV_HALO_X3, CONV_HALO8_X3, CONV_HALO_S2_X3, CONV_HALO8_S2_X3, CONVT_HALO_X3, CONVT_HALO8_X3,     // cnn_x3.hip: fp32 through the bf16 / fp16 split (plan option F32_SPLIT3)
+  CONV_HALO_BF16, CONV_HALO_BF16_S2, CONVT_HALO_BF16,                                                // cnn_bf16.hip
+};
+struct ConvVariant {   // (an argument the family's template does not have is 0)
+  int family;       // ConvFamily
+  int bm, bn;       // the tile: GEMM rows (pixels) x output channels per workgroup
+  int mode, bf16;   // CONV_IGEMM only: MODE_*, operand type
+  int rate;         // 1 / 2: the dilation; 3: a rate-2 layer on row-parity tiles (p.row_par; plan option X3_ROWPAR)
+  int apply;        // APPLY: the producer's LayerNorm is applied while staging the patch, the producer's buffer stays raw (CONVT_HALO_BF16: of the sources in
+                    // p.halo_apply; the fp32 conv-transposes have no such argument, they read p.halo_apply).  Written by plan_layers' raw-staging pass, after the choice
+  int planes;       // the split families: 3 = six products of bf16 parts, 2 = three products of fp16 parts (plan option F32_SPLIT_F16); else 0
+  int waves;        // the bf16 conv families: 4 / 8 wavefronts per workgroup (plan option BF16_WAVES)
+  bool is_halo() const { return family != CONV_IGEMM; }
+  bool is_convt_f32() const { return family == CONVT_HALO || family == CONVT_HALO_X3 || family == CONVT_HALO8_X3; }
+  bool is_convt() const { return is_convt_f32() || family == CONVT_HALO_BF16; }   // the two classes of one output-row parity per workgroup; either source may be staged raw
+  bool six_product() const { return family >= CONV_HALO_X3 && family <= CONVT_HALO8_X3; }   // reads the split weight planes (p.wpk_x3)
+  bool tile8() const { return family == CONV_HALO8_X3 || family == CONV_HALO8_S2_X3 || family == CONVT_HALO8_X3; }   // the 8 x 16-pixel tile (plan option X3_TILE8)
+};
 
 // One layer's launch, everything but the pointers resolved at plan time.
 struct LayerLaunch {
   ConvParams p;     // pointer members are filled per forward
-  int tile;         // TILE_*
+  ConvVariant variant;
   int nblocks, nfix;
   int inlaunch;     // the split tiles are summed inside the conv launch (tickets) rather than by conv_fixup_kernel
   int fuse_ln;      // head: applies its source's LayerNorm while loading (the source is not normalised in memory)
   int skip_apply;   // this layer's output is consumed raw by the head, or normalised by its consumer's launch: no ln_apply launch
-  int halo;         // conv_halo_kernel (fp32) / conv_halo_bf16_kernel instead of conv_igemm_kernel
-  int halo_s2;      // ... conv_halo_s2_kernel: the stride-2 3x3 layers through parity-plane patches (fp32)
-  int halo_x3;      // ... conv_halo_x3_kernel: fp32 through the 3-way bf16 split with six products (plan option F32_SPLIT3)
-  int halo_x2;      // ... its fp16 form: 2-way split, three products (plan option F32_SPLIT_F16; needs halo_x3)
-  int x3_th8;       // ... its 8 x 16-pixel tile (conv_halo8_x3_kernel: six-product form, rate 1; plan option X3_TILE8)
-  int hbm, hbn;     // bf16 halo tile: 128 x 128 or 256 x 64
-  int halo_t;       // convt_halo_kernel (conv-transpose, fp32): the two classes of one output-row parity per workgroup
-  int halo_tb;      // convt_halo_bf16_kernel (conv-transpose, bf16): the two classes of one output-row parity per workgroup
-  int halo_apply;   // ... applying the producer's LayerNorm while staging the patch (the producer's buffer stays raw)
   unsigned ln_blocks;
 };
-
 
 constexpr int HA_TP = 32;   // pixels per workgroup
 #ifndef MSI_HA_LG
@@ -165,11 +179,14 @@ struct HeadAsmParams {
 };
 
 // ---- launch entry points of the kernel families (each returns an MSI_* code; p carries every pointer) ----
-int launch_igemm(const LayerLaunch &Q, const ConvParams &p, int bf16, hipStream_t stream);                        // cnn_igemm.hip: Q.tile, p.mode; its split tiles' fix-up launch included
-int launch_fixup(int bm, int bn, int mode, unsigned grid_x, unsigned grid_y, const ConvParams &p, hipStream_t stream);   // cnn_igemm.hip: conv_fixup_kernel<bm, 64, mode> for the halo families
-int launch_halo_f32(const LayerLaunch &Q, const ConvParams &p, int rate, hipStream_t stream);                     // cnn_halo.hip: convt_halo_kernel / conv_halo_s2_kernel / conv_halo_kernel
-int launch_x3(const LayerLaunch &Q, const ConvParams &p, int rate, hipStream_t stream);                           // cnn_x3.hip: every split kernel (Q.halo_x3)
-int launch_bf16_halo(const LayerLaunch &Q, const ConvParams &p, int rate, bool eight_waves, hipStream_t stream);  // cnn_bf16.hip: Q.halo_tb, or Q.halo of a bf16 plan
+// launch_conv (cnn.hip) forwards to the unit of Q.variant.family, then launches conv_fixup_kernel where the plan sums the split tiles in a launch of their own.
+// Each family launcher is one switch over the record and fails with MSI_E_UNSUPPORTED on a record it has no instantiation for.
+int launch_conv(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream);
+int launch_igemm(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream);       // cnn_igemm.hip: CONV_IGEMM
+int launch_fixup(int bm, int bn, int mode, int raw16, unsigned grid_x, unsigned grid_y, const ConvParams &p, hipStream_t stream);   // cnn_igemm.hip: conv_fixup_kernel<bm, bn, mode, raw16>
+int launch_halo_f32(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream);    // cnn_halo.hip: CONV_HALO, CONV_HALO_S2, CONVT_HALO
+int launch_x3(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream);          // cnn_x3.hip: the six split families (ConvVariant::six_product)
+int launch_bf16_halo(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream);   // cnn_bf16.hip: CONV_HALO_BF16, CONV_HALO_BF16_S2, CONVT_HALO_BF16
 int launch_zero(void *p, size_t n16, hipStream_t stream);                                                         // cnn_tail.hip
 int launch_ln_finish(int batch, hipStream_t stream, const long long *sums, double inv_n, const double *scl, int *status, const float *gamma, const float *beta, int C,
                      float *aff, int raw16);
@@ -177,6 +194,9 @@ int launch_ln_apply(int bf16out, unsigned blocks, int batch, size_t lds, hipStre
                     const float *gamma, const float *beta, size_t per_sample, int C, float *aff, unsigned short *yb);
 int launch_head_assemble(int bf16in, int format, unsigned grid_x, size_t lds, hipStream_t stream, const HeadAsmParams &q);   // format = MSI_LAYERS_F32: head_assemble_kernel, else the packed form writing q.layers
 int debug_conv_occupancy(int lds_bytes);                                                                          // cnn_igemm.hip (tools/conv_timing.py)
+
+// A launcher's switch key: the family and those arguments of its template that the family has (each < 16), for `case` labels that read as the instantiation.
+constexpr int vkey(int family, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0) { return ((((family * 16 + a) * 16 + b) * 16 + c) * 16 + d) * 16 + e; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the function ON A DEVICE: set once per (instantiation,
 // device) -- `done` is a per-instantiation bit mask over the device ordinal, so a thread that drives a second GPU sets
@@ -190,6 +210,18 @@ inline int set_max_lds(const void *fn, int lds, unsigned long long &done, const 
   if (e != hipSuccess) return msi::fail(MSI_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
   if (tracked) done |= 1ull << dev;
   return MSI_OK;
+}
+
+// One instantiation's launch: above 64 KB of LDS it needs the attribute first (set_max_lds: one `done` mask per instantiation -- this template's own static).
+template <auto KERNEL, int LDS, int THREADS = 256>
+int launch_kernel(unsigned nblocks, const ConvParams &p, hipStream_t stream, const char *what) {
+  if constexpr (LDS > 65536) {
+    static thread_local unsigned long long done = 0;
+    int rc0 = set_max_lds(reinterpret_cast<const void *>(KERNEL), LDS, done, what);
+    if (rc0) return rc0;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(nblocks), dim3(THREADS), LDS, stream, p);
+  return msi::check_launch(what);
 }
 
 // a compile-time integer as a lambda argument: the k-steps of the kernels are generic lambdas called with their tap / step index (r05: they used to be macros)

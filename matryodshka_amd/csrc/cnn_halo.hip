@@ -843,26 +843,17 @@ convt_halo_kernel(const ConvParams p) {
 }  // namespace
 
 namespace msi_cnn {
-int launch_halo_f32(const LayerLaunch &Q, const ConvParams &p, int rate, hipStream_t stream) {
-  const dim3 grid(Q.nblocks), block(256);
-  if (Q.halo_t) {
-    hipLaunchKernelGGL(convt_halo_kernel, grid, block, ConvtHaloGeom::LDS_BYTES, stream, p);
-    int rc = msi::check_launch("convt_halo");
-    if (!rc && Q.nfix > 0 && p.tile_cnt == nullptr) rc = launch_fixup(64, 64, MODE_CONVT, Q.nfix, 2, p, stream);
-    return rc;
+int launch_halo_f32(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
+  const ConvVariant &V = Q.variant;
+  switch (vkey(V.family, V.rate, V.apply)) {   // <RATE, APPLY>
+    case vkey(CONV_HALO, 1, 0): return launch_kernel<conv_halo_kernel<1, 0>, HaloGeom<1>::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo");
+    case vkey(CONV_HALO, 1, 1): return launch_kernel<conv_halo_kernel<1, 1>, HaloGeom<1>::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo");
+    case vkey(CONV_HALO, 2, 0): return launch_kernel<conv_halo_kernel<2, 0>, HaloGeom<2>::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo");
+    case vkey(CONV_HALO, 2, 1): return launch_kernel<conv_halo_kernel<2, 1>, HaloGeom<2>::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo");
+    case vkey(CONV_HALO_S2, 0, 0): return launch_kernel<conv_halo_s2_kernel<0>, HaloGeomS2::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo");
+    case vkey(CONV_HALO_S2, 0, 1): return launch_kernel<conv_halo_s2_kernel<1>, HaloGeomS2::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo");
+    case vkey(CONVT_HALO): return launch_kernel<convt_halo_kernel, ConvtHaloGeom::LDS_BYTES>(Q.nblocks, p, stream, "convt_halo");   // (no APPLY argument: the kernel reads p.halo_apply)
   }
-  if (Q.halo_s2) {
-    if (Q.halo_apply) hipLaunchKernelGGL((conv_halo_s2_kernel<1>), grid, block, HaloGeomS2::LDS_BYTES, stream, p);
-    else hipLaunchKernelGGL((conv_halo_s2_kernel<0>), grid, block, HaloGeomS2::LDS_BYTES, stream, p);
-  } else if (rate == 1) {
-    if (Q.halo_apply) hipLaunchKernelGGL((conv_halo_kernel<1, 1>), grid, block, HaloGeom<1>::LDS_BYTES, stream, p);
-    else hipLaunchKernelGGL((conv_halo_kernel<1, 0>), grid, block, HaloGeom<1>::LDS_BYTES, stream, p);
-  } else {
-    if (Q.halo_apply) hipLaunchKernelGGL((conv_halo_kernel<2, 1>), grid, block, HaloGeom<2>::LDS_BYTES, stream, p);
-    else hipLaunchKernelGGL((conv_halo_kernel<2, 0>), grid, block, HaloGeom<2>::LDS_BYTES, stream, p);
-  }
-  int rc = msi::check_launch("conv_halo");
-  if (!rc && Q.nfix > 0 && p.tile_cnt == nullptr) rc = launch_fixup(64, 64, MODE_CONV, Q.nfix, 1, p, stream);
-  return rc;
+  return msi::fail(MSI_E_UNSUPPORTED, "conv_halo: no fp32 halo kernel of family %d with rate %d, APPLY %d", V.family, V.rate, V.apply);
 }
 }  // namespace msi_cnn

@@ -516,75 +516,48 @@ conv_fixup_kernel(const ConvParams p) {
 
 template <int BM, int BN, int MODE, int BF16>
 int launch_conv_mode(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
-  const size_t lds = (size_t)NSTAGE * (BM + BN) * ROW_BYTES;
-  if (lds > 64 * 1024) {
-    static thread_local unsigned long long done = 0;
-    int rc0 = set_max_lds(reinterpret_cast<const void *>(conv_igemm_kernel<BM, BN, MODE, BF16>), (int)lds, done, "conv");
-    if (rc0) return rc0;
-  }
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, MODE, BF16>), dim3(Q.nblocks + p.n_apply), dim3(256), lds, stream, p);
-  int rc = msi::check_launch("conv_igemm");
-  if (rc || Q.nfix == 0 || p.tile_cnt != nullptr) return rc;
-  if constexpr (BM * BN == 64 * 64) {   // (big tiles are never split)
-    hipLaunchKernelGGL((conv_fixup_kernel<BM, BN, MODE, (BF16 && MODE != MODE_HEAD) ? 1 : 0>), dim3(Q.nfix), dim3(256), 0, stream, p);
-    return msi::check_launch("conv_fixup");
-  } else {
-    return msi::fail(MSI_E_UNSUPPORTED, "conv: split big tile");
-  }
-}
-
-template <int BM, int BN>
-int launch_conv(const LayerLaunch &Q, const ConvParams &p, int bf16, hipStream_t stream) {
-  if constexpr (BM == 64 && BN == 128) {
-    if (bf16) return msi::fail(MSI_E_UNSUPPORTED, "conv: 64x128 is an fp32 tile");
-  } else if (bf16) {
-    switch (p.mode) {
-      case MODE_CONV: return launch_conv_mode<BM, BN, MODE_CONV, 1>(Q, p, stream);
-      case MODE_CONVT: return launch_conv_mode<BM, BN, MODE_CONVT, 1>(Q, p, stream);
-      default: return launch_conv_mode<BM, BN, MODE_HEAD, 1>(Q, p, stream);
-    }
-  }
-  if constexpr (BM * BN == 64 * 64) {
-    switch (p.mode) {
-      case MODE_CONV: return launch_conv_mode<BM, BN, MODE_CONV, 0>(Q, p, stream);
-      case MODE_CONVT: return launch_conv_mode<BM, BN, MODE_CONVT, 0>(Q, p, stream);
-      default: return launch_conv_mode<BM, BN, MODE_HEAD, 0>(Q, p, stream);
-    }
-#ifdef MSI_EXPERIMENTS
-  } else if constexpr (BM * BN == 128 * 64) {
-    switch (p.mode) {
-      case MODE_CONV: return launch_conv_mode<BM, BN, MODE_CONV, 0>(Q, p, stream);
-      case MODE_CONVT: return launch_conv_mode<BM, BN, MODE_CONVT, 0>(Q, p, stream);
-      default: return msi::fail(MSI_E_UNSUPPORTED, "conv: fp32 head uses the 64x64 tile");
-    }
-#endif
-  } else {
-    return msi::fail(MSI_E_UNSUPPORTED, "conv: the fp32 path is built for the 64x64, 128x64 and 64x128 tiles");
-  }
+  return launch_kernel<conv_igemm_kernel<BM, BN, MODE, BF16>, NSTAGE * (BM + BN) * ROW_BYTES>(Q.nblocks + p.n_apply, p, stream, "conv_igemm");
 }
 
 }  // namespace
 
 namespace msi_cnn {
-int launch_igemm(const LayerLaunch &Q, const ConvParams &p, int bf16, hipStream_t stream) {
-  switch (Q.tile) {
-    case TILE_128x128: return launch_conv<128, 128>(Q, p, bf16, stream);
-    case TILE_128x64: return launch_conv<128, 64>(Q, p, bf16, stream);
-#ifdef MSI_EXPERIMENTS
-    case TILE_64x128: return bf16 ? msi::fail(MSI_E_UNSUPPORTED, "conv: 64x128 is an fp32 tile") : launch_conv<64, 128>(Q, p, 0, stream);
-#else
-    case TILE_64x128: return msi::fail(MSI_E_UNSUPPORTED, "conv: the 64x128 fp32 tile is an experiment (MSI_EXPERIMENTS)");
+int launch_igemm(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
+  const ConvVariant &V = Q.variant;
+  switch (vkey(V.family, V.bm / 64, V.bn / 64, V.mode, V.bf16)) {   // <BM, BN (in 64s), MODE, BF16>
+    case vkey(CONV_IGEMM, 1, 1, MODE_CONV, 0): return launch_conv_mode<64, 64, MODE_CONV, 0>(Q, p, stream);
+    case vkey(CONV_IGEMM, 1, 1, MODE_CONVT, 0): return launch_conv_mode<64, 64, MODE_CONVT, 0>(Q, p, stream);
+    case vkey(CONV_IGEMM, 1, 1, MODE_HEAD, 0): return launch_conv_mode<64, 64, MODE_HEAD, 0>(Q, p, stream);
+    case vkey(CONV_IGEMM, 1, 1, MODE_CONV, 1): return launch_conv_mode<64, 64, MODE_CONV, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 1, 1, MODE_CONVT, 1): return launch_conv_mode<64, 64, MODE_CONVT, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 1, 1, MODE_HEAD, 1): return launch_conv_mode<64, 64, MODE_HEAD, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 2, 1, MODE_CONV, 1): return launch_conv_mode<128, 64, MODE_CONV, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 2, 1, MODE_CONVT, 1): return launch_conv_mode<128, 64, MODE_CONVT, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 2, 1, MODE_HEAD, 1): return launch_conv_mode<128, 64, MODE_HEAD, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 2, 2, MODE_CONV, 1): return launch_conv_mode<128, 128, MODE_CONV, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 2, 2, MODE_CONVT, 1): return launch_conv_mode<128, 128, MODE_CONVT, 1>(Q, p, stream);
+    case vkey(CONV_IGEMM, 2, 2, MODE_HEAD, 1): return launch_conv_mode<128, 128, MODE_HEAD, 1>(Q, p, stream);
+#ifdef MSI_EXPERIMENTS   // the fp32 tile experiments (plan options F32_TILE, F32_TILE_MASK; the fp32 head uses the 64x64 tile)
+    case vkey(CONV_IGEMM, 2, 1, MODE_CONV, 0): return launch_conv_mode<128, 64, MODE_CONV, 0>(Q, p, stream);
+    case vkey(CONV_IGEMM, 2, 1, MODE_CONVT, 0): return launch_conv_mode<128, 64, MODE_CONVT, 0>(Q, p, stream);
+    case vkey(CONV_IGEMM, 1, 2, MODE_CONV, 0): return launch_conv_mode<64, 128, MODE_CONV, 0>(Q, p, stream);
+    case vkey(CONV_IGEMM, 1, 2, MODE_CONVT, 0): return launch_conv_mode<64, 128, MODE_CONVT, 0>(Q, p, stream);
 #endif
-    default: return launch_conv<64, 64>(Q, p, bf16, stream);
   }
+  return msi::fail(MSI_E_UNSUPPORTED, "conv: no conv_igemm_kernel<%d, %d, %d, %d> (fp32: the 64x64 tile; 128x64 and 64x128 are experiments, MSI_EXPERIMENTS)", V.bm, V.bn, V.mode, V.bf16);
 }
-int launch_fixup(int bm, int bn, int mode, unsigned gx, unsigned gy, const ConvParams &p, hipStream_t stream) {
-  if (bn != 64) return msi::fail(MSI_E_UNSUPPORTED, "conv_fixup: tile %d x %d", bm, bn);
-  if (bm == 64 && mode == MODE_CONVT) hipLaunchKernelGGL((conv_fixup_kernel<64, 64, MODE_CONVT>), dim3(gx, gy), dim3(256), 0, stream, p);
-  else if (bm == 64 && mode == MODE_CONV) hipLaunchKernelGGL((conv_fixup_kernel<64, 64, MODE_CONV>), dim3(gx, gy), dim3(256), 0, stream, p);
-  else if (bm == 128 && mode == MODE_CONV) hipLaunchKernelGGL((conv_fixup_kernel<128, 64, MODE_CONV>), dim3(gx, gy), dim3(256), 0, stream, p);
-  else if (bm == 128 && mode == MODE_CONVT) hipLaunchKernelGGL((conv_fixup_kernel<128, 64, MODE_CONVT>), dim3(gx, gy), dim3(256), 0, stream, p);
-  else return msi::fail(MSI_E_UNSUPPORTED, "conv_fixup: tile %d x %d, mode %d", bm, bn, mode);
+int launch_fixup(int bm, int bn, int mode, int raw16, unsigned gx, unsigned gy, const ConvParams &p, hipStream_t stream) {
+  const dim3 grid(gx, gy), block(256);
+  switch (bn == 64 ? vkey(bm / 64, mode, raw16 ? 1 : 0) : -1) {   // <BM (in 64s), MODE, RAW16: the bf16 plans' fp16 raw output (tap kernel only)>; big tiles of the tap kernel are never split
+    case vkey(1, MODE_CONV, 0): hipLaunchKernelGGL((conv_fixup_kernel<64, 64, MODE_CONV, 0>), grid, block, 0, stream, p); break;
+    case vkey(1, MODE_CONVT, 0): hipLaunchKernelGGL((conv_fixup_kernel<64, 64, MODE_CONVT, 0>), grid, block, 0, stream, p); break;
+    case vkey(1, MODE_HEAD, 0): hipLaunchKernelGGL((conv_fixup_kernel<64, 64, MODE_HEAD, 0>), grid, block, 0, stream, p); break;
+    case vkey(1, MODE_CONV, 1): hipLaunchKernelGGL((conv_fixup_kernel<64, 64, MODE_CONV, 1>), grid, block, 0, stream, p); break;
+    case vkey(1, MODE_CONVT, 1): hipLaunchKernelGGL((conv_fixup_kernel<64, 64, MODE_CONVT, 1>), grid, block, 0, stream, p); break;
+    case vkey(2, MODE_CONV, 0): hipLaunchKernelGGL((conv_fixup_kernel<128, 64, MODE_CONV, 0>), grid, block, 0, stream, p); break;
+    case vkey(2, MODE_CONVT, 0): hipLaunchKernelGGL((conv_fixup_kernel<128, 64, MODE_CONVT, 0>), grid, block, 0, stream, p); break;
+    default: return msi::fail(MSI_E_UNSUPPORTED, "conv_fixup: tile %d x %d, mode %d%s", bm, bn, mode, raw16 ? ", fp16 raw output" : "");
+  }
   return msi::check_launch("conv_fixup");
 }
 int debug_conv_occupancy(int lds_bytes) {

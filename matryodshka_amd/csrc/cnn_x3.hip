@@ -1236,70 +1236,47 @@ convt_halo8_x3_kernel(const ConvParams p) {
 #endif
 }
 
+template <int R, int A, int N>
+int launch_s1(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
+  return launch_kernel<conv_halo_x3_kernel<R, A, N>, HaloGeomX3<R, x3_nstg(R, N), N>::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo_x3");
+}
+template <int A, int N>
+int launch_s2(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
+  return launch_kernel<conv_halo_s2_x3_kernel<A, N>, HaloGeomS2X3<N>::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo_x3");
+}
+
 }  // namespace
 
 namespace msi_cnn {
-int launch_x3(const LayerLaunch &Q, const ConvParams &p, int rate, hipStream_t stream) {
-  const dim3 grid(Q.nblocks), block(256);
-  if (Q.halo_t) {
-    constexpr int lds_ct3 = HaloGeomCT3<MSI_CT3_NSTG, 3>::LDS_BYTES, lds_ct2 = HaloGeomCT3<3, 2>::LDS_BYTES;
-    constexpr int lds_ct8 = HaloGeomCT3<MSI_CT3_NSTG, 3, 8>::LDS_BYTES;
-    static_assert(lds_ct8 <= 65536, "convt_halo8_x3_kernel: LDS without the launch attribute");
-    if (Q.x3_th8) hipLaunchKernelGGL(convt_halo8_x3_kernel, grid, block, lds_ct8, stream, p);
-    else if (Q.halo_x2) hipLaunchKernelGGL(convt_halo_x3_kernel<2>, grid, block, lds_ct2, stream, p);
-    else hipLaunchKernelGGL(convt_halo_x3_kernel<3>, grid, block, lds_ct3, stream, p);
-    int rc = msi::check_launch("convt_halo_x3");
-    if (!rc && Q.nfix > 0 && p.tile_cnt == nullptr) rc = launch_fixup(Q.x3_th8 ? 128 : 64, 64, MODE_CONVT, Q.nfix, 2, p, stream);
-    return rc;
+int launch_x3(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
+  const ConvVariant &V = Q.variant;
+  typedef HaloGeomX3<1, (MSI_X3_NSTG ? MSI_X3_NSTG : 2), 3, 8> G8;
+  typedef HaloGeomS2X3<3, 8> G8s;
+  switch (vkey(V.family, V.rate, V.apply, V.planes)) {   // <RATE (3: row-parity tiles), APPLY, planes>
+    case vkey(CONV_HALO_X3, 1, 0, 2): return launch_s1<1, 0, 2>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 1, 0, 3): return launch_s1<1, 0, 3>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 1, 1, 2): return launch_s1<1, 1, 2>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 1, 1, 3): return launch_s1<1, 1, 3>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 2, 0, 2): return launch_s1<2, 0, 2>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 2, 0, 3): return launch_s1<2, 0, 3>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 2, 1, 2): return launch_s1<2, 1, 2>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 2, 1, 3): return launch_s1<2, 1, 3>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 3, 0, 2): return launch_s1<3, 0, 2>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 3, 0, 3): return launch_s1<3, 0, 3>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 3, 1, 2): return launch_s1<3, 1, 2>(Q, p, stream);
+    case vkey(CONV_HALO_X3, 3, 1, 3): return launch_s1<3, 1, 3>(Q, p, stream);
+    case vkey(CONV_HALO8_X3, 0, 0, 3): return launch_kernel<conv_halo8_x3_kernel<0, 3>, G8::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo_x3");
+    case vkey(CONV_HALO8_X3, 0, 1, 3): return launch_kernel<conv_halo8_x3_kernel<1, 3>, G8::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo_x3");
+    case vkey(CONV_HALO_S2_X3, 0, 0, 2): return launch_s2<0, 2>(Q, p, stream);
+    case vkey(CONV_HALO_S2_X3, 0, 0, 3): return launch_s2<0, 3>(Q, p, stream);
+    case vkey(CONV_HALO_S2_X3, 0, 1, 2): return launch_s2<1, 2>(Q, p, stream);
+    case vkey(CONV_HALO_S2_X3, 0, 1, 3): return launch_s2<1, 3>(Q, p, stream);
+    case vkey(CONV_HALO8_S2_X3, 0, 0): return launch_kernel<conv_halo8_s2_x3_kernel<0>, G8s::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo_x3");
+    case vkey(CONV_HALO8_S2_X3, 0, 1): return launch_kernel<conv_halo8_s2_x3_kernel<1>, G8s::LDS_BYTES>(Q.nblocks, p, stream, "conv_halo_x3");
+    case vkey(CONVT_HALO_X3, 0, 0, 2): return launch_kernel<convt_halo_x3_kernel<2>, HaloGeomCT3<3, 2>::LDS_BYTES>(Q.nblocks, p, stream, "convt_halo_x3");
+    case vkey(CONVT_HALO_X3, 0, 0, 3): return launch_kernel<convt_halo_x3_kernel<3>, HaloGeomCT3<MSI_CT3_NSTG, 3>::LDS_BYTES>(Q.nblocks, p, stream, "convt_halo_x3");
+    case vkey(CONVT_HALO8_X3): return launch_kernel<convt_halo8_x3_kernel, HaloGeomCT3<MSI_CT3_NSTG, 3, 8>::LDS_BYTES>(Q.nblocks, p, stream, "convt_halo_x3");
   }
-  if (Q.halo_s2 && Q.x3_th8) {
-    typedef HaloGeomS2X3<3, 8> G8s_;
-    static_assert(G8s_::LDS_BYTES <= 65536, "conv_halo8_s2_x3_kernel: LDS without the launch attribute");
-    if (Q.halo_apply) hipLaunchKernelGGL((conv_halo8_s2_x3_kernel<1>), grid, block, G8s_::LDS_BYTES, stream, p);
-    else hipLaunchKernelGGL((conv_halo8_s2_x3_kernel<0>), grid, block, G8s_::LDS_BYTES, stream, p);
-  } else if (Q.halo_s2) {
-    if (Q.halo_x2) {
-      if (Q.halo_apply) hipLaunchKernelGGL((conv_halo_s2_x3_kernel<1, 2>), grid, block, HaloGeomS2X3<2>::LDS_BYTES, stream, p);
-      else hipLaunchKernelGGL((conv_halo_s2_x3_kernel<0, 2>), grid, block, HaloGeomS2X3<2>::LDS_BYTES, stream, p);
-    } else {
-      if (Q.halo_apply) hipLaunchKernelGGL((conv_halo_s2_x3_kernel<1, 3>), grid, block, HaloGeomS2X3<3>::LDS_BYTES, stream, p);
-      else hipLaunchKernelGGL((conv_halo_s2_x3_kernel<0, 3>), grid, block, HaloGeomS2X3<3>::LDS_BYTES, stream, p);
-    }
-  } else if (Q.x3_th8) {
-    typedef HaloGeomX3<1, (MSI_X3_NSTG ? MSI_X3_NSTG : 2), 3, 8> G8_;
-    static_assert(G8_::LDS_BYTES <= 65536, "conv_halo8_x3_kernel: LDS without the launch attribute");
-    if (Q.halo_apply) hipLaunchKernelGGL((conv_halo8_x3_kernel<1, 3>), grid, block, G8_::LDS_BYTES, stream, p);
-    else hipLaunchKernelGGL((conv_halo8_x3_kernel<0, 3>), grid, block, G8_::LDS_BYTES, stream, p);
-  } else {
-    static thread_local unsigned long long done2[12] = {0};       // (above 64 KB of LDS the launch needs the attribute)
-#define MSI_X3_LAUNCH(R, A, N)                                                                                         \
-  {                                                                                                                    \
-    typedef HaloGeomX3<R, x3_nstg(R, N), N> G_;                                                                        \
-    if (G_::LDS_BYTES > 65536) {                                                                                       \
-      int rc0 = set_max_lds(reinterpret_cast<const void *>(conv_halo_x3_kernel<R, A, N>), G_::LDS_BYTES, done2[(R - 1) * 4 + A * 2 + (N - 2)], "conv_halo_x3"); \
-      if (rc0) return rc0;                                                                                             \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((conv_halo_x3_kernel<R, A, N>), grid, block, G_::LDS_BYTES, stream, p);                          \
-  }
-    const int sel = (rate == 1 ? 0 : (p.row_par ? 8 : 4)) + (Q.halo_apply ? 2 : 0) + (Q.halo_x2 ? 0 : 1);
-    switch (sel) {
-      case 0: MSI_X3_LAUNCH(1, 0, 2) break;
-      case 1: MSI_X3_LAUNCH(1, 0, 3) break;
-      case 2: MSI_X3_LAUNCH(1, 1, 2) break;
-      case 3: MSI_X3_LAUNCH(1, 1, 3) break;
-      case 4: MSI_X3_LAUNCH(2, 0, 2) break;
-      case 5: MSI_X3_LAUNCH(2, 0, 3) break;
-      case 6: MSI_X3_LAUNCH(2, 1, 2) break;
-      case 7: MSI_X3_LAUNCH(2, 1, 3) break;
-      case 8: MSI_X3_LAUNCH(3, 0, 2) break;
-      case 9: MSI_X3_LAUNCH(3, 0, 3) break;
-      case 10: MSI_X3_LAUNCH(3, 1, 2) break;
-      default: MSI_X3_LAUNCH(3, 1, 3) break;
-    }
-#undef MSI_X3_LAUNCH
-  }
-  int rc = msi::check_launch("conv_halo_x3");
-  if (!rc && Q.nfix > 0 && p.tile_cnt == nullptr) rc = launch_fixup(Q.x3_th8 ? 128 : 64, 64, MODE_CONV, Q.nfix, 1, p, stream);
-  return rc;
+  return msi::fail(MSI_E_UNSUPPORTED, "conv_halo_x3: no split kernel of family %d with rate %d, APPLY %d, %d planes", V.family, V.rate, V.apply, V.planes);
 }
 }  // namespace msi_cnn

@@ -5,7 +5,7 @@ Mirrors the variable structure of the reference's `msi_coord_train_net`
 (nets.py:471-515) and `msi_train_net` (nets.py:387-450): TF scope `net/`,
 `<layer>/weights`, `<layer>/LayerNorm/{gamma,beta}`, `color_pred/{weights,biases}`
 (the variables test.py:191-202 restores).  The arithmetic lives in
-csrc/cnn.hip; nothing here computes a convolution.
+csrc/cnn*.hip; nothing here computes a convolution.
 """
 import math
 
@@ -106,7 +106,7 @@ def unflatten_params(blob, in_channels, num_outputs, ngf=64, coord_net=True):
 
 
 def pack_params(desc, blob):
-    """Parameter blob -> the MFMA-tile-ordered blob csrc/cnn.hip streams (host)."""
+    """Parameter blob -> the MFMA-tile-ordered blob the conv kernels stream (host: csrc/cnn_net.hip)."""
     blob = np.ascontiguousarray(blob, dtype=np.float32)
     need = N.lib.msi_net_param_floats(desc)
     if need == 0:

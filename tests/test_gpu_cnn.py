@@ -315,7 +315,7 @@ def test_full_size_network_properties_without_the_oracle(env, dtype):
 @pytest.mark.parametrize("gain", [1e-4, 1e4])
 def test_layernorm_follows_the_weight_scale(env, gain, dtype):
     """The LayerNorm sums are one-word fixed point inside a per-layer window whose exponent the packer takes from the
-    weights (cnn.hip: LN_S1_BITS), so the window follows any scale of the weights: a network whose conv / conv-transpose
+    weights (cnn_device.h: LN_S1_BITS), so the window follows any scale of the weights: a network whose conv / conv-transpose
     weights are ALL multiplied by 2^-13 (~1e-4) or 2^13 (~1e4) still matches the ORACLE run on the same scaled weights
     (fp64 two-pass statistics, eps 1e-12 -- which is why the small gain is not exactly invariant: var ~1e-8 against
     eps 1e-12 moves the prediction by ~2e-4, in the reference too) and msi_net_plan_status stays clean; the large gain

@@ -334,6 +334,34 @@ def test_weight_packing_index_level(native_lib, coord, dtype):
     assert off == packed.size
 
 
+def test_plan_layer_params_reports_its_size_and_checks_its_arguments(native_lib):
+    import ctypes
+    from matryodshka_amd import nets
+    N = native_lib
+    plan = N.NetPlan(nets.make_desc(1, 64, 128, 96, 32, 64, True))
+    need = ctypes.c_size_t(0)
+    assert N.lib.msi_net_plan_layer_params(plan.handle, 0, None, 0, ctypes.byref(need)) == 0 and need.value > 16
+    assert all(len(plan.layer_params(li)) == need.value for li in range(18))
+    buf = ctypes.create_string_buffer(need.value)
+    assert N.lib.msi_net_plan_layer_params(plan.handle, 0, buf, need.value - 1, None) != 0 and "needed" in N.last_error()
+    assert N.lib.msi_net_plan_layer_params(plan.handle, 18, buf, need.value, None) != 0
+    assert N.lib.msi_net_plan_layer_params(plan.handle, 0, None, 0, None) != 0 and N.lib.msi_net_plan_layer_params(None, 0, buf, need.value, None) != 0
+    # inlaunch, fuse_ln, skip_apply, ln_blocks behind the kernel argument: the fp32 head fuses its source's LayerNorm, whose ln_apply launch is skipped
+    tail = lambda li: list(np.frombuffer(plan.layer_params(li)[-16:], np.int32))
+    assert tail(17)[1] == 1 and tail(16)[2] == 1 and tail(17)[3] == 0 and tail(0)[3] > 0
+
+
+@pytest.mark.parametrize("which", ["A", "D"])
+def test_packed_weights_are_the_recorded_bits(native_lib, which):
+    """msi_net_pack_weights_host on numpy.random.default_rng(0) parameters, for descriptions A (fp32 CoordNet) and D (bf16, wrap padding) of
+    tests/test_plan_decomposition.py: the SHA-256 of the whole packed blob -- tap-kernel rows, bf16 / fp16 split planes, LayerNorm windows, CoordNet
+    tables -- is the one recorded in tests/golden/plan_digests.json before the packer moved to csrc/cnn_net.hip (tools/plan_golden.py)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import plan_golden
+    assert plan_golden.weights_digest(which) == plan_golden.golden()["weights|" + which]
+
+
 def test_plan_options_and_raw_layer_bookkeeping(native_lib):
     """Host logic of the plan object (no GPU needed: the CU count falls back to the default part): option validation, and
     which producers are left un-normalised in memory -- exactly those whose EVERY consumer applies the LayerNorm while

@@ -1,5 +1,5 @@
-"""Work decomposition of the conv kernels as a function of tiles against the CU count (plan_tiles / plan_layers in
-matryodshka_amd/csrc/cnn.hip), on the HOST: no GPU is needed to create a plan, set options and ask which kernel a layer takes.
+"""Work decomposition of the conv kernels as a function of tiles against the CU count (plan_tiles / choose_variant / plan_layers in
+matryodshka_amd/csrc/cnn_plan.hip), on the HOST: no GPU is needed to create a plan, set options and ask which kernel a layer takes.
 
 Plan option NUM_CUS (8 .. 4096) makes small grids reach what only the 160 x 320 and 320 x 640 shapes reach on a 256-CU
 device: tiles cut into K-ranges, the first tile group cut as well (split0 = 2), the in-launch hand-off and the fix-up
@@ -9,18 +9,25 @@ this module holds, without a GPU,
 
   * COVERAGE: which (kernel family, decomposition class) pairs each case reaches -- recomputed from the plans and compared,
     so that a planner change which turns a GPU case into a run of whole tiles fails here, before any GPU time;
-  * UNREACHABLE: the pairs the planner can never produce, each with the line of cnn.hip that says so (the text is looked
+  * UNREACHABLE: the pairs the planner can never produce, each with the line of cnn_plan.hip that says so (the text is looked
     for around that line, and the robustness sweep asserts that no plan produces the pair);
-  * the robustness sweep: every CU count 8 .. 320, 512 and 4096 under the options that move the decomposition.
+  * the robustness sweep: every CU count 8 .. 320, 512 and 4096 under the options that move the decomposition;
+  * the plan digests: one SHA-256 per (description, option set) over that sweep and one per DECOMP_CASES / OPTION_CASES plan, of every
+    layer's kernel name, workgroups, tiles cut and the bytes of msi_net_plan_layer_params (the planned kernel argument, inlaunch, fuse_ln,
+    skip_apply, ln_blocks), against tests/golden/plan_digests.json (tools/plan_golden.py computes and records them): a change of the
+    planner's code that is meant to change no plan changes none of them.
 
 Classes of a layer (msi_net_plan_layer_kernel's nsplit_tiles): "whole" = no tile is cut; "rem" = 0 < nsplit_tiles < NUM_CUS,
 the remainder group is cut; "both" = nsplit_tiles >= NUM_CUS, the first group is cut in two as well (NUM_CUS <= tiles < 2 NUM_CUS).
 """
 import os
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import plan_golden   # noqa: E402  (tools/plan_golden.py: the digest functions the recorder uses)
 ALL = 0x3ffff
 FORCE8 = ALL | (1 << 30)          # X3_TILE8: the 8-row tiles on every eligible layer, whatever its grid
 CLASSES = ("whole", "rem", "both")
@@ -104,16 +111,16 @@ SPLIT_FAMILIES = (
 )
 BF16_HALO_FAMILIES = ("conv_halo_bf16_kernel", "conv_halo_bf16_s2_kernel", "convt_halo_bf16_kernel")
 
-# (family, class) the planner can never produce: (line of matryodshka_amd/csrc/cnn.hip, text on that line, why)
+# (family, class) the planner can never produce: (line of matryodshka_amd/csrc/cnn_plan.hip, text on that line, why)
 UNREACHABLE = {
-    ("conv_halo_s2_kernel", "both"): (418, ">= 3L * pl->num_cus", "without the six-product form the stride-2 halo kernel is only chosen for "
+    ("conv_halo_s2_kernel", "both"): (137, ">= 3L * pl->num_cus", "without the six-product form the stride-2 halo kernel is only chosen for "
                                       "grids of at least 3 tiles per CU; split0 = 2 needs fewer than 2"),
-    ("conv_halo_bf16_kernel", "rem"): (444, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
-    ("conv_halo_bf16_kernel", "both"): (444, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
-    ("conv_halo_bf16_s2_kernel", "rem"): (450, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
-    ("conv_halo_bf16_s2_kernel", "both"): (450, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
-    ("convt_halo_bf16_kernel", "rem"): (481, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
-    ("convt_halo_bf16_kernel", "both"): (481, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
+    ("conv_halo_bf16_kernel", "rem"): (156, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
+    ("conv_halo_bf16_kernel", "both"): (156, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
+    ("conv_halo_bf16_s2_kernel", "rem"): (162, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
+    ("conv_halo_bf16_s2_kernel", "both"): (162, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
+    ("convt_halo_bf16_kernel", "rem"): (191, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
+    ("convt_halo_bf16_kernel", "both"): (191, "max_split = 1", "bf16 halo tiles are never cut into K-ranges"),
 }
 
 # (family, class) -> the DECOMP_CASES that reach it (test_coverage_table_is_what_the_plans_give recomputes this)
@@ -254,7 +261,7 @@ def test_back_to_back_cases_split_every_x3_family_they_run():
 
 
 def test_unreachable_pairs_cite_the_line_that_says_so():
-    lines = open(os.path.join(ROOT, "matryodshka_amd", "csrc", "cnn.hip")).read().split("\n")
+    lines = open(os.path.join(ROOT, "matryodshka_amd", "csrc", "cnn_plan.hip")).read().split("\n")
     for pair, (line, text, _) in UNREACHABLE.items():      # (within a few lines: an edit above them must not fail this)
         assert any(text in ln for ln in lines[max(0, line - 13):line + 12]), (pair, line, lines[line - 1])
 
@@ -315,7 +322,7 @@ def test_no_cu_count_breaks_a_plan(what, dtype, shape, coord):
                     assert slabs <= 2 * cus * MAX_SPLIT, (what, named, cus, li, kernel, nblocks, nsplit, ntiles)
                 else:               # (a conv-transpose halo tile whose two slabs per K-range did not fit fell back: 4-row tile, or the tap kernel)
                     assert kernel_w.startswith("convt_halo"), (what, named, cus, li, kernel, kernel_w)
-                # the slab workspace is sized for the K-ranges of fewer than 2 NUM_CUS tiles (cnn.hip: net.partial_bytes).
+                # the slab workspace is sized for the K-ranges of fewer than 2 NUM_CUS tiles (cnn_net.hip: net.partial_bytes).
                 # TAILSPLIT = 2 (the residency-aware form, not the default) cuts the tiles beyond a multiple of Q = 5 NUM_CUS
                 # instead: up to Q - 1 of them, in as many K-ranges as the same slabs hold (plan_tiles: `remq * sp > 2L *
                 # num_cus * MAX_SPLIT`; its own example is 3 200 tiles on 256 CUs = 2 560 whole + 640 x 2) -- there the
@@ -328,3 +335,22 @@ def test_no_cu_count_breaks_a_plan(what, dtype, shape, coord):
         plan.set_option(N.NET_OPT_NUM_CUS, default_cus)
         assert plan.kernels() == original, (what, named)
     assert not seen & set(UNREACHABLE), sorted(seen & set(UNREACHABLE))
+
+
+# ---- the plans themselves: digests recorded from the planner as it was before choose_variant (tools/plan_golden.py --record on that commit)
+@pytest.mark.parametrize("what,dtype,shape,coord", SWEEP_DESCS,
+                         ids=["%s-%s-%s-%s" % (d[0].replace(" ", "_"), d[1], "x".join(map(str, d[2])), "coord" if d[3] else "wrap") for d in SWEEP_DESCS])
+def test_sweep_plans_are_the_recorded_ones(what, dtype, shape, coord):
+    golden = plan_golden.golden()
+    for named in SWEEP_OPTIONS:
+        assert plan_golden.sweep_digest(dtype, shape, coord, named, SWEEP_CUS) == golden[plan_golden.sweep_key(dtype, shape, coord, named)], (what, named)
+
+
+def test_case_plans_are_the_recorded_ones():
+    golden = plan_golden.golden()
+    for case, extra in [(c, None) for c in DECOMP_CASES] + list(OPTION_CASES) + [(c, None) for c, _ in OPTION_CASES]:
+        assert plan_golden.plan_digest(plan_for(case, extra)) == golden[plan_golden.case_key(case, extra)], (case["id"], extra)
+    # nothing recorded that no test recomputes (the weight digests: tests/test_native_abi.py)
+    keys = {plan_golden.sweep_key(d[1], d[2], d[3], named) for d in SWEEP_DESCS for named in SWEEP_OPTIONS}
+    keys |= {plan_golden.case_key(c, e) for c, e in [(c, None) for c in DECOMP_CASES] + list(OPTION_CASES) + [(c, None) for c, _ in OPTION_CASES]}
+    assert set(golden) == keys | {"weights|" + w for w in plan_golden.WEIGHT_DESCS}

@@ -83,7 +83,7 @@ def poison_workspace(m, b, h, w, cin, nout, ngf):
     read the OTHER variant's correct raw outputs where its own variant computed no tile or lost a store.  On a poisoned
     workspace such an element stays NaN, and so does everything downstream of it.
 
-    The whole workspace is poisoned: nothing in it is written once and kept.  Its regions are (cnn.hip: build_net) the
+    The whole workspace is poisoned: nothing in it is written once and kept.  Its regions are (cnn_net.hip: build_net) the
     layers' raw outputs / published affines / bf16 activation copies, the K-range slabs, and the zero region (arrival
     tickets, LayerNorm sums, apply-ahead flags, status word) -- the first three are written by the forward that reads
     them, the last is cleared by every forward's first launch.  What IS written once outside the forward (packed weights,
