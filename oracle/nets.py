@@ -185,13 +185,18 @@ def conv_split_f16(fn, x, w):
     return fn(xh, wh) + (fn(xm, wh) + fn(xh, wm)) * (1.0 / 2048.0)
 
 
-def forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False):
+def forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False, forced_raw=None):
     """split3_products: False | True (six bf16 products, conv_split3) | "f16" (three fp16 products, conv_split_f16).
-    bf16: False | True | "scaled" (True with the fp16 raw storage's power-of-two pre-scale explicit: layer_norm_relu)."""
-    return _forward(weights, net_input, coord_net, return_activations, bf16, split3_products)
+    bf16: False | True | "scaled" (True with the fp16 raw storage's power-of-two pre-scale explicit: layer_norm_relu).
+    forced_raw: None | {layer name: [B,H,W,C] fp32 numpy} -- teacher forcing.  A layer named there still computes and records
+    its own raw output (acts[name + "/raw"]) from the inputs it has, but everything downstream of it carries on from
+    forced_raw[name] instead: LayerNorm statistics in fp64 of THOSE values, affine, ReLU, (bf16) rounding.  With every layer
+    forced to another implementation's stored raw outputs, acts[L + "/raw"] is what layer L alone should have made of that
+    implementation's own upstream results; the returned prediction is the head of the forced conv8_2."""
+    return _forward(weights, net_input, coord_net, return_activations, bf16, split3_products, forced_raw)
 
 
-def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False):
+def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False, forced_raw=None):
     """msi_coord_train_net (nets.py:471-515) / msi_train_net (:387-450).
     net_input: np [B,H,W,Cin] fp32.  Returns np [B,H,W,num_outputs] fp32.
 
@@ -206,6 +211,20 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
     x = rnd(torch.from_numpy(np.ascontiguousarray(np.transpose(net_input, (0, 3, 1, 2)))).float())
     acts = {}
     affines = {}
+
+    def forced(name, y, crop=None):
+        """y, or -- for a layer named in forced_raw -- the forced values in y's place (crop: the forced tensor covers
+        y[:, :, crop:-crop, crop:-crop] only and is pasted into a copy of y)."""
+        if forced_raw is None or name not in forced_raw:
+            return y
+        f = torch.from_numpy(np.ascontiguousarray(np.transpose(np.asarray(forced_raw[name], dtype=F32), (0, 3, 1, 2))))
+        if crop is None:
+            assert f.shape == y.shape, (name, tuple(f.shape), tuple(y.shape))
+            return f
+        y = y.clone()
+        assert f.shape == y[:, :, crop:-crop, crop:-crop].shape, (name, tuple(f.shape), tuple(y.shape))
+        y[:, :, crop:-crop, crop:-crop] = f
+        return y
 
     def ln(name, y):
         out = []
@@ -228,7 +247,7 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
         else:
             y = TF.conv2d(x, w, stride=stride, dilation=rate)
         acts[name + "/raw"] = y
-        y = rnd(ln(name, y))
+        y = rnd(ln(name, forced(name, y)))
         acts[name] = y
         return y
 
@@ -240,7 +259,7 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
             else:
                 y = TF.conv_transpose2d(x, w, stride=2, padding=1)
             acts[name + "/raw"] = y
-            y = rnd(ln(name, y))
+            y = rnd(ln(name, forced(name, y)))
         else:
             # nets.py:423-435: slim.conv2d_transpose(wrap_pad(skip, 2, 2), padding='VALID') runs under the
             # layer_norm arg_scope, so LayerNorm + ReLU cover the FULL (2H+10) x (2W+10) output -- zero rows and
@@ -248,7 +267,8 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
             # input expression (cnv6_1[:,5:-5,5:-5,:], nets.py:426)
             y = TF.conv_transpose2d(wrap_pad(x, 2, 2), w, stride=2, padding=0)
             acts[name + "/raw"] = y[:, :, 5:-5, 5:-5]
-            y = rnd(ln(name, y))
+            # (the statistics cover the uncropped output; an implementation stores the crop: forced values are pasted into the oracle's own border)
+            y = rnd(ln(name, forced(name, y, crop=5)))
             y = y[:, :, 5:-5, 5:-5]
         acts[name] = y
         return y

@@ -12,7 +12,7 @@ Tolerances (stated here because north_star's 1e-3 is the fp32 gate):
 import numpy as np
 import pytest
 
-from tests.util import make_inputs, poison_workspace, read_raw_output
+from tests.util import forced_gates, forced_layer_errors, make_inputs, poison_workspace, read_raw_output
 pytestmark = pytest.mark.gpu
 
 
@@ -162,12 +162,12 @@ def test_bf16_every_layer_tracks_the_bf16_oracle(env):
     pred = m.run_net(torch.from_numpy(x).cuda().bfloat16(), nout, ngf).cpu().numpy()
     ref, acts = onets.forward(weights, x, coord_net=True, return_activations=True, bf16=True)
     desc, packed, ws = m._net(b, h, w, cin, nout, ngf)
-    report = {}
+    report, raws = {}, {}
     for info in nets.layer_infos(desc):
         if info.kind == nets.KIND_HEAD:
             continue
         name = info.name.decode()
-        raw = read_raw_output(ws, packed, info, b, "bf16")
+        raw = raws[name] = read_raw_output(ws, packed, info, b, "bf16")
         assert np.isfinite(raw).all(), name
         o = acts[name + "/raw"]
         scale = np.abs(o).max()
@@ -179,6 +179,11 @@ def test_bf16_every_layer_tracks_the_bf16_oracle(env):
         assert mx <= gmx and mn <= gmn, (name, mx, mn, gmx, gmn)
     e = np.abs(pred - ref)
     assert e.max() <= 4e-2 and e.mean() <= 2e-3, (e.max(), e.mean())
+    # the gates above follow two free-running trajectories apart; fed the device's own raw outputs layer by layer (teacher forcing,
+    # tests/test_gpu_bf16_forced.py) the oracle holds all 17 layers to one tight gate
+    forced = forced_layer_errors(weights, x, True, raws, pred, gates=forced_gates(ngf), kernels=m._plan(b, h, w, cin, nout, ngf).kernels())
+    print("bf16 per-layer errors against the forced oracle (max, mean):", {k: ("%.1e" % v[0], "%.1e" % v[1]) for k, v in forced["layers"].items()}, "head", forced["head"])
+    assert not forced["failures"], "\n".join(forced["failures"])
 
 
 @pytest.mark.parametrize("coord,b,h,w,cin,nout,ngf", [(True, 1, 160, 320, 192, 64, 64), (False, 2, 64, 128, 64, 16, 64),

@@ -91,3 +91,72 @@ def poison_workspace(m, b, h, w, cin, nout, ngf):
     _, _, ws = m._net(b, h, w, cin, nout, ngf)
     ws.fill_(0xFF)
     return ws
+
+
+# ---- the teacher-forced layer check of the bf16 tier
+# Gates of forced_layer_errors, MEASURED ON THE CPU (tools/bf16_forced_gates.py, profiles/bf16_forced_gates.txt): 3 x the worst value of a
+# stand-in with exactly a correct kernel's freedoms, over the shapes of the tests that use them, two seeds each.  Never set from a device run.
+# Keyed by the network width ngf: a flipped bf16 operand weighs ~ 1 / sqrt(K) of a layer's scale and K follows ngf, and the narrow shapes' small layers
+# see the largest difference between statistics of stored and of unrounded values -- within one width all 17 layers share one gate, each width's gate is
+# 3 x the worst of ITS runs (so none is above 3 x the worst of all runs).  layer_bias: see forced_layer_errors; head_*: absolute, and include 2e-7 for msi_tanh.
+BF16_FORCED_GATES = {
+    16: dict(layer_max=4.39e-3, layer_mean=3.47e-4, layer_bias=1.98e-5, head_max=1.77e-2, head_mean=2.99e-5),   # worst 1.46e-3 1.16e-4 6.59e-6 | 5.89e-3 9.97e-6
+    32: dict(layer_max=2.04e-3, layer_mean=2.14e-4, layer_bias=1.20e-5, head_max=1.00e-2, head_mean=1.23e-5),   # worst 6.79e-4 7.12e-5 4.01e-6 | 3.34e-3 4.11e-6
+    64: dict(layer_max=1.79e-3, layer_mean=1.31e-4, layer_bias=2.48e-6, head_max=1.19e-2, head_mean=9.32e-6),   # worst 5.96e-4 4.37e-5 8.27e-7 | 3.95e-3 3.11e-6
+}
+
+
+def forced_gates(ngf):
+    """BF16_FORCED_GATES of a network of width ngf: a measured width, or -- ngf >= 64 -- the widest measured class (the runs at ngf = 144 stay below every
+    worst value of ngf = 64: beyond it the fp16 store is what is left)."""
+    return BF16_FORCED_GATES[64 if ngf >= 64 else ngf]
+
+
+def forced_layer_errors(weights, x, coord, raws, pred, gates=None, kernels=None):
+    """One run of the teacher-forced bf16 oracle (oracle/nets.py forward(bf16=True, forced_raw=raws)): every layer recomputed from the
+    raw outputs `raws` ({layer: [B,H,W,C] fp32}: tests.util.read_raw_output of a bf16 plan, or a stand-in's) of its OWN sources, so a
+    layer's error is that layer's alone -- summation order, the fp16 store, isolated operand flips -- at conv8_2 as at conv1_1.
+
+    Returns a dict:
+      "layers": {layer: (max, mean)} of |raws[layer] - forced oracle| / max |forced oracle's raw output|;
+      "bias":   {layer: mean of sign(oracle) (raws[layer] - oracle) / scale}: how far the stored values lean towards zero (-) or away
+                (+); round-to-nearest stores do not lean (|bias| ~ mean / sqrt(elements)), a truncating store leans by its whole mean error;
+      "head":   (max, mean) of |pred - forced prediction|, absolute (tanh output in [-1, 1]);
+    and, with `gates` (BF16_FORCED_GATES),
+      "over":   {layer: elements above the max gate}, "first": {layer: (b, y, x, c) of the first of them};
+      "failed_layers": layers (and "color_pred") that miss a gate, "failures": one line each, with the layer's kernel where
+                `kernels` (plan.kernels()) is given."""
+    from oracle import nets as onets
+    names = [t[0] for t in onets.layer_table(1, 1) if t[1] != "h"]
+    assert sorted(raws) == sorted(names), sorted(raws)
+    ref, acts = onets.forward(weights, x, coord_net=coord, return_activations=True, bf16=True, forced_raw=raws)
+    rep = dict(layers={}, bias={}, over={}, first={}, failed_layers=[], failures=[])
+    for li, name in enumerate(names):
+        o = acts[name + "/raw"]
+        assert raws[name].shape == o.shape, (name, raws[name].shape, o.shape)
+        scale = float(np.abs(o).max()) + 1e-30
+        d = (raws[name].astype(np.float64) - o) / scale
+        e = np.abs(d)
+        rep["layers"][name] = (float(e.max()), float(e.mean()))
+        rep["bias"][name] = float((np.sign(o) * d).mean())
+        if gates is None:
+            continue
+        over = e > gates["layer_max"]
+        rep["over"][name] = int(over.sum())
+        if rep["over"][name]:
+            rep["first"][name] = tuple(int(i) for i in np.argwhere(over)[0])
+        if rep["over"][name] or e.mean() > gates["layer_mean"] or abs(rep["bias"][name]) > gates["layer_bias"]:
+            rep["failed_layers"].append(name)
+            rep["failures"].append("%s%s: max %.2e (gate %.1e; %d of %d elements over it%s), mean %.2e (gate %.1e), bias %+.2e (gate %.1e)" % (
+                name, " [%s]" % kernels[li][0] if kernels else "", e.max(), gates["layer_max"], rep["over"][name], e.size,
+                ", first at (b, y, x, c) = %r" % (rep["first"][name],) if rep["over"][name] else "", e.mean(), gates["layer_mean"],
+                rep["bias"][name], gates["layer_bias"]))
+    eh = np.abs(np.asarray(pred, dtype=np.float64) - ref)
+    rep["head"] = (float(eh.max()), float(eh.mean()))
+    if gates is not None and (eh.max() > gates["head_max"] or eh.mean() > gates["head_mean"]):
+        over = eh > gates["head_max"]
+        rep["failed_layers"].append("color_pred")
+        rep["failures"].append("color_pred%s: max %.2e (gate %.1e; %d elements over it%s), mean %.2e (gate %.1e)" % (
+            " [%s]" % kernels[17][0] if kernels else "", eh.max(), gates["head_max"], int(over.sum()),
+            ", first at (b, y, x, c) = %r" % (tuple(int(i) for i in np.argwhere(over)[0]),) if over.any() else "", eh.mean(), gates["head_mean"]))
+    return rep
