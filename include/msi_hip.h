@@ -64,7 +64,8 @@ const char *msi_version(void);
  *   7: MSI_NET_OPT_X3_ROWPAR (round 5)
  *   8: msi_probe_matrix_rate (round 6)
  *   9: msi_perspective_sweep_volume_bf16
- *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images) */
+ *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images; msi_cube_render_views,
+ *      msi_equirect_to_cube_f32) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -360,6 +361,52 @@ int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_po
                          const float *tgt_intrinsics_inv, const float *depths, int32_t batch, int32_t views, int32_t height,
                          int32_t width, int32_t num_planes, int32_t out_height, int32_t out_width, float *out_rgb,
                          float *out_depth, msi_stream_t stream);
+
+/* ---- cube-map viewer of the PP path (MSI.cube_render_views / MSI.equirect_to_cube; no reference counterpart) ----------
+ * The cube frame is the camera frame of face 0: x right, y down, z forward.  Face f has orientation R_f, whose columns are
+ * the face camera's x, y, z axes in the cube frame:
+ *   f  0 front (+z)  1 right (+x)  2 back (-z)   3 left (-x)   4 up (-y)     5 down (+y)
+ *   x  (1,0,0)       (0,0,-1)      (-1,0,0)      (0,0,1)       (1,0,0)       (1,0,0)
+ *   y  (0,1,0)       (0,1,0)       (0,1,0)       (0,1,0)       (0,0,1)       (0,0,-1)
+ *   z  (0,0,1)       (1,0,0)       (0,0,-1)      (-1,0,0)      (0,-1,0)      (0,1,0)
+ * A cube stack is the native stack [6B,D,S,S] of square faces, face f of sample b at entry 6 b + f (what the PP network
+ * writes for a batch of 6B faces); texel (ix, iy) of layer d of face f is the cube-frame point R_f depths[d] K^-1 (ix, iy, 1)
+ * with the sample's stack camera K (integer-pixel convention of the MPI path), so layer d of the six faces is a cube shell
+ * of half-side depths[d].
+ *
+ * msi_cube_render_views: V views per sample in one launch, msi_render_views_f32's cameras, pose model and outputs.
+ *   layers            [6B,D,S,S] texels of `format` (MSI_LAYERS_F32, _RGBA8 or _RGBA16F), depths [D] far -> near, D <= 128
+ *   tgt_pose_rt       [B*V,4,4], tgt_pos [B*V,3]: direction rotated by pose[:3,:3], origin pose @ (tgt_pos[2], tgt_pos[1],
+ *                     tgt_pos[0], 1); this render frame (forward +x, down +y, right +z) maps to the cube frame by swapping x
+ *                     and z, so the centre of an equirect output looks at the centre of face 0
+ *   tgt_intrinsics    [B*V,3,3] (MSI_CAMERA_PINHOLE; trig unused), trig = the table of (out_height, out_width)
+ *                     (MSI_CAMERA_EQUIRECT; tgt_intrinsics unused)
+ *   stack_intrinsics  [B,3,3] the camera K shared by a sample's six faces
+ *   out_rgb [B,V,out_height,out_width,3], out_depth [B,V,out_height,out_width] (the composited d / D); either may be NULL
+ * Per shell, for origin o and direction r in the cube frame and h = depths[d]: t = min over the axes with r_k != 0 of
+ * (h sign(r_k) - o_k) / r_k, P = o + t r; the face is the axis of the largest |P_k| with its sign (ties: z, x, y);
+ * p = R_f^T P, u = fx p_x / h + cx, v = fy p_y / h + cy, both CLAMPED to [0, S-1], bilinear over the four texels of THAT face
+ * (clamp to edge: no zero padding, no fetch from the neighbouring face -- with fx = cx = S/2 a face covers [-1, 1 - 2/S] in
+ * tan space; fx = cx = (S-1)/2 makes it symmetric); composite strictly far to near: layer 0 replaces, then c a + acc (1 - a).
+ * A packed stack is decoded by the rule of msi_unpack_layers: the outputs are bit-identical to the same call on the unpacked
+ * stack.  status_device as in msi_render_views_f32: MSI_RENDER_STATUS_ORIGIN_OUTSIDE when a view's origin is not strictly
+ * inside the innermost shell (max |o_k| >= min depths, or NaN); its pixels are finite for finite inputs.  Every texel address
+ * is in range by construction for any input.
+ * Argument checks before any launch, MSI_E_BADARG unless noted: both outputs NULL; a NULL input (trig / tgt_intrinsics only
+ * for their camera); unknown format or camera; batch < 0 or non-positive face_size / num_planes ("bad dims"); views < 1; an
+ * output size below 1 x 1 (2 x 2 for the pinhole camera); num_planes > 128 -> MSI_E_UNSUPPORTED; a sample whose six face
+ * stacks reach 2^31 bytes (32-bit per-lane offsets); more than 2^31 - 8 workgroups.  batch = 0 returns MSI_OK, no launch. */
+int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                          const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
+                          int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
+                          int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                          msi_stream_t stream);
+/* Panorama -> six face images: image [B,H,W,C] fp32 (C in 1..4) -> out [B,6,S,S,C].  Texel (ix, iy) of face f looks along
+ * R_f K^-1 (ix, iy, 1) with intrinsics [B,3,3]; with x and z swapped that is a direction of the render frame, sampled at
+ * u = (atan2(z, x) + pi) / 2pi W - 0.5, v = (asin(y / |dir|) + pi/2) / pi H - 0.5 (the inverse of the lat-long grid of
+ * msi_build_trig_tables_host), bilinear, wrapping in u and clamping in v. */
+int msi_equirect_to_cube_f32(const float *image, const float *intrinsics, int32_t batch, int32_t height, int32_t width,
+                             int32_t channels, int32_t face_size, float *out, msi_stream_t stream);
 
 /* ---- image scores --------------------------------------------------------------------
  * eval.py:127-174 (tf.image.ssim, tf.image.psnr with max_val 255; the mean absolute difference of consecutive frames) for

@@ -4,6 +4,7 @@
 //   geo_layers.hip  K3 RGBA assembly, bilinear resize, the fused high-res layer stack, pack / unpack of the compact stacks
 //   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed sibling
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
+//   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
 // sharing is a contract.  What a single family uses lives in that family's unit.
 //
@@ -383,7 +384,7 @@ __device__ __forceinline__ float4 rgba16f_decode(u32x2_g q) {
   return t;
 }
 
-// ---- render (render_kernel, render_views_kernel and its packed sibling) and planar (mpi_render_views_kernel): the output modes, the layer fraction of
+// ---- render (render_kernel, render_views_kernel and its packed sibling), planar (mpi_render_views_kernel) and cube (cube_render_views_kernel): the output modes, the layer fraction of
 // over_composite_depth and ONE way to address and load a texel of a layer stack, fp32 or packed, so the many-views renders of both families read the
 // same bits from the same stack.
 enum RenderMode { RENDER_RGB = 1, RENDER_DEPTH = 2, RENDER_LAYERS = 4 };

@@ -1,0 +1,119 @@
+"""Cube-map conventions of the PP path (MSI.equirect_to_cube, MSI.infer_cube, MSI.cube_render_views; include/msi_hip.h
+states the same table for the C ABI).  Host-side helpers only: small pose and camera algebra in numpy (torch tensors are
+taken and returned as torch tensors on their device).
+
+The cube frame is the camera frame of face 0: x right, y down, z forward.  Face f has orientation R_f = FACE_ROTATIONS[f],
+whose COLUMNS are the face camera's x, y and z axes written in the cube frame:
+
+    f          looks along   x axis      y axis      z axis
+    0 front    +z            (1,0,0)     (0,1,0)     (0,0,1)
+    1 right    +x            (0,0,-1)    (0,1,0)     (1,0,0)
+    2 back     -z            (-1,0,0)    (0,1,0)     (0,0,-1)
+    3 left     -x            (0,0,1)     (0,1,0)     (-1,0,0)
+    4 up       -y            (1,0,0)     (0,0,1)     (0,-1,0)
+    5 down     +y            (1,0,0)     (0,0,-1)    (0,1,0)
+
+The renders' frame (render_views, cube_render_views: forward +x, down +y, right +z) is the cube frame with x and z swapped."""
+import numpy as np
+
+_AXES = [  # (x, y, z) axes of each face camera in the cube frame
+    ((1, 0, 0), (0, 1, 0), (0, 0, 1)),
+    ((0, 0, -1), (0, 1, 0), (1, 0, 0)),
+    ((-1, 0, 0), (0, 1, 0), (0, 0, -1)),
+    ((0, 0, 1), (0, 1, 0), (-1, 0, 0)),
+    ((1, 0, 0), (0, 0, 1), (0, -1, 0)),
+    ((1, 0, 0), (0, 0, -1), (0, 1, 0)),
+]
+FACE_ROTATIONS = np.stack([np.array(a, dtype=np.float64).T for a in _AXES])   # [6,3,3], columns = axes
+FACE_ROTATIONS.setflags(write=False)
+FACE_NAMES = ("front", "right", "back", "left", "up", "down")
+_SWAP_XZ = np.array([[0, 0, 1], [0, 1, 0], [1, 0, 0]], dtype=np.float64)
+
+
+def _face_4x4():
+    f = np.tile(np.eye(4), (6, 1, 1))
+    f[:, :3, :3] = FACE_ROTATIONS
+    return f
+
+
+def face_poses(pose):
+    """[...,4,4] -> [...,6,4,4]: entry f is F_f^T @ pose @ F_f with F_f = diag(R_f, 1) -- a camera pose of the cube frame
+    rewritten in each face's frame, the src_pose of format_network_input for that face.  Identity maps to identities and
+    entry 0 is the input."""
+    f = _face_4x4()
+    try:
+        import torch
+    except ImportError:     # pragma: no cover
+        torch = None
+    if torch is not None and torch.is_tensor(pose):
+        ft = torch.as_tensor(f, dtype=pose.dtype, device=pose.device)
+        return ft.transpose(-1, -2) @ pose[..., None, :, :] @ ft
+    pose = np.asarray(pose)
+    out = np.swapaxes(f, -1, -2) @ pose[..., None, :, :].astype(np.float64) @ f
+    return out.astype(pose.dtype if pose.dtype.kind == "f" else np.float64)
+
+
+def face_view_pose(f):
+    """The tgt_pose_rt [4,4] (fp32) with which a pinhole view from the centre of the cube looks through face f with the
+    face camera's orientation: R_f carried to the render frame, swap @ R_f @ swap, no translation."""
+    p = np.eye(4)
+    p[:3, :3] = _SWAP_XZ @ FACE_ROTATIONS[int(f)] @ _SWAP_XZ
+    return p.astype(np.float32)
+
+
+def face_view_intrinsics(k):
+    """The pinhole intrinsics (cx + 0.5, cy + 0.5) with which that view's pixel (i, j) lands exactly on texel (j, i) of the
+    face: the pinhole camera of the renders looks through pixel CENTRES, ((j + 0.5 - cx) / fx), the stack camera K uses the
+    MPI path's integer-pixel convention ((j - cx) / fx).  k [...,3,3] -> same shape, fp32."""
+    k = np.array(k, dtype=np.float64, copy=True)
+    k[..., 0, 2] += 0.5
+    k[..., 1, 2] += 0.5
+    return k.astype(np.float32)
+
+
+def default_face_intrinsics(face_size):
+    """The harness's PP intrinsics for a square face: fx = fy = cx = cy = S / 2 (a 90-degree face; it covers [-1, 1 - 2/S]
+    in tan space).  [3,3] fp32."""
+    s = float(face_size)
+    return np.array([[s / 2, 0, s / 2], [0, s / 2, s / 2], [0, 0, 1]], dtype=np.float32)
+
+
+def cube_view_shapes(stack_shape, pose_shape, pos_shape, size):
+    """The shape rules of MSI.cube_render_views, checked before anything touches a device: native stack [6B,D,S,S,4],
+    tgt_pose_rt [B,V,4,4], tgt_pos [B,V,3] ([V,4,4] / [V,3] when B = 1), size = (h, w) required.
+    Returns (B, V, S, D, h, w); ValueError otherwise."""
+    stack_shape, pose_shape, pos_shape = tuple(stack_shape), tuple(pose_shape), tuple(pos_shape)
+    if len(stack_shape) != 5 or stack_shape[-1] != 4:
+        raise ValueError("cube_render_views: the stack must be [6B,S,S,D,4], got native shape %s" % (stack_shape,))
+    n, d, h, w, _ = stack_shape
+    if n == 0 or n % 6:
+        raise ValueError("cube_render_views: the leading dimension is 6 faces per sample, %d is not a multiple of 6" % n)
+    if h != w:
+        raise ValueError("cube_render_views: cube faces are square, got %d x %d" % (h, w))
+    if size is None:
+        raise ValueError("cube_render_views: size=(h, w) is required for both cameras (a cube stack has no output size of its own)")
+    oh, ow = int(size[0]), int(size[1])
+    b = n // 6
+    if b == 1 and len(pose_shape) == 3 and len(pos_shape) == 2:
+        pose_shape, pos_shape = (1,) + pose_shape, (1,) + pos_shape
+    if len(pose_shape) != 4 or pose_shape[0] != b or pose_shape[2:] != (4, 4):
+        raise ValueError("tgt_pose_rt must be [B,V,4,4] with B = %d (or [V,4,4] for B = 1), got %s" % (b, pose_shape))
+    v = pose_shape[1]
+    if pos_shape != (b, v, 3):
+        raise ValueError("tgt_pos must be [B,V,3] = %s, got %s" % ((b, v, 3), pos_shape))
+    return b, v, h, d, oh, ow
+
+
+def check_origin_inside(tgt_pos, pose, planes):
+    """Host-side domain guard of MSI.cube_render_views: every view's ray origin, pose @ (tgt_pos[2], tgt_pos[1], tgt_pos[0], 1),
+    must lie strictly inside the innermost cube shell (max_k |o_k| < min planes; the x <-> z swap into the cube frame does not
+    change that maximum).  ValueError otherwise (NaN included).  Host arrays only: the caller skips it for device inputs."""
+    tp = np.asarray(tgt_pos, dtype=np.float64).reshape(-1, 3)
+    ps = np.asarray(pose, dtype=np.float64).reshape(-1, 4, 4)
+    if ps.shape[0] != tp.shape[0]:
+        return      # the shape check reports it
+    c = np.stack([tp[:, 2], tp[:, 1], tp[:, 0]], axis=1)
+    origin = np.einsum('bij,bj->bi', ps[:, :3, :3], c) + ps[:, :3, 3]
+    hmin = float(np.min(np.asarray(planes, dtype=np.float64)))
+    if not np.all(np.abs(origin).max(axis=1) < hmin):
+        raise ValueError("the target ray origin (pose @ tgt_pos) must lie inside the innermost cube shell (half-side %g)" % hmin)

@@ -898,6 +898,140 @@ class MSI(object):
                 "msi_mpi_render_views")
         return rgb, dep
 
+    # ------------------------------------------------------------------ cube-map viewer of the PP path (cubemap.py has the conventions)
+    def equirect_to_cube(self, image, face_size, intrinsics=None):
+        """Panorama [B,H,W,C] (fp32, C in 1..4) -> its six face images [B,6,S,S,C] (msi_equirect_to_cube_f32; no reference
+        counterpart), faces in cubemap.FACE_ROTATIONS order.  Texel (ix, iy) of face f looks along R_f K^-1 (ix, iy, 1);
+        intrinsics = the face camera K, [3,3] or [B,3,3], default cubemap.default_face_intrinsics(S).  Bilinear on the
+        panorama's lat-long grid, wrapping in longitude and clamping in latitude.  The panorama is taken as a
+        single-centre (equirectangular) image: the faces of an ODS panorama are not perspective images."""
+        from . import cubemap
+        image = self._f32(image)
+        if image.dim() != 4 or not 1 <= image.shape[-1] <= 4:
+            raise ValueError("equirect_to_cube: image must be [B,H,W,C] with C in 1..4, got %s" % (tuple(image.shape),))
+        b, h, w, c = image.shape
+        s = int(face_size)
+        if s < 1:
+            raise ValueError("equirect_to_cube: face_size must be positive")
+        k = self._f32(cubemap.default_face_intrinsics(s) if intrinsics is None else intrinsics).reshape(-1, 3, 3)
+        if k.shape[0] == 1 and b > 1:
+            k = k.expand(b, 3, 3)
+        if k.shape[0] != b:
+            raise ValueError("equirect_to_cube: intrinsics must be [3,3] or [B,3,3] with B = %d" % b)
+        k = k.contiguous()
+        out = torch.empty((b, 6, s, s, c), dtype=torch.float32, device=self.device)
+        N.check(N.lib.msi_equirect_to_cube_f32(image.data_ptr(), k.data_ptr(), b, h, w, c, s, out.data_ptr(), self._stream()),
+                "msi_equirect_to_cube_f32")
+        return out
+
+    def cube_render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, stack_intrinsics=None, camera='equirect',
+                          intrinsics=None, size=None, want_rgb=True, want_depth=True):
+        """V views of each CUBE of six face stacks in ONE launch (msi_cube_render_views; no reference counterpart) ->
+        (rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w]: the composited plane index / D of over_composite_depth); either is None
+        when switched off.  The planar twin of render_views; works on any model (the stack is what matters).
+
+        rgba_layers [6B,S,S,D,4] (a permuted view of the native [6B,D,S,S,4] stack -- what infer_cube / the PP network writes
+        for 6B faces -- goes through without a copy) or a PackedLayers of it; face f of sample b is entry 6 b + f, faces in
+        cubemap.FACE_ROTATIONS order.  Layer d of the six faces forms a cube shell of half-side planes[d]; a ray from inside
+        the innermost shell meets each shell once, on one face, and the D shells are composited far to near.  planes=None
+        takes the planes a PackedLayers carries (ValueError when it carries none); an fp32 stack needs planes.
+        stack_intrinsics: the camera K shared by a sample's six faces, [3,3] or [B,3,3], integer-pixel convention of the MPI
+        path; default cubemap.default_face_intrinsics(S).  With that default (fx = cx = S/2) a face covers [-1, 1 - 2/S] in
+        tan space, not [-1, 1]: the renderer CLAMPS TO THE EDGE inside the chosen face -- it neither zero-pads nor fetches
+        from the neighbouring face.  Pass fx = cx = (S-1)/2 for symmetric faces.
+        tgt_pose_rt [B,V,4,4], tgt_pos [B,V,3] ([V,4,4] / [V,3] when B = 1), camera, intrinsics: render_views' cameras and
+        pose model, unchanged; its frame (forward +x, down +y, right +z) maps to the cube frame (face 0's camera frame) by
+        swapping x and z, so the centre of an equirect output looks at the centre of face 0 and one set of arguments renders
+        an MSI and a cube stack of one scene.  size = (h, w) is required for both cameras.
+        Host-side poses and positions are checked before the launch (ValueError when an origin is not strictly inside the
+        innermost shell: max |o_k| >= min planes); device-side ones are flagged through render_status()."""
+        from . import cubemap
+        if camera not in self.CAMERAS:
+            raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
+        if not (want_rgb or want_depth):
+            raise ValueError("cube_render_views: want_rgb and want_depth are both False")
+        packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
+        if packed is not None:
+            native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
+            if planes is None:
+                planes = packed.planes
+        else:
+            native = self._native_layers(rgba_layers)
+        if planes is None:
+            raise ValueError("cube_render_views: planes is required (only a PackedLayers that carries its planes may leave it out)")
+        shape = lambda t: tuple(t.shape) if hasattr(t, "shape") else tuple(np.asarray(t).shape)
+        b, v, s, d, oh, ow = cubemap.cube_view_shapes(native.shape, shape(tgt_pose_rt), shape(tgt_pos), size)
+        if not any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, tgt_pose_rt, planes)):
+            cubemap.check_origin_inside(np.asarray(torch.as_tensor(tgt_pos)), np.asarray(torch.as_tensor(tgt_pose_rt)),
+                                        np.asarray(torch.as_tensor(planes)))
+        pose, pos = self._f32(tgt_pose_rt).reshape(b * v, 4, 4), self._f32(tgt_pos).reshape(b * v, 3)
+        depths = self._planes(planes)
+        if depths.numel() != d:
+            raise ValueError("len(planes) != number of layers")
+        ks = self._f32(cubemap.default_face_intrinsics(s) if stack_intrinsics is None else stack_intrinsics).reshape(-1, 3, 3)
+        if ks.shape[0] == 1 and b > 1:
+            ks = ks.expand(b, 3, 3)
+        if ks.shape[0] != b:
+            raise ValueError("stack_intrinsics must be [3,3] or [B,3,3] with B = %d" % b)
+        ks = ks.contiguous()
+        intr, trig = None, None
+        if camera == 'equirect':
+            trig = self._trig(oh, ow)
+        else:
+            if intrinsics is None:
+                raise ValueError("camera='pinhole' needs intrinsics")
+            intr = self._f32(intrinsics).reshape(-1, 3, 3)
+            if intr.shape[0] == 1:
+                intr = intr.expand(b * v, 3, 3).contiguous()
+            if intr.shape[0] != b * v:
+                raise ValueError("intrinsics must be [B,V,3,3] or [3,3]")
+        rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
+        dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
+        fmt = self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+        N.check(N.lib.msi_cube_render_views(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(),
+                                            depths.data_ptr(), _ptr(trig), b, v, s, d, self.CAMERAS[camera], oh, ow, _ptr(rgb),
+                                            _ptr(dep), self._render_status.data_ptr(), self._stream()), "msi_cube_render_views")
+        return rgb, dep
+
+    def infer_cube(self, raw_src_equirect, raw_ref_equirect, src_pose, face_size, planes, face_intrinsics=None,
+                   layer_format='f32', ngf=64, extra_outputs='', which_color_pred='blend_psv'):
+        """A 360-degree pair through the PP network, face by face: preprocess both panoramas [B,H,W,3], equirect_to_cube each,
+        view the faces as a batch [6B,S,S,3], format_network_input with ref_pose = I and src_pose =
+        cubemap.face_poses(src_pose) (src_pose [4,4] or [B,4,4]: the source camera in the cube frame = the reference
+        camera's frame), then infer_layers.  Returns the pred dict; its stack (pred['rgba_layers'] [6B,S,S,D,4] and / or
+        pred['packed_layers'], which carries `planes`) goes straight into cube_render_views.  Pure composition: no kernel of
+        its own.  For input_type='PP' models only.  The panoramas are single-centre equirectangular images: the faces of an
+        ODS panorama are not perspective images."""
+        from . import cubemap
+        if self.input_type != 'PP':
+            raise ValueError("infer_cube runs the perspective (PP) network on cube faces: build the model with input_type='PP'")
+        s = int(face_size)
+        d = len(planes)
+        src, ref = self.preprocess_image(raw_src_equirect), self.preprocess_image(raw_ref_equirect)
+        if src.dim() != 4 or src.shape[-1] != 3 or src.shape != ref.shape:
+            raise ValueError("infer_cube: the panoramas must be [B,H,W,3] and agree")
+        b = src.shape[0]
+        k = cubemap.default_face_intrinsics(s) if face_intrinsics is None else face_intrinsics
+        src_faces = self.equirect_to_cube(src, s, k).reshape(6 * b, s, s, 3)
+        ref_faces = self.equirect_to_cube(ref, s, k).reshape(6 * b, s, s, 3)
+        sp = self._f32(src_pose).reshape(-1, 4, 4)
+        if sp.shape[0] == 1 and b > 1:
+            sp = sp.expand(b, 4, 4)
+        if sp.shape[0] != b:
+            raise ValueError("infer_cube: src_pose must be [4,4] or [B,4,4] with B = %d" % b)
+        face_src = cubemap.face_poses(sp).reshape(6 * b, 4, 4).contiguous()
+        eye = torch.eye(4, dtype=torch.float32, device=self.device).expand(6 * b, 4, 4).contiguous()
+        kf = self._f32(k).reshape(-1, 3, 3)
+        if kf.shape[0] not in (1, b):
+            raise ValueError("infer_cube: face_intrinsics must be [3,3] or [B,3,3] with B = %d" % b)
+        kf = kf.expand(b, 3, 3)[:, None].expand(b, 6, 3, 3).reshape(6 * b, 3, 3).contiguous()
+        net_input = self.format_network_input(ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye)
+        pred = self.infer_layers(net_input, d, ngf, extra_outputs, which_color_pred, layer_format=layer_format)
+        if 'packed_layers' in pred:
+            pk = pred['packed_layers']
+            pred['packed_layers'] = PackedLayers(pk.data, pk.format, planes)
+        return pred
+
     # ------------------------------------------------------------------ image scores (eval.py:127-174 on the device)
     SCORE_TRANSFORMS = {'raw': N.MSI_SCORE_RAW, 'image': N.MSI_SCORE_IMAGE, 'depth': N.MSI_SCORE_DEPTH}
     SCORE_METRICS = {'mse': N.MSI_SCORE_MSE, 'psnr': N.MSI_SCORE_MSE, 'mae': N.MSI_SCORE_MAE, 'ssim': N.MSI_SCORE_SSIM}
