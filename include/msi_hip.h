@@ -521,11 +521,10 @@ typedef struct msi_net_plan msi_net_plan;
 #define MSI_NET_OPT_BIGTILE 2      /* bf16 tile choice: 0 never 128x128 / 128x64, 1 (default) by grid size, 2 always */
 #define MSI_NET_OPT_HEAD_FUSE_LN 3 /* 1 (default): the fp32 head applies its source's LayerNorm while loading      */
 #define MSI_NET_OPT_NUM_CUS 4      /* CUs the work decomposition balances over (default: the device's count)      */
-#define MSI_NET_OPT_F32_TILE 5     /* fp32 tile of the layers in F32_TILE_MASK: 0 = 64x64, 1 = 128x64, 2 = 64x128 (tuning)     */
-#define MSI_NET_OPT_F32_TILE_MASK 6 /* bit i = layer i (graph order) uses MSI_NET_OPT_F32_TILE                                 */
-#define MSI_NET_OPT_APPLY_AHEAD 7   /* 1: a layer's LayerNorm + ReLU is applied by the first workgroups of its consumer's launch,    */
-                                   /* overlapped with that layer's tiles (row counters); 0 (default): one ln_apply launch per layer */
-                                   /* -- bit-identical results; measured slower on MI355X (write-through hand-off), see DESIGN.md  */
+#define MSI_NET_OPT_F32_TILE 5     /* retired (were: the fp32 128x64 / 64x128 tap-kernel tiles and their per-layer mask, measured   */
+#define MSI_NET_OPT_F32_TILE_MASK 6 /* slower): 0 is accepted and does nothing, anything else is MSI_E_UNSUPPORTED (F32_TILE outside 0..2: MSI_E_BADARG) */
+#define MSI_NET_OPT_APPLY_AHEAD 7   /* retired (was: a layer's LayerNorm + ReLU applied by the first workgroups of its consumer's    */
+                                   /* launch, measured slower: DESIGN.md): 0 is accepted and does nothing, anything else is MSI_E_UNSUPPORTED */
 #define MSI_NET_OPT_HALO 8          /* default 5.  bit 0: the stride-1 3x3 layers run the halo-patch kernels (conv_halo_kernel fp32,   */
                                    /* conv_halo_bf16_kernel: one LDS-stationary halo patch per workgroup and input chunk, the          */
                                    /* producer's LayerNorm applied while staging it) and the bf16 conv-transposes                      */
@@ -599,8 +598,8 @@ int32_t msi_net_plan_layer_params(const msi_net_plan *plan, int32_t layer, void 
  * LayerNorm sum overflowed its fixed-point window (bit 1 of *status_bits: raw outputs > ~3000x the scale the weights
  * predict, or non-finite input; bf16 plans also set it when a raw output may have left the range of the fp16 it is
  * stored in -- some |x 2^-e - pivot| of a wave's 1 024 values above 32 752, i.e. > ~1000x that scale) or a variance fell below its resolution (bit 2: < ~1e-3 of that scale, or a constant
- * layer); bit 0: an apply-ahead wait timed out.  status_bits may be NULL.  The word is reset by the next forward. */
-#define MSI_NET_STATUS_APPLY_AHEAD_TIMEOUT 1
+ * layer).  status_bits may be NULL.  The word is reset by the next forward. */
+#define MSI_NET_STATUS_APPLY_AHEAD_TIMEOUT 1 /* bit 0: no kernel sets it any more (the number stays taken) */
 #define MSI_NET_STATUS_LN_OVERFLOW 2
 #define MSI_NET_STATUS_LN_UNDERFLOW 4
 #define MSI_NET_STATUS_F16_SPLIT_RANGE 8 /* an operand of a layer on the fp16 split (F32_SPLIT_F16) exceeded 65504: rerun with that option 0 */

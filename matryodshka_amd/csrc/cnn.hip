@@ -114,7 +114,7 @@ static int run_layers(const msi_net_plan *plan, const float *packed, const void 
   // tickets of the in-launch fix-ups and the LayerNorm sums start from zero
   // (a kernel of the library's own instead of hipMemsetAsync: the runtime's fill is a blit with its own barrier packets)
   {
-    const size_t n16 = net.zero_bytes / 16;               // zero_off and zero_bytes are multiples of 256
+    const size_t n16 = net.zero_bytes / 16;               // zero_off is a multiple of 256, zero_bytes of 64
     int rc0 = launch_zero(ws + net.zero_off, n16, stream);
     if (rc0) return rc0;
   }
@@ -149,17 +149,6 @@ static int run_layers(const msi_net_plan *plan, const float *packed, const void 
     p.status = reinterpret_cast<int *>(ws + net.err_off);
     p.partial = reinterpret_cast<float *>(ws + net.partial_off);
     p.tile_cnt = Q.inlaunch ? cnt + (size_t)li * CONV_SLOTS_PER_CU * plan->num_cus : nullptr;
-    if (p.n_apply > 0) {
-      const Layer &S = net.layers[L.src0];
-      p.ap_x = reinterpret_cast<float *>(ws + S.raw_off);
-      p.ap_yb = bf16 ? reinterpret_cast<unsigned short *>(ws + S.act_off) : nullptr;
-      p.ap_sums = reinterpret_cast<const long long *>(ws + S.sums_off);
-      p.ap_gamma = packed + S.gamma_off;
-      p.ap_beta = packed + S.beta_off;
-      p.ap_aff = reinterpret_cast<float *>(ws + S.aff_off);
-      p.ap_flags = reinterpret_cast<int *>(ws + S.flags_off);
-      p.ap_err = reinterpret_cast<int *>(ws + net.err_off);
-    }
 #if defined(MSI_CONV_TIMING) || defined(MSI_DEBUG_STATS)
     p.dbg = (li == g_timing_layer) ? g_timing_buf : nullptr;
 #endif
@@ -208,11 +197,10 @@ int32_t msi_net_plan_status(const msi_net_plan *plan, const void *workspace, msi
   if (e != hipSuccess) return msi::fail(MSI_E_LAUNCH, "net_plan_status: %s", hipGetErrorString(e));
   if (status_bits) *status_bits = word;
   if (word == 0) return MSI_OK;
-  return msi::fail(MSI_E_RANGE, "net_plan_status: 0x%x:%s%s%s%s", word,
+  return msi::fail(MSI_E_RANGE, "net_plan_status: 0x%x:%s%s%s", word,
                    (word & STATUS_F16_SPLIT_RANGE) ? " an operand of a layer on the fp16 split exceeded the fp16 range (|x| > 65504): set MSI_NET_OPT_F32_SPLIT_F16 = 0" : "",
                    (word & STATUS_LN_OVERFLOW) ? " a LayerNorm sum left its fixed-point window (raw convolution output far above the scale the weights predict: non-finite or mis-scaled input?)" : "",
-                   (word & STATUS_LN_UNDERFLOW) ? " a LayerNorm variance is below the resolution of its fixed-point window (raw convolution output far below the scale the weights predict, or constant)" : "",
-                   (word & STATUS_APPLY_AHEAD_TIMEOUT) ? " an apply-ahead wait timed out" : "");
+                   (word & STATUS_LN_UNDERFLOW) ? " a LayerNorm variance is below the resolution of its fixed-point window (raw convolution output far below the scale the weights predict, or constant)" : "");
 }
 
 // LayerNorm window calibration.  The fixed-point window of a layer's sums follows an exponent the packer ESTIMATES from the weights

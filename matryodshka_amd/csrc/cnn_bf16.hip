@@ -31,14 +31,10 @@ struct HaloGeomB {
   static constexpr int NLOAD = (NPX * 8 + 255) / 256;     // 8-channel patch slots per thread and chunk
 };
 
-#ifndef MSI_HALO_ABLATE   // timing experiments only (tools/_variants): 1 no weight DMA, 2 no patch traffic, 4 no k-step barrier, 8 no fragment reads
-#define MSI_HALO_ABLATE 0
-#endif
 template <int BM, int BN, int RATE, int APPLY, int NW>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 2)))
 conv_halo_bf16_kernel(const ConvParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int ABL = MSI_HALO_ABLATE;
 #ifdef MSI_CONV_TIMING
   const unsigned long long ts0 = __builtin_amdgcn_s_memtime(), ts0r = __builtin_amdgcn_s_memrealtime();   // (ts0r: the constant 100 MHz counter, tools/clock_probe.sh)
 #endif
@@ -201,15 +197,6 @@ conv_halo_bf16_kernel(const ConvParams p) {
     constexpr int AROW_ = 2 * G::ROW_PITCH;   /* next 32-pixel block: two patch rows down */
     v4f fa_[4][MT], fb_[4][NT];
     const unsigned bst_ = (unsigned)st * G::B_STAGE;
-    if (ABL & 8) {
-#pragma unroll
-      for (int q_ = 0; q_ < 4; ++q_) {
-#pragma unroll
-        for (int i_ = 0; i_ < MT; ++i_) asm volatile("" : "=v"(fa_[q_][i_]));
-#pragma unroll
-        for (int j_ = 0; j_ < NT; ++j_) asm volatile("" : "=v"(fb_[q_][j_]));
-      }
-    } else
 #pragma unroll
     for (int q_ = 0; q_ < 4; ++q_) {
       const unsigned ba_ = b_q[q_] + bst_;
@@ -230,24 +217,21 @@ conv_halo_bf16_kernel(const ConvParams p) {
     hq(IC<0>{}, fa_, fb_);
     bool issued_;
     {
-      if (!(ABL & 2) && TAP == 0 && c + 1 < c1) patch_load(c + 1);
+      if (TAP == 0 && c + 1 < c1) patch_load(c + 1);
       int sn_ = st + PD; sn_ = sn_ >= NSTG ? sn_ - NSTG : sn_;
       issued_ = (TAP + PD < 9) || (c + 1 < c1);
-      if (ABL & 1) { }
-      else if (TAP + PD < 9) { b_issue(c, TAP + PD, sn_); }
+      if (TAP + PD < 9) { b_issue(c, TAP + PD, sn_); }
       else if (c + 1 < c1) { b_issue(c + 1, TAP + PD - 9, sn_); }
     }
     hq(IC<1>{}, fa_, fb_); hq(IC<2>{}, fa_, fb_); hq(IC<3>{}, fa_, fb_);
-    if (ABL & 3) {
-      wait_vmcnt<0>();
-    } else if (PD == 2) {
+    if (PD == 2) {
       if (TAP == 0 && c + 1 < c1) wait_vmcnt<BI + NPL>();
       else if (issued_) wait_vmcnt<BI>();
       else wait_vmcnt<0>();
     } else {
       wait_vmcnt<0>();
     }
-    if (!(ABL & 4)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     st = st + 1 == NSTG ? 0 : st + 1;
   };
 
@@ -294,7 +278,7 @@ conv_halo_bf16_kernel(const ConvParams p) {
 #endif
   for (; c < c1; ++c) {
     htap(IC<0>{}); htap(IC<1>{}); htap(IC<2>{}); htap(IC<3>{}); htap(IC<4>{}); htap(IC<5>{}); htap(IC<6>{}); htap(IC<7>{}); htap(IC<8>{});
-    if (c + 1 < c1 && !(ABL & 2)) {
+    if (c + 1 < c1) {
       patch_store();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -871,11 +855,7 @@ convt_halo_bf16_kernel(const ConvParams p) {
 
 template <int BM, int BN, int RATE, int APPLY, int NW>
 int launch_halo_bf16(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
-#ifdef MSI_ONE_PER_CU   // timing experiment: one workgroup per CU (no co-resident workgroup's MFMAs)
-  constexpr int lds = 100 * 1024;
-#else
   constexpr int lds = HaloGeomB<BM, BN, RATE>::LDS_BYTES + (APPLY ? 8 * 512 : 0);   // + scale | shift of <= 512 input channels (4 KB: two workgroups per CU still fit)
-#endif
   static_assert(lds >= EPI_STAGE_BYTES, "the epilogue's staging strips");
   if (APPLY && p.C0 > 512) return msi::fail(MSI_E_UNSUPPORTED, "conv_halo_bf16: APPLY with more than 512 input channels");
   return launch_kernel<conv_halo_bf16_kernel<BM, BN, RATE, APPLY, NW>, lds, 64 * NW>(Q.nblocks, p, stream, "conv_halo_bf16");

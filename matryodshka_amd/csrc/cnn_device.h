@@ -59,8 +59,7 @@ constexpr int LN_SHARDS = 64, LN_WORDS = 2;
 constexpr int LN_S1_BITS = 24, LN_S2_BITS = 16;   // S1 = 2^(24 - e), S2 = 2^(16 - 2 e)
 constexpr int LN_SCL_DOUBLES = 4;                 // per layer in the packed blob: S1, S2, 1 / S1, 1 / S2
 constexpr double LN_UNDERFLOW_UNITS_SQ = 1e12;    // (1e6 units)^2 per contributing wave, see ln_mean_inv
-enum { STATUS_APPLY_AHEAD_TIMEOUT = 1, STATUS_LN_OVERFLOW = 2, STATUS_LN_UNDERFLOW = 4, STATUS_F16_SPLIT_RANGE = 8 };
-constexpr int AP_FLAG_STRIDE = 16;  // ints between two row counters of the apply-ahead hand-off: one counter per 64-byte line
+enum { STATUS_APPLY_AHEAD_TIMEOUT = 1 /* retired: no kernel sets it */, STATUS_LN_OVERFLOW = 2, STATUS_LN_UNDERFLOW = 4, STATUS_F16_SPLIT_RANGE = 8 };
 constexpr int HEAD_MAX_C = 256;   // the head's fused LayerNorm keeps scale | shift of its source in LDS
 
 enum { MODE_CONV = 0, MODE_CONVT = 1, MODE_HEAD = 2 };
@@ -73,7 +72,7 @@ struct ConvParams {
   const float *coord_bias;   // CoordNet: contribution of the |sin(lat)| channel, [Mh][COORD_CLASSES][cb_stride] fp32, or null
   int cb_stride;
   const double *ln_scl;      // fixed-point scales of THIS layer's LayerNorm sums {S1, S2, 1 / S1, 1 / S2} (packed blob)
-  const double *ln_scl_src, *ln_scl_src1;   // ... of the source layers whose sums ln_sums / ln_sums1 (ap_sums) are
+  const double *ln_scl_src, *ln_scl_src1;   // ... of the source layers whose sums ln_sums / ln_sums1 are
   int *status;               // the plan's status word (STATUS_* bits, zeroed per forward)
   const long long *ln_sums;  // head, fp32 only: the LayerNorm sums of the source layer; its affine (+ ReLU) is applied while
                              // loading (the source buffer then holds the RAW conv output); null = source already normalised
@@ -103,18 +102,6 @@ struct ConvParams {
   int halo_xor;              // 8 (conv_halo_kernel) / 0: odd rows of a halo tile map lane l to column (l & 15) ^ halo_xor (HaloGeom)
   int row_par;               // 1 (rate-2 layers of the split kernels, r05): a halo tile's rows are every OTHER image row -- tile row index t = 2 t' + parity covers rows
                              // 2 TH t' + parity + 2 r: a dilation-2 convolution restricted to one row parity is a dilation-1 convolution along H (halo_row)
-  // "apply-ahead": the first n_apply workgroups of the launch normalise source 0 (LayerNorm + ReLU of the producer layer)
-  // while the tile workgroups behind them already compute; see apply_ahead() below.  n_apply = 0: source 0 is
-  // normalised already (separate ln_apply launch, or the network input).
-  float *ap_x;               // raw fp32 output of the producer, normalised in place (fp32 path) ...
-  unsigned short *ap_yb;     // ... or written as bf16 into the operand copy (bf16 path), else null
-  const long long *ap_sums;  // the producer's LayerNorm sums [B][LN_SHARDS][4]
-  const float *ap_gamma, *ap_beta;
-  float *ap_aff;             // published affine [B][scale | shift] (tests)
-  int *ap_flags;             // [B][Hin][AP_FLAG_STRIDE] completed units per input row (zeroed per forward)
-  int *ap_err;               // set to 1 if a tile workgroup gave up waiting (never in a healthy launch)
-  double ap_inv_n;
-  int n_apply, ap_units_per_row, ap_unit_vec, ap_row_vec;   // workgroups; units per row; float4 per unit / per row
 #if defined(MSI_CONV_TIMING) || defined(MSI_DEBUG_STATS)
   unsigned long long *dbg;   // [block][6]: s_memtime at start, loop start, loop end, end; HW_ID; XCC_ID (tools/conv_timing.py)
 #endif
@@ -292,7 +279,7 @@ __device__ __forceinline__ v4f lds_read128(unsigned addr) {
   v4f v;
   if constexpr (OFF < 65536) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  } else {  // beyond the 16-bit immediate (only the experimental big tiles): one VALU add
+  } else {  // beyond the 16-bit immediate (the third stage of a 128x128 tile's ring, MSI_NSTAGE = 3): one VALU add
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr + (OFF & ~0xffff)), "n"(OFF & 0xffff) : "memory");
   }
   return v;
@@ -509,9 +496,6 @@ constexpr int EPI_STAGE_BYTES = 48 * 1024;   // emit_whole_tile's staging strips
 #ifndef MSI_EPI_NT   // experiment (r06): 1 = non-temporal stores of the staged epilogue's raw outputs
 #define MSI_EPI_NT 0
 #endif
-#ifndef MSI_EPI_ABLATE   // timing experiments only: 1 no stores, 2 no statistics atomics, 4 no statistics arithmetic
-#define MSI_EPI_ABLATE 0
-#endif
 #ifdef MSI_CONV_TIMING
 #define MSI_STAMP(k) { if (p.dbg && tid == 0) p.dbg[(size_t)blockIdx.x * 24 + (k)] = __builtin_amdgcn_s_memtime(); }
 #else
@@ -610,15 +594,13 @@ __device__ __forceinline__ void emit_whole_tile(const ConvParams &p, f32x16 (&ac
         hw[q] = u2_t{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
       }
     }
-    if (!(MSI_EPI_ABLATE & 1)) {
 #pragma unroll
-      for (int q = 0; q < NG; ++q) {
-        char *dst = staged ? wp + i * (32 * PITCH) : yp[i];
-        if (RAW16) *reinterpret_cast<u2_t *>(dst + ((q >> 2) * 32 + 8 * (q & 3)) * 2) = hw[q];
-        else *reinterpret_cast<v4f *>(dst + ((q >> 2) * 32 + 8 * (q & 3)) * 4) = v4f{ya[q].x, ya[q].y, yc[q].x, yc[q].y};
-      }
+    for (int q = 0; q < NG; ++q) {
+      char *dst = staged ? wp + i * (32 * PITCH) : yp[i];
+      if (RAW16) *reinterpret_cast<u2_t *>(dst + ((q >> 2) * 32 + 8 * (q & 3)) * 2) = hw[q];
+      else *reinterpret_cast<v4f *>(dst + ((q >> 2) * 32 + 8 * (q & 3)) * 4) = v4f{ya[q].x, ya[q].y, yc[q].x, yc[q].y};
     }
-    if (want_stats && !(MSI_EPI_ABLATE & 4)) {
+    if (want_stats) {
 #pragma unroll
       for (int q = 0; q < NG; ++q) { ya[q] -= pv; yc[q] -= pv; }
 #pragma unroll
@@ -634,7 +616,7 @@ __device__ __forceinline__ void emit_whole_tile(const ConvParams &p, f32x16 (&ac
   const v2f t1 = (s1v[0] + s1v[1]) + (s1v[2] + s1v[3]), t2 = (s2v[0] + s2v[1]) + (s2v[2] + s2v[3]);
   float s1 = t1.x + t1.y, s2 = t2.x + t2.y;
   // ---- the strip's pieces -> memory ----
-  if (staged && !(MSI_EPI_ABLATE & 1)) {
+  if (staged) {
     const char *rp = wst + (lane / NP) * PITCH + (lane % NP) * 16;
     v4f pc[MT][NRD];
 #pragma unroll
@@ -668,7 +650,7 @@ __device__ __forceinline__ void emit_whole_tile(const ConvParams &p, f32x16 (&ac
   if (want_stats) {
     s1 = wave_sum(s1); s2 = wave_sum(s2);
     MSI_STAMP(18)
-    if (lane == 0 && !(MSI_EPI_ABLATE & 2)) {
+    if (lane == 0) {
       const double P = (double)pv_s, n = (double)(MT * NT * 16 * 64), a = (double)s1;
       const double u1 = RAW16 ? 16777216.0 : scl_s1, u2 = RAW16 ? 65536.0 : scl_s2;
       // RAW16: the tile was just stored as fp16 of y = x 2^-e, which is +-inf beyond 65504.  s2 = sum (y - pivot)^2 over the wave
@@ -769,8 +751,7 @@ __device__ __forceinline__ void emit_tile_impl(const ConvParams &p, f32x16 (&acc
             const v4f bs = *reinterpret_cast<const v4f *>(p.bias + n);
             v.x = msi_tanh(v.x + bs.x); v.y = msi_tanh(v.y + bs.y); v.z = msi_tanh(v.z + bs.z); v.w = msi_tanh(v.w + bs.w);
           }
-          if (MSI_EPI_ABLATE & 1) {
-          } else if (sok && RAW16) {   // (Cout % 4 == 0 in a bf16 plan: whole 8-byte pieces)
+          if (sok && RAW16) {   // (Cout % 4 == 0 in a bf16 plan: whole 8-byte pieces)
             typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
             typedef unsigned u2_t __attribute__((ext_vector_type(2)));
             const h2_t lo = {(_Float16)(v.x * raw_mul), (_Float16)(v.y * raw_mul)}, hi = {(_Float16)(v.z * raw_mul), (_Float16)(v.w * raw_mul)};
@@ -786,7 +767,7 @@ __device__ __forceinline__ void emit_tile_impl(const ConvParams &p, f32x16 (&acc
               if (n + 3 < p.Cout) dst[3] = v.w;
             }
           }
-          if (want_stats && !(MSI_EPI_ABLATE & 4)) {
+          if (want_stats) {
             const float dx = v.x - pivot, dy = v.y - pivot, dz = v.z - pivot, dw = v.w - pivot;
             if (INTERIOR || n + 3 < p.Cout) {
               s1 += (dx + dy) + (dz + dw);
@@ -806,7 +787,7 @@ __device__ __forceinline__ void emit_tile_impl(const ConvParams &p, f32x16 (&acc
     s1 = wave_sum(s1);
     s2 = wave_sum(s2);
     const float wcnt = INTERIOR ? (float)(MT * NT * 16 * 64) : wave_sum(cnt);
-    if (lane == 0 && wcnt > 0.f && !(MSI_EPI_ABLATE & 2)) {
+    if (lane == 0 && wcnt > 0.f) {
       const double P = (double)pivot, n = (double)wcnt, a = (double)s1;
       long long *dst = p.sums + ((size_t)b * LN_SHARDS + ((blockIdx.x * 4 + wave) & (LN_SHARDS - 1))) * LN_WORDS;   // (any spread will do)
       // (RAW16, see emit_whole_tile: here the sums are in x, the stored value is x raw_mul)
@@ -867,132 +848,6 @@ __device__ __forceinline__ void load_coord_bias(const ConvParams &p, int tile_m,
   }
 }
 
-
-#ifdef MSI_EXPERIMENTS   // measured-slower variants (apply-ahead, fp32 128x64 / 64x128 tiles) are compiled only on request:
-// MSI_CNN_DEFINES=-DMSI_EXPERIMENTS python -m matryodshka_amd.build --force; the default library has no kernel with spills
-// ---- apply-ahead: LayerNorm + ReLU of the producer inside the consumer's launch ------------------------------
-// The LayerNorm of layer N needs all of layer N (global statistics), so it cannot be folded into N's epilogue, and the
-// k-loop of layer N+1 has no VALU slot for it; as a launch of its own it is an HBM-bound pass (read + write every
-// activation: 0.15 ms of a 2.7 ms frame) during which the matrix pipes idle, plus a kernel boundary per layer.
-// Here the first n_apply workgroups of layer N+1's launch do that pass -- row by row, in place, publishing a counter per
-// input row -- and every tile workgroup waits only for the input rows its halo touches: the HBM-bound pass overlaps
-// the MFMA-bound one.  The unit sequence is dealt out like the tiles (XCD x sweeps the x-th eighth of the rows, in
-// order), so the rows a tile workgroup needs first are normalised first, by workgroups of its own XCD.
-// Hand-off (cdna_hip_programming.md, write-through form): the apply workgroups read the raw values with sc1 loads (the
-// raw lines never enter an L1) and write the normalised ones with sc1 stores (write-through), drain vmcnt, barrier,
-// one relaxed agent-scope atomic per unit; a tile workgroup polls the counters of its rows with relaxed agent-scope
-// loads and only then issues its first DMA -- no line of the activation is fetched by anyone before it is final, so
-// no cache holds a stale copy.  Dead-lock freedom: the apply workgroups have the lowest block indices, never wait,
-// and are all resident before any tile workgroup can occupy their slots; the wait is bounded anyway (ap_err).
-__device__ __forceinline__ void apply_ahead(const ConvParams &p, char *smem, int tid) {
-  float *s_aff = reinterpret_cast<float *>(smem);                 // scale[C0] | shift[C0]
-  double *s_stat = reinterpret_cast<double *>(smem + 2 * 512 * 4 + 64);
-  const int C = p.C0;
-  const int upr = p.ap_units_per_row;
-  const long units_per_sample = (long)p.Hin * upr;
-  // batch is not a kernel parameter: the grid covers ntiles = tiles per sample * batch
-  const int batch = p.ntiles / (p.tiles_m * p.tiles_n * p.nclass);
-  const long total = units_per_sample * batch;
-  const long per = (total + 7) / 8;                                // units of one XCD's range
-  const int x = blockIdx.x & 7;
-  const __amdgpu_buffer_rsrc_t rs_aff = __builtin_amdgcn_make_buffer_rsrc((void *)p.ap_aff, 0, 0x7fffffff, 0x00020000);
-  (void)rs_aff;
-  int cur_b = -1;
-  for (long l = blockIdx.x >> 3; l < per; l += p.n_apply >> 3) {
-    const long u = (long)x * per + l;
-    if (u >= total) break;
-    const int b = (int)(u / units_per_sample);
-    const long ur = u - (long)b * units_per_sample;
-    const int row = (int)(ur / upr), part = (int)(ur - (long)row * upr);
-    if (b != cur_b) {   // (the sweep is in order: the sample changes at most a few times per workgroup)
-      __syncthreads();
-      ln_mean_inv(p.ap_sums + (size_t)b * LN_SHARDS * LN_WORDS, p.ap_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-      const double mu = s_stat[0], inv = s_stat[1];
-      for (int c = tid; c < C; c += 256) {
-        const double sc = inv * (double)p.ap_gamma[c];
-        const float fs = (float)sc, ft = (float)((double)p.ap_beta[c] - mu * sc);
-        s_aff[c] = fs;
-        s_aff[C + c] = ft;
-        if (row == 0 && part == 0) {   // exactly one workgroup per sample starts at its first unit
-          p.ap_aff[(size_t)b * 2 * C + c] = fs;
-          p.ap_aff[(size_t)b * 2 * C + C + c] = ft;
-        }
-      }
-      __syncthreads();
-      cur_b = b;
-    }
-    const size_t row_elems = (size_t)p.ap_row_vec * 4;
-    const size_t base = ((size_t)b * p.Hin + row) * row_elems;    // element offset of the row
-    const int v0 = part * p.ap_unit_vec;
-    const int v1 = min(v0 + p.ap_unit_vec, p.ap_row_vec);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.ap_x + base), 0, (int)(row_elems * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rd = p.ap_yb ? __builtin_amdgcn_make_buffer_rsrc((void *)(p.ap_yb + base), 0, (int)(row_elems * 2), 0x00020000) : rs;
-    auto bf16_bits = [](float f) __attribute__((always_inline)) -> unsigned {
-      const unsigned uu = __builtin_bit_cast(unsigned, f);
-      return (uu + 0x7fffu + ((uu >> 16) & 1u)) >> 16;
-    };
-    for (int v = v0 + tid; v < v1; v += 4 * 256) {
-      v4f xv[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)   // out-of-range offsets read zeros and are not stored
-        xv[k] = __builtin_bit_cast(v4f, (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)((v + 256 * k) * 16), 0, 16));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int vv = v + 256 * k;
-        if (vv >= v1) break;
-        const int c = (vv * 4) % C;                               // C % 4 == 0: a float4 never straddles channels' wrap
-        const v4f s4 = *reinterpret_cast<const v4f *>(s_aff + c), t4 = *reinterpret_cast<const v4f *>(s_aff + C + c);
-        v4f y;
-        y.x = fmaxf(xv[k].x * s4.x + t4.x, 0.f); y.y = fmaxf(xv[k].y * s4.y + t4.y, 0.f);
-        y.z = fmaxf(xv[k].z * s4.z + t4.z, 0.f); y.w = fmaxf(xv[k].w * s4.w + t4.w, 0.f);
-        if (p.ap_yb) {
-          typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
-          const v2u_t o = {bf16_bits(y.x) | (bf16_bits(y.y) << 16), bf16_bits(y.z) | (bf16_bits(y.w) << 16)};
-          __builtin_amdgcn_raw_buffer_store_b64(o, rd, (unsigned)(vv * 8), 0, 16);
-        } else {
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, y), rs, (unsigned)(vv * 16), 0, 16);
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's write-through stores have left
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(p.ap_flags + ((size_t)b * p.Hin + row) * AP_FLAG_STRIDE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// A tile workgroup's side, in two steps so that the round trip of the counter loads hides behind the prologue:
-// rows_probe (right after the tile decode) -- lane l loads the counter of input row r0 + l once;
-// rows_wait (before the first DMA) -- all done: nothing more; else ONE lane polls the missing rows, last row first
-// (the sweep is in row order), one counter per 64-byte line: thousands of lanes polling a few shared lines starve the
-// apply workgroups' own counter updates (measured: +30 % on every layer).
-__device__ __forceinline__ int rows_probe(const ConvParams &p, int b, int r0, int r1, int tid) {
-  const int r = r0 + tid;
-  if (r > r1) return 0x7fffffff;
-  return __hip_atomic_load(p.ap_flags + ((size_t)b * p.Hin + r) * AP_FLAG_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void rows_wait(const ConvParams &p, int b, int r0, int r1, int probed, int tid, int *s_flag) {
-  const bool ready = probed >= p.ap_units_per_row;
-  if (tid < 64) {   // rows of one tile fit one wave's lanes (host-checked: <= 64 input rows per tile)
-    const bool all = __builtin_amdgcn_ballot_w64(!ready) == 0;
-    if (tid == 0) *s_flag = all ? 1 : 0;
-  }
-  __syncthreads();
-  if (*s_flag) return;
-  if (tid == 0) {
-    int spins = 0;
-    for (int r = r1; r >= r0; --r) {
-      const int *f = p.ap_flags + ((size_t)b * p.Hin + r) * AP_FLAG_STRIDE;
-      while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p.ap_units_per_row) {
-        __builtin_amdgcn_s_sleep(32);
-        if (++spins > (1 << 20)) { __hip_atomic_fetch_or(p.ap_err, STATUS_APPLY_AHEAD_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); r = r0; break; }   // ~1 s: something is badly wrong; do not hang the GPU
-      }
-    }
-  }
-  __syncthreads();
-}
-
-#endif  // MSI_EXPERIMENTS
 
 // k-step J of a 32-channel group of the stride-2 form -> tap (unit by unit: the four units' taps in the order the patches are swapped) and unit
 __device__ constexpr int s2_tap(int J) { return J == 0 ? 0 : J == 1 ? 2 : J == 2 ? 6 : J == 3 ? 8 : J == 4 ? 1 : J == 5 ? 7 : J == 6 ? 3 : J == 7 ? 5 : 4; }

@@ -35,20 +35,10 @@ conv_igemm_kernel(const ConvParams p) {
   // XCD-aware order for the whole tiles: workgroup b runs on XCD b % 8 (observed, speed only) and
   // each XCD has a private L2; consecutive tiles share halo rows and weights, so every XCD gets a
   // CONTIGUOUS range of tiles instead of every eighth one (bijective remap).
-#ifdef MSI_EXPERIMENTS
-  if (p.n_apply > 0 && (int)blockIdx.x < p.n_apply) {   // apply-ahead workgroup (see apply_ahead)
-    apply_ahead(p, smem, tid);
-    return;
-  }
-#endif
   const int S = p.ksteps;
   int t, k0 = 0, k1 = S, ks = 0, slot = 0;   // slot: index of this K-range's partial accumulator
   {
-#ifdef MSI_EXPERIMENTS
-    const int bid = (int)blockIdx.x - p.n_apply;   // (n_apply is a multiple of 8: the XCD of a tile workgroup is still bid % 8)
-#else
     const int bid = (int)blockIdx.x;
-#endif
     if (bid < p.nb_main && p.split0 == 1) {
       const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
       t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
@@ -89,21 +79,6 @@ conv_igemm_kernel(const ConvParams p) {
   const int mtot = p.Mh * p.Mw;
   const int wrap_w = p.wrap ? p.Win : 0;
   const bool wrapt = MODE == MODE_CONVT && p.wrap != 0;
-  // apply-ahead: source 0 is being normalised by the first workgroups of this launch; the tile needs input rows
-  // [ap_r0, ap_r1] of it (source 1, the skip, was normalised by an earlier launch).  Probe their counters now.
-#ifdef MSI_EXPERIMENTS
-  int ap_r0 = 0, ap_r1 = -1, ap_probe = 0;
-  if (p.n_apply > 0) {
-    const int m_lo = tile_m * BM, m_hi = min(m_lo + BM, mtot) - 1;
-    const int mh_lo = (int)udiv_magic((unsigned)m_lo, (unsigned)p.Mw, p.mg_mw), mh_hi = (int)udiv_magic((unsigned)m_hi, (unsigned)p.Mw, p.mg_mw);
-    if (MODE == MODE_CONV) { ap_r0 = mh_lo * p.stride - p.pad_t; ap_r1 = mh_hi * p.stride - p.pad_t + 2 * p.rate; }
-    else if (MODE == MODE_CONVT) { ap_r0 = mh_lo - 1; ap_r1 = wrapt ? mh_hi : mh_hi + 1; }
-    else { ap_r0 = mh_lo; ap_r1 = mh_hi; }
-    ap_r0 = max(ap_r0, 0);
-    ap_r1 = min(ap_r1, p.Hin - 1);
-    ap_probe = rows_probe(p, b, ap_r0, ap_r1, tid);
-  }
-#endif
 
   // ---- DMA lane mapping: instruction i of this wave fills LDS rows [wave*BM/4 + 8i, +8);
   // lane -> (row = lane>>3, 16-byte slot = lane&7); the slot holds data chunk slot ^ ((row>>1)&7).
@@ -262,10 +237,6 @@ _Pragma("unroll")                                                               
       }                                                                                                                          \
     }                                                                                                                            \
   }
-
-#ifdef MSI_EXPERIMENTS
-  if (p.n_apply > 0) rows_wait(p, b, ap_r0, ap_r1, ap_probe, tid, reinterpret_cast<int *>(smem));   // (LDS is still unused)
-#endif
 
   // fp32 head: the affine of its source's LayerNorm (scale | shift per channel) from the source's sums -> LDS; the
   // k-step issue applies it (+ ReLU) while loading, so the source is read RAW and never normalised in memory
@@ -516,7 +487,7 @@ conv_fixup_kernel(const ConvParams p) {
 
 template <int BM, int BN, int MODE, int BF16>
 int launch_conv_mode(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) {
-  return launch_kernel<conv_igemm_kernel<BM, BN, MODE, BF16>, NSTAGE * (BM + BN) * ROW_BYTES>(Q.nblocks + p.n_apply, p, stream, "conv_igemm");
+  return launch_kernel<conv_igemm_kernel<BM, BN, MODE, BF16>, NSTAGE * (BM + BN) * ROW_BYTES>(Q.nblocks, p, stream, "conv_igemm");
 }
 
 }  // namespace
@@ -537,14 +508,8 @@ int launch_igemm(const LayerLaunch &Q, const ConvParams &p, hipStream_t stream) 
     case vkey(CONV_IGEMM, 2, 2, MODE_CONV, 1): return launch_conv_mode<128, 128, MODE_CONV, 1>(Q, p, stream);
     case vkey(CONV_IGEMM, 2, 2, MODE_CONVT, 1): return launch_conv_mode<128, 128, MODE_CONVT, 1>(Q, p, stream);
     case vkey(CONV_IGEMM, 2, 2, MODE_HEAD, 1): return launch_conv_mode<128, 128, MODE_HEAD, 1>(Q, p, stream);
-#ifdef MSI_EXPERIMENTS   // the fp32 tile experiments (plan options F32_TILE, F32_TILE_MASK; the fp32 head uses the 64x64 tile)
-    case vkey(CONV_IGEMM, 2, 1, MODE_CONV, 0): return launch_conv_mode<128, 64, MODE_CONV, 0>(Q, p, stream);
-    case vkey(CONV_IGEMM, 2, 1, MODE_CONVT, 0): return launch_conv_mode<128, 64, MODE_CONVT, 0>(Q, p, stream);
-    case vkey(CONV_IGEMM, 1, 2, MODE_CONV, 0): return launch_conv_mode<64, 128, MODE_CONV, 0>(Q, p, stream);
-    case vkey(CONV_IGEMM, 1, 2, MODE_CONVT, 0): return launch_conv_mode<64, 128, MODE_CONVT, 0>(Q, p, stream);
-#endif
   }
-  return msi::fail(MSI_E_UNSUPPORTED, "conv: no conv_igemm_kernel<%d, %d, %d, %d> (fp32: the 64x64 tile; 128x64 and 64x128 are experiments, MSI_EXPERIMENTS)", V.bm, V.bn, V.mode, V.bf16);
+  return msi::fail(MSI_E_UNSUPPORTED, "conv: no conv_igemm_kernel<%d, %d, %d, %d> (fp32: the 64x64 tile only)", V.bm, V.bn, V.mode, V.bf16);
 }
 int launch_fixup(int bm, int bn, int mode, int raw16, unsigned gx, unsigned gy, const ConvParams &p, hipStream_t stream) {
   const dim3 grid(gx, gy), block(256);

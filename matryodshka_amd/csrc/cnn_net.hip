@@ -151,11 +151,7 @@ int build_net(const msi_net_desc *d, int num_cus, Net &net) {
     net.layers[i].sums_off = zoff;
     if (net.layers[i].kind != MODE_HEAD) zoff += (size_t)d->batch * LN_SHARDS * LN_WORDS * sizeof(long long);
   }
-  for (int i = 0; i < MSI_NET_NUM_LAYERS; ++i) {
-    net.layers[i].flags_off = zoff;
-    if (net.layers[i].kind != MODE_HEAD) zoff += (size_t)d->batch * net.layers[i].out_h * AP_FLAG_STRIDE * sizeof(int);
-  }
-  net.err_off = zoff;
+  net.err_off = zoff;   // (the sums are 1 KB per sample and layer: 256-byte aligned)
   zoff += 64;
   net.zero_bytes = zoff - net.zero_off;
   net.ws_bytes = round_up(zoff, 256);

@@ -26,7 +26,6 @@ struct Layer {
   size_t raw_off, aff_off;                // bytes inside the workspace
   size_t act_off;                         // bf16 path: normalised bf16 activation (the next layer's operand)
   size_t sums_off;                        // LayerNorm sums [B][LN_SHARDS][LN_WORDS] int64
-  size_t flags_off;                       // apply-ahead row counters of THIS layer's output [B][out_h] ints
 };
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -36,7 +35,7 @@ struct Net {
   size_t param_floats = 0, packed_floats = 0, ws_bytes = 0, partial_off = 0, partial_bytes = 0;
   size_t zero_off = 0, zero_bytes = 0;   // [tickets of the in-launch fix-up | LayerNorm sums]: one memset per forward
   size_t cnt_off = 0;   // arrival tickets: [layer][5 * num_cus] ints
-  size_t err_off = 0;   // one int: a tile workgroup gave up waiting for apply-ahead rows (stays 0)
+  size_t err_off = 0;   // one int: the plan's status word (STATUS_* bits), behind the LayerNorm sums
   // bf16 plans: the head's weights (rounded to bf16) once more as fp32 rows, for the fused tail (head_assemble_kernel
   // runs the 1x1 head on the fp32 MFMA: exact products of bf16 values, fp32 accumulate -- the bf16 head's arithmetic)
   size_t head_f32_off = 0;

@@ -96,12 +96,6 @@ int choose_variant(const msi_net_plan *pl, int li, int exclude, ConvVariant &v, 
   } else if (bf16 && L.cout % 64 == 0 && bigmode != 0 && ((tiles_big >= 4L * pl->num_cus && L.cin <= 128) || bigmode == 2)) {
     v.bm = 128; v.bn = 64;   // Cout = 64, short K (conv8_2: 495 vs 599 us; conv1_1 / conv8_1 are faster at 64x64)
   }
-  // fp32 tile experiments (per-layer mask in MSI_NET_OPT_F32_TILE_MASK): 128x64 (MT = 2) or 64x128 (NT = 2) instead of
-  // 64x64 on the layers whose bit is set -- more MFMA work per prologue / epilogue and per DMA byte
-  if (!bf16 && ((pl->opt[MSI_NET_OPT_F32_TILE_MASK] >> li) & 1) && L.kind != MODE_HEAD) {
-    if (pl->opt[MSI_NET_OPT_F32_TILE] == 1) { v.bm = 128; v.bn = 64; }
-    else if (pl->opt[MSI_NET_OPT_F32_TILE] == 2 && L.cout % 128 == 0) { v.bm = 64; v.bn = 128; }
-  }
   const bool tile64 = v.bm == 64 && v.bn == 64;   // (the fp32 halo-patch kernels replace the 64x64 tap kernel only)
   const bool halo_ok = !((pl->opt[MSI_NET_OPT_HALO_SKIP] >> li) & 1);
   // the six-product form (plan option F32_SPLIT3) of a halo-patch layer, its fp16 form (F32_SPLIT_F16), the 8-row tiles' bit and grid rule (X3_TILE8)
@@ -109,7 +103,7 @@ int choose_variant(const msi_net_plan *pl, int li, int exclude, ConvVariant &v, 
   const int planes = ((pl->opt[MSI_NET_OPT_F32_SPLIT_F16] >> li) & 1) ? 2 : 3;
   const bool tile8_bit = (pl->opt[MSI_NET_OPT_X3_TILE8] >> li) & 1, tile8_force = (pl->opt[MSI_NET_OPT_X3_TILE8] >> 30) & 1;
   // halo-patch kernel (conv_halo_kernel): stride-1 3x3 layers with one source, fp32, whole 4 x 16 tiles and 32-channel chunks
-  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 1) && !bf16 && !pl->opt[MSI_NET_OPT_APPLY_AHEAD] && tile64 &&
+  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 1) && !bf16 && tile64 &&
       L.kind == MODE_CONV && L.stride == 1 && L.src1 < 0 && L.in_h % 4 == 0 && L.in_w % 16 == 0 && L.c0 % 32 == 0 &&
       (L.rate == 1 || L.rate == 2)) {
     v.family = CONV_HALO; v.rate = L.rate;
@@ -129,7 +123,7 @@ int choose_variant(const msi_net_plan *pl, int li, int exclude, ConvVariant &v, 
   }
   // stride-2 halo kernel (conv_halo_s2_kernel; HALO bit 2): the stride-2 3x3 layers, fp32, one source, whole 4 x 16 tiles of the
   // OUTPUT grid, an even input (TF SAME then pads one row / column at the far side only) or wrap_pad(1, 1) + VALID
-  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 4) && !bf16 && !pl->opt[MSI_NET_OPT_APPLY_AHEAD] && tile64 &&
+  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 4) && !bf16 && tile64 &&
       L.kind == MODE_CONV && L.stride == 2 && L.rate == 1 && L.src1 < 0 && L.in_h % 2 == 0 && L.in_w % 2 == 0 &&
       L.out_h % 4 == 0 && L.out_w % 16 == 0 && L.c0 % 32 == 0 && p.pad_t == p.pad_l && (p.pad_t == 0 || p.pad_t == 1) &&
       // (measured at 640 x 320: conv1_2 / conv2_2 gain their producers' ln_apply launches, -22 / -11 us for +4 / +3 us of
@@ -149,14 +143,14 @@ int choose_variant(const msi_net_plan *pl, int li, int exclude, ConvVariant &v, 
   }
   // bf16 halo-patch kernel (conv_halo_bf16_kernel): the same layers with 64-channel chunks and whole
   // 8 x 16 pixel x 128 channel or 16 x 16 x 64 tiles
-  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 1) && bf16 && !pl->opt[MSI_NET_OPT_APPLY_AHEAD] && L.kind == MODE_CONV && L.stride == 1 && L.src1 < 0 && L.in_w % 16 == 0 &&
+  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 1) && bf16 && L.kind == MODE_CONV && L.stride == 1 && L.src1 < 0 && L.in_w % 16 == 0 &&
       L.c0 % 64 == 0 && bigmode != 0) {
     if (L.cout % 128 == 0 && L.in_h % 8 == 0 && (L.rate == 1 || L.rate == 2)) { v.family = CONV_HALO_BF16; v.bm = 128; v.bn = 128; v.rate = L.rate; v.waves = pl->opt[MSI_NET_OPT_BF16_WAVES] == 8 ? 8 : 4; }
     else if (L.cout == 64 && L.in_h % 16 == 0 && L.rate == 1) { v.family = CONV_HALO_BF16; v.bm = 256; v.bn = 64; v.rate = 1; v.waves = 4; }
     if (v.family == CONV_HALO_BF16) { p.halo_tx = L.in_w / 16; max_split = 1; }
   }
   // ... and its stride-2 form (conv_halo_bf16_s2_kernel; HALO bit 2): whole 8 x 16 x 128 tiles of the OUTPUT grid, an even input
-  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 4) && bf16 && !pl->opt[MSI_NET_OPT_APPLY_AHEAD] && L.kind == MODE_CONV && L.stride == 2 && L.rate == 1 &&
+  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 4) && bf16 && L.kind == MODE_CONV && L.stride == 2 && L.rate == 1 &&
       L.src1 < 0 && L.in_h % 2 == 0 && L.in_w % 2 == 0 && L.out_h % 8 == 0 && L.out_w % 16 == 0 && L.c0 % 64 == 0 && L.cout % 128 == 0 &&
       p.pad_t == p.pad_l && (p.pad_t == 0 || p.pad_t == 1) && bigmode != 0) {
     v.family = CONV_HALO_BF16_S2; v.bm = 128; v.bn = 128; v.waves = 4; p.halo_tx = L.out_w / 16; max_split = 1;
@@ -165,8 +159,7 @@ int choose_variant(const msi_net_plan *pl, int li, int exclude, ConvVariant &v, 
   // 4 x 16 input tiles and 32-channel chunks of both sources; one workgroup per output-row parity (enumerated as two "classes")
   if (!(exclude & NO_CONVT_HALO) &&
       halo_ok && ((pl->opt[MSI_NET_OPT_HALO] & 2) || (x3_on && pl->opt[MSI_NET_OPT_HALO] != 0)) && !bf16   // (HALO = 0: no halo-patch kernel at all)
-      && !pl->opt[MSI_NET_OPT_APPLY_AHEAD] &&
-      tile64 && L.kind == MODE_CONVT && ((!L.wrapt && L.in_h % 4 == 0 && L.in_w % 16 == 0) || (L.wrapt && x3_on)) &&
+      && tile64 && L.kind == MODE_CONVT && ((!L.wrapt && L.in_h % 4 == 0 && L.in_w % 16 == 0) || (L.wrapt && x3_on)) &&
       L.c0 % 32 == 0 && L.c1 % 32 == 0) {   // (wrapt: (H + 1) x (W + 5) GEMM rows per class in ragged 4 x 16 tiles -- the split form only)
     // (r04 kept msi_train_net's VALID transposes off the fp16 form: one wave's share of the layer's sum of squares came out low in ~0.1 % of
     // back-to-back forwards.  r05 found the instruction: a compiler-made `v_pk_mul_f32 d, a, b op_sel:[0,1] op_sel_hi:[1,0]` of the generic
@@ -184,7 +177,7 @@ int choose_variant(const msi_net_plan *pl, int li, int exclude, ConvVariant &v, 
   }
   // bf16 conv-transpose halo kernel (convt_halo_bf16_kernel): SAME conv-transposes, 64-channel chunks of both sources,
   // whole 8 x 16 x 128 or 16 x 16 x 64 tiles, one workgroup per output-row parity (enumerated as two "classes")
-  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 1) && bf16 && !pl->opt[MSI_NET_OPT_APPLY_AHEAD] && L.kind == MODE_CONVT && !L.wrapt &&
+  if (halo_ok && (pl->opt[MSI_NET_OPT_HALO] & 1) && bf16 && L.kind == MODE_CONVT && !L.wrapt &&
       L.in_w % 16 == 0 && L.c0 % 64 == 0 && L.c1 % 64 == 0 && bigmode != 0) {
     if (L.cout % 128 == 0 && L.in_h % 8 == 0) { v.family = CONVT_HALO_BF16; v.bm = 128; v.bn = 128; }
     else if (L.cout == 64 && L.in_h % 8 == 0) { v.family = CONVT_HALO_BF16; v.bm = 128; v.bn = 64; }   // (256 x 64 with two classes spills: 128 accumulator + 80 fragment registers)
@@ -248,20 +241,6 @@ int plan_layers(msi_net_plan *pl) {
       p.ln_inv_n = 1.0 / net.layers[L.src0].ln_count;
     }
     Q.skip_apply = fuse_head_ln && li == head_src;
-    // apply-ahead (see apply_ahead): this launch also normalises its source 0
-    if (pl->opt[MSI_NET_OPT_APPLY_AHEAD] && !bf16 && L.src0 >= 0 && L.kind != MODE_HEAD && L.c0 <= 512 && L.c0 % 4 == 0 &&   // (bf16: fp16 raw outputs, r03)
-        ((long)L.in_w * L.c0) % 4 == 0) {
-      constexpr int UNIT_VEC = 2048;   // float4 per unit: 32 KB of fp32
-      p.ap_row_vec = L.in_w * L.c0 / 4;
-      p.ap_unit_vec = UNIT_VEC;
-      p.ap_units_per_row = (p.ap_row_vec + UNIT_VEC - 1) / UNIT_VEC;
-      p.ap_inv_n = 1.0 / net.layers[L.src0].ln_count;
-      const long units = (long)desc->batch * L.in_h * p.ap_units_per_row;
-      long n = 2L * pl->num_cus;                      // two apply workgroups per CU keep ~8 MB of loads in flight
-      if (n > units) n = units;
-      p.n_apply = (int)((n + 7) / 8 * 8);
-      pl->launch[L.src0].skip_apply = 1;              // (the producer precedes its consumer in graph order)
-    }
     // The kernel, then its tiles.  A conv-transpose halo kernel keeps two slabs per K-range: where they do not fit the partial-accumulator workspace the layer
     // chooses again without that family -- the 8-row tile falls back to the 4-row tile, the 4-row tile to the tap kernel.
     for (int exclude = 0;;) {
@@ -335,10 +314,7 @@ int msi_net_plan_create(const msi_net_desc *desc, msi_net_plan **out) {
   pl->opt[MSI_NET_OPT_BIGTILE] = 1;
   pl->opt[MSI_NET_OPT_HEAD_FUSE_LN] = 1;
   pl->opt[MSI_NET_OPT_NUM_CUS] = pl->num_cus;
-  pl->opt[MSI_NET_OPT_APPLY_AHEAD] = 0;   // measured r02_h: correct and bit-identical, but 2.69 vs 2.56 ms per network
   pl->opt[MSI_NET_OPT_HALO] = 5;   // bits 0 and 2 (bit 1, the fp32 conv-transpose halo kernel: measured slower than the tap kernel + ln_apply, see the kernel)
-  pl->opt[MSI_NET_OPT_F32_TILE] = 0;
-  pl->opt[MSI_NET_OPT_F32_TILE_MASK] = 0;
   pl->opt[MSI_NET_OPT_UNIFORM_SPLIT] = 0;
   pl->opt[MSI_NET_OPT_SPLIT_OVERHEAD] = 0;
   pl->opt[MSI_NET_OPT_BF16_WAVES] = 8;
@@ -362,6 +338,11 @@ void msi_net_plan_destroy(msi_net_plan *plan) { delete plan; }
 int msi_net_plan_set_option(msi_net_plan *plan, int32_t option, int32_t value) {
   MSI_REQUIRE(plan, "net_plan_set_option: null plan");
   MSI_REQUIRE(option >= 0 && option < MSI_NET_OPT_COUNT, "net_plan_set_option: unknown option %d", option);
+  if (option == MSI_NET_OPT_F32_TILE || option == MSI_NET_OPT_F32_TILE_MASK || option == MSI_NET_OPT_APPLY_AHEAD) {   // retired keys: 0 is all they take
+    if (option == MSI_NET_OPT_F32_TILE) MSI_REQUIRE(value >= 0 && value <= 2, "net_plan_set_option: f32 tile %d", value);
+    if (value != 0) return msi::fail(MSI_E_UNSUPPORTED, "net_plan_set_option: option %d was an experiment (measured slower) whose code this library no longer has", option);
+    return MSI_OK;
+  }
   if (option == MSI_NET_OPT_NUM_CUS) {
     MSI_REQUIRE(value >= 8 && value <= 4096, "net_plan_set_option: num_cus %d out of range", value);
     plan->num_cus = value;
@@ -369,13 +350,7 @@ int msi_net_plan_set_option(msi_net_plan *plan, int32_t option, int32_t value) {
   if (option == MSI_NET_OPT_BIGTILE) MSI_REQUIRE(value >= 0 && value <= 2, "net_plan_set_option: bigtile %d", value);
   if (option == MSI_NET_OPT_HALO) MSI_REQUIRE(value >= 0 && value <= 7, "net_plan_set_option: halo %d (bit 0 conv, bit 1 conv-transpose, bit 2 stride-2 conv)", value);
   if (option == MSI_NET_OPT_TAILSPLIT) MSI_REQUIRE(value >= 0 && value <= 2, "net_plan_set_option: tailsplit %d", value);
-  if (option == MSI_NET_OPT_F32_TILE) MSI_REQUIRE(value >= 0 && value <= 2, "net_plan_set_option: f32 tile %d", value);
   if (option == MSI_NET_OPT_BF16_WAVES) MSI_REQUIRE(value == 4 || value == 8, "net_plan_set_option: bf16 waves %d (4 or 8)", value);
-#ifndef MSI_EXPERIMENTS
-  if ((option == MSI_NET_OPT_F32_TILE || option == MSI_NET_OPT_F32_TILE_MASK || option == MSI_NET_OPT_APPLY_AHEAD) && value != 0)
-    return msi::fail(MSI_E_UNSUPPORTED, "net_plan_set_option: option %d is an experiment this library was not built with "
-                     "(MSI_CNN_DEFINES=-DMSI_EXPERIMENTS python -m matryodshka_amd.build --force)", option);
-#endif
   const int old = plan->opt[option];
   plan->opt[option] = value;
   int rc = plan_layers(plan);
@@ -419,7 +394,7 @@ int32_t msi_net_plan_layer_kernel(const msi_net_plan *plan, int32_t layer, char 
     case CONVT_HALO_BF16: snprintf(name, name_bytes, "convt_halo_bf16_kernel<%d, %d, %d>", V.bm, V.bn, V.apply); break;
     default: return msi::fail(MSI_E_UNSUPPORTED, "net_plan_layer_kernel: unknown kernel family %d", V.family);
   }
-  if (nblocks) *nblocks = Q.nblocks + Q.p.n_apply;
+  if (nblocks) *nblocks = Q.nblocks;
   if (nsplit_tiles) *nsplit_tiles = Q.nfix;
   return MSI_OK;
 }

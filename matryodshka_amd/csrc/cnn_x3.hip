@@ -25,9 +25,6 @@ namespace {
                       // way: 92.5 vs 99.7 us); 2 / 3 force it (tuning)
 #define MSI_X3_NSTG 0
 #endif
-#ifndef MSI_X3_ABLATE   // timing experiments only (wrong results): 1 no weight DMA, 4 no per-tap barrier, 8 no fragment reads, 16 no MFMAs, 32 no patch swap
-#define MSI_X3_ABLATE 0
-#endif
 // NPL = 3: x = h + m + l in bf16, six products (F32_SPLIT3).  NPL = 2: x = h + m' 2^-11 in fp16, three products h.h + (h.m' + m'.h) 2^-11
 // (F32_SPLIT_F16: 22 significand bits per operand, operands limited to the fp16 RANGE -- the patch store flags |x| > 65504 in the status word)
 #ifndef MSI_X2_NSTG   // weight ring of the fp16 form (half the matrix work per tap: the DMA latency budget of a two-stage ring is one SHORT tap)
@@ -143,7 +140,6 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   int c = c0, cpar = 0;   // chunk of the k-loop and (two-stage ring) its stage parity: captured by the k-step lambdas below
   (void)cpar;
   auto b_issue = [&](const int c, const int tap, const int st) __attribute__((always_inline)) {
-    if (MSI_X3_ABLATE & 1) return;
     char *sB_ = smem + G::A_BYTES + st * G::B_STAGE + wave * 16 * G::B_ROW;
     const int soff_ = (tap * CH + c) * NPL * plane_bytes;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void *)sB_, 16, b_voff, soff_, 0, 0);
@@ -324,7 +320,6 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
       split_mfma<3>(acc[1][0], acc_lo, xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
-    if (!(MSI_X3_ABLATE & 8))
 #pragma unroll
       for (int s_ = 0; s_ < 2; ++s_) {
       ah_[s_] = s_ == 0 ? lds_read128<AOFF_>(a_base) : lds_read128<AOFF_ + 32>(a_base);
@@ -339,14 +334,12 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
       for (int s_ = 0; s_ < 2; ++s_) {
       if (s_ == 0) wait_lgkm6<6>(ah_[0], bh_[0], am_[0], bm_[0], al_[0], bl_[0]);
       else wait_lgkm6<0>(ah_[1], bh_[1], am_[1], bm_[1], al_[1], bl_[1]);
-      if (!(MSI_X3_ABLATE & 16)) {
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm_[s_]), __builtin_bit_cast(bf16x8, am_[s_]), acc[0][0], 0, 0, 0);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh_[s_]), __builtin_bit_cast(bf16x8, al_[s_]), acc[0][0], 0, 0, 0);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bl_[s_]), __builtin_bit_cast(bf16x8, ah_[s_]), acc[0][0], 0, 0, 0);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh_[s_]), __builtin_bit_cast(bf16x8, am_[s_]), acc[0][0], 0, 0, 0);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm_[s_]), __builtin_bit_cast(bf16x8, ah_[s_]), acc[0][0], 0, 0, 0);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh_[s_]), __builtin_bit_cast(bf16x8, ah_[s_]), acc[0][0], 0, 0, 0);
-      }
       __builtin_amdgcn_sched_barrier(0);
       if (s_ == 0) {
         if (TAP == 0 && c + 1 < c1) patch_load(c + 1);
@@ -367,7 +360,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
       else if (issued_) wait_vmcnt<NPL>();
       else wait_vmcnt<0>();
     }
-    if (!(MSI_X3_ABLATE & 4)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
   };
 
   // ---- prologue: first patch, first two weight k-steps ----
@@ -391,7 +384,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   for (; c < c1; ++c) {
     cpar = (c - c0) & 1;   // (two-stage ring: nine k-steps per chunk flip the stage parity)
     htap(IC<0>{}); htap(IC<1>{}); htap(IC<2>{}); htap(IC<3>{}); htap(IC<4>{}); htap(IC<5>{}); htap(IC<6>{}); htap(IC<7>{}); htap(IC<8>{});
-    if (c + 1 < c1 && !(MSI_X3_ABLATE & 32)) {   // every wave has read the last tap of this chunk (closing barrier of tap 8): swap the patch
+    if (c + 1 < c1) {   // every wave has read the last tap of this chunk (closing barrier of tap 8): swap the patch
       patch_store();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -545,9 +538,6 @@ struct HaloGeomS2X3 {
 
 #ifndef MSI_S2X_WAVES
 #define MSI_S2X_WAVES 3
-#ifndef MSI_S2X3_ABLATE   // timing experiments only (wrong results): 1 no weight DMA, 4 no per-k-step barrier, 8 no fragment reads, 16 no MFMAs, 32 no patch swap, 64 no patch loads
-#define MSI_S2X3_ABLATE 0
-#endif
 #endif
 // TH = 8 (r05, conv_halo8_s2_x3_kernel, six-product form): 8 x 16 output pixels per workgroup -- a wave owns four output rows = TWO 32-pixel blocks that share the weight fragments;
 // the four unit patches are 9 x 17 pixels and serve twice the outputs per swap; 58.0 KB of LDS: two workgroups per CU.  Grid rule as for the other 8-row tiles.
@@ -601,7 +591,6 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
   const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wpk_x3, 0, (int)((size_t)S * NP * plane_bytes), 0x00020000);
   const unsigned b_voff = (unsigned)((tile_n * 64 + wave * 16 + (lane >> 2)) * G::B_ROW + (lane & 3) * 16);
   auto b_issue = [&](const int c, const int tap, const int st) __attribute__((always_inline)) {
-    if (MSI_S2X3_ABLATE & 1) return;
     char *sB_ = smem + G::A_BYTES + st * G::B_STAGE + wave * 16 * G::B_ROW;
     const int soff_ = (tap * CH + c) * NP * plane_bytes;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void *)sB_, 16, b_voff, soff_, 0, 0);
@@ -659,7 +648,6 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
   // patch of (group c, unit U) -> registers (+ gamma / beta of the lane's channels with unit 0)
   auto patch_load = [&](const int c, auto U_c) __attribute__((always_inline)) {
     constexpr int U = decltype(U_c)::value;
-    if (MSI_S2X3_ABLATE & 64) return;
 #pragma unroll
     for (int k_ = 0; k_ < NLOAD; ++k_)
       araw[k_] = __builtin_bit_cast(v4f, (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(rsrc_a, voff[U][k_], c * ROW_BYTES, 0));
@@ -749,7 +737,6 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
       split_mfma<3>(acc[1][0], acc_lo, xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
-    if (!(MSI_S2X3_ABLATE & 8))
 #pragma unroll
     for (int s_ = 0; s_ < 2; ++s_) {
       ah_[s_] = s_ == 0 ? lds_read128<AOFF_>(a_base) : lds_read128<AOFF_ + 32>(a_base);
@@ -770,7 +757,7 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
         if (s_ == 0) wait_lgkm4<4>(ah_[0], bh_[0], am_[0], bm_[0]);
         else wait_lgkm4<0>(ah_[1], bh_[1], am_[1], bm_[1]);
       }
-      if (!(MSI_S2X3_ABLATE & 16)) split_mfma<NP>(acc[0][0], acc_lo, ah_[s_], am_[s_], al_[s_], bh_[s_], bm_[s_], bl_[s_]);
+      split_mfma<NP>(acc[0][0], acc_lo, ah_[s_], am_[s_], al_[s_], bh_[s_], bm_[s_], bl_[s_]);
       __builtin_amdgcn_sched_barrier(0);
       if (s_ == 0) {
         if (FIRST_ && more_) {
@@ -795,8 +782,8 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
       else if (issued_) wait_vmcnt<NP>();
       else wait_vmcnt<0>();
     }
-    if (!(MSI_S2X3_ABLATE & 4)) __builtin_amdgcn_s_barrier();
-    if (LAST_ && more_ && !(MSI_S2X3_ABLATE & 32)) {   /* every wave has read this unit's last tap: swap the patch */
+    __builtin_amdgcn_s_barrier();
+    if (LAST_ && more_) {   /* every wave has read this unit's last tap: swap the patch */
       patch_store(IC<(U_ + 1) & 3>{});
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -886,9 +873,6 @@ struct HaloGeomCT3 : HaloGeomX3<1, NS, NPL, TH> {
 #ifndef MSI_CT_MAXW
 #define MSI_CT_MAXW 8
 #endif
-#ifndef MSI_CT3_ABLATE   // timing experiments only (wrong results): bits as MSI_S2X3_ABLATE
-#define MSI_CT3_ABLATE 0
-#endif
 #ifndef MSI_CT3_NSTG   // weight ring of the six-product conv-transpose kernel: 2 (r05: 48.4 KB of LDS, three workgroups per CU; eight k-steps per chunk, so the
 #define MSI_CT3_NSTG 2 // stage of k-step J is the literal J & 1 and the DMA of k-step J + 1 goes out at the head of k-step J) or 3 (r04: 60.7 KB, two per CU)
 #endif
@@ -948,7 +932,6 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
   const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wpk_x3, 0, (int)((size_t)4 * S * NP * plane_bytes), 0x00020000);
   const unsigned b_voff = (unsigned)((tile_n * 64 + wave * 16 + (lane >> 2)) * G::B_ROW + (lane & 3) * 16);
   auto b_issue = [&](const int cls, const int tap, const int c, const int st) __attribute__((always_inline)) {
-    if (MSI_CT3_ABLATE & 1) return;
     char *sB_ = smem + G::A_BYTES + st * G::B_STAGE + wave * 16 * G::B_ROW;
     const int soff_ = (cls * S + tap * CH + c) * NP * plane_bytes;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_void *)sB_, 16, b_voff, soff_, 0, 0);
@@ -996,7 +979,6 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
   int src_ld = 0;                                         // source of the patch held in araw
   // patch of chunk c -> registers (+ gamma / beta of the lane's channels when that source is raw)
   auto patch_load = [&](const int c) __attribute__((always_inline)) {
-    if (MSI_CT3_ABLATE & 64) return;
     const int s_ = c >= p.cpt0 ? 1 : 0, cc_ = s_ ? c - p.cpt0 : c;
     const unsigned cb_ = (unsigned)((s_ ? p.C1 : p.C0) * 4);
     src_ld = s_;
@@ -1107,7 +1089,6 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
       split_mfma<3>(acc[PWC_][1][0], acc_lo[PWC_], xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
-    if (!(MSI_CT3_ABLATE & 8))
 #pragma unroll
     for (int s_ = 0; s_ < 2; ++s_) {
       ah_[s_] = s_ == 0 ? lds_read128<COFF_>(ab_) : lds_read128<COFF_ + 32>(ab_);
@@ -1128,7 +1109,7 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
         if (s_ == 0) wait_lgkm4<4>(ah_[0], bh_[0], am_[0], bm_[0]);
         else wait_lgkm4<0>(ah_[1], bh_[1], am_[1], bm_[1]);
       }
-      if (!(MSI_CT3_ABLATE & 16)) split_mfma<NP>(acc[PWC_][0][0], acc_lo[PWC_], ah_[s_], am_[s_], al_[s_], bh_[s_], bm_[s_], bl_[s_]);
+      split_mfma<NP>(acc[PWC_][0][0], acc_lo[PWC_], ah_[s_], am_[s_], al_[s_], bh_[s_], bm_[s_], bl_[s_]);
       __builtin_amdgcn_sched_barrier(0);
       if (s_ == 0) {
         if (J == 0 && c + 1 < c1) patch_load(c + 1);
@@ -1147,7 +1128,7 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
     } else if (J == 0 && c + 1 < c1) wait_vmcnt<NP + NPLD>();
     else if (issued_) wait_vmcnt<NP>();
     else wait_vmcnt<0>();
-    if (!(MSI_CT3_ABLATE & 4)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     st = st + 1 == NSTG ? 0 : st + 1;
   };
 
@@ -1174,7 +1155,7 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
   __builtin_amdgcn_s_barrier();
   for (; c < c1; ++c) {
     ctstep(IC<0>{}); ctstep(IC<1>{}); ctstep(IC<2>{}); ctstep(IC<3>{}); ctstep(IC<4>{}); ctstep(IC<5>{}); ctstep(IC<6>{}); ctstep(IC<7>{});
-    if (c + 1 < c1 && !(MSI_CT3_ABLATE & 32)) {
+    if (c + 1 < c1) {
       patch_store();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();

@@ -137,27 +137,14 @@ render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt
     const float v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
 #endif
 
-#ifdef MSI_RENDER_ABLATE_MATH   // timing experiment only (wrong pixels): identity warp, no per-layer angle math
-    const TapsR tp4 = make_taps_ranged((float)j + 0.3f + 0.001f * radius, (float)i + 0.3f, width, height);
-    (void)u; (void)v;
-#else
     const TapsR tp4 = make_taps_ranged(u, v, width, height);
-#endif
     // one descriptor per layer (scalar work): 32-bit texel offsets also for stacks beyond 2 GiB
     const __amdgpu_buffer_rsrc_t L = __builtin_amdgcn_make_buffer_rsrc((void *)(rgba + ((size_t)b * nd + d) * hw), 0, layer_bytes, 0x00020000);
     typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
     const float4 A = __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, tp4.oa << 4, 0, 0));
-#if defined(MSI_RENDER_ABLATE_TAPS) && MSI_RENDER_ABLATE_TAPS == 3   // timing experiments only (wrong pixels): one / two of the four corner loads
-    const float4 Bv = A, C = A, Dv = A;
-#elif defined(MSI_RENDER_ABLATE_TAPS)
-    const float4 Bv = A;
-    const float4 C = __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, tp4.oc << 4, 0, 0));
-    const float4 Dv = C;
-#else
     const float4 Bv = __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, tp4.ob << 4, 0, 0));
     const float4 C = __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, tp4.oc << 4, 0, 0));
     const float4 Dv = __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, tp4.od << 4, 0, 0));
-#endif
     const float al = blend4(tp4, A.w, Bv.w, C.w, Dv.w);
     if (MODE & RENDER_LAYERS) {
       float4 o;

@@ -154,32 +154,7 @@ __device__ __forceinline__ float t_div(float a, float b) {
 #endif
 }
 
-__device__ __forceinline__ float t_atan2(float y, float x) {
-#if MSI_FAST_TAIL
-  const float ax = fabsf(x), ay = fabsf(y);
-  const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-  float a = mn * __builtin_amdgcn_rcpf(mx);
-  a = (mx == 0.0f) ? 0.0f : a;                                // atan2(+-0, +-0) = +-0 / +-pi like libm
-  const float s = a * a;
-  float p = -0.0040545277297496796f;
-  p = __builtin_fmaf(p, s, 0.021862812340259552f);
-  p = __builtin_fmaf(p, s, -0.05591211095452309f);
-  p = __builtin_fmaf(p, s, 0.09642180800437927f);
-  p = __builtin_fmaf(p, s, -0.13908623158931732f);
-  p = __builtin_fmaf(p, s, 0.19946564733982086f);
-  p = __builtin_fmaf(p, s, -0.33329859375953674f);
-  p = __builtin_fmaf(p, s, 0.9999993443489075f);
-  float r = p * a;
-  r = (ay > ax) ? 1.57079632679489662f - r : r;
-  r = (x < 0.0f || (x == 0.0f && __builtin_signbitf(x))) ? 3.14159265358979324f - r : r;
-  r = (mx != mx || mn != mn) ? __builtin_nanf("") : r;        // NaN in -> NaN out (the callers test for it)
-  return __builtin_copysignf(r, y);
-#else
-  return atan2f(y, x);
-#endif
-}
-
-// atan on [-1, 1] (the polynomial of t_atan2 without its range reduction) and the two angles of a point (x, y, z) with
+// atan on [-1, 1] (an odd polynomial of degree 15, 1.3e-7 rad) and the two angles of a point (x, y, z) with
 // horizontal distance h = sqrt(x^2 + z^2) and norm R through half-angle forms, tan(a / 2) = sin a / (1 + cos a):
 //   atan2(y, h) = 2 atan(y / (h + R))                       (|phi| <= pi/2: the argument is in [-1, 1] as it is)
 //   atan2(z, x) = 2 atan(z / (h + x))            for x >= 0,
@@ -206,10 +181,7 @@ __device__ __forceinline__ float t_atan_unit(float a) {
 }
 
 __device__ __forceinline__ void t_angles(float x, float y, float z, float R, float &theta_neg, float &phi) {
-#if defined(MSI_RENDER_OLD_ANGLES)   // (A/B: the r03 form, two range-reduced atan2)
-  theta_neg = -t_atan2(z, x);
-  phi = t_atan2(y, t_sqrt(x * x + z * z));
-#elif MSI_FAST_TAIL
+#if MSI_FAST_TAIL
   const float h = __builtin_amdgcn_sqrtf(x * x + z * z);
   const float den = fmaxf(h + fabsf(x), 1.17549435e-38f);               // (x = z = 0: 0 / tiny = 0)
   const float a2 = 2.0f * t_atan_unit(z * __builtin_amdgcn_rcpf(den));
@@ -286,14 +258,14 @@ __device__ __forceinline__ void ods_tail(const OdsQuad &q, float order, const Pi
   const float dzf = q.zlx ? -dz : -dx;
   dx = dxf;
   dz = dzf;
-#if MSI_FAST_TAIL && !defined(MSI_SWEEP_OLD_ANGLES)
-  // (r04: the render kernel's half-angle forms -- one square root more, two range reductions less; where disc < 0 everything
+#if MSI_FAST_TAIL
+  // (r04: the render kernel's half-angle forms -- one square root more, two range reductions less than two atan2; where disc < 0 everything
   // here is NaN or garbage and the override below applies, as before)
   float theta, phi;
   t_angles(dx, q.y, dz, t_sqrt((dx * dx + dz * dz) + q.y * q.y), theta, phi);
 #else
-  const float theta = -t_atan2(dz, dx);
-  float phi = t_atan2(q.y, t_sqrt(dx * dx + dz * dz));
+  const float theta = -atan2f(dz, dx);
+  float phi = atan2f(q.y, t_sqrt(dx * dx + dz * dz));
 #endif
   if (phi != phi) phi = 1.0f;
   phi = (phi <= K.half_pi) ? phi : K.half_pi;
@@ -332,15 +304,9 @@ __device__ __forceinline__ float blend4(const TapsB &t, float a, float b, float 
 }
 __device__ __forceinline__ void gather3(__amdgpu_buffer_rsrc_t img, const TapsB &t, float *out) {
   const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oa, 0, 0));
-#ifdef MSI_SWEEP_ABLATE_TAPS   // timing experiment only (wrong volume): two of the four corner loads
-  const f32x3_g b = a;
-  const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oc, 0, 0));
-  const f32x3_g d = c;
-#else
   const f32x3_g b = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.ob, 0, 0));
   const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oc, 0, 0));
   const f32x3_g d = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.od, 0, 0));
-#endif
   out[0] = blend4(t, a.x, b.x, c.x, d.x);
   out[1] = blend4(t, a.y, b.y, c.y, d.y);
   out[2] = blend4(t, a.z, b.z, c.z, d.z);
@@ -349,17 +315,13 @@ __device__ __forceinline__ void gather3(__amdgpu_buffer_rsrc_t img, const TapsB 
 // ---- sweep, layers (pack / unpack / hres) and planar: the 16-byte store of every streaming kernel; its host side is beyond_infinity_cache below.
 // The 16-byte pieces of a wave's whole-pixel strip.  nt != 0 (block-uniform; the host sets it when the volume is larger than the 256-MB Infinity Cache): non-temporal
 // stores -- a volume that cannot stay cached until conv1_1 reads it should not evict what can (r06, same-box A/B at configs[2]: sweep 1.07 -> 0.98 ms per 16 frames;
-// configs[3] -1 %; at batch 1 the 157-MB volume stays cached and keeps plain stores).  -DMSI_SWEEP_ABLATE_STORE: timing experiment only (no stores at all).
+// configs[3] -1 %; at batch 1 the 157-MB volume stays cached and keeps plain stores).
 __device__ __forceinline__ void sweep_store16(uint4 *dst, const uint4 &v, int nt) {
-#ifdef MSI_SWEEP_ABLATE_STORE
-  if (nt < 0) *dst = v;
-#else
   if (nt) {
     __builtin_nontemporal_store(v.x, &dst->x); __builtin_nontemporal_store(v.y, &dst->y); __builtin_nontemporal_store(v.z, &dst->z); __builtin_nontemporal_store(v.w, &dst->w);
   } else {
     *dst = v;
   }
-#endif
 }
 
 // ---- render (render_views_packed_kernel) and layers (unpack_layers_kernel): ONE decode rule, so a render from a packed stack is bit-identical to

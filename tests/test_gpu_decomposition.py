@@ -26,8 +26,7 @@ each on a workspace poisoned with NaN bytes (tests.util.poison_workspace):
 NUM_CUS only steers the host-side decomposition (how many workgroups, which tiles are cut, how large the slab and ticket
 regions are); no kernel assumes that its workgroups are co-resident.  The split-K hand-off never waits: a workgroup stores
 its slab, takes a ticket with one atomic add and returns unless it is the last arriver, which sums the slabs (cnn_x3.hip /
-cnn_halo.hip / cnn_igemm.hip: `if (*s_old != nsp - 1) return;`).  The only spin loop in the library is the apply-ahead wait
-of cnn_device.h, which a plan can only enable in a build with MSI_EXPERIMENTS.  So CU counts below and above the device's
+cnn_halo.hip / cnn_igemm.hip: `if (*s_old != nsp - 1) return;`).  No kernel of the library has a spin loop.  So CU counts below and above the device's
 (up to 320 here; a 304-CU part's decomposition is one of the cases) cannot hang, and slabs / tickets are sized from the
 same NUM_CUS the decomposition uses.
 

@@ -85,7 +85,7 @@ def poison_workspace(m, b, h, w, cin, nout, ngf):
 
     The whole workspace is poisoned: nothing in it is written once and kept.  Its regions are (cnn_net.hip: build_net) the
     layers' raw outputs / published affines / bf16 activation copies, the K-range slabs, and the zero region (arrival
-    tickets, LayerNorm sums, apply-ahead flags, status word) -- the first three are written by the forward that reads
+    tickets, LayerNorm sums, status word) -- the first three are written by the forward that reads
     them, the last is cleared by every forward's first launch.  What IS written once outside the forward (packed weights,
     LayerNorm windows, msi_net_plan_calibrate's result) lives in the packed blob, which this does not touch."""
     _, _, ws = m._net(b, h, w, cin, nout, ngf)

@@ -8,7 +8,9 @@ the bytes of msi_net_plan_layer_params (the planned kernel argument, then inlaun
 tests/test_plan_decomposition.py, which imports the digest functions below); the weight digests are those of tests/test_native_abi.py.
 
   python tools/plan_golden.py            recompute everything and compare with the file (exit 1 on a difference)
-  python tools/plan_golden.py --record   write the file -- from the commit BEFORE a planner change, never from the changed planner"""
+  python tools/plan_golden.py --record   write the file -- from the commit BEFORE a planner change, never from the changed planner
+A change of the argument record's SIZE (members added to or removed from ConvParams) moves every plan digest: it is re-recorded from the changed tree only
+after a byte-for-byte comparison of every layer record of every plan above against the parent's -- names, workgroups, tiles cut, the common part of the bytes."""
 import hashlib
 import json
 import os
