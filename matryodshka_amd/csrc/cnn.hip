@@ -45,6 +45,8 @@
 // Tiling: 256 threads = 4 wavefronts (2x2), wave tile (BM/2)x(BN/2) of 32x32 MFMA tiles, BK=32;
 // work decomposition ("tail split": the tiles of the partial last wave are cut along K inside the launch, the
 // last arriving workgroup of a tile sums the partial accumulators) and the measured alternatives: DESIGN.md 4.
+// The decomposition (tile_work, tile_index), the hand-off (splitk_arrive, splitk_sum), the LayerNorm affine a consumer applies while staging
+// (ln_affine_read, ln_scale_shift) and the timing stamps (ConvStamps) are in cnn_device.h; a kernel that spells one of them out says why at the place.
 #include "cnn_plan.h"
 
 namespace msi_cnn {

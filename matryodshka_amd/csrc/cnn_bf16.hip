@@ -35,9 +35,8 @@ template <int BM, int BN, int RATE, int APPLY, int NW>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 2)))
 conv_halo_bf16_kernel(const ConvParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#ifdef MSI_CONV_TIMING
-  const unsigned long long ts0 = __builtin_amdgcn_s_memtime(), ts0r = __builtin_amdgcn_s_memrealtime();   // (ts0r: the constant 100 MHz counter, tools/clock_probe.sh)
-#endif
+  ConvStamps stamps;
+  stamps.begin();
   typedef HaloGeomB<BM, BN, RATE> G;
   constexpr int NTHR = 64 * NW, WR = NW / 2;                   // NW = 4 or 8 waves in WR x 2: a wave owns 32 MT x 32 NT of the tile
   constexpr int R = RATE, PW = G::PW, NPX = G::NPX, NLOAD = (NPX * 8 + NTHR - 1) / NTHR, MT = BM / (32 * WR), NT = BN / 64;
@@ -50,21 +49,9 @@ conv_halo_bf16_kernel(const ConvParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int CH = p.cpt0;                                  // 64-channel chunks of the input
-  int t;
-  {   // XCD x works through the x-th eighth of the tiles (M tiles fastest: neighbours share halo rows and weights in its L2)
-    const int bid = blockIdx.x;
-    const int q = p.ntiles >> 3, r = p.ntiles & 7, xcd = bid & 7, local = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  }
-  int tile_m, tile_n, b;
-  {
-    int r = t;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  // XCD x works through the x-th eighth of the tiles (M tiles fastest: neighbours share halo rows and weights in its L2)
+  const TileIndex ti = tile_index(p, xcd_contiguous(blockIdx.x, p.ntiles));
+  const int tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   // (requested here, used after the index arithmetic and the patch requests: the lane's shard of the source's LayerNorm sums, and
   // the layer's own window exponent for the epilogue -- neither round trip is then waited for where it is needed)
   LnShard shard = {0, 0};
@@ -251,10 +238,9 @@ conv_halo_bf16_kernel(const ConvParams p) {
     const float g0 = p.ln_gamma[ch0], b0 = p.ln_beta[ch0], g1 = p.ln_gamma[ch1], b1 = p.ln_beta[ch1];
     ln_mean_inv_pre(shard, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
     MSI_STAMP(8)
-    const double mu = s_stat[0];
-    const float inv_f = (float)s_stat[1], mu_hi = (float)mu, mu_lo = (float)(mu - (double)mu_hi);
     const float up_f = (float)(p.ln_scl_src[2] * 16777216.0);   // 2^e of the source layer's window
-    __syncthreads();
+    const LnAffine a = ln_affine_read(s_stat);
+    const float inv_f = a.inv, mu_hi = a.mu_hi, mu_lo = a.mu_lo;
     if (tid < C) {
       const float su = inv_f * g0;
       s_tab[C + tid] = __builtin_fmaf(-mu_lo, su, __builtin_fmaf(-mu_hi, su, b0));
@@ -273,9 +259,7 @@ conv_halo_bf16_kernel(const ConvParams p) {
   patch_store();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-#ifdef MSI_CONV_TIMING
-  const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
-#endif
+  stamps.loop();
   for (; c < c1; ++c) {
     htap(IC<0>{}); htap(IC<1>{}); htap(IC<2>{}); htap(IC<3>{}); htap(IC<4>{}); htap(IC<5>{}); htap(IC<6>{}); htap(IC<7>{}); htap(IC<8>{});
     if (c + 1 < c1) {
@@ -284,18 +268,9 @@ conv_halo_bf16_kernel(const ConvParams p) {
       __builtin_amdgcn_s_barrier();
     }
   }
-#ifdef MSI_CONV_TIMING
-  const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-#endif
+  stamps.tail();
   emit_tile<BM, BN, MODE_CONV, 1, WR>(p, acc, tile_m, tile_n, 0, b, tid, smem, raw_mul_pre);   // (the k-loop ended with a barrier: LDS is free)
-#ifdef MSI_CONV_TIMING
-  if (p.dbg && tid == 0) {
-    unsigned long long *o = p.dbg + (size_t)blockIdx.x * 24;
-    o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = __builtin_amdgcn_s_memtime(); o[22] = ts0r; o[23] = __builtin_amdgcn_s_memrealtime();
-    o[4] = __builtin_amdgcn_s_getreg(4 | (31 << 11));
-    o[5] = __builtin_amdgcn_s_getreg(20 | (31 << 11));
-  }
-#endif
+  stamps.write(p, tid);
 #endif
 }
 
@@ -334,21 +309,9 @@ conv_halo_bf16_s2_kernel(const ConvParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int CH = p.cpt0;                                  // 64-channel chunks of the input
-  int t;
-  {   // XCD x works through the x-th eighth of the tiles (M tiles fastest: neighbours share halo rows and weights in its L2)
-    const int bid = blockIdx.x;
-    const int q = p.ntiles >> 3, r = p.ntiles & 7, xcd = bid & 7, local = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  }
-  int tile_m, tile_n, b;
-  {
-    int r = t;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  // XCD x works through the x-th eighth of the tiles (M tiles fastest: neighbours share halo rows and weights in its L2)
+  const TileIndex ti = tile_index(p, xcd_contiguous(blockIdx.x, p.ntiles));
+  const int tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   const float raw_mul_pre = (float)(p.ln_scl[0] * (1.0 / 16777216.0));   // 2^-e (scalar load)
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
   const int oh0 = tyi * G::TH, ow0 = (tile_m - tyi * p.halo_tx) * 16;
@@ -537,10 +500,9 @@ conv_halo_bf16_s2_kernel(const ConvParams p) {
     const int ch0 = tid < C ? tid : 0, ch1 = tid + NTHR < C ? tid + NTHR : 0;
     const float g0 = p.ln_gamma[ch0], b0 = p.ln_beta[ch0], g1 = p.ln_gamma[ch1], b1 = p.ln_beta[ch1];
     ln_mean_inv(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-    const double mu = s_stat[0];
-    const float inv_f = (float)s_stat[1], mu_hi = (float)mu, mu_lo = (float)(mu - (double)mu_hi);
     const float up_f = (float)(p.ln_scl_src[2] * 16777216.0);   // 2^e of the source layer's window
-    __syncthreads();
+    const LnAffine a = ln_affine_read(s_stat);
+    const float inv_f = a.inv, mu_hi = a.mu_hi, mu_lo = a.mu_lo;
     if (tid < C) {
       const float su = inv_f * g0;
       s_tab[C + tid] = __builtin_fmaf(-mu_lo, su, __builtin_fmaf(-mu_hi, su, b0));
@@ -583,6 +545,7 @@ template <int BM, int BN, int APPLY>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 convt_halo_bf16_kernel(const ConvParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  // (ConvStamps' statements, spelled out here and below: with the struct the -DMSI_CONV_TIMING build of this kernel assigns other scalar registers)
 #ifdef MSI_CONV_TIMING
   const unsigned long long ts0 = __builtin_amdgcn_s_memtime(), ts0r = __builtin_amdgcn_s_memrealtime();   // (ts0r: the constant 100 MHz counter, tools/clock_probe.sh)
 #endif
@@ -595,22 +558,8 @@ convt_halo_bf16_kernel(const ConvParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int CH = p.cpt0 + p.cpt1;                         // 64-channel chunks of both sources
-  int t;
-  {
-    const int bid = blockIdx.x;
-    const int q = p.ntiles >> 3, r = p.ntiles & 7, xcd = bid & 7, local = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-  }
-  int ph, tile_m, tile_n, b;
-  {   // row parity fastest (p.nclass = 2 here), then M tiles, N tiles, samples
-    int r = t;
-    ph = r & 1; r >>= 1;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  const TileIndex ti = tile_index<TILE_ROW_PARITY>(p, xcd_contiguous(blockIdx.x, p.ntiles));   // row parity fastest (p.nclass = 2 here), then M tiles, N tiles, samples
+  const int ph = ti.cls, tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
   const int oh0 = tyi * G::TH, ow0 = (tile_m - tyi * p.halo_tx) * 16;
   const int H = p.Hin, W = p.Win;
@@ -806,14 +755,14 @@ convt_halo_bf16_kernel(const ConvParams p) {
     double *s_stat = reinterpret_cast<double *>(smem);
     if (p.halo_apply & 1) {
       ln_mean_inv(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-      const double mu = s_stat[0];
+      const double mu = s_stat[0];   // (ln_affine_read, spelled out: through it the APPLY instantiation assigns other registers)
       inv0 = (float)s_stat[1]; mh0 = (float)mu; ml0 = (float)(mu - (double)mh0);
       up0 = (float)(p.ln_scl_src[2] * 16777216.0);
       __syncthreads();
     }
     if (p.halo_apply & 2) {
       ln_mean_inv(p.ln_sums1 + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n1, p.ln_scl_src1, p.status, s_stat, tid);
-      const double mu = s_stat[0];
+      const double mu = s_stat[0];   // (ln_affine_read, spelled out: through it the APPLY instantiation assigns other registers)
       inv1 = (float)s_stat[1]; mh1 = (float)mu; ml1 = (float)(mu - (double)mh1);
       up1 = (float)(p.ln_scl_src1[2] * 16777216.0);
       __syncthreads();

@@ -9,6 +9,15 @@
 //   cnn_tail.hip   fused tail (head + RGBA assembly; its body is cnn_tail_head_assemble.inc, shared by the fp32 and the packed kernels), LayerNorm finish / apply, zero
 // Here: constants, ConvParams, the per-layer launch record (namespace msi_cnn: shared TYPES need one identity across translation units), the device helpers
 // of the k-loops and the epilogue (anonymous namespace: every unit inlines its own), and the launch entry points each family exports.
+// Shared pieces of the kernel bodies (device side, each exists once):
+//   tile_work / xcd_contiguous   blockIdx.x -> tile, K-range, slot: the tail split and the XCD-contiguous tile order
+//   tile_index                   tile -> [class | row parity,] M tile, N tile, sample
+//   splitk_arrive / splitk_sum   the in-launch hand-off of a split tile's K-range partial sums (dump_acc, sum_slabs: the slab layout)
+//   ln_mean_inv, ln_affine_read, ln_scale_shift   a producer's LayerNorm statistics -> the affine a consumer applies while staging its patch
+//   ConvStamps                   the -DMSI_CONV_TIMING phase stamps tools/conv_timing.py reads
+//   emit_tile, load_coord_bias   the epilogue of a finished tile
+// Where a kernel still spells one of these out, a comment at the place says which and why: the rewrite had to leave every kernel's instruction stream as it
+// was, in the default build and in the -DMSI_CONV_TIMING, -DMSI_NSTAGE=3 and three-stage-ring builds (tools/isa_diff.py; profiles/shared_conv_pieces_isa.txt).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -248,6 +257,72 @@ __device__ __forceinline__ int halo_row(const ConvParams &p, int tyi, int r, int
   return p.row_par ? (tyi >> 1) * (2 * rows_per_tile) + (tyi & 1) + 2 * r : tyi * rows_per_tile + r;
 }
 
+// ---- work decomposition: "tail split" -----------------------------------------------------------
+// All output tiles of a layer are co-resident (five workgroups fit a CU), so the launch takes as
+// long as the busiest CU: with T tiles on 256 CUs that is ceil(T/256) tile-times although the
+// average is T/256 (800 tiles: 4 vs 3.125 -> 78 %).  The first n_main = 256*floor(T/256) tiles are
+// therefore computed whole (every CU gets the same number), and each of the remaining tiles is cut
+// into `split` K-ranges computed by separate, short workgroups of the SAME launch whose partial
+// accumulators the last arriver (splitk_arrive, splitk_sum) or conv_fixup_kernel sums in k order.
+// XCD-aware order for the whole tiles: workgroup b runs on XCD b % 8 (observed, speed only) and
+// each XCD has a private L2; consecutive tiles share halo rows and weights, so every XCD gets a
+// CONTIGUOUS range of tiles instead of every eighth one (bijective remap of [0, n)).
+__device__ __forceinline__ int xcd_contiguous(int bid, int n) {
+  const int q = n >> 3, r = n & 7, xcd = bid & 7, local = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+}
+// This workgroup's tile t and its K-range [k0, k1) of the n units the kernel cuts (k-steps: conv_igemm_kernel; whole chunks: the halo kernels); ks = index of the range
+// within its tile, slot = index of the range's partial accumulator (consecutive in workgroup order), full = the whole tile (nothing to hand off).
+// (the member order and the declaration order inside tile_work are part of the instruction-identity record: profiles/shared_conv_pieces_isa.txt)
+struct TileWork { int t, k0, ks, slot, k1; bool full; };
+__device__ __forceinline__ TileWork tile_work(const ConvParams &p, int n) {
+  TileWork w = {0, 0, 0, 0, n, true};
+  const int bid = (int)blockIdx.x;
+  if (bid < p.nb_main && p.split0 == 1) {
+    w.t = xcd_contiguous(bid, p.n_main);
+  } else {
+    unsigned mg;
+    int tbase, r, sp;
+    if (bid < p.nb_main) { sp = p.split0; mg = p.mg_sp0; r = bid; tbase = 0; }
+    else { sp = p.split; mg = p.mg_sp; r = bid - p.nb_main; tbase = p.n_main; }
+    const int tl = (int)udiv_magic((unsigned)r, (unsigned)sp, mg);
+    w.ks = r - tl * sp;
+    w.t = tbase + tl;
+    w.k0 = (int)udiv_magic((unsigned)(w.ks * n), (unsigned)sp, mg);
+    w.k1 = (int)udiv_magic((unsigned)((w.ks + 1) * n), (unsigned)sp, mg);
+    w.slot = bid - (p.split0 == 1 ? p.nb_main : 0);
+  }
+  w.full = (w.k0 == 0) & (w.k1 == n);
+  return w;
+}
+
+// Tile t -> [class,] M tile, N tile, sample.  Tile order: M tiles fastest (measured on the same box: 3.03 ms per frame vs 3.11 ms with N tiles
+// fastest and 3.09 ms for the previous 3-D grid without the tail split).
+// conv-transpose: the parity class is the FASTEST index -- the four classes of an M tile read the same input pixels,
+// and as neighbours in the order they run on the same XCD at about the same time (one fetch into its L2 instead of
+// four through HBM: the bf16 conv-transposes were bound by exactly that traffic)
+enum { TILE_NO_CLASS = 0,      // nclass = 1: cls = 0
+       TILE_CLASSES = 1,       // cls = t % p.nclass (conv_igemm_kernel, conv_fixup_kernel)
+       TILE_ROW_PARITY = 2 };  // cls = t & 1: the output-row parity ph of the conv-transpose halo kernels (p.nclass = 2)
+struct TileIndex { int tile_m, tile_n, cls, b; };
+template <int CLASS_MODE = TILE_NO_CLASS>
+__device__ __forceinline__ TileIndex tile_index(const ConvParams &p, int t) {
+  int tile_m, tile_n, cls = 0, b;
+  int r = t;
+  if (CLASS_MODE == TILE_CLASSES) {
+    const int q0 = (int)udiv_magic((unsigned)r, (unsigned)p.nclass, p.mg_nc);
+    cls = r - q0 * p.nclass; r = q0;
+  } else if (CLASS_MODE == TILE_ROW_PARITY) {
+    cls = r & 1; r >>= 1;
+  }
+  const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
+  tile_m = r - q1 * p.tiles_m; r = q1;
+  const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
+  tile_n = r - q2 * p.tiles_n;
+  b = q2;
+  return TileIndex{tile_m, tile_n, cls, b};
+}
+
 // tanh of the 1x1 head (nets.py:509-515) as (e^{2|x|} - 1) / (e^{2|x|} + 1) on the hardware exp2 / rcp (1 ulp each): absolute error
 // 2.0e-7 over [-20, 20] (measured against fp64 on 2^24 points: tools/ubench/tanh_err.hip; the gate is 1e-3), 8 VALU
 // instead of the ~35 of the library routine -- the fused tail runs sixteen of them per lane on two of its four waves, which,
@@ -407,6 +482,24 @@ __device__ __forceinline__ void ln_mean_inv(const long long *sums, double inv_n,
 __device__ __forceinline__ void ln_mean_inv_pre(LnShard pre, double inv_n, const double *scl, int *status, double *s_stat, int tid) {
   ln_mean_inv_impl<true>(nullptr, pre, inv_n, scl, status, s_stat, tid);
 }
+// What a kernel that applies its producer's LayerNorm while staging keeps of those statistics: 1 / sigma and the mean as hi + lo floats (fp32 operations only from here on).
+// ln_affine_read: s_stat -> registers, called by all threads right after ln_mean_inv / ln_mean_inv_pre; ends with a barrier (s_stat usually sits in LDS the patch reuses).
+struct LnAffine { float inv, mu_hi, mu_lo; };
+__device__ __forceinline__ LnAffine ln_affine_read(const double *s_stat) {
+  const double mu = s_stat[0];
+  LnAffine a;
+  a.inv = (float)s_stat[1];
+  a.mu_hi = (float)mu;
+  a.mu_lo = (float)(mu - (double)a.mu_hi);
+  __syncthreads();
+  return a;
+}
+// the affine of the lane's four channels: scale = inv * gamma; shift = beta - mean * scale (ln_apply_kernel's expressions: same bits)
+__device__ __forceinline__ void ln_scale_shift(const LnAffine &a, const v4f &g4, const v4f &be4, v4f &s4, v4f &t4) {
+  s4 = a.inv * g4;
+  const v4f nh = {-a.mu_hi, -a.mu_hi, -a.mu_hi, -a.mu_hi}, nl = {-a.mu_lo, -a.mu_lo, -a.mu_lo, -a.mu_lo};
+  t4 = __builtin_elementwise_fma(nl, s4, __builtin_elementwise_fma(nh, s4, be4));
+}
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
@@ -472,6 +565,75 @@ __device__ __forceinline__ void sum_slabs(f32x16 (&acc)[MT][NT], __amdgpu_buffer
           }
         }
   }
+}
+
+// -DMSI_CONV_TIMING: a workgroup's phase stamps, p.dbg[block][24] as tools/conv_timing.py reads them: [0] kernel entry, [1] k-loop start, [2] k-loop end, [3] now (write),
+// [4] HW_ID, [5] XCC_ID, [22] / [23] entry and now on the constant 100 MHz counter (tools/clock_probe.sh); emit_whole_tile's MSI_STAMPs fill [16..21].  Empty otherwise.
+struct ConvStamps {
+#ifdef MSI_CONV_TIMING
+  unsigned long long ts0, ts0r, ts1, ts2;
+  __device__ __forceinline__ void begin() { ts0 = __builtin_amdgcn_s_memtime(); ts0r = __builtin_amdgcn_s_memrealtime(); }
+  __device__ __forceinline__ void loop() { ts1 = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void tail() { ts2 = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void write(const ConvParams &p, int tid) const {
+    if (p.dbg && tid == 0) {
+      unsigned long long *o = p.dbg + (size_t)blockIdx.x * 24;
+      o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = __builtin_amdgcn_s_memtime(); o[22] = ts0r; o[23] = __builtin_amdgcn_s_memrealtime();
+      o[4] = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_ID: wave, simd, cu, sh, se ...
+      o[5] = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // XCC_ID
+    }
+  }
+#else
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void loop() {}
+  __device__ __forceinline__ void tail() {}
+  __device__ __forceinline__ void write(const ConvParams &, int) const {}
+#endif
+};
+
+// K-range of a split tile (!w.full): the raw accumulators go to this range's slab; the LAST of the tile's workgroups to
+// arrive sums the slabs in k order (deterministic whoever is last) and emits the tile.  Hand-off per cdna_hip_programming.md
+// (in-launch split-K, write-through form): sc1 slab stores -> vmcnt(0) -> workgroup barrier -> one lane takes a relaxed
+// agent-scope ticket; the last arriver reads the slabs with sc1 loads.  In a kernel:
+//     if (!w.full) { if (!splitk_arrive(p, acc, w, smem, tid)) return;  splitk_sum(p, acc, w, tid); }
+// (two calls: the accumulators are rewritten by the second only, so the first's result is nothing but the branch of the early leavers.)
+// (a slab: every thread's MT x NT x 16 accumulators in dump_acc's order = the BM x BN tile)
+// Users: conv_halo_s2_kernel and conv_halo_s2_x3_body.  conv_igemm_kernel, conv_halo_kernel and conv_halo_x3_body spell the same sequence out, and the two
+// fp32 conv-transpose halo kernels their two-class form of it (class-minor slabs: slot stride 2, slab stride 2 SLAB; no closing barrier) -- the comments there say
+// why.  A change to the fences, the cache policy (MSI_HANDOFF_AUX, handoff_release / handoff_acquire above: those are shared by all) or the ticket has to be made
+// here and at those five places.
+// splitk_arrive: dump and ticket; true in the last arriver, false in the others, which are done.  p.tile_cnt == nullptr
+// (plan option MSI_NET_OPT_FIXUP_KERNEL): plain stores, false everywhere -- conv_fixup_kernel sums and emits in a launch of
+// its own.  smem: the ticket's broadcast word (all LDS reads of the k-loop are behind its last barrier).
+template <int MT, int NT>
+__device__ __forceinline__ bool splitk_arrive(const ConvParams &p, const f32x16 (&acc)[MT][NT], const TileWork &w, char *smem, int tid) {
+  constexpr int TILE = MT * NT * 16 * 256, SLAB = TILE * 4;
+  const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)w.slot * TILE), 0, SLAB, 0x00020000);
+  if (p.tile_cnt == nullptr) {
+    dump_acc<MT, NT, 0>(acc, rsrc_p, tid);
+    return false;
+  }
+  dump_acc<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_p, tid);
+  const int nsp = w.t < p.n_main ? p.split0 : p.split;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's slab stores have left (sc1: written through)
+  handoff_release();
+  __syncthreads();
+  int *s_old = reinterpret_cast<int *>(smem);
+  if (tid == 0)
+    *s_old = __hip_atomic_fetch_add(p.tile_cnt + (w.t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  return *s_old == nsp - 1;
+}
+// splitk_sum, in the last arriver: acc = the sum of the tile's slabs; ends with a barrier (every thread has read the ticket's
+// word before the epilogue's staging strips reuse LDS).
+template <int MT, int NT>
+__device__ __forceinline__ void splitk_sum(const ConvParams &p, f32x16 (&acc)[MT][NT], const TileWork &w, int tid) {
+  constexpr int TILE = MT * NT * 16 * 256, SLAB = TILE * 4;
+  const int nsp = w.t < p.n_main ? p.split0 : p.split;
+  handoff_acquire();
+  const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)(w.slot - w.ks) * TILE), 0, nsp * SLAB, 0x00020000);
+  sum_slabs<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_t, nsp, SLAB, tid);
+  __syncthreads();
 }
 
 // ---- epilogue of one finished tile: CoordNet table, bias + tanh (head), store, LayerNorm sums -----
@@ -847,7 +1009,6 @@ __device__ __forceinline__ void load_coord_bias(const ConvParams &p, int tile_m,
     cbv[g] = *reinterpret_cast<const v4f *>(cbrow + n);
   }
 }
-
 
 // k-step J of a 32-channel group of the stride-2 form -> tap (unit by unit: the four units' taps in the order the patches are swapped) and unit
 __device__ constexpr int s2_tap(int J) { return J == 0 ? 0 : J == 1 ? 2 : J == 2 ? 6 : J == 3 ? 8 : J == 4 ? 1 : J == 5 ? 7 : J == 6 ? 3 : J == 7 ? 5 : 4; }

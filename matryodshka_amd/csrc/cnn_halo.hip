@@ -39,44 +39,18 @@ conv_halo_kernel(const ConvParams p) {
   typedef HaloGeom<RATE> G;
   constexpr int R = RATE, PW = G::PW, NPX = G::NPX, NLOAD = G::NLOAD;
   constexpr int MT = 1, NT = 1;
-#ifdef MSI_CONV_TIMING
-  const unsigned long long ts0 = __builtin_amdgcn_s_memtime(), ts0r = __builtin_amdgcn_s_memrealtime();   // (ts0r: the constant 100 MHz counter, tools/clock_probe.sh)
-#endif
+  ConvStamps stamps;
+  stamps.begin();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  // ---- work decomposition: as conv_igemm_kernel (tail split), K-ranges in whole chunks ----
+  // ---- work decomposition: tail split (tile_work), K-ranges in whole chunks ----
   const int CH = p.cpt0;                                  // 32-channel chunks of the input
-  int t, c0 = 0, c1 = CH, ks = 0, slot = 0;
-  {
-    const int bid = blockIdx.x;
-    if (bid < p.nb_main && p.split0 == 1) {
-      const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    } else {
-      int sp, r, tbase;
-      unsigned mg;
-      if (bid < p.nb_main) { sp = p.split0; mg = p.mg_sp0; r = bid; tbase = 0; }
-      else { sp = p.split; mg = p.mg_sp; r = bid - p.nb_main; tbase = p.n_main; }
-      const int tl = (int)udiv_magic((unsigned)r, (unsigned)sp, mg);
-      ks = r - tl * sp;
-      t = tbase + tl;
-      c0 = (int)udiv_magic((unsigned)(ks * CH), (unsigned)sp, mg);
-      c1 = (int)udiv_magic((unsigned)((ks + 1) * CH), (unsigned)sp, mg);
-      slot = bid - (p.split0 == 1 ? p.nb_main : 0);
-    }
-  }
-  const bool full = (c0 == 0) & (c1 == CH);
-  int tile_m, tile_n, b;
-  {
-    int r = t;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;                                               // (nclass = 1)
-  }
+  const TileWork w = tile_work(p, CH);
+  const int c0 = w.k0, c1 = w.k1;
+  const TileIndex ti = tile_index(p, w.t);               // (nclass = 1)
+  const int tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   LnShard shard = {0, 0};   // (the lane's shard of the source's LayerNorm sums: requested here, reduced after the patch requests)
   if (APPLY) shard = ln_shard_load(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, tid);
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
@@ -119,7 +93,7 @@ conv_halo_kernel(const ConvParams p) {
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x0 + (size_t)b * in_bytes), 0, (int)in_bytes, 0x00020000);
 
   // producer's LayerNorm: mean / inv once per workgroup; the per-channel affine per chunk (the lane's four channels)
-  float inv_f = 1.f, mu_hi = 0.f, mu_lo = 0.f;
+  LnAffine ln = {1.f, 0.f, 0.f};
   bool has_pad = false;                                   // wave-uniform: any of the wave's patch pixels is padding
   if (APPLY) {
     bool bad = false;
@@ -141,11 +115,7 @@ conv_halo_kernel(const ConvParams p) {
   // registers -> LDS patch, the producer's affine + ReLU applied (ln_apply_kernel's expressions: same bits)
   auto patch_store = [&]() __attribute__((always_inline)) {
     v4f s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
-    if (APPLY) {   /* scale = inv * gamma; shift = beta - mean * scale with the mean as hi + lo floats: fp32 ops only */
-      s4 = inv_f * g4;
-      const v4f nh = {-mu_hi, -mu_hi, -mu_hi, -mu_hi}, nl = {-mu_lo, -mu_lo, -mu_lo, -mu_lo};
-      t4 = __builtin_elementwise_fma(nl, s4, __builtin_elementwise_fma(nh, s4, be4));
-    }
+    if (APPLY) ln_scale_shift(ln, g4, be4, s4, t4);
 #pragma unroll
     for (int k_ = 0; k_ < NLOAD; ++k_) {
       v4f y = araw[k_];
@@ -223,19 +193,13 @@ conv_halo_kernel(const ConvParams p) {
   if (APPLY) {   // the sums' round trip rides on the patch's (s_stat sits in the A region: read back before the patch lands)
     double *s_stat = reinterpret_cast<double *>(smem);
     ln_mean_inv_pre(shard, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-    const double mu = s_stat[0];
-    inv_f = (float)s_stat[1];
-    mu_hi = (float)mu;
-    mu_lo = (float)(mu - (double)mu_hi);
-    __syncthreads();
+    ln = ln_affine_read(s_stat);
   }
   wait_vmcnt<0>();
   patch_store();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-#ifdef MSI_CONV_TIMING
-  const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
-#endif
+  stamps.loop();
   for (; c < c1; ++c) {
     htap(IC<0>{}); htap(IC<1>{}); htap(IC<2>{}); htap(IC<3>{}); htap(IC<4>{}); htap(IC<5>{}); htap(IC<6>{}); htap(IC<7>{}); htap(IC<8>{});
     if (c + 1 < c1) {   // every wave has read the last tap of this chunk (closing barrier of tap 8): swap the patch
@@ -245,47 +209,34 @@ conv_halo_kernel(const ConvParams p) {
     }
   }
 
-  // ---- epilogue: as conv_igemm_kernel ----
-#ifdef MSI_CONV_TIMING
-  const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-  auto stamp = [&]() __attribute__((always_inline)) {
-    if (p.dbg && tid == 0) {
-      unsigned long long *o = p.dbg + (size_t)blockIdx.x * 24;
-      o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = __builtin_amdgcn_s_memtime(); o[22] = ts0r; o[23] = __builtin_amdgcn_s_memrealtime();
-      o[4] = __builtin_amdgcn_s_getreg(4 | (31 << 11));
-      o[5] = __builtin_amdgcn_s_getreg(20 | (31 << 11));
-    }
-  };
-#endif
-  if (!full) {
+  // ---- epilogue: split-K hand-off (cnn_device.h), then the tile ----
+  stamps.tail();
+  // (splitk_arrive / splitk_sum, spelled out: through them the -DMSI_CONV_TIMING build of this kernel changes)
+  if (!w.full) {
     constexpr int SLAB = 64 * 64 * 4;
-    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)slot * (64 * 64)), 0, SLAB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)w.slot * (64 * 64)), 0, SLAB, 0x00020000);
     if (p.tile_cnt == nullptr) {
       dump_acc<MT, NT, 0>(acc, rsrc_p, tid);
-#ifdef MSI_CONV_TIMING
-      stamp();
-#endif
+      stamps.write(p, tid);
       return;
     }
     dump_acc<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_p, tid);
-    const int nsp = t < p.n_main ? p.split0 : p.split;
+    const int nsp = w.t < p.n_main ? p.split0 : p.split;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     handoff_release();
     __syncthreads();
     int *s_old = reinterpret_cast<int *>(smem);
     if (tid == 0)
-      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (w.t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (*s_old != nsp - 1) return;
     handoff_acquire();
-    const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)(slot - ks) * (64 * 64)), 0, nsp * SLAB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)(w.slot - w.ks) * (64 * 64)), 0, nsp * SLAB, 0x00020000);
     sum_slabs<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_t, nsp, SLAB, tid);
     __syncthreads();   // (every thread has read s_old before the epilogue's strips reuse LDS)
   }
   emit_tile<64, 64, MODE_CONV>(p, acc, tile_m, tile_n, 0, b, tid, cbv, p.coord_bias != nullptr, smem);
-#ifdef MSI_CONV_TIMING
-  stamp();
-#endif
+  stamps.write(p, tid);
 #endif
 }
 
@@ -324,37 +275,12 @@ conv_halo_s2_kernel(const ConvParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  // ---- work decomposition: as conv_halo_kernel (tail split; K-ranges in whole 32-channel groups) ----
+  // ---- work decomposition: tail split (tile_work), K-ranges in whole 32-channel groups ----
   const int CH = p.cpt0;
-  int t, c0 = 0, c1 = CH, ks = 0, slot = 0;
-  {
-    const int bid = blockIdx.x;
-    if (bid < p.nb_main && p.split0 == 1) {
-      const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    } else {
-      int sp, r, tbase;
-      unsigned mg;
-      if (bid < p.nb_main) { sp = p.split0; mg = p.mg_sp0; r = bid; tbase = 0; }
-      else { sp = p.split; mg = p.mg_sp; r = bid - p.nb_main; tbase = p.n_main; }
-      const int tl = (int)udiv_magic((unsigned)r, (unsigned)sp, mg);
-      ks = r - tl * sp;
-      t = tbase + tl;
-      c0 = (int)udiv_magic((unsigned)(ks * CH), (unsigned)sp, mg);
-      c1 = (int)udiv_magic((unsigned)((ks + 1) * CH), (unsigned)sp, mg);
-      slot = bid - (p.split0 == 1 ? p.nb_main : 0);
-    }
-  }
-  const bool full = (c0 == 0) & (c1 == CH);
-  int tile_m, tile_n, b;
-  {
-    int r = t;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  const TileWork w = tile_work(p, CH);
+  const int c0 = w.k0, c1 = w.k1;
+  const TileIndex ti = tile_index(p, w.t);
+  const int tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
   const int oh0 = tyi * 4, ow0 = (tile_m - tyi * p.halo_tx) * 16;   // the tile of the OUTPUT grid
   const int H = p.Hin, W = p.Win, C = p.C0;
@@ -405,7 +331,7 @@ conv_halo_s2_kernel(const ConvParams p) {
     }
   }
 
-  float inv_f = 1.f, mu_hi = 0.f, mu_lo = 0.f;
+  LnAffine ln = {1.f, 0.f, 0.f};
   bool has_pad = false;                                   // wave-uniform: any of the wave's patch pixels (any unit) is padding
   if (APPLY) {
     bool bad = false;
@@ -430,11 +356,7 @@ conv_halo_s2_kernel(const ConvParams p) {
   // registers -> LDS patch, the producer's affine + ReLU applied (ln_apply_kernel's expressions: same bits)
   auto patch_store = [&](auto U_c) __attribute__((always_inline)) {
     constexpr int U = decltype(U_c)::value;
-    if (APPLY && U == 0) {
-      s4 = inv_f * g4;
-      const v4f nh = {-mu_hi, -mu_hi, -mu_hi, -mu_hi}, nl = {-mu_lo, -mu_lo, -mu_lo, -mu_lo};
-      t4 = __builtin_elementwise_fma(nl, s4, __builtin_elementwise_fma(nh, s4, be4));
-    }
+    if (APPLY && U == 0) ln_scale_shift(ln, g4, be4, s4, t4);
 #pragma unroll
     for (int k_ = 0; k_ < NLOAD; ++k_) {
       v4f y = araw[k_];
@@ -513,11 +435,7 @@ conv_halo_s2_kernel(const ConvParams p) {
   if (APPLY) {
     double *s_stat = reinterpret_cast<double *>(smem);
     ln_mean_inv(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-    const double mu = s_stat[0];
-    inv_f = (float)s_stat[1];
-    mu_hi = (float)mu;
-    mu_lo = (float)(mu - (double)mu_hi);
-    __syncthreads();
+    ln = ln_affine_read(s_stat);
   }
   wait_vmcnt<0>();
   patch_store(IC<0>{});
@@ -527,28 +445,10 @@ conv_halo_s2_kernel(const ConvParams p) {
     s2step(IC<0>{}); s2step(IC<1>{}); s2step(IC<2>{}); s2step(IC<3>{}); s2step(IC<4>{}); s2step(IC<5>{}); s2step(IC<6>{}); s2step(IC<7>{}); s2step(IC<8>{});
   }
 
-  // ---- epilogue: as conv_halo_kernel ----
-  if (!full) {
-    constexpr int SLAB = 64 * 64 * 4;
-    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)slot * (64 * 64)), 0, SLAB, 0x00020000);
-    if (p.tile_cnt == nullptr) {
-      dump_acc<MT, NT, 0>(acc, rsrc_p, tid);
-      return;
-    }
-    dump_acc<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_p, tid);
-    const int nsp = t < p.n_main ? p.split0 : p.split;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    handoff_release();
-    __syncthreads();
-    int *s_old = reinterpret_cast<int *>(smem);
-    if (tid == 0)
-      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (*s_old != nsp - 1) return;
-    handoff_acquire();
-    const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)(slot - ks) * (64 * 64)), 0, nsp * SLAB, 0x00020000);
-    sum_slabs<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_t, nsp, SLAB, tid);
-    __syncthreads();   // (s_old has been read by every thread before the strip below reuses LDS)
+  // ---- epilogue: split-K hand-off (cnn_device.h), then the tile ----
+  if (!w.full) {
+    if (!splitk_arrive<MT, NT>(p, acc, w, smem, tid)) return;
+    splitk_sum<MT, NT>(p, acc, w, tid);
   }
   emit_tile<64, 64, MODE_CONV>(p, acc, tile_m, tile_n, 0, b, tid, smem);
 #endif
@@ -589,12 +489,12 @@ convt_halo_kernel(const ConvParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int CH = p.cpt0 + p.cpt1;                         // 32-channel chunks of both sources
+  // (tile_work(p, CH), spelled out: through the helper this kernel's prologue comes out in another order)
   int t, c0 = 0, c1 = CH, ks = 0, slot = 0;
   {
     const int bid = blockIdx.x;
     if (bid < p.nb_main && p.split0 == 1) {
-      const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+      t = xcd_contiguous(bid, p.n_main);
     } else {
       int sp, r, tbase;
       unsigned mg;
@@ -609,16 +509,8 @@ convt_halo_kernel(const ConvParams p) {
     }
   }
   const bool full = (c0 == 0) & (c1 == CH);
-  int ph, tile_m, tile_n, b;
-  {   // row parity fastest (p.nclass = 2 here), then M tiles, N tiles, samples
-    int r = t;
-    ph = r & 1; r >>= 1;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  const TileIndex ti = tile_index<TILE_ROW_PARITY>(p, t);   // row parity fastest (p.nclass = 2 here), then M tiles, N tiles, samples
+  const int ph = ti.cls, tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
   const int oh0 = tyi * 4, ow0 = (tile_m - tyi * p.halo_tx) * 16;
   const int H = p.Hin, W = p.Win;
@@ -696,7 +588,7 @@ convt_halo_kernel(const ConvParams p) {
     v4f s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
     if (ap_) {
       const float ih_ = src_ld ? inv_f[1] : inv_f[0], mh_ = src_ld ? mu_hi[1] : mu_hi[0], ml_ = src_ld ? mu_lo[1] : mu_lo[0];
-      s4 = ih_ * g4;
+      s4 = ih_ * g4;   // (ln_scale_shift, spelled out: through it this kernel's prologue changes)
       const v4f nh = {-mh_, -mh_, -mh_, -mh_}, nl = {-ml_, -ml_, -ml_, -ml_};
       t4 = __builtin_elementwise_fma(nl, s4, __builtin_elementwise_fma(nh, s4, be4));
     }
@@ -779,15 +671,13 @@ convt_halo_kernel(const ConvParams p) {
     double *s_stat = reinterpret_cast<double *>(smem);
     if (p.halo_apply & 1) {
       ln_mean_inv(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-      const double mu = s_stat[0];
-      inv_f[0] = (float)s_stat[1]; mu_hi[0] = (float)mu; mu_lo[0] = (float)(mu - (double)mu_hi[0]);
-      __syncthreads();
+      const LnAffine a = ln_affine_read(s_stat);
+      inv_f[0] = a.inv; mu_hi[0] = a.mu_hi; mu_lo[0] = a.mu_lo;
     }
     if (p.halo_apply & 2) {
       ln_mean_inv(p.ln_sums1 + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n1, p.ln_scl_src1, p.status, s_stat, tid);
-      const double mu = s_stat[0];
-      inv_f[1] = (float)s_stat[1]; mu_hi[1] = (float)mu; mu_lo[1] = (float)(mu - (double)mu_hi[1]);
-      __syncthreads();
+      const LnAffine a = ln_affine_read(s_stat);
+      inv_f[1] = a.inv; mu_hi[1] = a.mu_hi; mu_lo[1] = a.mu_lo;
     }
   }
   wait_vmcnt<0>();
@@ -804,6 +694,8 @@ convt_halo_kernel(const ConvParams p) {
   }
 
   // ---- epilogue: two class tiles ----
+  // (the hand-off of cnn_device.h in its two-class form -- class-minor slabs: slot stride 2, slab stride 2 SLAB, no closing barrier -- spelled out: written over a
+  // two-class splitk_arrive / splitk_sum this kernel's instruction stream changes)
   if (!full) {
     constexpr int SLAB = 64 * 64 * 4;
     if (p.tile_cnt == nullptr) {                          // separate fix-up launch (conv_fixup_kernel, class = blockIdx.y)

@@ -25,23 +25,16 @@ conv_igemm_kernel(const ConvParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  // ---- work decomposition: "tail split" ----------------------------------------------------------
-  // All output tiles of a layer are co-resident (five workgroups fit a CU), so the launch takes as
-  // long as the busiest CU: with T tiles on 256 CUs that is ceil(T/256) tile-times although the
-  // average is T/256 (800 tiles: 4 vs 3.125 -> 78 %).  The first n_main = 256*floor(T/256) tiles are
-  // therefore computed whole (every CU gets the same number), and each of the remaining tiles is cut
-  // into `split` K-ranges computed by separate, short workgroups of the SAME launch whose partial
-  // accumulators conv_fixup_kernel sums in k order.
-  // XCD-aware order for the whole tiles: workgroup b runs on XCD b % 8 (observed, speed only) and
-  // each XCD has a private L2; consecutive tiles share halo rows and weights, so every XCD gets a
-  // CONTIGUOUS range of tiles instead of every eighth one (bijective remap).
+  // ---- work decomposition: the tail split of cnn_device.h (tile_work) over the k-steps.  This kernel spells out tile_work, the split-K hand-off
+  // (splitk_arrive / splitk_sum) and ConvStamps: it reads k1 outside its lambdas, the halo kernels inside theirs, so the compiler turns k1 into a value at another
+  // time and tile_work reproduces the halo kernels' order of the initial moves, not this one; behind the hand-off's calls and with the stamps in a struct the
+  // -DMSI_CONV_TIMING build of every instantiation changes (profiles/shared_conv_pieces_isa.txt) ----
   const int S = p.ksteps;
   int t, k0 = 0, k1 = S, ks = 0, slot = 0;   // slot: index of this K-range's partial accumulator
   {
     const int bid = (int)blockIdx.x;
     if (bid < p.nb_main && p.split0 == 1) {
-      const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+      t = xcd_contiguous(bid, p.n_main);
     } else {
       int sp, r, tbase;
       unsigned mg;
@@ -56,22 +49,8 @@ conv_igemm_kernel(const ConvParams p) {
     }
   }
   const bool full = (k0 == 0) & (k1 == S);
-  int tile_m, tile_n, cls, b;
-  {
-    // tile order: M tiles fastest (measured on the same box: 3.03 ms per frame vs 3.11 ms with N tiles
-    // fastest and 3.09 ms for the previous 3-D grid without the tail split)
-    // conv-transpose: the parity class is the FASTEST index -- the four classes of an M tile read the same input pixels,
-    // and as neighbours in the order they run on the same XCD at about the same time (one fetch into its L2 instead of
-    // four through HBM: the bf16 conv-transposes were bound by exactly that traffic)
-    int r = t;
-    const int q0 = (int)udiv_magic((unsigned)r, (unsigned)p.nclass, p.mg_nc);
-    cls = r - q0 * p.nclass; r = q0;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  const TileIndex ti = tile_index<TILE_CLASSES>(p, t);
+  const int tile_m = ti.tile_m, tile_n = ti.tile_n, cls = ti.cls, b = ti.b;
   constexpr bool CB_PRE = BM == 64 && BN == 64 && MODE == MODE_CONV && !BF16;
   v4f cbv[4];
   if constexpr (CB_PRE) load_coord_bias(p, tile_m, tile_n, tid, cbv);   // in flight during the prologue and the k-loop
@@ -396,11 +375,7 @@ _Pragma("unroll")                                                               
 
   // ---- epilogue ------------------------------------------------------------------------------
   if (!full) {
-    // K-range of a split tile: the raw accumulators go to this range's slab; the LAST of the tile's workgroups to
-    // arrive sums the slabs in k order (deterministic whoever is last) and emits the tile.  Hand-off per
-    // cdna_hip_programming.md (in-launch split-K, write-through form): sc1 slab stores -> vmcnt(0) -> workgroup
-    // barrier -> one lane takes a relaxed agent-scope ticket; the last arriver reads the slabs with sc1 loads.
-    // (Plan option MSI_NET_OPT_FIXUP_KERNEL: plain stores here, conv_fixup_kernel as a separate launch.)
+    // K-range of a split tile: the hand-off described at splitk_arrive (cnn_device.h), spelled out (see above)
     constexpr int SLAB = BM * BN * 4;
     const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(
         (void *)(p.partial + (size_t)slot * (BM * BN)), 0, SLAB, 0x00020000);
@@ -459,7 +434,7 @@ conv_fixup_kernel(const ConvParams p) {
                                   : (t < p.n_main ? t * p.split0 : p.nb_main + (t - p.n_main) * p.split);
   int tile_m, tile_n, cls, b;
   {
-    int r = t;   // same order as conv_igemm_kernel: class fastest, then M tiles
+    int r = t;   // tile_index<TILE_CLASSES>, spelled out: through the helper the conv-transpose instantiations leave the tile_m / tile_n arithmetic above the slab sums
     const int q0 = (int)udiv_magic((unsigned)r, (unsigned)p.nclass, p.mg_nc);
     cls = r - q0 * p.nclass; r = q0;
     const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);

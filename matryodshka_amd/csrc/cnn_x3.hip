@@ -14,7 +14,7 @@ namespace {
 // way) and split there -- three v_cvt_pk_bf16_f32 pairs and two exact subtractions per float4 -- into three 64-byte planes per
 // pixel (pixel stride 208 B: 13 x 16, odd, so the fragment reads stay conflict-free with the row pitch / column rotation of
 // HaloGeom).  The weights are split on the host at pack time (x3 block of the packed blob).  Everything around the k-loop --
-// work decomposition, tail split, in-launch hand-off, epilogue, LayerNorm sums -- is conv_halo_kernel's.
+// work decomposition, tail split, in-launch hand-off, epilogue, LayerNorm sums -- is what conv_halo_kernel has, from the same pieces of cnn_device.h.
 // Numerics: oracle emulation of this arithmetic against the fp32 oracle at the configs[1] frame: pred 3.0e-6, rgba 1.9e-6,
 // rgb 1.0e-6 max-abs (profiles/r04_split3_numerics.txt: the native fp32 path's own summation-order error is 4.5e-6 on pred).
 #ifndef MSI_X3_EARLY_DMA
@@ -73,8 +73,67 @@ __device__ __forceinline__ void wait_lgkm6(v4f &a, v4f &b, v4f &c, v4f &d, v4f &
 #ifndef MSI_X2_LATE_CB
 #define MSI_X2_LATE_CB 1
 #endif
+// ---- shared pieces of the split kernels (NP = 3: bf16 h | m | l, six products; NP = 2: fp16 h | m', three) ----
 template <int NP>
-__device__ __forceinline__ void split_mfma(f32x16 &acc, f32x16 &lo, const v4f &ah, const v4f &am, const v4f &al, const v4f &bh, const v4f &bm, const v4f &bl);
+__device__ __forceinline__ void split_store(char *smem, unsigned off, v4f y, unsigned &amax) {
+  typedef unsigned u2x_t __attribute__((ext_vector_type(2)));
+  if (NP == 2) {   // y = h + m' 2^-11, fp16 parts (round to nearest even; y - h is exact in fp32)
+    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+    f16_range_track(amax, y);
+    const h2_t ha = {(_Float16)y.x, (_Float16)y.y}, hb = {(_Float16)y.z, (_Float16)y.w};
+    const h2_t ma = {(_Float16)((y.x - (float)ha.x) * 2048.f), (_Float16)((y.y - (float)ha.y) * 2048.f)};
+    const h2_t mb = {(_Float16)((y.z - (float)hb.x) * 2048.f), (_Float16)((y.w - (float)hb.y) * 2048.f)};
+    if (off != 0xffffffffu) {
+      *reinterpret_cast<u2x_t *>(smem + off) = u2x_t{__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb)};
+      *reinterpret_cast<u2x_t *>(smem + off + 64) = u2x_t{__builtin_bit_cast(unsigned, ma), __builtin_bit_cast(unsigned, mb)};
+    }
+  } else {         // y = h + m + l, bf16 parts (round to nearest even; y - h and (y - h) - m are exact in fp32)
+    unsigned h0, h1, m0, m1, l0, l1;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(h0) : "v"(y.x), "v"(y.y));
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(h1) : "v"(y.z), "v"(y.w));
+    v4f r = y - v4f{__builtin_bit_cast(float, h0 << 16), __builtin_bit_cast(float, h0 & 0xffff0000u),
+                    __builtin_bit_cast(float, h1 << 16), __builtin_bit_cast(float, h1 & 0xffff0000u)};
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(m0) : "v"(r.x), "v"(r.y));
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(m1) : "v"(r.z), "v"(r.w));
+    r = r - v4f{__builtin_bit_cast(float, m0 << 16), __builtin_bit_cast(float, m0 & 0xffff0000u),
+                __builtin_bit_cast(float, m1 << 16), __builtin_bit_cast(float, m1 & 0xffff0000u)};
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(l0) : "v"(r.x), "v"(r.y));
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(l1) : "v"(r.z), "v"(r.w));
+    if (off != 0xffffffffu) {
+      *reinterpret_cast<u2x_t *>(smem + off) = u2x_t{h0, h1};
+      *reinterpret_cast<u2x_t *>(smem + off + 64) = u2x_t{m0, m1};
+      *reinterpret_cast<u2x_t *>(smem + off + 128) = u2x_t{l0, l1};
+    }
+  }
+}
+// the products of one K16 step (weights = the MFMA's row operand), small terms first; NP = 2: lo collects h.m' + m'.h
+template <int NP>
+__device__ __forceinline__ void split_mfma(f32x16 &acc, f32x16 &lo, const v4f &ah, const v4f &am, const v4f &al, const v4f &bh, const v4f &bm, const v4f &bl) {
+  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+  typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+  if (NP == 2) {
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bm), __builtin_bit_cast(f16x8, ah), lo, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, ah), acc, 0, 0, 0);
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, am), lo, 0, 0, 0);
+  } else {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, am), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, al), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bl), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, am), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
+  }
+}
+// NP = 2, after the k-loop: acc += lo 2^-11; an operand beyond the fp16 range (h = inf, m' = NaN) is reported
+template <int NP>
+__device__ __forceinline__ void split_finish(f32x16 &acc, const f32x16 &lo, unsigned amax, int lane, int *status) {
+  if (NP == 2) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = __builtin_fmaf(lo[r], 1.f / 2048.f, acc[r]);
+    if (__builtin_amdgcn_ballot_w64(amax > F16_MAX_BITS) != 0 && lane == 0) atomicOr(status, STATUS_F16_SPLIT_RANGE);
+  }
+}
+
 // TH = 4: the 4 x 16-pixel x 64-channel tile (one 32 x 32 accumulator per wave).  TH = 8 (r05, conv_halo8_x3_kernel, six-product form at rate 1): an 8 x 16-pixel
 // tile -- a wave owns four tile rows = TWO 32 x 32 accumulators that share the weight fragments (18 instead of 24 fragment reads per 24 MFMAs), the 10 x 18 patch
 // serves twice the outputs of the 6 x 18 one (halo 1.41 instead of 1.69), and per output pixel the workgroup moves HALF the weight bytes from L2 into LDS and runs
@@ -86,43 +145,19 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   static_assert(RATE != 3 || TH == 4, "row-parity tiles: four rows");
   constexpr int MT = TH / 4, NT = 1, BM = 16 * TH;
   static_assert(TH == 4 || (TH == 8 && NPL == 3 && RATE == 1), "the 8-row tile is built for the six-product form at rate 1");
+  // (ConvStamps' statements, spelled out here and below: with the struct the -DMSI_CONV_TIMING build of the APPLY fp16-form and the 8-row instantiations changes)
 #ifdef MSI_CONV_TIMING
   const unsigned long long ts0 = __builtin_amdgcn_s_memtime(), ts0r = __builtin_amdgcn_s_memrealtime();   // (ts0r: the constant 100 MHz counter, tools/clock_probe.sh)
 #endif
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  // ---- work decomposition: as conv_igemm_kernel (tail split), K-ranges in whole chunks ----
+  // ---- work decomposition: tail split (tile_work), K-ranges in whole chunks ----
   const int CH = p.cpt0;                                  // 32-channel chunks of the input
-  int t, c0 = 0, c1 = CH, ks = 0, slot = 0;
-  {
-    const int bid = blockIdx.x;
-    if (bid < p.nb_main && p.split0 == 1) {
-      const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    } else {
-      int sp, r, tbase;
-      unsigned mg;
-      if (bid < p.nb_main) { sp = p.split0; mg = p.mg_sp0; r = bid; tbase = 0; }
-      else { sp = p.split; mg = p.mg_sp; r = bid - p.nb_main; tbase = p.n_main; }
-      const int tl = (int)udiv_magic((unsigned)r, (unsigned)sp, mg);
-      ks = r - tl * sp;
-      t = tbase + tl;
-      c0 = (int)udiv_magic((unsigned)(ks * CH), (unsigned)sp, mg);
-      c1 = (int)udiv_magic((unsigned)((ks + 1) * CH), (unsigned)sp, mg);
-      slot = bid - (p.split0 == 1 ? p.nb_main : 0);
-    }
-  }
-  const bool full = (c0 == 0) & (c1 == CH);
-  int tile_m, tile_n, b;
-  {
-    int r = t;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;                                               // (nclass = 1)
-  }
+  const TileWork w = tile_work(p, CH);
+  const int c0 = w.k0, c1 = w.k1;
+  const TileIndex ti = tile_index(p, w.t);               // (nclass = 1)
+  const int tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   LnShard shard = {0, 0};   // (the lane's shard of the source's LayerNorm sums: requested here, reduced after the patch requests)
   if (APPLY) shard = ln_shard_load(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, tid);
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
@@ -168,7 +203,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x0 + (size_t)b * in_bytes), 0, (int)in_bytes, 0x00020000);
 
   // producer's LayerNorm: mean / inv once per workgroup; the per-channel affine per chunk (the lane's four channels)
-  float inv_f = 1.f, mu_hi = 0.f, mu_lo = 0.f;
+  LnAffine ln = {1.f, 0.f, 0.f};
   bool has_pad = false;                                   // wave-uniform: any of the wave's patch pixels is padding
   if (APPLY) {
     bool bad = false;
@@ -191,11 +226,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   // registers -> LDS patch, the producer's affine + ReLU applied (ln_apply_kernel's expressions: same bits)
   auto patch_store = [&]() __attribute__((always_inline)) {
     v4f s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
-    if (APPLY) {   /* scale = inv * gamma; shift = beta - mean * scale with the mean as hi + lo floats: fp32 ops only */
-      s4 = inv_f * g4;
-      const v4f nh = {-mu_hi, -mu_hi, -mu_hi, -mu_hi}, nl = {-mu_lo, -mu_lo, -mu_lo, -mu_lo};
-      t4 = __builtin_elementwise_fma(nl, s4, __builtin_elementwise_fma(nh, s4, be4));
-    }
+    if (APPLY) ln_scale_shift(ln, g4, be4, s4, t4);
 #pragma unroll
     for (int k_ = 0; k_ < NLOAD; ++k_) {
       v4f y = araw[k_];
@@ -203,37 +234,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
         y = __builtin_elementwise_max(__builtin_elementwise_fma(y, s4, t4), v4f{0.f, 0.f, 0.f, 0.f});
         if (has_pad && !pok[k_]) y = v4f{0.f, 0.f, 0.f, 0.f};   /* padding is zero AFTER the normalisation */
       }
-      if (NPL == 2) {   /* y = h + m' 2^-11, fp16 parts (round to nearest even; y - h is exact in fp32) */
-        typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-        typedef unsigned u2x_t __attribute__((ext_vector_type(2)));
-        f16_range_track(amax_, y);
-        const h2_t ha = {(_Float16)y.x, (_Float16)y.y}, hb = {(_Float16)y.z, (_Float16)y.w};
-        const h2_t ma = {(_Float16)((y.x - (float)ha.x) * 2048.f), (_Float16)((y.y - (float)ha.y) * 2048.f)};
-        const h2_t mb = {(_Float16)((y.z - (float)hb.x) * 2048.f), (_Float16)((y.w - (float)hb.y) * 2048.f)};
-        if (lds_a[k_] != 0xffffffffu) {
-          *reinterpret_cast<u2x_t *>(smem + lds_a[k_]) = u2x_t{__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb)};
-          *reinterpret_cast<u2x_t *>(smem + lds_a[k_] + 64) = u2x_t{__builtin_bit_cast(unsigned, ma), __builtin_bit_cast(unsigned, mb)};
-        }
-      } else {
-      /* y = h + m + l, bf16 parts (round to nearest even; y - h and (y - h) - m are exact in fp32) */
-      unsigned h0, h1, m0, m1, l0, l1;
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(h0) : "v"(y.x), "v"(y.y));
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(h1) : "v"(y.z), "v"(y.w));
-      v4f r = y - v4f{__builtin_bit_cast(float, h0 << 16), __builtin_bit_cast(float, h0 & 0xffff0000u),
-                      __builtin_bit_cast(float, h1 << 16), __builtin_bit_cast(float, h1 & 0xffff0000u)};
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(m0) : "v"(r.x), "v"(r.y));
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(m1) : "v"(r.z), "v"(r.w));
-      r = r - v4f{__builtin_bit_cast(float, m0 << 16), __builtin_bit_cast(float, m0 & 0xffff0000u),
-                  __builtin_bit_cast(float, m1 << 16), __builtin_bit_cast(float, m1 & 0xffff0000u)};
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(l0) : "v"(r.x), "v"(r.y));
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(l1) : "v"(r.z), "v"(r.w));
-      if (lds_a[k_] != 0xffffffffu) {
-        typedef unsigned u2x_t __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<u2x_t *>(smem + lds_a[k_]) = u2x_t{h0, h1};
-        *reinterpret_cast<u2x_t *>(smem + lds_a[k_] + 64) = u2x_t{m0, m1};
-        *reinterpret_cast<u2x_t *>(smem + lds_a[k_] + 128) = u2x_t{l0, l1};
-      }
-    }
+      split_store<NPL>(smem, lds_a[k_], y, amax_);
     }
   };
   // ---- MFMA side ----
@@ -248,7 +249,6 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
 #pragma unroll
   for (int s_ = 0; s_ < 2; ++s_)
     b_s[s_] = lds_base + G::A_BYTES + (wn * 32 + frow) * G::B_ROW + (((2 * s_ + fh) ^ ((frow >> 2) & 3)) << 4);
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   f32x16 acc[MT][1], acc_lo;   // (NPL == 2: acc = h.h, acc_lo = (h.m' + m'.h), folded as acc + acc_lo 2^-11 after the loop)
 #pragma unroll
@@ -284,6 +284,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
       for (int s_ = 0; s_ < 2; ++s_) {
         if (s_ == 0) wait_lgkm4<4>(ah_[0], bh_[0], am_[0], bm_[0]);
         else wait_lgkm4<0>(ah_[1], bh_[1], am_[1], bm_[1]);
+        /* (split_mfma<2>, spelled out: through the helper the fp16-form instantiations hold acc and acc_lo in each other's registers) */
         acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bm_[s_]), __builtin_bit_cast(f16x8, ah_[s_]), acc_lo, 0, 0, 0);
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh_[s_]), __builtin_bit_cast(f16x8, ah_[s_]), acc[0][0], 0, 0, 0);
         acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh_[s_]), __builtin_bit_cast(f16x8, am_[s_]), acc_lo, 0, 0, 0);
@@ -334,12 +335,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
       for (int s_ = 0; s_ < 2; ++s_) {
       if (s_ == 0) wait_lgkm6<6>(ah_[0], bh_[0], am_[0], bm_[0], al_[0], bl_[0]);
       else wait_lgkm6<0>(ah_[1], bh_[1], am_[1], bm_[1], al_[1], bl_[1]);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm_[s_]), __builtin_bit_cast(bf16x8, am_[s_]), acc[0][0], 0, 0, 0);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh_[s_]), __builtin_bit_cast(bf16x8, al_[s_]), acc[0][0], 0, 0, 0);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bl_[s_]), __builtin_bit_cast(bf16x8, ah_[s_]), acc[0][0], 0, 0, 0);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh_[s_]), __builtin_bit_cast(bf16x8, am_[s_]), acc[0][0], 0, 0, 0);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm_[s_]), __builtin_bit_cast(bf16x8, ah_[s_]), acc[0][0], 0, 0, 0);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh_[s_]), __builtin_bit_cast(bf16x8, ah_[s_]), acc[0][0], 0, 0, 0);
+      split_mfma<3>(acc[0][0], acc_lo, ah_[s_], am_[s_], al_[s_], bh_[s_], bm_[s_], bl_[s_]);
       __builtin_amdgcn_sched_barrier(0);
       if (s_ == 0) {
         if (TAP == 0 && c + 1 < c1) patch_load(c + 1);
@@ -368,11 +364,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   if (APPLY) {   // the sums' round trip rides on the patch's (s_stat sits in the A region: read back before the patch lands)
     double *s_stat = reinterpret_cast<double *>(smem);
     ln_mean_inv_pre(shard, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-    const double mu = s_stat[0];
-    inv_f = (float)s_stat[1];
-    mu_hi = (float)mu;
-    mu_lo = (float)(mu - (double)mu_hi);
-    __syncthreads();
+    ln = ln_affine_read(s_stat);
   }
   wait_vmcnt<0>();
   patch_store();
@@ -391,14 +383,9 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
     }
   }
   if (MSI_X2_LATE_CB && NPL == 2) load_coord_bias(p, tile_m, tile_n, tid, cbv);   // (fp16 form: 16 registers less through the loop -- a fourth workgroup per CU)
-  if (NPL == 2) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][0][r] = __builtin_fmaf(acc_lo[r], 1.f / 2048.f, acc[0][0][r]);
-    // an operand beyond the fp16 range became inf (h) and NaN (m'): the layer's output is garbage -- say so
-    if (__builtin_amdgcn_ballot_w64(amax_ > F16_MAX_BITS) != 0 && lane == 0) atomicOr(p.status, STATUS_F16_SPLIT_RANGE);
-  }
+  split_finish<NPL>(acc[0][0], acc_lo, amax_, lane, p.status);
 
-  // ---- epilogue: as conv_igemm_kernel ----
+  // ---- epilogue: split-K hand-off (cnn_device.h), then the tile ----
 #ifdef MSI_CONV_TIMING
   const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
   auto stamp = [&]() __attribute__((always_inline)) {
@@ -410,9 +397,10 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
     }
   };
 #endif
-  if (!full) {
+  // (splitk_arrive / splitk_sum, spelled out: through them the fp16-form instantiations schedule one address instruction of the slab stores elsewhere)
+  if (!w.full) {
     constexpr int SLAB = BM * 64 * 4;
-    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)slot * (BM * 64)), 0, SLAB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)w.slot * (BM * 64)), 0, SLAB, 0x00020000);
     if (p.tile_cnt == nullptr) {
       dump_acc<MT, NT, 0>(acc, rsrc_p, tid);
 #ifdef MSI_CONV_TIMING
@@ -421,17 +409,17 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
       return;
     }
     dump_acc<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_p, tid);
-    const int nsp = t < p.n_main ? p.split0 : p.split;
+    const int nsp = w.t < p.n_main ? p.split0 : p.split;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     handoff_release();
     __syncthreads();
     int *s_old = reinterpret_cast<int *>(smem);
     if (tid == 0)
-      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (w.t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (*s_old != nsp - 1) return;
     handoff_acquire();
-    const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)(slot - ks) * (BM * 64)), 0, nsp * SLAB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)(w.slot - w.ks) * (BM * 64)), 0, nsp * SLAB, 0x00020000);
     sum_slabs<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_t, nsp, SLAB, tid);
     __syncthreads();   // (every thread has read s_old before the epilogue's strips reuse LDS)
   }
@@ -457,67 +445,6 @@ conv_halo8_x3_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   conv_halo_x3_body<1, APPLY, NPL, 8>(p, smem);
 #endif
-}
-
-// ---- shared pieces of the split kernels' stride-2 / conv-transpose forms (NP = 3: bf16 h | m | l, six products; NP = 2: fp16 h | m', three) ----
-template <int NP>
-__device__ __forceinline__ void split_store(char *smem, unsigned off, v4f y, unsigned &amax) {
-  typedef unsigned u2x_t __attribute__((ext_vector_type(2)));
-  if (NP == 2) {   // y = h + m' 2^-11, fp16 parts (round to nearest even; y - h is exact in fp32)
-    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-    f16_range_track(amax, y);
-    const h2_t ha = {(_Float16)y.x, (_Float16)y.y}, hb = {(_Float16)y.z, (_Float16)y.w};
-    const h2_t ma = {(_Float16)((y.x - (float)ha.x) * 2048.f), (_Float16)((y.y - (float)ha.y) * 2048.f)};
-    const h2_t mb = {(_Float16)((y.z - (float)hb.x) * 2048.f), (_Float16)((y.w - (float)hb.y) * 2048.f)};
-    if (off != 0xffffffffu) {
-      *reinterpret_cast<u2x_t *>(smem + off) = u2x_t{__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb)};
-      *reinterpret_cast<u2x_t *>(smem + off + 64) = u2x_t{__builtin_bit_cast(unsigned, ma), __builtin_bit_cast(unsigned, mb)};
-    }
-  } else {         // y = h + m + l, bf16 parts (see conv_halo_x3_kernel)
-    unsigned h0, h1, m0, m1, l0, l1;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(h0) : "v"(y.x), "v"(y.y));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(h1) : "v"(y.z), "v"(y.w));
-    v4f r = y - v4f{__builtin_bit_cast(float, h0 << 16), __builtin_bit_cast(float, h0 & 0xffff0000u),
-                    __builtin_bit_cast(float, h1 << 16), __builtin_bit_cast(float, h1 & 0xffff0000u)};
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(m0) : "v"(r.x), "v"(r.y));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(m1) : "v"(r.z), "v"(r.w));
-    r = r - v4f{__builtin_bit_cast(float, m0 << 16), __builtin_bit_cast(float, m0 & 0xffff0000u),
-                __builtin_bit_cast(float, m1 << 16), __builtin_bit_cast(float, m1 & 0xffff0000u)};
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(l0) : "v"(r.x), "v"(r.y));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(l1) : "v"(r.z), "v"(r.w));
-    if (off != 0xffffffffu) {
-      *reinterpret_cast<u2x_t *>(smem + off) = u2x_t{h0, h1};
-      *reinterpret_cast<u2x_t *>(smem + off + 64) = u2x_t{m0, m1};
-      *reinterpret_cast<u2x_t *>(smem + off + 128) = u2x_t{l0, l1};
-    }
-  }
-}
-// the products of one K16 step (weights = the MFMA's row operand), small terms first; NP = 2: lo collects h.m' + m'.h
-template <int NP>
-__device__ __forceinline__ void split_mfma(f32x16 &acc, f32x16 &lo, const v4f &ah, const v4f &am, const v4f &al, const v4f &bh, const v4f &bm, const v4f &bl) {
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-  if (NP == 2) {
-    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bm), __builtin_bit_cast(f16x8, ah), lo, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, ah), acc, 0, 0, 0);
-    lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, am), lo, 0, 0, 0);
-  } else {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, am), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, al), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bl), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, am), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
-  }
-}
-// NP = 2, after the k-loop: acc += lo 2^-11; an operand beyond the fp16 range (h = inf, m' = NaN) is reported
-template <int NP>
-__device__ __forceinline__ void split_finish(f32x16 &acc, const f32x16 &lo, unsigned amax, int lane, int *status) {
-  if (NP == 2) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = __builtin_fmaf(lo[r], 1.f / 2048.f, acc[r]);
-    if (__builtin_amdgcn_ballot_w64(amax > F16_MAX_BITS) != 0 && lane == 0) atomicOr(status, STATUS_F16_SPLIT_RANGE);
-  }
 }
 
 // ---- the stride-2 halo-patch kernel through the six-product bf16 split (conv_halo_s2_kernel x conv_halo_x3_kernel; r04) ----------
@@ -550,37 +477,12 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  // ---- work decomposition: as conv_halo_kernel (tail split; K-ranges in whole 32-channel groups) ----
+  // ---- work decomposition: tail split (tile_work), K-ranges in whole 32-channel groups ----
   const int CH = p.cpt0;
-  int t, c0 = 0, c1 = CH, ks = 0, slot = 0;
-  {
-    const int bid = blockIdx.x;
-    if (bid < p.nb_main && p.split0 == 1) {
-      const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    } else {
-      int sp, r, tbase;
-      unsigned mg;
-      if (bid < p.nb_main) { sp = p.split0; mg = p.mg_sp0; r = bid; tbase = 0; }
-      else { sp = p.split; mg = p.mg_sp; r = bid - p.nb_main; tbase = p.n_main; }
-      const int tl = (int)udiv_magic((unsigned)r, (unsigned)sp, mg);
-      ks = r - tl * sp;
-      t = tbase + tl;
-      c0 = (int)udiv_magic((unsigned)(ks * CH), (unsigned)sp, mg);
-      c1 = (int)udiv_magic((unsigned)((ks + 1) * CH), (unsigned)sp, mg);
-      slot = bid - (p.split0 == 1 ? p.nb_main : 0);
-    }
-  }
-  const bool full = (c0 == 0) & (c1 == CH);
-  int tile_m, tile_n, b;
-  {
-    int r = t;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  const TileWork w = tile_work(p, CH);
+  const int c0 = w.k0, c1 = w.k1;
+  const TileIndex ti = tile_index(p, w.t);
+  const int tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
   const int oh0 = tyi * TH, ow0 = (tile_m - tyi * p.halo_tx) * 16;   // the tile of the OUTPUT grid
   const int H = p.Hin, W = p.Win, C = p.C0;
@@ -659,11 +561,7 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
   // registers -> LDS patch, the producer's affine + ReLU applied (ln_apply_kernel's expressions: same bits)
   auto patch_store = [&](auto U_c) __attribute__((always_inline)) {
     constexpr int U = decltype(U_c)::value;
-    if (APPLY && U == 0) {
-      s4 = inv_f * g4;
-      const v4f nh = {-mu_hi, -mu_hi, -mu_hi, -mu_hi}, nl = {-mu_lo, -mu_lo, -mu_lo, -mu_lo};
-      t4 = __builtin_elementwise_fma(nl, s4, __builtin_elementwise_fma(nh, s4, be4));
-    }
+    if (APPLY && U == 0) ln_scale_shift(LnAffine{inv_f, mu_hi, mu_lo}, g4, be4, s4, t4);
 #pragma unroll
     for (int k_ = 0; k_ < NLOAD; ++k_) {
       v4f y = araw[k_];
@@ -794,11 +692,8 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
   if (APPLY) {
     double *s_stat = reinterpret_cast<double *>(smem);
     ln_mean_inv(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-    const double mu = s_stat[0];
-    inv_f = (float)s_stat[1];
-    mu_hi = (float)mu;
-    mu_lo = (float)(mu - (double)mu_hi);
-    __syncthreads();
+    const LnAffine a = ln_affine_read(s_stat);
+    inv_f = a.inv; mu_hi = a.mu_hi; mu_lo = a.mu_lo;
   }
   wait_vmcnt<0>();
   patch_store(IC<0>{});
@@ -811,28 +706,10 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
   }
   split_finish<NP>(acc[0][0], acc_lo, amax_, lane, p.status);
 
-  // ---- epilogue: as conv_halo_kernel ----
-  if (!full) {
-    constexpr int SLAB = BM * 64 * 4;
-    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)slot * (BM * 64)), 0, SLAB, 0x00020000);
-    if (p.tile_cnt == nullptr) {
-      dump_acc<MT, NT, 0>(acc, rsrc_p, tid);
-      return;
-    }
-    dump_acc<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_p, tid);
-    const int nsp = t < p.n_main ? p.split0 : p.split;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    handoff_release();
-    __syncthreads();
-    int *s_old = reinterpret_cast<int *>(smem);
-    if (tid == 0)
-      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (*s_old != nsp - 1) return;
-    handoff_acquire();
-    const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + (size_t)(slot - ks) * (BM * 64)), 0, nsp * SLAB, 0x00020000);
-    sum_slabs<MT, NT, MSI_HANDOFF_AUX>(acc, rsrc_t, nsp, SLAB, tid);
-    __syncthreads();   // (s_old has been read by every thread before the strip below reuses LDS)
+  // ---- epilogue: split-K hand-off (cnn_device.h), then the tile ----
+  if (!w.full) {
+    if (!splitk_arrive<MT, NT>(p, acc, w, smem, tid)) return;
+    splitk_sum<MT, NT>(p, acc, w, tid);
   }
   emit_tile<BM, 64, MODE_CONV>(p, acc, tile_m, tile_n, 0, b, tid, smem);
 }
@@ -890,36 +767,10 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int CH = p.cpt0 + p.cpt1;                         // 32-channel chunks of both sources
-  int t, c0 = 0, c1 = CH, ks = 0, slot = 0;
-  {
-    const int bid = blockIdx.x;
-    if (bid < p.nb_main && p.split0 == 1) {
-      const int q = p.n_main >> 3, r = p.n_main & 7, xcd = bid & 7, local = bid >> 3;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    } else {
-      int sp, r, tbase;
-      unsigned mg;
-      if (bid < p.nb_main) { sp = p.split0; mg = p.mg_sp0; r = bid; tbase = 0; }
-      else { sp = p.split; mg = p.mg_sp; r = bid - p.nb_main; tbase = p.n_main; }
-      const int tl = (int)udiv_magic((unsigned)r, (unsigned)sp, mg);
-      ks = r - tl * sp;
-      t = tbase + tl;
-      c0 = (int)udiv_magic((unsigned)(ks * CH), (unsigned)sp, mg);
-      c1 = (int)udiv_magic((unsigned)((ks + 1) * CH), (unsigned)sp, mg);
-      slot = bid - (p.split0 == 1 ? p.nb_main : 0);
-    }
-  }
-  const bool full = (c0 == 0) & (c1 == CH);
-  int ph, tile_m, tile_n, b;
-  {   // row parity fastest (p.nclass = 2 here), then M tiles, N tiles, samples
-    int r = t;
-    ph = r & 1; r >>= 1;
-    const int q1 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_m, p.mg_tm);
-    tile_m = r - q1 * p.tiles_m; r = q1;
-    const int q2 = (int)udiv_magic((unsigned)r, (unsigned)p.tiles_n, p.mg_tn);
-    tile_n = r - q2 * p.tiles_n;
-    b = q2;
-  }
+  const TileWork w = tile_work(p, CH);
+  const int c0 = w.k0, c1 = w.k1;
+  const TileIndex ti = tile_index<TILE_ROW_PARITY>(p, w.t);   // row parity fastest (p.nclass = 2 here), then M tiles, N tiles, samples
+  const int ph = ti.cls, tile_m = ti.tile_m, tile_n = ti.tile_n, b = ti.b;
   const int tyi = (int)udiv_magic((unsigned)tile_m, (unsigned)p.halo_tx, p.mg_htx);
   const int oh0 = tyi * TH, ow0 = (tile_m - tyi * p.halo_tx) * 16;
   const int H = p.Hin, W = p.Win;
@@ -1007,7 +858,7 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
     v4f s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
     if (ap_) {
       const float ih_ = src_ld ? inv_f[1] : inv_f[0], mh_ = src_ld ? mu_hi[1] : mu_hi[0], ml_ = src_ld ? mu_lo[1] : mu_lo[0];
-      s4 = ih_ * g4;
+      s4 = ih_ * g4;   // (ln_scale_shift, spelled out: through it this kernel's prologue changes)
       const v4f nh = {-mh_, -mh_, -mh_, -mh_}, nl = {-ml_, -ml_, -ml_, -ml_};
       t4 = __builtin_elementwise_fma(nl, s4, __builtin_elementwise_fma(nh, s4, be4));
     }
@@ -1138,15 +989,13 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
     double *s_stat = reinterpret_cast<double *>(smem);
     if (p.halo_apply & 1) {
       ln_mean_inv(p.ln_sums + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n, p.ln_scl_src, p.status, s_stat, tid);
-      const double mu = s_stat[0];
-      inv_f[0] = (float)s_stat[1]; mu_hi[0] = (float)mu; mu_lo[0] = (float)(mu - (double)mu_hi[0]);
-      __syncthreads();
+      const LnAffine a = ln_affine_read(s_stat);
+      inv_f[0] = a.inv; mu_hi[0] = a.mu_hi; mu_lo[0] = a.mu_lo;
     }
     if (p.halo_apply & 2) {
       ln_mean_inv(p.ln_sums1 + (size_t)b * LN_SHARDS * LN_WORDS, p.ln_inv_n1, p.ln_scl_src1, p.status, s_stat, tid);
-      const double mu = s_stat[0];
-      inv_f[1] = (float)s_stat[1]; mu_hi[1] = (float)mu; mu_lo[1] = (float)(mu - (double)mu_hi[1]);
-      __syncthreads();
+      const LnAffine a = ln_affine_read(s_stat);
+      inv_f[1] = a.inv; mu_hi[1] = a.mu_hi; mu_lo[1] = a.mu_lo;
     }
   }
   wait_vmcnt<0>();
@@ -1165,34 +1014,36 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
   split_finish<NP>(acc[1][0][0], acc_lo[1], amax_, lane, p.status);
 
   // ---- epilogue: two class tiles ----
-  if (!full) {
+  // (the hand-off of cnn_device.h in its two-class form -- class-minor slabs: slot stride 2, slab stride 2 SLAB, no closing barrier -- spelled out: written over a
+  // two-class splitk_arrive / splitk_sum this body's instruction stream changes from its first instructions on)
+  if (!w.full) {
     constexpr int SLAB = BM * 64 * 4;
     if (p.tile_cnt == nullptr) {                          // separate fix-up launch (conv_fixup_kernel, class = blockIdx.y)
 #pragma unroll
       for (int cl = 0; cl < 2; ++cl) {
-        const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + ((size_t)slot * 2 + cl) * (BM * 64)), 0, SLAB, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + ((size_t)w.slot * 2 + cl) * (BM * 64)), 0, SLAB, 0x00020000);
         dump_acc<MT, 1, 0>(acc[cl], rsrc_p, tid);
       }
       return;
     }
 #pragma unroll
     for (int cl = 0; cl < 2; ++cl) {
-      const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + ((size_t)slot * 2 + cl) * (BM * 64)), 0, SLAB, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + ((size_t)w.slot * 2 + cl) * (BM * 64)), 0, SLAB, 0x00020000);
       dump_acc<MT, 1, MSI_HANDOFF_AUX>(acc[cl], rsrc_p, tid);
     }
-    const int nsp = t < p.n_main ? p.split0 : p.split;
+    const int nsp = w.t < p.n_main ? p.split0 : p.split;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     handoff_release();
     __syncthreads();
     int *s_old = reinterpret_cast<int *>(smem);
     if (tid == 0)
-      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      *s_old = __hip_atomic_fetch_add(p.tile_cnt + (w.t - (p.split0 == 1 ? p.n_main : 0)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (*s_old != nsp - 1) return;
     handoff_acquire();
 #pragma unroll
     for (int cl = 0; cl < 2; ++cl) {
-      const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + ((size_t)(slot - ks) * 2 + cl) * (BM * 64)), 0, nsp * 2 * SLAB, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc((void *)(p.partial + ((size_t)(w.slot - w.ks) * 2 + cl) * (BM * 64)), 0, nsp * 2 * SLAB, 0x00020000);
       sum_slabs<MT, 1, MSI_HANDOFF_AUX>(acc[cl], rsrc_t, nsp, 2 * SLAB, tid);
     }
   }
