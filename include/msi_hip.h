@@ -285,6 +285,37 @@ int msi_render_views_packed(const void *layers, int32_t format, const float *tgt
                             int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
                             int32_t camera, int32_t out_height, int32_t out_width,
                             float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
+/* The ODS stereo camera of the viewer (MSI.render_views(camera='ods'), MSI.render_ods_pair; no reference counterpart): V ODS
+ * views of each MSI per launch -- both eyes of a stereo 360 frame are V = 2 -- from a stack of any `format` (MSI_LAYERS_*),
+ * at any output size, rgb and one-channel depth.  It is the MSI_CAMERA_EQUIRECT camera of msi_render_views_f32 with the ray
+ * origin moved onto the viewing circle (it is an entry point of its own, not a camera code: the codes of the three
+ * *_render_views functions stay 0 and 1).  Pixel (i, j) of the lat-long grid of the OUTPUT size, before the pose:
+ *     direction  r = (cos S_j cos T_i, sin T_i, sin S_j cos T_i)                               -- the equirect camera's
+ *     origin     c = (tgt_pos[2] + sin S_j * e, tgt_pos[1], tgt_pos[0] + (-cos S_j) * e)       -- e = eye_radius[b*V + v]
+ *   then r <- pose[:3,:3] r, c <- pose (c, 1) and the per-layer arithmetic of msi_render_views_f32, op for op.
+ *   (sin S, 0, -cos S) . r = 0: the ray is tangent to the circle of radius |e| around the head position.  e is SIGNED:
+ *   e = +baseline is the left eye (the reference's order = +1, its ref image), e = -baseline the right eye (the src image).
+ *   layers [B,D,H,W] texels of `format`, depths [D] (far -> near), tgt_pose_rt [B*V,4,4], tgt_pos [B*V,3], eye_radius [B*V]
+ *   (view v of sample b at index b*V + v), trig = the msi_build_trig_tables_host table of (out_height, out_width);
+ *   out_rgb [B,V,out_height,out_width,3], out_depth [B,V,out_height,out_width]; either may be NULL, not both.
+ * Three facts fix the convention (tests/test_ods_views_cpu.py holds the composed CPU reference to them, the GPU tests the kernel):
+ *   1. e = 0 is the equirect camera: the outputs are bit-identical to msi_render_views_f32 / msi_render_views_packed with
+ *      MSI_CAMERA_EQUIRECT for the same poses, positions and size.
+ *   2. Output column j is column W-1-j of msi_render_ods_f32 (which keeps the reference's order, mirrored against its inputs):
+ *      at the stack's size with tgt_pos = 0, e = order * intrinsics[b,0,0] and the same pose the two agree to rounding (the
+ *      trig table is not exactly symmetric, so not bit for bit).
+ *   3. It is upright and the eye sign is the sweep's: an image swept with msi_ods_sphere_sweep_f32 (order, one depth) and
+ *      rendered back as a single opaque layer with e = order * baseline reproduces the image unflipped; e = -order * baseline
+ *      does not.
+ * status_device (may be NULL): the origin differs from pixel to pixel here, so MSI_RENDER_STATUS_ORIGIN_OUTSIDE is set when ANY
+ * rendered pixel's origin is not strictly inside every sphere it is intersected with, or is NaN -- also when only a part of
+ * the circle leaves the innermost sphere (every lane tests its own origin; one atomic OR per wavefront).  Pixels stay finite
+ * (clamped discriminant), as in the other renders.  batch = 0 returns MSI_OK after validation, without a launch. */
+int msi_render_ods_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                         const float *eye_radius, const float *depths, const float *trig,
+                         int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                         int32_t out_height, int32_t out_width,
+                         float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -25,6 +25,10 @@ weights are used (there is no network access for the pretrained checkpoint), ste
 levels the PNG files hold) and writes <output_root>/<experiment>/scores.json: example names, ssim and psnr per example, their means,
 and with on_video the mean absolute difference of consecutive output_tgt / output_depth frames per scene -- the numbers of
 matryodshka_amd.evaluate without reading the files back.
+`--recon_score` (with --score, ODS inputs) also renders each sample's two INPUT eyes back from its MSI -- one MSI.render_ods_pair
+launch at the sample's own baseline, identity pose -- writes them as recon_ref_<dir>.png / recon_src_<dir>.png (upright, unlike
+the reference-compatible output_ref / output_src) and scores them against ref_image / src_image the same way: scores.json gains
+recon_ref_ssim, recon_ref_psnr, recon_src_ssim, recon_src_psnr and their mean_recon_* means.
 Host I/O only: all arithmetic is in libmsi_hip.so.
 """
 import argparse
@@ -121,6 +125,7 @@ class DeviceScores(object):
     def __init__(self, model, keep_frames=False):
         self.model, self.keep_frames = model, keep_frames
         self.names, self.scores, self.frames = [], [], {}
+        self.recon = None       # --recon_score: {"ref": [score dicts], "src": [...]}, one entry per scored sample
 
     def add(self, dirname, scene, tgt_image, output_tgt, output_depth=None):
         """tgt_image: the float image handed to write_image; output_tgt / output_depth: the uint8 device images written."""
@@ -131,11 +136,26 @@ class DeviceScores(object):
         if self.keep_frames:
             self.frames.setdefault(scene, []).append((dirname, output_tgt, output_depth))
 
+    def add_recon(self, ref_image, src_image, recon_ref, recon_src):
+        """--recon_score: the float input images handed to write_image and the uint8 device images of the two eyes rendered back."""
+        import torch
+        if self.recon is None:
+            self.recon = {"ref": [], "src": []}
+        for key, image, recon in (("ref", ref_image, recon_ref), ("src", src_image, recon_src)):
+            tgt = torch.from_numpy(np.clip(np.asarray(image), 0, 255).astype("uint8")).to(self.model.device)
+            self.recon[key].append(self.model.score_views(recon, tgt, metrics=("ssim", "psnr")))
+
     def table(self):
         import torch
         ssim, psnr = ([float(s[k]) for s in self.scores] for k in ("ssim", "psnr"))
         table = {"examples": self.names, "ssim": ssim, "psnr": psnr,
                  "mean_ssim": float(np.mean(ssim)) if ssim else None, "mean_psnr": float(np.mean(psnr)) if psnr else None}
+        if self.recon is not None:
+            for eye in ("ref", "src"):
+                for k in ("ssim", "psnr"):
+                    vals = [float(s[k]) for s in self.recon[eye]]
+                    table["recon_%s_%s" % (eye, k)] = vals
+                    table["mean_recon_%s_%s" % (eye, k)] = float(np.mean(vals)) if vals else None
         if self.keep_frames:
             table["consecutive"] = []
             for scene in sorted(self.frames):
@@ -150,10 +170,11 @@ class DeviceScores(object):
 
 
 def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_outputs, output_dir, dirname,
-               which_color_pred="blend_psv", jitter_pose=None, msi_format=None, scorer=None, scene=None):
+               which_color_pred="blend_psv", jitter_pose=None, msi_format=None, scorer=None, scene=None, recon=False):
     """One iteration of the loop at test.py:199-281.  images = (ref, src, tgt) float [H,W,3] in [0,1]
     (image order ref, src, tgt: data_loader.py:134-136).  msi_format ('rgba8' | 'rgba16f'): the sample's inference also
-    emits the packed stack, saved as msi_<dirname>.npz; every other output is unchanged."""
+    emits the packed stack, saved as msi_<dirname>.npz; every other output is unchanged.  recon (--recon_score; needs scorer):
+    both input eyes rendered back from the MSI in one launch, written as recon_ref_* / recon_src_* and scored."""
     import torch
     ref, src, tgt = (torch.from_numpy(np.ascontiguousarray(x[None])) for x in images)
     eye = np.eye(4, dtype=np.float32)[None]
@@ -207,6 +228,12 @@ def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_o
         write_image(os.path.join(output_dir, "output_tgt_%s.png" % dirname), rgb8.cpu().numpy())
         write_image(os.path.join(output_dir, "output_depth_%s.png" % dirname), dep8.cpu().numpy())
         if scorer is not None:
+            if recon:       # (before scorer.add: a sample the domain guard refuses here adds to neither list)
+                pair = model.render_ods_pair(outs["rgba_layers"], planes, intrinsics=intr)       # [1,2,H,W,3]: left = ref, right = src
+                pair8 = model.deprocess_image(pair[0])
+                write_image(os.path.join(output_dir, "recon_ref_%s.png" % dirname), pair8[0].cpu().numpy())
+                write_image(os.path.join(output_dir, "recon_src_%s.png" % dirname), pair8[1].cpu().numpy())
+                scorer.add_recon(ref[0].numpy() * 255.0, src[0].numpy() * 255.0, pair8[0], pair8[1])
             scorer.add(dirname, scene, tgt[0].numpy() * 255.0, rgb8, dep8)
         if jouts is not None:        # test.py:160-165 renders through the jitter pose; :237-240 (the reference reads a
             # 'jitter_output_depth' it never produces -- here the depth is rendered the same way)
@@ -362,10 +389,17 @@ def main(argv=None):
     ap.add_argument("--score", action="store_true",
                     help="score output_tgt against tgt_image on the device (MSI.score_views) and write <experiment>/scores.json: ssim and "
                          "psnr per example and their means; with on_video also the consecutive-frame differences per scene; default: off")
+    ap.add_argument("--recon_score", action="store_true",
+                    help="with --score, ODS inputs: render both input eyes back from each sample's MSI in one launch (MSI.render_ods_pair), "
+                         "write recon_ref_<dir>.png / recon_src_<dir>.png and add their ssim / psnr against ref_image / src_image to scores.json")
     ap.add_argument("--strict", action="store_true",
                     help="abort at the first sample whose LayerNorm statistics leave the kernels' fixed-point window or whose target "
                          "position lies outside the innermost sphere (default: write UNRELIABLE.txt next to its files and go on)")
     args = ap.parse_args(argv)
+    if args.recon_score and not args.score:
+        ap.error("--recon_score needs --score")
+    if args.recon_score and args.input_type != "ODS":
+        ap.error("--recon_score renders ODS eyes: --input_type ODS only")
     if args.num_psv_planes != args.num_msi_planes:
         raise SystemExit("--num_psv_planes must equal --num_msi_planes (msi.py:138 indexes the source volume with num_msi_planes)")
     if "high_res" in args.test_type and args.input_type != "ODS":
@@ -419,7 +453,7 @@ def main(argv=None):
                         jitter = poses.random_rotation(args.rot_factor, args.tr_factor, jitter_rng)
                     run_sample(model, images, cam[0], cam[1:4], planes, d, args.ngf, args.test_outputs, out_dir, dirname,
                                which_color_pred=args.which_color_pred, jitter_pose=jitter, msi_format=args.msi_format,
-                               scorer=scorer, scene=scene)
+                               scorer=scorer, scene=scene, recon=args.recon_score)
                 model.render_status()        # raises if a render's ray origin was outside the innermost sphere
             except (MsiError, ValueError) as e:
                 # a sample whose statistics leave the LayerNorm window (a heuristic built from the weights) or whose target lies

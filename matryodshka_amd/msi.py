@@ -610,10 +610,11 @@ class MSI(object):
         return out
 
     # ------------------------------------------------------------------ viewer: many views of one MSI per launch
-    CAMERAS = {'equirect': N.MSI_CAMERA_EQUIRECT, 'pinhole': N.MSI_CAMERA_PINHOLE}
+    # ('ods' is not a camera code of the native library: it has its own entry point, msi_render_ods_views)
+    CAMERAS = {'equirect': N.MSI_CAMERA_EQUIRECT, 'pinhole': N.MSI_CAMERA_PINHOLE, 'ods': None}
 
     def render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, camera='equirect', intrinsics=None, size=None,
-                     want_rgb=True, want_depth=True):
+                     want_rgb=True, want_depth=True, eye=None, baseline=None):
         """V views of each MSI in ONE launch (msi_render_views_f32; no reference counterpart) -> (rgb, depth):
         rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w] (one channel: msi_render_equirect_depth(...)[..., 0]); either is None
         when switched off.
@@ -629,13 +630,26 @@ class MSI(object):
                       along (1, (i + 0.5 - cy) / fy, (j + 0.5 - cx) / fx) before the pose: forward +x, image-down +y,
                       image-right +z -- with an identity pose the centre pixel looks where the centre of an equirect
                       render looks, with the same orientation.
+          'ods':      the eye panoramas of a stereo 360 frame (msi_render_ods_views): the equirect camera with the ray origin
+                      moved onto the viewing circle around the head position, (tgt_pos[2] + sin S * e, tgt_pos[1],
+                      tgt_pos[0] - cos S * e) before the pose, e = eye * baseline.  eye (required): +1 / 'left' (the
+                      reference's order = +1, the ref image) or -1 / 'right' (the src image), one for every view or an array
+                      [V] / [B,V].  baseline: a float, [B] or [B,V] (>= 0); None takes intrinsics[:, 0, 0], where the reference
+                      keeps it (intrinsics [B,3,3] or [1,3,3]).  With baseline 0 it is the equirect camera, bit for bit; the
+                      image is upright, i.e. msi_render_ods_view's flipped left-to-right.  eye and baseline belong to this
+                      camera only.
         Host-side poses and positions are checked for every view before the launch (ValueError when an origin is not
-        inside the innermost sphere); device-side ones are flagged through render_status().
+        inside the innermost sphere -- for 'ods': when |pose @ swap(tgt_pos)| + |e| >= min |planes|, which keeps the whole
+        circle inside); device-side ones are flagged through render_status().
         rgba_layers may be a PackedLayers (pack_layers; msi_render_views_packed): the kernel gathers from the compact stack
         itself and the outputs are bit-identical to rendering unpack_layers(rgba_layers).  planes=None then takes the planes
         the PackedLayers carries (ValueError when it carries none); for an fp32 stack planes is required."""
         if camera not in self.CAMERAS:
-            raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
+            raise ValueError("camera must be 'equirect', 'pinhole' or 'ods', not %r" % (camera,))
+        if camera != 'ods' and (eye is not None or baseline is not None):
+            raise ValueError("render_views: eye and baseline belong to camera='ods', not %r" % (camera,))
+        if camera == 'ods' and eye is None:
+            raise ValueError("render_views: camera='ods' needs eye (+1 / 'left' or -1 / 'right', or an array [V] / [B,V])")
         if not (want_rgb or want_depth):
             raise ValueError("render_views: want_rgb and want_depth are both False")
         packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
@@ -648,7 +662,8 @@ class MSI(object):
         if planes is None:
             raise ValueError("render_views: planes is required (only a PackedLayers that carries its planes may leave it out)")
         b, d, h, w, _ = native.shape
-        self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
+        if camera != 'ods':
+            self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
         pose, pos = self._f32(tgt_pose_rt), self._f32(tgt_pos)
         if b == 1 and pose.dim() == 3 and pos.dim() == 2:
             pose, pos = pose[None], pos[None]
@@ -661,6 +676,19 @@ class MSI(object):
         if depths.numel() != d:
             raise ValueError("len(planes) != number of layers")
         intr, trig = None, None
+        if camera == 'ods':
+            oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
+            radius = self._eye_radius(eye, baseline, intrinsics, b, v)
+            self._ods_domain_guard(tgt_pos, tgt_pose_rt, planes, radius)
+            radius = self._f32(radius).reshape(b * v)
+            rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
+            dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
+            fmt = self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+            N.check(N.lib.msi_render_ods_views(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(), radius.data_ptr(),
+                                               depths.data_ptr(), self._trig(oh, ow).data_ptr(), b, v, h, w, d, oh, ow,
+                                               _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream()),
+                    "msi_render_ods_views")
+            return rgb, dep
         if camera == 'equirect':
             oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
             trig = self._trig(oh, ow)
@@ -685,6 +713,95 @@ class MSI(object):
                                            _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep),
                                            self._render_status.data_ptr(), self._stream()), "msi_render_views_f32")
         return rgb, dep
+
+    EYES = {'left': 1.0, 'right': -1.0}
+
+    def _eye_radius(self, eye, baseline, intrinsics, b, v):
+        """The signed radius e = eye * baseline of every view, [B,V]: a numpy array when eye and baseline are host-side (values
+        checked here: eye in +-1, baseline finite and >= 0), a device tensor when either lives on the device (shapes only: no sync)."""
+        if isinstance(eye, str):
+            if eye not in self.EYES:
+                raise ValueError("eye must be +1 / 'left' or -1 / 'right', not %r" % (eye,))
+            eye = self.EYES[eye]
+        if baseline is None:
+            if intrinsics is None:
+                raise ValueError("camera='ods' needs baseline, or intrinsics [B,3,3] that carry it in [:, 0, 0]")
+            intr = intrinsics if torch.is_tensor(intrinsics) else np.asarray(intrinsics, dtype=np.float32)
+            if tuple(intr.shape) not in ((b, 3, 3), (1, 3, 3)):
+                raise ValueError("intrinsics must be [B,3,3] = %s or [1,3,3], got %s" % ((b, 3, 3), tuple(intr.shape)))
+            baseline = intr[:, 0, 0] if intr.shape[0] == b else intr[0, 0, 0]
+        if any(torch.is_tensor(t) and t.is_cuda for t in (eye, baseline)):
+            ey, bl = self._f32(eye), self._f32(baseline)
+            broadcast = torch.broadcast_to
+        else:
+            ey = np.asarray(eye.cpu() if torch.is_tensor(eye) else eye, dtype=np.float32)
+            bl = np.asarray(baseline.cpu() if torch.is_tensor(baseline) else baseline, dtype=np.float32)
+            broadcast = lambda x, shape: np.array(np.broadcast_to(x, shape), dtype=np.float32)      # (a writable copy)
+            if not np.all(np.abs(ey) == 1.0):
+                raise ValueError("eye must be +1 (left) or -1 (right)")
+            if not (np.all(np.isfinite(bl)) and np.all(bl >= 0)):
+                raise ValueError("baseline must be finite and >= 0")
+        if tuple(ey.shape) not in ((), (v,), (b, v)):
+            raise ValueError("eye must be a scalar, [V] or [B,V] = %s, got %s" % ((b, v), tuple(ey.shape)))
+        if tuple(bl.shape) not in ((), (b,), (b, v)):
+            raise ValueError("baseline must be a scalar, [B] or [B,V] = %s, got %s" % ((b, v), tuple(bl.shape)))
+        if bl.ndim == 1:
+            bl = bl.reshape(b, 1)                                   # ([B]: per sample, also when B = V)
+        return broadcast(ey * bl, (b, v))
+
+    @staticmethod
+    def _ods_domain_guard(tgt_pos, pose, planes, radius):
+        """_domain_guard for the ODS camera (host-side only, skipped when any input lives on the device: the kernel flags those):
+        every point of the viewing circle is within |e| of the head position pose @ swap(tgt_pos), so
+        |pose @ swap(tgt_pos)| + |e| < min |planes| is sufficient for every origin of the view to lie inside the innermost sphere."""
+        if any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, pose, planes, radius)):
+            return
+        tp = np.asarray(torch.as_tensor(tgt_pos), dtype=np.float64).reshape(-1, 3)
+        c = np.stack([tp[:, 2], tp[:, 1], tp[:, 0]], axis=1)
+        ps = np.asarray(torch.as_tensor(pose), dtype=np.float64).reshape(-1, 4, 4)
+        e = np.abs(np.asarray(radius, dtype=np.float64).reshape(-1))
+        if ps.shape[0] != c.shape[0] or e.shape[0] != c.shape[0]:
+            return      # the shape checks report it
+        centre = np.einsum('bij,bj->bi', ps[:, :3, :3], c) + ps[:, :3, 3]
+        pl = np.asarray(planes.cpu() if torch.is_tensor(planes) else planes, dtype=np.float64)
+        if not np.all(np.linalg.norm(centre, axis=1) + e < np.abs(pl).min()):
+            raise ValueError("the ODS viewing circle (|pose @ tgt_pos| + |eye * baseline|) must lie inside the innermost sphere "
+                             "(radius %g)" % np.abs(pl).min())
+
+    def render_ods_pair(self, rgba_layers, planes=None, baseline=None, intrinsics=None, tgt_pose_rt=None, tgt_pos=None, size=None,
+                        layout='views', want_depth=False):
+        """Both eyes of each sample's stereo 360 frame in ONE launch (render_views(camera='ods') with V = 2: left then right,
+        sharing one pose and head position) -> rgb, or (rgb, depth) with want_depth.
+        tgt_pose_rt [B,4,4] (or one [4,4]; default identity), tgt_pos [B,3] (or one [3]; default 0); planes, baseline,
+        intrinsics and size as in render_views -- with the sample's own baseline, identity pose and position 0 the two views are
+        the input pair (ref image = left) as the MSI reproduces it.
+        layout='views': rgb [B,2,h,w,3], depth [B,2,h,w].  'top_bottom': the SAME storage as [B,2h,w,3] / [B,2h,w], left eye on
+        top -- the delivery format of 360 players, without a copy."""
+        if layout not in ('views', 'top_bottom'):
+            raise ValueError("layout must be 'views' or 'top_bottom', not %r" % (layout,))
+        b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]
+
+        def per_view(x, default, tail):
+            if x is None:
+                return np.tile(default, (b, 2) + (1,) * len(tail))
+            x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+            if tuple(x.shape) == tail:
+                x = x.expand((b,) + tail)
+            if tuple(x.shape) != (b,) + tail:
+                raise ValueError("render_ods_pair: expected %s or %s, got %s" % ((b,) + tail, tail, tuple(x.shape)))
+            return x[:, None].expand((b, 2) + tail)
+        pose = per_view(tgt_pose_rt, np.eye(4, dtype=np.float32), (4, 4))
+        pos = per_view(tgt_pos, np.zeros(3, np.float32), (3,))
+        if baseline is not None:
+            shape = tuple(baseline.shape) if hasattr(baseline, "shape") else np.shape(baseline)
+            if shape not in ((), (b,)):
+                raise ValueError("render_ods_pair: baseline must be a float or [B] = %s, got %s" % ((b,), shape))
+        rgb, dep = self.render_views(rgba_layers, pose, pos, planes, camera='ods', intrinsics=intrinsics, size=size,
+                                     want_rgb=True, want_depth=want_depth, eye=np.array([1.0, -1.0], np.float32), baseline=baseline)
+        if layout == 'top_bottom':
+            rgb = rgb.view(b, 2 * rgb.shape[2], rgb.shape[3], 3)
+            dep = dep.view(b, 2 * dep.shape[2], dep.shape[3]) if dep is not None else None
+        return (rgb, dep) if want_depth else rgb
 
     # ------------------------------------------------------------------ compact stacks (matryodshka_amd/packed.py)
     LAYER_FORMATS = {'rgba8': N.MSI_LAYERS_RGBA8, 'rgba16f': N.MSI_LAYERS_RGBA16F}
@@ -946,7 +1063,7 @@ class MSI(object):
         Host-side poses and positions are checked before the launch (ValueError when an origin is not strictly inside the
         innermost shell: max |o_k| >= min planes); device-side ones are flagged through render_status()."""
         from . import cubemap
-        if camera not in self.CAMERAS:
+        if camera not in ('equirect', 'pinhole'):
             raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
         if not (want_rgb or want_depth):
             raise ValueError("cube_render_views: want_rgb and want_depth are both False")
