@@ -106,7 +106,10 @@ __device__ __forceinline__ void split_store(char *smem, unsigned off, v4f y, uns
     }
   }
 }
-// the products of one K16 step (weights = the MFMA's row operand), small terms first; NP = 2: lo collects h.m' + m'.h
+// the products of one K16 step (weights = the MFMA's row operand), small terms first; NP = 2: lo collects h.m' + m'.h.  NP = 3: lo collects the five small products and
+// acc h.h alone -- with all six in one accumulator every k-step rounds six times at the full magnitude of the running sum, and the chain's error against fp64 (rms 7e-7 ..
+// 9e-7 of the layer at K = 4608) is 2.4 x that of one rounding per k-step; lo's roundings are 2^-8 of that.  One more accumulator per 32 x 32 block: NP = 6 keeps the single
+// accumulator for the one tile that has no registers for it (convt_halo8_x3_kernel: four blocks; 256 VGPRs and scratch with four more).
 template <int NP>
 __device__ __forceinline__ void split_mfma(f32x16 &acc, f32x16 &lo, const v4f &ah, const v4f &am, const v4f &al, const v4f &bh, const v4f &bm, const v4f &bl) {
   typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -115,22 +118,32 @@ __device__ __forceinline__ void split_mfma(f32x16 &acc, f32x16 &lo, const v4f &a
     lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bm), __builtin_bit_cast(f16x8, ah), lo, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, ah), acc, 0, 0, 0);
     lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, am), lo, 0, 0, 0);
-  } else {
+  } else if (NP == 6) {   // all six into acc (the 8-row conv-transpose tile: four accumulators, no registers for four more)
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, am), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, al), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bl), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, am), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
+  } else {
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, am), lo, 0, 0, 0);
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, al), lo, 0, 0, 0);
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bl), __builtin_bit_cast(bf16x8, ah), lo, 0, 0, 0);
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, am), lo, 0, 0, 0);
+    lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bm), __builtin_bit_cast(bf16x8, ah), lo, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bh), __builtin_bit_cast(bf16x8, ah), acc, 0, 0, 0);
   }
 }
-// NP = 2, after the k-loop: acc += lo 2^-11; an operand beyond the fp16 range (h = inf, m' = NaN) is reported
+// after the k-loop.  NP = 2: acc += lo 2^-11; an operand beyond the fp16 range (h = inf, m' = NaN) is reported.  NP = 3: acc += lo
 template <int NP>
 __device__ __forceinline__ void split_finish(f32x16 &acc, const f32x16 &lo, unsigned amax, int lane, int *status) {
   if (NP == 2) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = __builtin_fmaf(lo[r], 1.f / 2048.f, acc[r]);
     if (__builtin_amdgcn_ballot_w64(amax > F16_MAX_BITS) != 0 && lane == 0) atomicOr(status, STATUS_F16_SPLIT_RANGE);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] += lo[r];
   }
 }
 
@@ -250,11 +263,11 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   for (int s_ = 0; s_ < 2; ++s_)
     b_s[s_] = lds_base + G::A_BYTES + (wn * 32 + frow) * G::B_ROW + (((2 * s_ + fh) ^ ((frow >> 2) & 3)) << 4);
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-  f32x16 acc[MT][1], acc_lo;   // (NPL == 2: acc = h.h, acc_lo = (h.m' + m'.h), folded as acc + acc_lo 2^-11 after the loop)
+  f32x16 acc[MT][1], acc_lo, acc_lo1;   // (NPL == 2: acc = h.h, acc_lo = (h.m' + m'.h), folded as acc + acc_lo 2^-11 after the loop; NPL == 3: acc_lo / acc_lo1 = the small products of block 0 / 1)
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][0][r] = acc_lo[r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[i][0][r] = acc_lo[r] = acc_lo1[r] = 0.f;
 
   // one k-step = tap TAP of the current chunk, weights in ring stage TAP % 3; the DMA of the k-step two ahead is issued
   // after the first MFMA quarter; before the closing barrier the NEXT k-step's weights must have landed: every VMEM
@@ -312,13 +325,13 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
       xh_[1][1] = lds_read128<A1_ + 32>(a_base); xm_[1][1] = lds_read128<A1_ + 96>(a_base); xl_[1][1] = lds_read128<A1_ + 160>(a_base);
       if (TAP == 0 && c + 1 < c1) patch_load(c + 1);
       wait_lgkm6<9>(xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
-      split_mfma<3>(acc[1][0], acc_lo, xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
+      split_mfma<3>(acc[1][0], acc_lo1, xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
       __builtin_amdgcn_sched_barrier(0);
       wait_lgkm6<3>(bh_[1], bm_[1], bl_[1], xh_[1][0], xm_[1][0], xl_[1][0]);
       split_mfma<3>(acc[0][0], acc_lo, xh_[1][0], xm_[1][0], xl_[1][0], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
       wait_lgkm6<0>(xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
-      split_mfma<3>(acc[1][0], acc_lo, xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
+      split_mfma<3>(acc[1][0], acc_lo1, xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
@@ -384,6 +397,7 @@ __device__ __forceinline__ void conv_halo_x3_body(const ConvParams &p, char *sme
   }
   if (MSI_X2_LATE_CB && NPL == 2) load_coord_bias(p, tile_m, tile_n, tid, cbv);   // (fp16 form: 16 registers less through the loop -- a fourth workgroup per CU)
   split_finish<NPL>(acc[0][0], acc_lo, amax_, lane, p.status);
+  if constexpr (MT == 2 && NPL == 3) split_finish<3>(acc[1][0], acc_lo1, amax_, lane, p.status);   // (block 1's small products; the 8-row tile has the six-product form only)
 
   // ---- epilogue: split-K hand-off (cnn_device.h), then the tile ----
 #ifdef MSI_CONV_TIMING
@@ -583,10 +597,10 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
   for (int s_ = 0; s_ < 2; ++s_)
     b_s[s_] = lds_base + G::A_BYTES + (wn * 32 + frow) * G::B_ROW + (((2 * s_ + fh) ^ ((frow >> 2) & 3)) << 4);
   typedef __bf16 bf16x8 __attribute__((ext_vector_type(8), unused));
-  f32x16 acc[MT][1], acc_lo;
+  f32x16 acc[MT][1], acc_lo, acc_lo1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    acc_lo[r] = 0.f;
+    acc_lo[r] = acc_lo1[r] = 0.f;
 #pragma unroll
     for (int i = 0; i < MT; ++i) acc[i][0][r] = 0.f;
   }
@@ -626,13 +640,13 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
         else patch_load(c + 1, IC<0>{});
       }
       wait_lgkm6<9>(xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
-      split_mfma<3>(acc[1][0], acc_lo, xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
+      split_mfma<3>(acc[1][0], acc_lo1, xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
       __builtin_amdgcn_sched_barrier(0);
       wait_lgkm6<3>(bh_[1], bm_[1], bl_[1], xh_[1][0], xm_[1][0], xl_[1][0]);
       split_mfma<3>(acc[0][0], acc_lo, xh_[1][0], xm_[1][0], xl_[1][0], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
       wait_lgkm6<0>(xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
-      split_mfma<3>(acc[1][0], acc_lo, xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
+      split_mfma<3>(acc[1][0], acc_lo1, xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
@@ -705,6 +719,7 @@ __device__ __forceinline__ void conv_halo_s2_x3_body(const ConvParams &p, char *
     s2step(IC<5>{}); s2step(IC<6>{}); s2step(IC<7>{}); s2step(IC<8>{});
   }
   split_finish<NP>(acc[0][0], acc_lo, amax_, lane, p.status);
+  if constexpr (MT == 2 && NP == 3) split_finish<3>(acc[1][0], acc_lo1, amax_, lane, p.status);   // (block 1's small products; the 8-row tile has the six-product form only)
 
   // ---- epilogue: split-K hand-off (cnn_device.h), then the tile ----
   if (!w.full) {
@@ -887,7 +902,7 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
   for (int s_ = 0; s_ < 2; ++s_)
     b_s[s_] = lds_base + G::A_BYTES + (wn * 32 + frow) * G::B_ROW + (((2 * s_ + fh) ^ ((frow >> 2) & 3)) << 4);
   typedef __bf16 bf16x8 __attribute__((ext_vector_type(8), unused));
-  f32x16 acc[2][MT][1], acc_lo[2];   // [class][32-pixel block]
+  f32x16 acc[2][MT][1], acc_lo[2];   // [class][32-pixel block]; acc_lo: the class's small products (MT = 1; the 8-row tile keeps one accumulator per block: split_mfma<6>)
 #pragma unroll
   for (int cl = 0; cl < 2; ++cl)
 #pragma unroll
@@ -925,19 +940,19 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
       xh_[0][1] = lds_read128<C1_>(ab_); xm_[0][1] = lds_read128<C1_ + 64>(ab_); xl_[0][1] = lds_read128<C1_ + 128>(ab_);
       bh_[1] = lds_read128<0>(b_s[1] + bst_); bm_[1] = lds_read128<G::B_PLANE>(b_s[1] + bst_); bl_[1] = lds_read128<2 * G::B_PLANE>(b_s[1] + bst_);
       wait_lgkm6<6>(bh_[0], bm_[0], bl_[0], xh_[0][0], xm_[0][0], xl_[0][0]);
-      split_mfma<3>(acc[PWC_][0][0], acc_lo[PWC_], xh_[0][0], xm_[0][0], xl_[0][0], bh_[0], bm_[0], bl_[0]);
+      split_mfma<6>(acc[PWC_][0][0], acc_lo[PWC_], xh_[0][0], xm_[0][0], xl_[0][0], bh_[0], bm_[0], bl_[0]);
       __builtin_amdgcn_sched_barrier(0);
       xh_[1][0] = lds_read128<COFF_ + 32>(ab_); xm_[1][0] = lds_read128<COFF_ + 96>(ab_); xl_[1][0] = lds_read128<COFF_ + 160>(ab_);
       xh_[1][1] = lds_read128<C1_ + 32>(ab_); xm_[1][1] = lds_read128<C1_ + 96>(ab_); xl_[1][1] = lds_read128<C1_ + 160>(ab_);
       if (J == 0 && c + 1 < c1) patch_load(c + 1);
       wait_lgkm6<9>(xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
-      split_mfma<3>(acc[PWC_][1][0], acc_lo[PWC_], xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
+      split_mfma<6>(acc[PWC_][1][0], acc_lo[PWC_], xh_[0][1], xm_[0][1], xl_[0][1], bh_[0], bm_[0], bl_[0]);
       __builtin_amdgcn_sched_barrier(0);
       wait_lgkm6<3>(bh_[1], bm_[1], bl_[1], xh_[1][0], xm_[1][0], xl_[1][0]);
-      split_mfma<3>(acc[PWC_][0][0], acc_lo[PWC_], xh_[1][0], xm_[1][0], xl_[1][0], bh_[1], bm_[1], bl_[1]);
+      split_mfma<6>(acc[PWC_][0][0], acc_lo[PWC_], xh_[1][0], xm_[1][0], xl_[1][0], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
       wait_lgkm6<0>(xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
-      split_mfma<3>(acc[PWC_][1][0], acc_lo[PWC_], xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
+      split_mfma<6>(acc[PWC_][1][0], acc_lo[PWC_], xh_[1][1], xm_[1][1], xl_[1][1], bh_[1], bm_[1], bl_[1]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
@@ -1010,8 +1025,10 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
       __builtin_amdgcn_s_barrier();
     }
   }
-  split_finish<NP>(acc[0][0][0], acc_lo[0], amax_, lane, p.status);
-  split_finish<NP>(acc[1][0][0], acc_lo[1], amax_, lane, p.status);
+  if constexpr (MT == 1) {   // (the 8-row tile runs split_mfma<6>: everything is in acc already, acc_lo is never written)
+    split_finish<NP>(acc[0][0][0], acc_lo[0], amax_, lane, p.status);
+    split_finish<NP>(acc[1][0][0], acc_lo[1], amax_, lane, p.status);
+  }
 
   // ---- epilogue: two class tiles ----
   // (the hand-off of cnn_device.h in its two-class form -- class-minor slabs: slot stride 2, slab stride 2 SLAB, no closing barrier -- spelled out: written over a
@@ -1052,7 +1069,7 @@ __device__ __forceinline__ void convt_halo_x3_body(const ConvParams &p, char *sm
 }
 
 template <int NP>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, MSI_CT_MAXW)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP == 3 ? 3 : 2, MSI_CT_MAXW)))   // (NP = 3: two more accumulators; asked for three waves the allocator stays at 168 VGPRs, left alone it takes 170 = two waves)
 convt_halo_x3_kernel(const ConvParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];

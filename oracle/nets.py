@@ -185,18 +185,40 @@ def conv_split_f16(fn, x, w):
     return fn(xh, wh) + (fn(xm, wh) + fn(xh, wm)) * (1.0 / 2048.0)
 
 
-def forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False, forced_raw=None):
-    """split3_products: False | True (six bf16 products, conv_split3) | "f16" (three fp16 products, conv_split_f16).
+def forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False, forced_raw=None,
+            precision="fp32", forced_act=None):
+    """split3_products: False | True (six bf16 products, conv_split3) | "f16" (three fp16 products, conv_split_f16) | a callable
+    (layer name, fn, x, w) -> fn's result by an arithmetic of the caller's (tools/f32_forced_gates.py: one of the two forms with a fault in one layer).
+    Every convolution, conv-transpose (msi_train_net's VALID ones included) and the head is computed in the chosen form.
     bf16: False | True | "scaled" (True with the fp16 raw storage's power-of-two pre-scale explicit: layer_norm_relu).
     forced_raw: None | {layer name: [B,H,W,C] fp32 numpy} -- teacher forcing.  A layer named there still computes and records
     its own raw output (acts[name + "/raw"]) from the inputs it has, but everything downstream of it carries on from
     forced_raw[name] instead: LayerNorm statistics in fp64 of THOSE values, affine, ReLU, (bf16) rounding.  With every layer
     forced to another implementation's stored raw outputs, acts[L + "/raw"] is what layer L alone should have made of that
-    implementation's own upstream results; the returned prediction is the head of the forced conv8_2."""
-    return _forward(weights, net_input, coord_net, return_activations, bf16, split3_products, forced_raw)
+    implementation's own upstream results; the returned prediction is the head of the forced conv8_2.
+    forced_act: None | {layer name: [B,H,W,C] fp32 numpy} -- the same for an implementation that keeps a layer's ACTIVATION (LayerNorm + ReLU applied in place)
+    and no raw output: the layer records its own raw output and its own activation (acts[name]), its consumers read forced_act[name] (msi_train_net's
+    conv-transposes: the [5:-5] crop, which is all a consumer reads).  A layer is named in at most one of the two.
+    precision: "fp32" | "fp64" -- "fp64" is the high-precision reference of the fp32 tier: the same graph with every tensor and every operation in
+    torch.float64 (convolutions, conv-transposes, the coordinate channel -- whose VALUES stay the fp32 ones of add_sph_coords, they are the network's --
+    LayerNorm with an unrounded affine, ReLU, the head and tanh); results are returned as float64 arrays.  Not combined with bf16 or split3_products."""
+    return _forward(weights, net_input, coord_net, return_activations, bf16, split3_products, forced_raw, precision, forced_act)
 
 
-def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False, forced_raw=None):
+def _layer_norm_relu_f64(x, gamma, beta, affine_out=None):
+    """layer_norm_relu entirely in fp64: two-pass statistics, the affine unrounded."""
+    mean = x.mean(dim=(1, 2, 3), keepdim=True)
+    var = ((x - mean) ** 2).mean(dim=(1, 2, 3), keepdim=True)
+    inv = torch.rsqrt(var + LN_EPS)
+    scale = inv * torch.from_numpy(gamma).view(1, -1, 1, 1).double()
+    shift = torch.from_numpy(beta).view(1, -1, 1, 1).double() - mean * scale
+    if affine_out is not None:
+        affine_out.append(torch.stack([scale.flatten(1), shift.flatten(1)], dim=1).numpy())
+    return torch.relu(x * scale + shift)
+
+
+def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=False, split3_products=False, forced_raw=None,
+             precision="fp32", forced_act=None):
     """msi_coord_train_net (nets.py:471-515) / msi_train_net (:387-450).
     net_input: np [B,H,W,Cin] fp32.  Returns np [B,H,W,num_outputs] fp32.
 
@@ -206,9 +228,18 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
     LayerNorm statistics are taken from the unrounded accumulators, the raw convolution output is kept as
     fp16 (r03: half the activation bytes; measured here: mean |bf16 variant - fp32 network| + 0.3 %, max within
     its seed-to-seed noise; a bf16 raw output would be + 19 %) and the affine, the head bias and tanh are fp32."""
+    assert precision in ("fp32", "fp64"), precision
+    f64 = precision == "fp64"
+    assert not (f64 and (bf16 or split3_products)), "precision='fp64' is the plain graph in float64"
+    assert not (set(forced_raw or ()) & set(forced_act or ())), "a layer is forced by its raw output or by its activation"
+    dt = torch.float64 if f64 else torch.float32
     rnd = bf16_round if bf16 else (lambda t: t)
     split_fn = conv_split_f16 if split3_products == "f16" else conv_split3
-    x = rnd(torch.from_numpy(np.ascontiguousarray(np.transpose(net_input, (0, 3, 1, 2)))).float())
+
+    def split_of(name):     # the layer's product form (a callable split3_products is told the layer)
+        return (lambda fn, a, b_: split3_products(name, fn, a, b_)) if callable(split3_products) else split_fn
+
+    x = rnd(torch.from_numpy(np.ascontiguousarray(np.transpose(net_input, (0, 3, 1, 2)))).to(dt))
     acts = {}
     affines = {}
 
@@ -217,7 +248,7 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
         y[:, :, crop:-crop, crop:-crop] only and is pasted into a copy of y)."""
         if forced_raw is None or name not in forced_raw:
             return y
-        f = torch.from_numpy(np.ascontiguousarray(np.transpose(np.asarray(forced_raw[name], dtype=F32), (0, 3, 1, 2))))
+        f = torch.from_numpy(np.ascontiguousarray(np.transpose(np.asarray(forced_raw[name], dtype=F32), (0, 3, 1, 2)))).to(dt)
         if crop is None:
             assert f.shape == y.shape, (name, tuple(f.shape), tuple(y.shape))
             return f
@@ -228,14 +259,25 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
 
     def ln(name, y):
         out = []
-        y = layer_norm_relu(y, weights[name + "/LayerNorm/gamma"], weights[name + "/LayerNorm/beta"], affine_out=out, raw16=bf16)
+        if f64:
+            y = _layer_norm_relu_f64(y, weights[name + "/LayerNorm/gamma"], weights[name + "/LayerNorm/beta"], affine_out=out)
+        else:
+            y = layer_norm_relu(y, weights[name + "/LayerNorm/gamma"], weights[name + "/LayerNorm/beta"], affine_out=out, raw16=bf16)
         affines[name] = out[0]
         return y
 
+    def handed_on(name, y):
+        """The activation y of layer `name` as its consumers read it: y, or forced_act[name] in its place."""
+        if forced_act is None or name not in forced_act:
+            return y
+        f = torch.from_numpy(np.ascontiguousarray(np.transpose(np.asarray(forced_act[name], dtype=F32), (0, 3, 1, 2)))).to(dt)
+        assert f.shape == y.shape, (name, tuple(f.shape), tuple(y.shape))
+        return f
+
     def conv(name, x, stride=1, rate=1):
-        w = rnd(_conv_w(weights[name + "/weights"]))
+        w = rnd(_conv_w(weights[name + "/weights"])).to(dt)
         if coord_net:
-            x = rnd(add_sph_coords(x))
+            x = rnd(add_sph_coords(x)).to(dt)
             _, _, h, wd = x.shape
             pt, pb = _same_pad(h, 2 * rate + 1, stride)
             pl, pr = _same_pad(wd, 2 * rate + 1, stride)
@@ -243,19 +285,19 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
         else:
             x = wrap_pad(x, rate, rate)
         if split3_products:
-            y = split_fn(lambda a, b_: TF.conv2d(a, b_, stride=stride, dilation=rate), x, w)
+            y = split_of(name)(lambda a, b_: TF.conv2d(a, b_, stride=stride, dilation=rate), x, w)
         else:
             y = TF.conv2d(x, w, stride=stride, dilation=rate)
         acts[name + "/raw"] = y
         y = rnd(ln(name, forced(name, y)))
         acts[name] = y
-        return y
+        return handed_on(name, y)
 
     def convT(name, x):
-        w = rnd(_convT_w(weights[name + "/weights"]))
+        w = rnd(_convT_w(weights[name + "/weights"])).to(dt)
         if coord_net:
             if split3_products:
-                y = split_fn(lambda a, b_: TF.conv_transpose2d(a, b_, stride=2, padding=1), x, w)
+                y = split_of(name)(lambda a, b_: TF.conv_transpose2d(a, b_, stride=2, padding=1), x, w)
             else:
                 y = TF.conv_transpose2d(x, w, stride=2, padding=1)
             acts[name + "/raw"] = y
@@ -265,13 +307,16 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
             # layer_norm arg_scope, so LayerNorm + ReLU cover the FULL (2H+10) x (2W+10) output -- zero rows and
             # wrap columns of the border included -- and the [5:-5] crop happens afterwards, in the consumer's
             # input expression (cnv6_1[:,5:-5,5:-5,:], nets.py:426)
-            y = TF.conv_transpose2d(wrap_pad(x, 2, 2), w, stride=2, padding=0)
+            if split3_products:
+                y = split_of(name)(lambda a, b_: TF.conv_transpose2d(a, b_, stride=2, padding=0), wrap_pad(x, 2, 2), w)
+            else:
+                y = TF.conv_transpose2d(wrap_pad(x, 2, 2), w, stride=2, padding=0)
             acts[name + "/raw"] = y[:, :, 5:-5, 5:-5]
             # (the statistics cover the uncropped output; an implementation stores the crop: forced values are pasted into the oracle's own border)
             y = rnd(ln(name, forced(name, y, crop=5)))
             y = y[:, :, 5:-5, 5:-5]
         acts[name] = y
-        return y
+        return handed_on(name, y)
 
     with torch.no_grad():
         c11 = conv("conv1_1", x)
@@ -291,10 +336,10 @@ def _forward(weights, net_input, coord_net=True, return_activations=False, bf16=
         c72 = conv("conv7_2", c71)
         c81 = convT("conv8_1", torch.cat([c72, c12], dim=1))
         c82 = conv("conv8_2", c81)
-        w = rnd(_conv_w(weights["color_pred/weights"]))
-        b = torch.from_numpy(weights["color_pred/biases"])
+        w = rnd(_conv_w(weights["color_pred/weights"])).to(dt)
+        b = torch.from_numpy(weights["color_pred/biases"]).to(dt)
         if split3_products:
-            pred = torch.tanh(split_fn(lambda a, b_: TF.conv2d(a, b_), c82, w) + b.view(1, -1, 1, 1))
+            pred = torch.tanh(split_of("color_pred")(lambda a, b_: TF.conv2d(a, b_), c82, w) + b.view(1, -1, 1, 1))
         else:
             pred = torch.tanh(TF.conv2d(c82, w, bias=b))
     out = np.ascontiguousarray(pred.permute(0, 2, 3, 1).numpy())

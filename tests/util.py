@@ -160,3 +160,83 @@ def forced_layer_errors(weights, x, coord, raws, pred, gates=None, kernels=None)
             " [%s]" % kernels[17][0] if kernels else "", eh.max(), gates["head_max"], int(over.sum()),
             ", first at (b, y, x, c) = %r" % (tuple(int(i) for i in np.argwhere(over)[0]),) if over.any() else "", eh.mean(), gates["head_mean"]))
     return rep
+
+
+# ---- the teacher-forced layer check of the fp32 tier, against an fp64 reference
+# Gates of forced_layer_errors_f32 per ARITHMETIC of a layer's kernel, MEASURED ON THE CPU (tools/f32_forced_gates.py, profiles/f32_forced_gates.txt): 3 x the worst
+# value, over all 17 layers, shapes A / B / C / E of tests/test_plan_decomposition.py at ngf 32 and 64 and five seeds each, of the oracle's own emulation of that
+# arithmetic (forward(split3_products=True | "f16" | False, forced_raw=R)) against forward(precision="fp64", forced_raw=R).  Never set from a device run.
+# layer_*: relative to the fp64 tensor's max-abs (max) and rms (rms); head_*: the same of the tanh output (the head always runs the native tap kernel: its gates are "native"'s).
+F32_FORCED_GATES = {
+    "x3": dict(layer_max=1.40e-6, layer_rms=5.23e-7, head_max=9.36e-7, head_rms=2.04e-7),         # worst 4.665e-7 1.743e-7 | 3.121e-7 6.797e-8
+    "f16": dict(layer_max=3.12e-6, layer_rms=1.25e-6, head_max=1.98e-6, head_rms=3.63e-7),        # worst 1.039e-6 4.168e-7 | 6.600e-7 1.210e-7
+    "native": dict(layer_max=3.41e-6, layer_rms=1.26e-6, head_max=1.83e-6, head_rms=3.03e-7),     # worst 1.138e-6 4.202e-7 | 6.113e-7 1.009e-7
+}
+
+
+def f32_arithmetic(kernel):
+    """The arithmetic of an fp32 plan's kernel, read off its msi_net_plan_layer_kernel name: "x3" (six bf16 products), "f16" (three fp16 products: the split
+    kernels whose last template argument, the plane count, is 2) or "native" (fp32 MFMA: conv_halo*_kernel, conv_igemm_kernel)."""
+    if "_x3_kernel" not in kernel:
+        return "native"
+    return "f16" if "_x3_kernel<" in kernel and kernel.endswith("2>") else "x3"
+
+
+def rel_max_rms(got, ref):
+    """(max |got - ref| / max |ref|, rms (got - ref) / rms ref), in fp64."""
+    ref = np.asarray(ref, dtype=np.float64)
+    d = np.asarray(got, dtype=np.float64) - ref
+    return (float(np.abs(d).max() / (np.abs(ref).max() + 1e-300)), float(np.sqrt((d * d).mean()) / (np.sqrt((ref * ref).mean()) + 1e-300)))
+
+
+def forced_layer_errors_f32(weights, x, coord, stored, normalized, pred, gates=None, kernels=None):
+    """One run of the teacher-forced fp64 oracle (oracle/nets.py forward(precision="fp64", forced_raw=..., forced_act=...)) on what an fp32 plan left in its
+    workspace: `stored` = {layer: [B,H,W,C] fp32} for all 17 layers, `normalized` = the layers whose buffer holds the ACTIVATION (the plan applied LayerNorm + ReLU
+    in place: msi_net_plan_layer_is_normalized != 0), every other buffer the raw output.  Every layer is recomputed in fp64 from the stored tensors of its OWN
+    sources, so a layer's error is that layer's alone: its product form, its summation order, its operands' planes.  A normalized layer forces its consumers
+    with the stored activation and is compared as an activation (the oracle's own LayerNorm + ReLU, in fp64, of its own fp64 raw output); it is never left out.
+
+    Returns a dict:
+      "layers":   {layer: (max, rms)} of stored - fp64, the max relative to the fp64 tensor's max-abs, the rms to its rms;
+      "compared": {layer: "raw" | "activation"};
+      "head":     (max, rms) of pred - the forced fp64 prediction, relative in the same way;
+    and, with `gates` (F32_FORCED_GATES) and `kernels` (plan.kernels(): 18 entries whose first item is the kernel name; each layer is held to the gates of
+    f32_arithmetic(its kernel)),
+      "over":     {layer: elements above the max gate}, "first": {layer: (b, y, x, c) of the first of them};
+      "failed_layers": layers (and "color_pred") that miss a gate, "failures": one line each, with the layer's kernel."""
+    from oracle import nets as onets
+    names = [t[0] for t in onets.layer_table(1, 1) if t[1] != "h"]
+    assert sorted(stored) == sorted(names), sorted(stored)
+    normalized = set(normalized)
+    assert normalized <= set(names), sorted(normalized)
+    assert gates is None or (kernels is not None and len(kernels) == 18), "gates are per kernel arithmetic: pass the plan's kernels"
+    ref, acts = onets.forward(weights, x, coord_net=coord, return_activations=True, precision="fp64",
+                              forced_raw={n: stored[n] for n in names if n not in normalized},
+                              forced_act={n: stored[n] for n in names if n in normalized})
+    rep = dict(layers={}, compared={}, over={}, first={}, failed_layers=[], failures=[])
+    for li, name in enumerate(names):
+        what = "activation" if name in normalized else "raw"
+        o = acts[name] if name in normalized else acts[name + "/raw"]
+        assert stored[name].shape == o.shape, (name, stored[name].shape, o.shape)
+        rep["compared"][name] = what
+        rep["layers"][name] = mx, rms = rel_max_rms(stored[name], o)
+        if gates is None:
+            continue
+        g = gates[f32_arithmetic(kernels[li][0])]
+        over = np.abs(stored[name].astype(np.float64) - o) > g["layer_max"] * np.abs(o).max()
+        rep["over"][name] = int(over.sum())
+        if rep["over"][name]:
+            rep["first"][name] = tuple(int(i) for i in np.argwhere(over)[0])
+        if not (mx <= g["layer_max"] and rms <= g["layer_rms"]):         # (a NaN fails)
+            rep["failed_layers"].append(name)
+            rep["failures"].append("%s [%s, %s, %s]: max %.2e (gate %.2e; %d of %d elements over it%s), rms %.2e (gate %.2e)" % (
+                name, kernels[li][0], f32_arithmetic(kernels[li][0]), what, mx, g["layer_max"], rep["over"][name], over.size,
+                ", first at (b, y, x, c) = %r" % (rep["first"][name],) if rep["over"][name] else "", rms, g["layer_rms"]))
+    rep["head"] = hmx, hrms = rel_max_rms(pred, ref)
+    if gates is not None:
+        g = gates[f32_arithmetic(kernels[17][0])]
+        if not (hmx <= g["head_max"] and hrms <= g["head_rms"]):
+            rep["failed_layers"].append("color_pred")
+            rep["failures"].append("color_pred [%s, %s]: max %.2e (gate %.2e), rms %.2e (gate %.2e)" % (
+                kernels[17][0], f32_arithmetic(kernels[17][0]), hmx, g["head_max"], hrms, g["head_rms"]))
+    return rep
