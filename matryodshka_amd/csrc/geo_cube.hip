@@ -13,22 +13,11 @@
 
 namespace {
 
-template <int FMT> struct CubeTexelShift { static constexpr int value = TexelShift<FMT>::value; };
-template <> struct CubeTexelShift<MSI_LAYERS_F32> { static constexpr int value = 4; };
-
-template <int FMT>
-__device__ __forceinline__ float4 cube_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
-  if constexpr (FMT == MSI_LAYERS_F32)
-    return layer_tap(L, texel);
-  else
-    return packed_layer_tap<FMT>(L, texel);
-}
-
 // One thread per target pixel, the whole far-to-near composite in that thread (strictly sequential, as mpi_render_views_kernel: layer 0
 // replaces, then c a + acc (1 - a)); a workgroup is 64 x 4 pixels of one (sample, view), a wave one row.
-//   grid    1-D, sample -> view -> 4-row group -> 64-pixel block with render_views_kernel's XCD-aware mapping: the views of one cube follow each
+//   grid    1-D, sample -> view -> 4-row group -> 64-pixel block with the XCD-aware mapping of every many-views render (ViewBlock, geometry_device.h): the views of one cube follow each
 //           other through the Infinity Cache and adjacent row groups share an XCD's L2.
-//   rays    render_views_kernel's, op for op: (cos S cos T, sin T, sin S cos T) on the lat-long grid of the output or (1, (i + 0.5 - cy) / fy,
+//   rays    render_views_kernel's (view_ray and apply_pose, geometry_device.h): (cos S cos T, sin T, sin S cos T) on the lat-long grid of the output or (1, (i + 0.5 - cy) / fy,
 //           (j + 0.5 - cx) / fx), rotated by pose[:3,:3]; origin pose @ (tgt_pos[2], tgt_pos[1], tgt_pos[0], 1).  That render frame (forward +x,
 //           down +y, right +z) becomes the cube frame by swapping x and z.  Pose, origin and both cameras are wave-uniform (scalar loads).
 //   shell   For origin o, direction r and half-side h: t = min over the axes of (h sign(r_k) - o_k) / r_k, evaluated as h / |r_k| - o_k / r_k
@@ -51,46 +40,18 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
                          const float *__restrict__ depths, const float *__restrict__ trig, int batch, int views, int face, int nd,
                          int out_h, int out_w, float *__restrict__ out_rgb, float *__restrict__ out_depth, DepthFrac F,
                          int *__restrict__ status) {
-  const unsigned gx = (unsigned)(out_w + 63) >> 6, gy = (unsigned)(out_h + 3) >> 2;
-  const unsigned nblk = gx * gy * (unsigned)views * (unsigned)batch, per = gridDim.x >> 3;
-  const unsigned lin = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-  if (lin >= nblk) return;                              // (grid rounded up to a multiple of 8; whole workgroups leave)
-  const unsigned rowb = lin / gx;
-  const int j = (int)(lin - rowb * gx) * 64 + threadIdx.x;
-  const unsigned bv = rowb / gy;                        // sample * views + view
-  const int i = (int)(rowb - bv * gy) * 4 + threadIdx.y;
-  const int b = (int)(bv / (unsigned)views);
+  ViewBlock<4> k(out_h, out_w, views, batch);
+  if (k.past_end()) return;                             // (grid rounded up to a multiple of 8; whole workgroups leave)
+  k.decode(views);
+  const unsigned bv = k.bv;
+  const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;                 // (no barrier below; lane (0, 0) of a workgroup is always inside)
 
-  float rx, ry, rz;
-  if (CAMERA == MSI_CAMERA_PINHOLE) {
-    const float *Kv = intrinsics + (size_t)bv * 9;      // fx . cx / . fy cy
-    rx = 1.0f;
-    ry = (((float)i + 0.5f) - Kv[5]) / Kv[4];
-    rz = (((float)j + 0.5f) - Kv[2]) / Kv[0];
-  } else {
-    const float cs = trig[j], ss = trig[out_w + j];
-    const float ct = trig[2 * out_w + i], st = trig[2 * out_w + out_h + i];
-    rx = cs * ct; ry = st; rz = ss * ct;
-  }
-  const float *tp = tgt_pos + (size_t)bv * 3;
-  float cx = tp[2], cy = tp[1], cz = tp[0];
-  const float *P = pose_rt + (size_t)bv * 16;
-  {
-    const float x = (P[0] * rx + P[1] * ry) + P[2] * rz;
-    const float y = (P[4] * rx + P[5] * ry) + P[6] * rz;
-    const float z = (P[8] * rx + P[9] * ry) + P[10] * rz;
-    rx = x; ry = y; rz = z;
-  }
-  {
-    const float x = ((P[0] * cx + P[1] * cy) + P[2] * cz) + P[3] * 1.0f;
-    const float y = ((P[4] * cx + P[5] * cy) + P[6] * cz) + P[7] * 1.0f;
-    const float z = ((P[8] * cx + P[9] * cy) + P[10] * cz) + P[11] * 1.0f;
-    cx = x; cy = y; cz = z;
-  }
+  ViewRay r = view_ray<CAMERA>(intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);
+  apply_pose(pose_rt + (size_t)bv * 16, r);
   // render frame -> cube frame: x <-> z
-  const float dx = rz, dy = ry, dz = rx;
-  const float ox = cz, oy = cy, oz = cx;
+  const float dx = r.rz, dy = r.ry, dz = r.rx;
+  const float ox = r.cz, oy = r.cy, oz = r.cx;
   // t_k = h / |r_k| - o_k / r_k
   const float inf = __builtin_inff();
   const float ax = dx != 0.0f ? 1.0f / fabsf(dx) : inf, bx = dx != 0.0f ? ox / dx : 0.0f;
@@ -101,7 +62,7 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
   const float kfx = Ks[0], kcx = Ks[2], kfy = Ks[4], kcy = Ks[5];
   const float sm1 = (float)(face - 1);
   const unsigned ss2 = (unsigned)face * (unsigned)face, fstride = ss2 * (unsigned)nd;     // texels of a layer / of a face's stack
-  const size_t sample_bytes = ((size_t)6 * fstride) << CubeTexelShift<FMT>::value;          // (< 2^31, checked on the host)
+  const size_t sample_bytes = ((size_t)6 * fstride) << StackTexel<FMT>::shift;          // (< 2^31, checked on the host)
   const __amdgpu_buffer_rsrc_t L =
       __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + (size_t)b * sample_bytes), 0, (int)sample_bytes, 0x00020000);
   float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f;
@@ -129,21 +90,23 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
     const int x1 = min(x0 + 1, face - 1), y1 = min(y0 + 1, face - 1);
     const unsigned base = f * fstride + (unsigned)d * ss2;
     const unsigned r0 = base + (unsigned)y0 * (unsigned)face, r1 = base + (unsigned)y1 * (unsigned)face;
-    const float4 A = cube_tap<FMT>(L, r0 + (unsigned)x0), Bv = cube_tap<FMT>(L, r0 + (unsigned)x1);
-    const float4 C = cube_tap<FMT>(L, r1 + (unsigned)x0), Dv = cube_tap<FMT>(L, r1 + (unsigned)x1);
+    const float4 A = StackTexel<FMT>::tap(L, r0 + (unsigned)x0), Bv = StackTexel<FMT>::tap(L, r0 + (unsigned)x1);
+    const float4 C = StackTexel<FMT>::tap(L, r1 + (unsigned)x0), Dv = StackTexel<FMT>::tap(L, r1 + (unsigned)x1);
     const float wa = dy1 * dx1, wb = dy1 * dx0, wc = dy0 * dx1, wd = dy0 * dx0;
-    const float al = ((wa * A.w + wb * Bv.w) + wc * C.w) + wd * Dv.w;
+    float4 c;
+    c.w = ((wa * A.w + wb * Bv.w) + wc * C.w) + wd * Dv.w;
+    c.x = ((wa * A.x + wb * Bv.x) + wc * C.x) + wd * Dv.x;
+    c.y = ((wa * A.y + wb * Bv.y) + wc * C.y) + wd * Dv.y;
+    c.z = ((wa * A.z + wb * Bv.z) + wc * C.z) + wd * Dv.z;
+    const float al = c.w;
     if (MODE & RENDER_RGB) {
-      const float r = ((wa * A.x + wb * Bv.x) + wc * C.x) + wd * Dv.x;
-      const float g = ((wa * A.y + wb * Bv.y) + wc * C.y) + wd * Dv.y;
-      const float bl = ((wa * A.z + wb * Bv.z) + wc * C.z) + wd * Dv.z;
       if (d == 0) {
-        o0 = r; o1 = g; o2 = bl;
+        o0 = c.x; o1 = c.y; o2 = c.z;
       } else {
         const float om = 1.0f - al;
-        o0 = r * al + o0 * om;
-        o1 = g * al + o1 * om;
-        o2 = bl * al + o2 * om;
+        o0 = c.x * al + o0 * om;
+        o1 = c.y * al + o1 * om;
+        o2 = c.z * al + o2 * om;
       }
     }
     if (MODE & RENDER_DEPTH) {   // over_composite_depth: 0 at layer 0, then (d / D) a + out (1 - a)
@@ -156,12 +119,7 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
     const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
     if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
   }
-  const size_t pix = ((size_t)bv * out_h + i) * out_w + j;
-  if (MODE & RENDER_RGB) {
-    float *o = out_rgb + pix * 3;
-    o[0] = o0; o[1] = o1; o[2] = o2;
-  }
-  if (MODE & RENDER_DEPTH) out_depth[pix] = od;
+  store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
 }
 
 // Panorama -> six face images: image [B,H,W,C] (C <= 4) -> out [B,6,S,S,C].  Texel (ix, iy) of face f looks along R_f K^-1 (ix, iy, 1) in the
@@ -240,43 +198,16 @@ int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_p
   MSI_REQUIRE(face_size < (1 << 15) && (long)face_size * face_size * 6 * num_planes * texel_bytes < (1L << 31),   // (< 2^30 * 6 * 128 * 16)
               "cube_render_views: a sample's six face stacks (6 x %d x %d x %d texels of %d bytes) reach 2^31 bytes (32-bit offsets)",
               num_planes, face_size, face_size, texel_bytes);
-  const long lim = (1L << 31) - 8;
-  long nblk = (long)((out_width + 63) / 64) * ((out_height + 3) / 4);     // (each factor < 2^31: checked before every product)
-  MSI_REQUIRE(nblk < lim, "cube_render_views: too many target pixels for one launch");
-  nblk *= views;
-  MSI_REQUIRE(nblk < lim, "cube_render_views: too many target pixels for one launch");
-  nblk *= batch;
-  MSI_REQUIRE(nblk < lim, "cube_render_views: too many target pixels for one launch");
+  unsigned grid;
+  if (const int e = view_grid("cube_render_views", (long)((out_width + 63) / 64) * ((out_height + 3) / 4), views, batch, &grid)) return e;
   if (batch == 0) return MSI_OK;
-  const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(64, 4);
-  DepthFrac F;
-  for (int d = 0; d < DEPTH_FRAC_MAX; ++d) F.f[d] = d < num_planes ? (float)((double)d / (double)num_planes) : 0.0f;
-  const int mode = (out_rgb ? RENDER_RGB : 0) | (out_depth ? RENDER_DEPTH : 0);
+  const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);
-#define MSI_LAUNCH_CUBE(M, CAM, FMT_)                                                                                                  \
-  hipLaunchKernelGGL((cube_render_views_kernel<M, CAM, FMT_>), grid, block, 0, s, layers, tgt_pose_rt, tgt_pos, tgt_intrinsics,       \
-                     stack_intrinsics, depths, trig, batch, views, face_size, num_planes, out_height, out_width, out_rgb, out_depth, F, \
-                     status_device)
-#define MSI_LAUNCH_CUBE_F(M, CAM)                                             \
-  switch (format) {                                                           \
-    case MSI_LAYERS_RGBA8: MSI_LAUNCH_CUBE(M, CAM, MSI_LAYERS_RGBA8); break;     \
-    case MSI_LAYERS_RGBA16F: MSI_LAUNCH_CUBE(M, CAM, MSI_LAYERS_RGBA16F); break; \
-    default: MSI_LAUNCH_CUBE(M, CAM, MSI_LAYERS_F32); break;                   \
-  }
-#define MSI_LAUNCH_CUBE_M(CAM)                                                      \
-  switch (mode) {                                                                   \
-    case RENDER_RGB: MSI_LAUNCH_CUBE_F(RENDER_RGB, CAM) break;                      \
-    case RENDER_DEPTH: MSI_LAUNCH_CUBE_F(RENDER_DEPTH, CAM) break;                  \
-    default: MSI_LAUNCH_CUBE_F(RENDER_RGB | RENDER_DEPTH, CAM) break;               \
-  }
-  if (camera == MSI_CAMERA_PINHOLE) {
-    MSI_LAUNCH_CUBE_M(MSI_CAMERA_PINHOLE)
-  } else {
-    MSI_LAUNCH_CUBE_M(MSI_CAMERA_EQUIRECT)
-  }
-#undef MSI_LAUNCH_CUBE_M
-#undef MSI_LAUNCH_CUBE_F
-#undef MSI_LAUNCH_CUBE
+  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_camera(camera, [&](auto CAM) { for_format(format, [&](auto FMT) {
+    hipLaunchKernelGGL((cube_render_views_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>), dim3(grid), dim3(64, 4), 0, s,
+                       layers, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch, views, face_size, num_planes,
+                       out_height, out_width, out_rgb, out_depth, F, status_device);
+  }); }); });
   return msi::check_launch("cube_render_views");
 }
 

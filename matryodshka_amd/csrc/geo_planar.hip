@@ -333,7 +333,7 @@ mpi_render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ tgt
 // divide_safe on ws, the two IEEE divides, the (-1, W) x (-1, H) test, floor, the four weights, the sum order w00 a00 + w11 a11 + w01 a01 +
 // w10 a10 and the strictly sequential composite in one thread -- so at the stack's own size its rgb has the bits of msi_mpi_render_f32.
 // What changes is the plumbing:
-//   grid    1-D, sample -> view -> 4-row group -> 64-pixel block with render_views_kernel's XCD-aware mapping: the views of one stack follow
+//   grid    1-D, sample -> view -> 4-row group -> 64-pixel block with the XCD-aware mapping of every many-views render (ViewBlock, geometry_device.h): the views of one stack follow
 //           each other through the Infinity Cache and adjacent row groups share an XCD's L2.  A workgroup is 64 x 4 pixels of one (sample,
 //           view), a wave one row; its D inverse homographies (source K of sample b, pose and inverse target K of view (b, v)) are computed
 //           once in the prologue into LDS.
@@ -347,26 +347,14 @@ mpi_render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ tgt
 //           their layer value is selected to zero: no divergent branch around the loads, same bits for the pixels inside.
 //   loop    unrolled by 4: the warp of a layer does not depend on the running composite, so the taps of several layers are in flight under
 //           the sequential blend.
-template <int FMT>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mpi_layer_rsrc(const void *layers, int b, int nd, int d, size_t hw) {
-  if constexpr (FMT == MSI_LAYERS_F32)
-    return layer_rsrc(static_cast<const float4 *>(layers), b, nd, d, hw, (int)(hw << 4));   // (H * W < 2^24, checked on the host)
-  else
-    return packed_layer_rsrc<FMT>(layers, b, nd, d, hw, (int)(hw << TexelShift<FMT>::value));
-}
-
 // the texel at offset `texel` of layer L when ok, else the zeros of fetch_or_zero
 template <int FMT>
 __device__ __forceinline__ float4 mpi_tap(__amdgpu_buffer_rsrc_t L, int texel, bool ok) {
-  if constexpr (FMT == MSI_LAYERS_F32) {
-    return layer_tap(L, ok ? (unsigned)texel : 0x80000000u >> 4);
-  } else {
-    float4 t = packed_layer_tap<FMT>(L, ok ? (unsigned)texel : 0x80000000u >> TexelShift<FMT>::value);
-    if constexpr (FMT == MSI_LAYERS_RGBA8) {   // (code 0 is colour -1; alpha 0 and the rgba16f zeros are 0 already)
-      t.x = ok ? t.x : 0.0f; t.y = ok ? t.y : 0.0f; t.z = ok ? t.z : 0.0f;
-    }
-    return t;
+  float4 t = StackTexel<FMT>::tap(L, ok ? (unsigned)texel : 0x80000000u >> StackTexel<FMT>::shift);
+  if constexpr (FMT == MSI_LAYERS_RGBA8) {   // (code 0 is colour -1; alpha 0 and the fp32 / rgba16f zeros are 0 already)
+    t.x = ok ? t.x : 0.0f; t.y = ok ? t.y : 0.0f; t.z = ok ? t.z : 0.0f;
   }
+  return t;
 }
 
 template <int MODE, int FMT>
@@ -376,15 +364,11 @@ mpi_render_views_kernel(const void *__restrict__ layers, const float *__restrict
                         int height, int width, int nd, int out_h, int out_w, float *__restrict__ out_rgb,
                         float *__restrict__ out_depth, DepthFrac F) {
   __shared__ float hom[MPI_MAX_PLANES][9];
-  const unsigned gx = (unsigned)(out_w + 63) >> 6, gy = (unsigned)(out_h + 3) >> 2;
-  const unsigned nblk = gx * gy * (unsigned)views * (unsigned)batch, per = gridDim.x >> 3;
-  const unsigned lin = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-  if (lin >= nblk) return;                              // (grid rounded up to a multiple of 8; whole workgroups leave)
-  const unsigned rowb = lin / gx;
-  const int j = (int)(lin - rowb * gx) * 64 + threadIdx.x;
-  const unsigned bv = rowb / gy;                        // sample * views + view
-  const int i = (int)(rowb - bv * gy) * 4 + threadIdx.y;
-  const int b = (int)(bv / (unsigned)views);
+  ViewBlock<4> k(out_h, out_w, views, batch);
+  if (k.past_end()) return;                             // (grid rounded up to a multiple of 8; whole workgroups leave)
+  k.decode(views);
+  const unsigned bv = k.bv;
+  const int i = k.i, j = k.j, b = k.b;
   const int tid = threadIdx.y * 64 + threadIdx.x;
   if (tid < nd) {   // mpi_render_kernel's prologue, op for op
     const float *P = tgt_pose + (size_t)bv * 16;
@@ -441,35 +425,32 @@ mpi_render_views_kernel(const void *__restrict__ layers, const float *__restrict
     const float dx = (float)cx - x, dy = (float)cy - y;
     const bool x0 = inside && fx >= 0, x1 = inside && cx < width, y0 = fy >= 0, y1 = cy < height;
     const int r0 = fy * width, r1 = r0 + width;
-    const __amdgpu_buffer_rsrc_t L = mpi_layer_rsrc<FMT>(layers, b, nd, d, hw);
+    const __amdgpu_buffer_rsrc_t L = StackTexel<FMT>::layer(layers, b, nd, d, hw, (int)(hw << StackTexel<FMT>::shift));   // (H * W < 2^24, checked on the host)
     const float4 a00 = mpi_tap<FMT>(L, r0 + fx, x0 && y0), a11 = mpi_tap<FMT>(L, r1 + cx, x1 && y1);
     const float4 a01 = mpi_tap<FMT>(L, r1 + fx, x0 && y1), a10 = mpi_tap<FMT>(L, r0 + cx, x1 && y0);
     const float w00 = dx * dy, w11 = (1.0f - dx) * (1.0f - dy), w01 = dx * (1.0f - dy), w10 = (1.0f - dx) * dy;
-    const float al = inside ? ((w00 * a00.w + w11 * a11.w) + w01 * a01.w) + w10 * a10.w : 0.0f;
+    float4 c;   // (zero for a pixel that samples outside)
+    c.w = inside ? ((w00 * a00.w + w11 * a11.w) + w01 * a01.w) + w10 * a10.w : 0.0f;
+    c.x = inside ? ((w00 * a00.x + w11 * a11.x) + w01 * a01.x) + w10 * a10.x : 0.0f;
+    c.y = inside ? ((w00 * a00.y + w11 * a11.y) + w01 * a01.y) + w10 * a10.y : 0.0f;
+    c.z = inside ? ((w00 * a00.z + w11 * a11.z) + w01 * a01.z) + w10 * a10.z : 0.0f;
+    const float al = c.w;
     if (MODE & RENDER_RGB) {
-      const float r = inside ? ((w00 * a00.x + w11 * a11.x) + w01 * a01.x) + w10 * a10.x : 0.0f;
-      const float g = inside ? ((w00 * a00.y + w11 * a11.y) + w01 * a01.y) + w10 * a10.y : 0.0f;
-      const float bl = inside ? ((w00 * a00.z + w11 * a11.z) + w01 * a01.z) + w10 * a10.z : 0.0f;
       if (d == 0) {
-        o0 = r; o1 = g; o2 = bl;
+        o0 = c.x; o1 = c.y; o2 = c.z;
       } else {
         const float om = 1.0f - al;
-        o0 = r * al + o0 * om;
-        o1 = g * al + o1 * om;
-        o2 = bl * al + o2 * om;
+        o0 = c.x * al + o0 * om;
+        o1 = c.y * al + o1 * om;
+        o2 = c.z * al + o2 * om;
       }
     }
-    if (MODE & RENDER_DEPTH) {   // over_composite_depth (projector.py:225-244): 0 at layer 0, then (d / D) a + out (1 - a)
+    if (MODE & RENDER_DEPTH) {   // over_composite_depth: 0 at layer 0, then (d / D) a + out (1 - a)
       if (d == 0) od = 0.0f;
       else od = F.f[d] * al + od * (1.0f - al);
     }
   }
-  const size_t pix = ((size_t)bv * out_h + i) * out_w + j;
-  if (MODE & RENDER_RGB) {
-    float *o = out_rgb + pix * 3;
-    o[0] = o0; o[1] = o1; o[2] = o2;
-  }
-  if (MODE & RENDER_DEPTH) out_depth[pix] = od;
+  store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
 }
 
 }  // namespace
@@ -565,35 +546,15 @@ int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_po
   if (num_planes > MPI_MAX_PLANES)
     return msi::fail(MSI_E_UNSUPPORTED, "mpi_render_views: at most %d planes", MPI_MAX_PLANES);
   MSI_REQUIRE((long)height * width < (1L << 24), "mpi_render_views: layers of more than 2^24 texels (24-bit texel offsets)");
-  const long lim = (1L << 31) - 8;
-  long nblk = (long)((out_width + 63) / 64) * ((out_height + 3) / 4);     // (each factor < 2^31: checked before every product)
-  MSI_REQUIRE(nblk < lim, "mpi_render_views: too many target pixels for one launch");
-  nblk *= views;
-  MSI_REQUIRE(nblk < lim, "mpi_render_views: too many target pixels for one launch");
-  nblk *= batch;
-  MSI_REQUIRE(nblk < lim, "mpi_render_views: too many target pixels for one launch");
+  unsigned grid;
+  if (const int e = view_grid("mpi_render_views", (long)((out_width + 63) / 64) * ((out_height + 3) / 4), views, batch, &grid)) return e;
   if (batch == 0) return MSI_OK;
-  const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(64, 4);
-  DepthFrac F;
-  for (int d = 0; d < DEPTH_FRAC_MAX; ++d) F.f[d] = d < num_planes ? (float)((double)d / (double)num_planes) : 0.0f;
-  const int mode = (out_rgb ? RENDER_RGB : 0) | (out_depth ? RENDER_DEPTH : 0);
+  const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);
-#define MSI_LAUNCH_MPI_VIEWS(M, FMT_)                                                                                             \
-  hipLaunchKernelGGL((mpi_render_views_kernel<M, FMT_>), grid, block, 0, s, layers, tgt_pose, intrinsics, tgt_intrinsics_inv, depths, \
-                     batch, views, height, width, num_planes, out_height, out_width, out_rgb, out_depth, F)
-#define MSI_LAUNCH_MPI_VIEWS_M(FMT_)                                                \
-  switch (mode) {                                                                   \
-    case RENDER_RGB: MSI_LAUNCH_MPI_VIEWS(RENDER_RGB, FMT_); break;                 \
-    case RENDER_DEPTH: MSI_LAUNCH_MPI_VIEWS(RENDER_DEPTH, FMT_); break;             \
-    default: MSI_LAUNCH_MPI_VIEWS(RENDER_RGB | RENDER_DEPTH, FMT_); break;          \
-  }
-  switch (format) {
-    case MSI_LAYERS_RGBA8: MSI_LAUNCH_MPI_VIEWS_M(MSI_LAYERS_RGBA8) break;
-    case MSI_LAYERS_RGBA16F: MSI_LAUNCH_MPI_VIEWS_M(MSI_LAYERS_RGBA16F) break;
-    default: MSI_LAUNCH_MPI_VIEWS_M(MSI_LAYERS_F32) break;
-  }
-#undef MSI_LAUNCH_MPI_VIEWS_M
-#undef MSI_LAUNCH_MPI_VIEWS
+  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_format(format, [&](auto FMT) {
+    hipLaunchKernelGGL((mpi_render_views_kernel<decltype(M)::value, decltype(FMT)::value>), dim3(grid), dim3(64, 4), 0, s, layers, tgt_pose,
+                       intrinsics, tgt_intrinsics_inv, depths, batch, views, height, width, num_planes, out_height, out_width, out_rgb, out_depth, F);
+  }); });
   return msi::check_launch("mpi_render_views");
 }
 

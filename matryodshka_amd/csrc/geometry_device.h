@@ -2,7 +2,7 @@
 //   geo_prep.hip    K5 pre/deprocess (single and pair), pose composition, the host-built trig tables
 //   geo_sweep.hip   K1 ODS sphere sweep: ods_sweep_kernel, ods_sweep_lds_kernel
 //   geo_layers.hip  K3 RGBA assembly, bilinear resize, the fused high-res layer stack, pack / unpack of the compact stacks
-//   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed sibling
+//   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed form
 //   geo_ods.hip     K4 with the ODS stereo camera: render_ods_views_kernel (both eyes of a stack per launch, fp32 or packed stacks)
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 #include "msi_common.h"
 
@@ -347,9 +348,11 @@ __device__ __forceinline__ float4 rgba16f_decode(u32x2_g q) {
   return t;
 }
 
-// ---- render (render_kernel, render_views_kernel and its packed sibling), planar (mpi_render_views_kernel) and cube (cube_render_views_kernel): the output modes, the layer fraction of
-// over_composite_depth and ONE way to address and load a texel of a layer stack, fp32 or packed, so the many-views renders of both families read the
-// same bits from the same stack.
+// ---- render, ods, planar (mpi_render_views_kernel) and cube: the output modes, the layer fraction of over_composite_depth, ONE way to address and load a
+// texel of a layer stack, fp32 or packed, so the many-views renders of every family read the same bits from the same stack, and the pieces those
+// renders are made of (block decode, rays and pose, the sphere renders' per-layer step and segment combine, the pixel store).  The pieces take and
+// return VALUES: a piece that updates a kernel's accumulators through references changes the order in which the compiler promotes them to registers,
+// and with it the instruction stream (profiles/shared_render_pieces_isa.txt has what each form did).
 enum RenderMode { RENDER_RGB = 1, RENDER_DEPTH = 2, RENDER_LAYERS = 4 };
 
 // (i / len) of projector.py:242 per layer: a Python double division converted to an fp32 tensor constant.  Tabulated on the
@@ -358,34 +361,266 @@ enum RenderMode { RENDER_RGB = 1, RENDER_DEPTH = 2, RENDER_LAYERS = 4 };
 constexpr int DEPTH_FRAC_MAX = 128;
 struct DepthFrac { float f[DEPTH_FRAC_MAX]; };
 
-// Layer d of sample b of a [B,D,H,W,4] stack as a buffer resource: 32-bit texel offsets also for stacks beyond 2 GiB.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t layer_rsrc(const float4 *rgba, int b, int nd, int d, size_t hw, int layer_bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(rgba + ((size_t)b * nd + d) * hw), 0, layer_bytes, 0x00020000);
-}
-
-__device__ __forceinline__ float4 layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
-  typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
-  return __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, texel << 4, 0, 0));
-}
-
-template <int FMT> struct TexelShift {   // log2 of the bytes per texel
-  static_assert(FMT == MSI_LAYERS_RGBA8 || FMT == MSI_LAYERS_RGBA16F, "a packed texel format");
-  static constexpr int value = FMT == MSI_LAYERS_RGBA8 ? 2 : 3;
+// ONE texel policy for every render that reads a [B,D,H,W,4] stack -- fp32 (a 16-byte load) or packed (rgba16f: 8 bytes, rgba8: 4, decoded by the
+// rule above): shift = log2 of the bytes per texel, layer = the buffer resource of layer d of sample b (32-bit texel offsets also for stacks beyond
+// 2 GiB; layer_bytes = hw << shift, H * W < 2^24 checked on the host), tap = the four fp32 values of one texel of that resource.  A tap of a packed
+// stack is ONE load decoded to what msi_unpack_layers writes for that texel (rgba8: 11 VALU per tap -- four v_cvt_f32_ubyte, three subtracts, four
+// multiplies; rgba16f: four v_cvt_f32_f16), so a render from a packed stack is bit-identical to the render of the unpacked one.
+template <int FMT> struct StackTexel {
+  static_assert(FMT == MSI_LAYERS_F32 || FMT == MSI_LAYERS_RGBA8 || FMT == MSI_LAYERS_RGBA16F, "a texel format of msi_hip.h");
+  static constexpr int shift = FMT == MSI_LAYERS_F32 ? 4 : FMT == MSI_LAYERS_RGBA16F ? 3 : 2;
+  static __device__ __forceinline__ __amdgpu_buffer_rsrc_t layer(const void *layers, int b, int nd, int d, size_t hw, int layer_bytes) {
+    if constexpr (FMT == MSI_LAYERS_F32)
+      return __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const float4 *>(layers) + ((size_t)b * nd + d) * hw), 0, layer_bytes, 0x00020000);
+    else
+      return __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + ((((size_t)b * nd + d) * hw) << shift)), 0, layer_bytes, 0x00020000);
+  }
+  static __device__ __forceinline__ float4 tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
+    if constexpr (FMT == MSI_LAYERS_F32) {
+      typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
+      return __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, texel << 4, 0, 0));
+    } else if constexpr (FMT == MSI_LAYERS_RGBA8) {
+      return rgba8_decode(__builtin_amdgcn_raw_buffer_load_b32(L, texel << 2, 0, 0));
+    } else {
+      return rgba16f_decode((u32x2_g)__builtin_amdgcn_raw_buffer_load_b64(L, texel << 3, 0, 0));
+    }
+  }
 };
 
-// layer_rsrc / layer_tap for a packed stack
-template <int FMT>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t packed_layer_rsrc(const void *layers, int b, int nd, int d, size_t hw, int layer_bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + ((((size_t)b * nd + d) * hw) << TexelShift<FMT>::value)),
-                                           0, layer_bytes, 0x00020000);
+// ---- the many-views renders (render, ods, cube, planar): which pixel a thread renders.  A workgroup is 64 consecutive pixels of ROWS target rows of
+// one (sample, view); the 1-D grid runs sample -> view -> row group -> 64-pixel block.
+// XCD-aware: workgroup ids go round-robin over the 8 XCDs and each XCD has its own L2, so XCD x takes the x-th eighth of that sequence, in order:
+// vertically adjacent target rows -- which share their bilinear tap rows -- are gathered through the SAME L2 (with rows dealt round-robin every tap
+// row was fetched by two XCDs: 2.3x the stack's bytes at D = 64, batch 16; 1.43x at the BASELINE size), and the V views of one stack follow each other
+// (its texels stay in the Infinity Cache while they render).  The host rounds the grid up to a multiple of 8 (view_grid below): whole workgroups
+// past the end (past_end()) leave before decode().  ROWS = 1: the row is the group and threadIdx.y is free (the sphere renders' layer segments); ROWS = 4: a
+// wave is one row.  j may lie past the row end.
+template <int ROWS> struct ViewBlock {
+  unsigned gx, gy, nblk, lin;
+  unsigned bv;   // sample * views + view
+  int b, i, j;
+  __device__ __forceinline__ ViewBlock(int out_h, int out_w, int views, int batch) {
+    gx = (unsigned)(out_w + 63) >> 6, gy = ROWS == 1 ? (unsigned)out_h : (unsigned)(out_h + ROWS - 1) / ROWS;
+    nblk = gx * gy * (unsigned)views * (unsigned)batch;
+    const unsigned per = gridDim.x >> 3;
+    lin = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+  }
+  __device__ __forceinline__ bool past_end() const { return lin >= nblk; }
+  __device__ __forceinline__ void decode(int views) {   // (after past_end)
+    const unsigned rowb = lin / gx;
+    j = (int)(lin - rowb * gx) * 64 + threadIdx.x;
+    bv = rowb / gy;
+    i = ROWS == 1 ? (int)(rowb - bv * gy) : (int)(rowb - bv * gy) * ROWS + threadIdx.y;
+    b = (int)(bv / (unsigned)views);
+  }
+};
+
+// A ray of a target view: direction r, origin c.  view_ray gives both BEFORE the pose for the cameras of render_views and cube_render_views
+// (pose, origin and K of a view are wave-uniform: scalar loads):
+//   MSI_CAMERA_EQUIRECT  (cos S cos T, sin T, sin S cos T) on the lat-long grid of the OUTPUT size (trig = its table)
+//   MSI_CAMERA_PINHOLE   (1, (i + 0.5 - cy) / fy, (j + 0.5 - cx) / fx): forward +x, image-down +y, image-right +z -- the
+//                        orientation of the equirect render around its centre pixel (IEEE divides: per pixel, not per layer)
+// with the origin (tgt_pos[2], tgt_pos[1], tgt_pos[0]) for both; apply_pose is r <- pose[:3,:3] r, c <- pose (c, 1) of every render
+// (spherical.py:303-310 / transform_ray :70-94), terms summed left to right.
+struct ViewRay { float rx, ry, rz, cx, cy, cz; };
+
+template <int CAMERA>
+__device__ __forceinline__ ViewRay view_ray(const float *intrinsics, const float *trig, const float *tgt_pos, unsigned bv, int i, int j, int out_h,
+                                            int out_w) {
+  ViewRay r;
+  if (CAMERA == MSI_CAMERA_PINHOLE) {
+    const float *Kv = intrinsics + (size_t)bv * 9;      // fx . cx / . fy cy
+    r.rx = 1.0f;
+    r.ry = (((float)i + 0.5f) - Kv[5]) / Kv[4];
+    r.rz = (((float)j + 0.5f) - Kv[2]) / Kv[0];
+  } else {
+    const float cs = trig[j], ss = trig[out_w + j];
+    const float ct = trig[2 * out_w + i], st = trig[2 * out_w + out_h + i];
+    r.rx = cs * ct; r.ry = st; r.rz = ss * ct;
+  }
+  const float *tp = tgt_pos + (size_t)bv * 3;
+  r.cx = tp[2]; r.cy = tp[1]; r.cz = tp[0];
+  return r;
 }
 
-template <int FMT>
-__device__ __forceinline__ float4 packed_layer_tap(__amdgpu_buffer_rsrc_t L, unsigned texel) {
-  if constexpr (FMT == MSI_LAYERS_RGBA8)
-    return rgba8_decode(__builtin_amdgcn_raw_buffer_load_b32(L, texel << 2, 0, 0));
-  else
-    return rgba16f_decode((u32x2_g)__builtin_amdgcn_raw_buffer_load_b64(L, texel << 3, 0, 0));
+__device__ __forceinline__ void apply_pose(const float *P, ViewRay &r) {
+  {
+    const float x = (P[0] * r.rx + P[1] * r.ry) + P[2] * r.rz;
+    const float y = (P[4] * r.rx + P[5] * r.ry) + P[6] * r.rz;
+    const float z = (P[8] * r.rx + P[9] * r.ry) + P[10] * r.rz;
+    r.rx = x; r.ry = y; r.rz = z;
+  }
+  {
+    const float x = ((P[0] * r.cx + P[1] * r.cy) + P[2] * r.cz) + P[3] * 1.0f;
+    const float y = ((P[4] * r.cx + P[5] * r.cy) + P[6] * r.cz) + P[7] * 1.0f;
+    const float z = ((P[8] * r.cx + P[9] * r.cy) + P[10] * r.cz) + P[11] * 1.0f;
+    r.cx = x; r.cy = y; r.cz = z;
+  }
+}
+
+// The running far-to-near composite of a pixel (pj.over_composite, projector.py:259-263, and over_composite_depth, :239-242) and its step for layer d
+// with the blended texel c = (r, g, b, alpha): layer 0 replaces (the farthest layer's alpha is ignored; depth 0), every other layer is
+// c a + out (1 - a) for the colour and frac a + out (1 - a) for the depth, frac() = (d / D) as an fp32 constant (DepthFrac).  tr is the
+// transmittance of the layers so far, for renders that combine partial composites.
+struct Composite { float o0, o1, o2, od, tr; };
+
+template <int MODE, class Frac>
+__device__ __forceinline__ Composite over_step(float o0, float o1, float o2, float od, float tr, int d, const float4 &c, Frac frac) {
+  const float al = c.w;
+  if (MODE & RENDER_RGB) {
+    if (d == 0) {
+      o0 = c.x; o1 = c.y; o2 = c.z;
+    } else {
+      const float om = 1.0f - al;
+      o0 = c.x * al + o0 * om;
+      o1 = c.y * al + o1 * om;
+      o2 = c.z * al + o2 * om;
+    }
+  }
+  if (MODE & RENDER_DEPTH) {
+    if (d == 0) od = 0.0f;
+    else od = frac() * al + od * (1.0f - al);
+  }
+  tr = tr * (1.0f - al);
+  return Composite{o0, o1, o2, od, tr};
+}
+
+// rgb [B,V,h,w,3] and one-channel depth [B,V,h,w] of the many-views renders (a wave's 64 pixels are one contiguous 768-byte rgb run and one
+// 256-byte depth run)
+template <int MODE>
+__device__ __forceinline__ void store_pixel(float *out_rgb, float *out_depth, size_t pix, float o0, float o1, float o2, float od) {
+  if (MODE & RENDER_RGB) {
+    float *p = out_rgb + pix * 3;
+    p[0] = o0; p[1] = o1; p[2] = o2;
+  }
+  if (MODE & RENDER_DEPTH) out_depth[pix] = od;
+}
+
+// ---- K4, the sphere renders (render_kernel, render_views_kernel, render_views_packed_kernel: geo_render.hip; render_ods_views_kernel: geo_ods.hip):
+// fused reprojection + wrap-around bilinear gather + over-composite, built from ONE set of pieces.  One thread per target pixel and layer segment, block = 64 pixels of
+// one target row x RENDER_SEGS layer segments (a wavefront = 64 consecutive columns, so each tap row is a ~1 KiB coalesced float4 segment and
+// vertically adjacent rows share tap rows in L2): a pixel's D layers are split over RENDER_SEGS threads (same lane, different waves), each
+// compositing its contiguous range of layers from transparent black,
+//   C <- rgb a + C (1-a),   T <- T (1-a),
+// and the segments are combined back to front, out = C_3 + T_3 (C_2 + T_2 (C_1 + T_1 C_0)) (the over operator is associative; rounding differs
+// from the strictly sequential form by ~1e-7).  One thread per pixel left the chip with 3 200 wavefronts for 8 192 wave slots and a 32-deep chain
+// of dependent-latency gathers per thread.  The ray/sphere quadratic's a and b do not depend on the layer, so per layer only sqrt, one divide
+// and the two angles remain; every texel of the D x H x W x 4 stack is fetched from HBM once.
+// What a kernel keeps for itself: where its ray comes from, the status word, and what it stores; render_kernel also keeps its own text of the
+// per-layer step and the over step (as pieces they change some of its instantiations: profiles/shared_render_pieces_isa.txt).
+constexpr int RENDER_SEGS = 4;   // layer segments per pixel (threads in y)
+
+struct SphereBlock : ViewBlock<1> {
+  int seg;
+  bool valid;    // j < out_w; decode clamps j into the row
+  using ViewBlock<1>::ViewBlock;
+  __device__ __forceinline__ void decode(int views, int out_w) {
+    ViewBlock<1>::decode(views);
+    // (a wavefront is one threadIdx.y: telling the compiler keeps the layer index -- and with it the per-layer buffer
+    // descriptor -- in SGPRs; without it every gather sat in a readfirstlane waterfall loop, ~12 instructions each)
+    seg = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    valid = j < out_w;
+    j = valid ? j : out_w - 1;      // (lanes past the row end compute a duplicate and store nothing: no early return before the barrier)
+  }
+};
+
+// The status word of a sphere render: qc_max, the max over a thread's layers of |origin|^2 - radius^2, is >= 0 when the ray origin (cc = |origin|^2)
+// is not inside every sphere it was intersected with, and cc is NaN for a NaN pose / target position (fmaxf drops NaNs and leaves qc_max at -1 --
+// tested separately): outside the reference's domain (spherical.py:316-318 takes the square root of a negative number there).  The clamp
+// in SphereStack::layer kept the pixels finite; each kernel ORs MSI_RENDER_STATUS_ORIGIN_OUTSIDE into *status on `!(qc_max < 0.0f) || cc != cc`.
+
+// the layer-independent part of the ray/sphere quadratic |c + t r|^2 = radius^2 of ray r (after the pose)
+struct SphereQuad { float qb, cc, qb2, fa, ta, inv_ta; };
+
+__device__ __forceinline__ SphereQuad sphere_quad(const ViewRay &r) {
+  SphereQuad q;
+  const float qa = (r.rx * r.rx + r.ry * r.ry) + r.rz * r.rz;
+  q.qb = 2.0f * ((r.rx * r.cx + r.ry * r.cy) + r.rz * r.cz);
+  q.cc = (r.cx * r.cx + r.cy * r.cy) + r.cz * r.cz;
+  q.qb2 = q.qb * q.qb;
+  q.fa = 4.0f * qa; q.ta = 2.0f * qa;
+  q.inv_ta = __builtin_amdgcn_rcpf(q.ta);
+  return q;
+}
+
+// (i / len) of projector.py:242 for layer d, tabulated up to DEPTH_FRAC_MAX layers
+__device__ __forceinline__ float depth_frac(const DepthFrac &F, int d, int nd) {
+  return nd <= DEPTH_FRAC_MAX ? F.f[d] : (float)((double)d / (double)nd);
+}
+
+// The layers of sample b as a sphere render sees them: layer(d, ...) is the per-layer step, from the quadratic to the four taps to the blended
+// texel (r, g, b, alpha) of layer d along ray r; the layers first(seg) .. end(seg) are segment seg's.
+template <int FMT> struct SphereStack {
+  const void *layers;
+  const float *depths;
+  int b, nd, height, width;
+  size_t hw;          // source layer size
+  int layer_bytes;    // (H * W < 2^24, checked on the host)
+  __device__ __forceinline__ SphereStack(const void *layers_, const float *depths_, int b_, int nd_, int height_, int width_)
+      : layers(layers_), depths(depths_), b(b_), nd(nd_), height(height_), width(width_), hw((size_t)height_ * width_),
+        layer_bytes((int)(hw << StackTexel<FMT>::shift)) {}
+  __device__ __forceinline__ int first(int seg) const { return (seg * nd) / RENDER_SEGS; }
+  __device__ __forceinline__ int end(int seg) const { return ((seg + 1) * nd) / RENDER_SEGS; }
+
+  struct Step { float4 c; float qc_max; };
+  __device__ __forceinline__ Step layer(int d, const ViewRay &r, const SphereQuad &q, const PixConsts &K, float qc_max) const {
+    Step s;
+    const float radius = depths[d];
+    const float qc = q.cc - radius * radius;
+    s.qc_max = fmaxf(qc_max, qc);
+    const float disc = q.qb2 - q.fa * qc;
+    // disc >= 0 whenever the ray origin is inside the sphere (the documented domain; the host-side guard of the MSI class
+    // enforces it for host inputs).  Outside it the reference takes sqrt of a negative number and casts NaN to int
+    // (undefined); the clamp keeps device-side inputs finite and changes nothing inside the domain.
+    // (no branch of the reference depends on these values: the whole chain is continuous -> 1-ulp primitives)
+#if MSI_FAST_TAIL
+    const float num = t_sqrt(fmaxf(disc, 0.0f)) - q.qb;           // t = num / ta with the pixel's 1 / ta (one correction step: <= 1 ulp)
+    const float tq = num * q.inv_ta;
+    const float t = __builtin_fmaf(__builtin_fmaf(-tq, q.ta, num), q.inv_ta, tq);
+#else
+    const float t = t_div(-q.qb + t_sqrt(fmaxf(disc, 0.0f)), q.ta);
+#endif
+    const float x = r.cx + t * r.rx;
+    const float y = r.cy + t * r.ry;
+    const float z = r.cz + t * r.rz;
+    // project_spherical (spherical.py:243-246) + theta_phi_to_pixels (:54-68); the point lies on the layer's sphere: |P| = radius
+    float theta, phi;
+    t_angles(x, y, z, radius, theta, phi);
+#if MSI_FAST_TAIL
+    const float u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
+    const float v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
+#else
+    const float u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
+    const float v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
+#endif
+    const TapsR tp4 = make_taps_ranged(u, v, width, height);
+    // one descriptor per layer (scalar work)
+    const __amdgpu_buffer_rsrc_t L = StackTexel<FMT>::layer(layers, b, nd, d, hw, layer_bytes);
+    const float4 A = StackTexel<FMT>::tap(L, tp4.oa), Bv = StackTexel<FMT>::tap(L, tp4.ob), C = StackTexel<FMT>::tap(L, tp4.oc), Dv = StackTexel<FMT>::tap(L, tp4.od);
+    s.c.w = blend4(tp4, A.w, Bv.w, C.w, Dv.w);
+    s.c.x = blend4(tp4, A.x, Bv.x, C.x, Dv.x);
+    s.c.y = blend4(tp4, A.y, Bv.y, C.y, Dv.y);
+    s.c.z = blend4(tp4, A.z, Bv.z, C.z, Dv.z);
+    return s;
+  }
+};
+
+// The segments of a pixel through LDS, combined back to front in the thread of segment 0, which hands the finished pixel to store(o0, o1, o2, od).
+template <class Store>
+__device__ __forceinline__ void sphere_combine(const SphereBlock &s, float o0, float o1, float o2, float od, float tr, Store store) {
+  __shared__ float s_part[RENDER_SEGS][64][5];
+  const int seg = s.seg;
+  s_part[seg][threadIdx.x][0] = o0; s_part[seg][threadIdx.x][1] = o1; s_part[seg][threadIdx.x][2] = o2;
+  s_part[seg][threadIdx.x][3] = od; s_part[seg][threadIdx.x][4] = tr;
+  __syncthreads();
+  if (seg != 0 || !s.valid) return;
+#pragma unroll
+  for (int sg = 1; sg < RENDER_SEGS; ++sg) {    // segment 0 holds the farthest layers
+    const float *q = s_part[sg][threadIdx.x];
+    o0 = q[0] + q[4] * o0; o1 = q[1] + q[4] * o1; o2 = q[2] + q[4] * o2;
+    od = q[3] + q[4] * od;
+  }
+  store(o0, o1, o2, od);
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------------------------------
@@ -399,6 +634,50 @@ int grid_1d(size_t n) {
 
 // sweep, layers, planar: non-temporal stores (sweep_store16 and its siblings) for a destination that cannot stay in the 256-MiB Infinity Cache anyway
 bool beyond_infinity_cache(size_t bytes) { return bytes > ((size_t)256 << 20); }
+
+// render, ods, planar, cube: the grid of a many-views launch (ViewBlock), blocks_per_view x views x batch workgroups rounded up to a multiple of 8; each
+// factor is < 2^31 and every product is checked before the next
+int view_grid(const char *who, long blocks_per_view, int views, int batch, unsigned *grid) {
+  const long lim = (1L << 31) - 8;
+  long nblk = blocks_per_view;
+  MSI_REQUIRE(nblk < lim, "%s: too many target pixels for one launch", who);
+  nblk *= views;
+  MSI_REQUIRE(nblk < lim, "%s: too many target pixels for one launch", who);
+  nblk *= batch;
+  MSI_REQUIRE(nblk < lim, "%s: too many target pixels for one launch", who);
+  *grid = (unsigned)((nblk + 7) / 8 * 8);
+  return MSI_OK;
+}
+
+DepthFrac depth_fractions(int num_planes) {
+  DepthFrac F;
+  for (int d = 0; d < DEPTH_FRAC_MAX; ++d) F.f[d] = d < num_planes ? (float)((double)d / (double)num_planes) : 0.0f;
+  return F;
+}
+
+inline int render_mode(const void *out_rgb, const void *out_depth) { return (out_rgb ? RENDER_RGB : 0) | (out_depth ? RENDER_DEPTH : 0); }
+
+// the launch tables: f is called with the run-time value as a compile-time constant, f(Const<V>{}); in f, `decltype(c)::value` is a template argument.
+// (mode: rgb, depth or both; format: one of MSI_LAYERS_*, validated by the caller; camera: MSI_CAMERA_EQUIRECT or MSI_CAMERA_PINHOLE, validated)
+template <int V> using Const = std::integral_constant<int, V>;
+template <class F> void for_mode(int mode, F f) {
+  switch (mode) {
+    case RENDER_RGB: f(Const<RENDER_RGB>{}); break;
+    case RENDER_DEPTH: f(Const<RENDER_DEPTH>{}); break;
+    default: f(Const<RENDER_RGB | RENDER_DEPTH>{}); break;
+  }
+}
+template <class F> void for_format(int format, F f) {
+  switch (format) {
+    case MSI_LAYERS_RGBA8: f(Const<MSI_LAYERS_RGBA8>{}); break;
+    case MSI_LAYERS_RGBA16F: f(Const<MSI_LAYERS_RGBA16F>{}); break;
+    default: f(Const<MSI_LAYERS_F32>{}); break;
+  }
+}
+template <class F> void for_camera(int camera, F f) {
+  if (camera == MSI_CAMERA_PINHOLE) f(Const<MSI_CAMERA_PINHOLE>{});
+  else f(Const<MSI_CAMERA_EQUIRECT>{});
+}
 
 // render (RAY_PERSPECTIVE) and planar: spherical.uv_grid (spherical.py:46-48) = tf.linspace(-1 + 1/n, 1 - 1/n, n) with its fp32 semantics; v[i] = start + step * i
 struct UvGrid { float start, step; };

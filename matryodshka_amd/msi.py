@@ -613,6 +613,48 @@ class MSI(object):
     # ('ods' is not a camera code of the native library: it has its own entry point, msi_render_ods_views)
     CAMERAS = {'equirect': N.MSI_CAMERA_EQUIRECT, 'pinhole': N.MSI_CAMERA_PINHOLE, 'ods': None}
 
+    def _stack_args(self, rgba_layers, planes, who):
+        """A stack [B,H,W,D,4] or a PackedLayers -> (native stack on this device, the PackedLayers or None, planes, native format
+        code); planes=None takes the planes a PackedLayers carries."""
+        packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
+        if packed is not None:
+            native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
+            if planes is None:
+                planes = packed.planes
+        else:
+            native = self._native_layers(rgba_layers)
+        if planes is None:
+            raise ValueError("%s: planes is required (only a PackedLayers that carries its planes may leave it out)" % who)
+        return native, packed, planes, self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+
+    def _view_poses(self, name, tgt_pose, tgt_pos, b):
+        """Per-view poses [B,V,4,4] and, where the camera has them, positions [B,V,3] ([V,4,4] / [V,3] when B = 1) -> fp32
+        (pose, pos, V)."""
+        pose = self._f32(tgt_pose)
+        pos = None if tgt_pos is None else self._f32(tgt_pos)
+        if b == 1 and pose.dim() == 3 and (pos is None or pos.dim() == 2):
+            pose, pos = pose[None], None if pos is None else pos[None]
+        if pose.dim() != 4 or pose.shape[0] != b or tuple(pose.shape[2:]) != (4, 4):
+            raise ValueError("%s must be [B,V,4,4] with B = %d (or [V,4,4] for B = 1), got %s" % (name, b, tuple(pose.shape)))
+        v = pose.shape[1]
+        if pos is not None and tuple(pos.shape) != (b, v, 3):
+            raise ValueError("tgt_pos must be [B,V,3] = %s, got %s" % ((b, v, 3), tuple(pos.shape)))
+        return pose, pos, v
+
+    def _pinhole_intrinsics(self, intrinsics, b, v):
+        """[B,V,3,3] or one [3,3] for every view -> fp32 [B*V,3,3]."""
+        intr = self._f32(intrinsics).reshape(-1, 3, 3)
+        if intr.shape[0] == 1:
+            intr = intr.expand(b * v, 3, 3).contiguous()
+        if intr.shape[0] != b * v:
+            raise ValueError("intrinsics must be [B,V,3,3] or [3,3]")
+        return intr
+
+    def _view_outputs(self, b, v, oh, ow, want_rgb, want_depth):
+        rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
+        dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
+        return rgb, dep
+
     def render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, camera='equirect', intrinsics=None, size=None,
                      want_rgb=True, want_depth=True, eye=None, baseline=None):
         """V views of each MSI in ONE launch (msi_render_views_f32; no reference counterpart) -> (rgb, depth):
@@ -652,26 +694,11 @@ class MSI(object):
             raise ValueError("render_views: camera='ods' needs eye (+1 / 'left' or -1 / 'right', or an array [V] / [B,V])")
         if not (want_rgb or want_depth):
             raise ValueError("render_views: want_rgb and want_depth are both False")
-        packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
-        if packed is not None:
-            native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
-            if planes is None:
-                planes = packed.planes
-        else:
-            native = self._native_layers(rgba_layers)
-        if planes is None:
-            raise ValueError("render_views: planes is required (only a PackedLayers that carries its planes may leave it out)")
+        native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "render_views")
         b, d, h, w, _ = native.shape
         if camera != 'ods':
             self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
-        pose, pos = self._f32(tgt_pose_rt), self._f32(tgt_pos)
-        if b == 1 and pose.dim() == 3 and pos.dim() == 2:
-            pose, pos = pose[None], pos[None]
-        if pose.dim() != 4 or pose.shape[0] != b or tuple(pose.shape[2:]) != (4, 4):
-            raise ValueError("tgt_pose_rt must be [B,V,4,4] with B = %d (or [V,4,4] for B = 1), got %s" % (b, tuple(pose.shape)))
-        v = pose.shape[1]
-        if tuple(pos.shape) != (b, v, 3):
-            raise ValueError("tgt_pos must be [B,V,3] = %s, got %s" % ((b, v, 3), tuple(pos.shape)))
+        pose, pos, v = self._view_poses("tgt_pose_rt", tgt_pose_rt, tgt_pos, b)
         depths = self._planes(planes)
         if depths.numel() != d:
             raise ValueError("len(planes) != number of layers")
@@ -681,9 +708,7 @@ class MSI(object):
             radius = self._eye_radius(eye, baseline, intrinsics, b, v)
             self._ods_domain_guard(tgt_pos, tgt_pose_rt, planes, radius)
             radius = self._f32(radius).reshape(b * v)
-            rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
-            dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
-            fmt = self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+            rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
             N.check(N.lib.msi_render_ods_views(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(), radius.data_ptr(),
                                                depths.data_ptr(), self._trig(oh, ow).data_ptr(), b, v, h, w, d, oh, ow,
                                                _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream()),
@@ -696,15 +721,10 @@ class MSI(object):
             if size is None or intrinsics is None:
                 raise ValueError("camera='pinhole' needs size=(h, w) and intrinsics")
             oh, ow = int(size[0]), int(size[1])
-            intr = self._f32(intrinsics).reshape(-1, 3, 3)
-            if intr.shape[0] == 1:
-                intr = intr.expand(b * v, 3, 3).contiguous()
-            if intr.shape[0] != b * v:
-                raise ValueError("intrinsics must be [B,V,3,3] or [3,3]")
-        rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
-        dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
+            intr = self._pinhole_intrinsics(intrinsics, b, v)
+        rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
         if packed is not None:
-            N.check(N.lib.msi_render_views_packed(native.data_ptr(), self.LAYER_FORMATS[packed.format], pose.data_ptr(), pos.data_ptr(),
+            N.check(N.lib.msi_render_views_packed(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(),
                                                   _ptr(intr), depths.data_ptr(), _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow,
                                                   _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream()),
                     "msi_render_views_packed")
@@ -974,23 +994,10 @@ class MSI(object):
             raise ValueError("mpi_render_views: pass tgt_intrinsics or intrinsics_inv, not both")
         if intrinsics is None:
             raise ValueError("mpi_render_views: intrinsics (the stack's camera) is required")
-        packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
-        if packed is not None:
-            native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
-            if planes is None:
-                planes = packed.planes
-        else:
-            native = self._native_layers(rgba_layers)
-        if planes is None:
-            raise ValueError("mpi_render_views: planes is required (only a PackedLayers that carries its planes may leave it out)")
+        native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "mpi_render_views")
         b, d, h, w, _ = native.shape
-        pose = self._f32(tgt_pose)
-        if b == 1 and pose.dim() == 3:
-            pose = pose[None]
-        if pose.dim() != 4 or pose.shape[0] != b or tuple(pose.shape[2:]) != (4, 4):
-            raise ValueError("tgt_pose must be [B,V,4,4] with B = %d (or [V,4,4] for B = 1), got %s" % (b, tuple(pose.shape)))
+        pose, _, v = self._view_poses("tgt_pose", tgt_pose, None, b)
         pose = pose.contiguous()
-        v = pose.shape[1]
         intr = self._f32(intrinsics).reshape(-1, 3, 3)
         if intr.shape[0] == 1 and b > 1:
             intr = intr.expand(b, 3, 3)
@@ -1007,9 +1014,7 @@ class MSI(object):
         if depths.numel() != d:
             raise ValueError("len(planes) != number of layers")
         oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
-        rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
-        dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
-        fmt = self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+        rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
         N.check(N.lib.msi_mpi_render_views(native.data_ptr(), fmt, pose.data_ptr(), intr.data_ptr(), k_inv.data_ptr(),
                                            depths.data_ptr(), b, v, h, w, d, oh, ow, _ptr(rgb), _ptr(dep), self._stream()),
                 "msi_mpi_render_views")
@@ -1067,15 +1072,7 @@ class MSI(object):
             raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
         if not (want_rgb or want_depth):
             raise ValueError("cube_render_views: want_rgb and want_depth are both False")
-        packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
-        if packed is not None:
-            native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
-            if planes is None:
-                planes = packed.planes
-        else:
-            native = self._native_layers(rgba_layers)
-        if planes is None:
-            raise ValueError("cube_render_views: planes is required (only a PackedLayers that carries its planes may leave it out)")
+        native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "cube_render_views")
         shape = lambda t: tuple(t.shape) if hasattr(t, "shape") else tuple(np.asarray(t).shape)
         b, v, s, d, oh, ow = cubemap.cube_view_shapes(native.shape, shape(tgt_pose_rt), shape(tgt_pos), size)
         if not any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, tgt_pose_rt, planes)):
@@ -1097,14 +1094,8 @@ class MSI(object):
         else:
             if intrinsics is None:
                 raise ValueError("camera='pinhole' needs intrinsics")
-            intr = self._f32(intrinsics).reshape(-1, 3, 3)
-            if intr.shape[0] == 1:
-                intr = intr.expand(b * v, 3, 3).contiguous()
-            if intr.shape[0] != b * v:
-                raise ValueError("intrinsics must be [B,V,3,3] or [3,3]")
-        rgb = torch.empty((b, v, oh, ow, 3), dtype=torch.float32, device=self.device) if want_rgb else None
-        dep = torch.empty((b, v, oh, ow), dtype=torch.float32, device=self.device) if want_depth else None
-        fmt = self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+            intr = self._pinhole_intrinsics(intrinsics, b, v)
+        rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
         N.check(N.lib.msi_cube_render_views(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(),
                                             depths.data_ptr(), _ptr(trig), b, v, s, d, self.CAMERAS[camera], oh, ow, _ptr(rgb),
                                             _ptr(dep), self._render_status.data_ptr(), self._stream()), "msi_cube_render_views")
