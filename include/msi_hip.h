@@ -65,7 +65,7 @@ const char *msi_version(void);
  *   8: msi_probe_matrix_rate (round 6)
  *   9: msi_perspective_sweep_volume_bf16
  *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images; msi_cube_render_views,
- *      msi_equirect_to_cube_f32) */
+ *      msi_equirect_to_cube_f32; msi_sparse_index_tiles, msi_sparse_gather_tiles, msi_sparse_expand, msi_render_views_sparse) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -316,6 +316,49 @@ int msi_render_ods_views(const void *layers, int32_t format, const float *tgt_po
                          int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
                          int32_t out_height, int32_t out_width,
                          float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
+/* Sparse layer stacks (MSI.sparsify_layers / densify_layers / render_views on a SparseLayers; no reference counterpart): a packed
+ * stack (MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F; fp32 pools are not built) that stores only the tiles a sphere render can see.
+ * matryodshka_amd/sparse.py holds the same rule in numpy (sparsify_np / expand_np); the kernels are tested against it bit for bit.
+ *   tile         4 rows x 16 columns of texels; H % 4 == 0 and W % 16 == 0, otherwise MSI_E_UNSUPPORTED.
+ *   empty texel  its alpha DECODES to zero: code 0 (rgba8), +0 or -0 (rgba16f).
+ *   keep         tile (ty, tx) of layer d of sample b is kept iff d == 0 (the composite takes layer 0's colour whatever its alpha)
+ *                or any texel within Chebyshev distance 1 of the tile -- its 6 x 18 window, x modulo W and y modulo H, as the
+ *                bilinear taps of the sphere renders wrap -- is not empty.  Consequence: a bilinear footprint with ANY of its
+ *                four taps in a dropped tile has four zero alphas, so the layer contributes nothing to that pixel.
+ *   table        int32 [B,D,H/4,W/16]: the tile's index among the kept tiles of its own layer, in row-major tile order, or -1
+ *   layer_start  int64 [B*D+1]: exclusive prefix sum of the kept tiles per layer; layer_start[B*D] = T
+ *   pool         [T][4][16] texels; tile k of layer (b, d) is pool[layer_start[b*D+d] + k].  16-byte aligned.
+ * msi_sparse_index_tiles applies the rule to a dense packed stack: it writes the final table and counts_out [B*D], the kept tiles per
+ * layer (two launches; no atomic decides an index: the result is the same bytes every time).  The prefix sum of the counts and the
+ * allocation of the pool are the caller's.  msi_sparse_gather_tiles copies the kept tiles into pool_out; msi_sparse_expand writes
+ * the dense stack back, all-zero bytes in dropped tiles.  table, layer_start and the pool must belong together (the entry points
+ * trust them: they address the pool through them).
+ * msi_render_views_sparse is msi_render_views_packed (eye_radius == NULL; camera = MSI_CAMERA_EQUIRECT or MSI_CAMERA_PINHOLE) and
+ * msi_render_ods_views (eye_radius [B*V] non-NULL with MSI_CAMERA_EQUIRECT: the same origin formula, the same per-lane status
+ * vote) reading a sparse stack: per layer a lane looks its tap tiles up in the table; with all four present it loads and blends
+ * exactly as the dense kernels do, otherwise the layer's step is skipped (and when no lane of a wavefront has a present
+ * footprint the texel loads are not issued).  CONTRACT: colours are finite in texels whose alpha is zero (always true for rgba8;
+ * an rgba16f inf / NaN colour under a zero alpha is outside it: the dense render turns it into NaN, this one skips it).  Then
+ * every output element compares == to msi_render_views_packed / msi_render_ods_views on the original dense stack and on
+ * msi_sparse_expand's output: the same bits, except that a zero may differ in sign (a skipped step does not add c * 0).  The
+ * status word is the dense kernels' (qc_max sees every layer).
+ * Argument checks before any HIP call, in this order, MSI_E_BADARG unless noted.  Tile entry points: a NULL pointer; unknown
+ * format (MSI_LAYERS_F32 included); non-positive dims (batch < 0); H % 4 or W % 16 -> MSI_E_UNSUPPORTED; H * W >= 2^24.
+ * msi_render_views_sparse: both outputs NULL; a NULL pool / table / layer_start / pose / position / depths; unknown format;
+ * unknown camera; a NULL trig (equirect) / intrinsics (pinhole); eye_radius with the pinhole camera; bad dims; the tile
+ * divisibility -> MSI_E_UNSUPPORTED; views < 1; output size below 1 x 1 (2 x 2 pinhole); H * W >= 2^24; the grid limit of the
+ * other views renders.  batch = 0 returns MSI_OK after validation, without a launch. */
+int msi_sparse_index_tiles(const void *layers, int32_t format, int32_t batch, int32_t num_planes, int32_t height, int32_t width,
+                           int32_t *table_out, int32_t *counts_out, msi_stream_t stream);
+int msi_sparse_gather_tiles(const void *layers, int32_t format, const int32_t *table, const int64_t *layer_start, int32_t batch,
+                            int32_t num_planes, int32_t height, int32_t width, void *pool_out, msi_stream_t stream);
+int msi_sparse_expand(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format, int32_t batch,
+                      int32_t num_planes, int32_t height, int32_t width, void *layers_out, msi_stream_t stream);
+int msi_render_views_sparse(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format,
+                            const float *tgt_pose_rt, const float *tgt_pos, const float *intrinsics, const float *eye_radius,
+                            const float *depths, const float *trig, int32_t batch, int32_t views, int32_t height, int32_t width,
+                            int32_t num_planes, int32_t camera, int32_t out_height, int32_t out_width, float *out_rgb,
+                            float *out_depth, int32_t *status_device, msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "PackedLayers":      # (packed.py does not load the library: a saved stack can be read on a host without a GPU)
         from .packed import PackedLayers
         return PackedLayers
+    if name == "SparseLayers":      # (sparse.py neither)
+        from .sparse import SparseLayers
+        return SparseLayers
     raise AttributeError(name)

@@ -4,6 +4,7 @@
 //   geo_layers.hip  K3 RGBA assembly, bilinear resize, the fused high-res layer stack, pack / unpack of the compact stacks
 //   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed form
 //   geo_ods.hip     K4 with the ODS stereo camera: render_ods_views_kernel (both eyes of a stack per launch, fp32 or packed stacks)
+//   geo_sparse.hip  K4 from a sparse stack: the tile index / gather / expand kernels and render_views_sparse_kernel (the cameras of render and ods)
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the

@@ -18,6 +18,10 @@ camera lines (`scene ref src tgt input_offset tgt_offset`, datasets.py:427-437) 
 `--msi_format rgba8|rgba16f` also keeps each sample's MSI as a compact stack: the inference launch that writes the fp32 layers
 emits the packed ones as well, saved with their planes as `msi_<dir>.npz` (PackedLayers.save) -- the stored-frame feed of
 MSI.render_views; in the high_res modes the high-res stack is kept the same way, as `msi_hres_<dir>.npz` (MSI.hres_layers).
+`--msi_sparse` (with --msi_format, ODS inputs) saves `msi_<dir>.npz` as a SparseLayers instead (MSI.sparsify_layers of the packed stack:
+only the 4 x 16 tiles a sphere render can see; SparseLayers.load reads it, MSI.render_views renders from it with the dense
+render's pixels), prints each sample's occupancy and bytes and writes them to <output_root>/<experiment>/sparse.json -- how sparse
+the stacks of real content are is read off here.  The high-res stack of `--test_type high_res` (`msi_hres_<dir>.npz`) is not sparsified.
 `--checkpoint` reads a TF V2 checkpoint directly (tf_checkpoint.py), `--weights` an .npz of the TF variables
 (see nets.variable_shapes); without either Xavier-initialised
 weights are used (there is no network access for the pretrained checkpoint), step.txt then says 0.
@@ -111,10 +115,21 @@ def write_layer_outputs(outs, jouts, src, ref, num_planes, test_outputs, output_
                 write_image(os.path.join(output_dir, "jitter_msi_rgb_%.2d.png" % i), (jr[0, :, :, i, :3] + 1.) / 2. * 255)
 
 
-def save_packed_msi(outs, output_dir, dirname):
-    """--msi_format: the sample's packed stack (with its planes) as msi_<dirname>.npz next to its other files."""
-    if "packed_layers" in outs:
-        outs["packed_layers"].save(os.path.join(output_dir, "msi_%s.npz" % dirname))
+def save_packed_msi(outs, output_dir, dirname, model=None, sparse_log=None):
+    """--msi_format: the sample's packed stack (with its planes) as msi_<dirname>.npz next to its other files.  sparse_log (--msi_sparse; a
+    list, needs model): the file is the stack's SparseLayers instead, and the sample's occupancy and bytes are appended to the list."""
+    if "packed_layers" not in outs:
+        return
+    packed = outs["packed_layers"]
+    if sparse_log is None:
+        packed.save(os.path.join(output_dir, "msi_%s.npz" % dirname))
+        return
+    sparse = model.sparsify_layers(packed)
+    sparse.save(os.path.join(output_dir, "msi_%s.npz" % dirname))
+    entry = dict(name=dirname, occupancy=sparse.occupancy, nbytes=sparse.nbytes, dense_nbytes=packed.nbytes)
+    sparse_log.append(entry)
+    print("Sparse MSI of %s: occupancy %.4f, %d bytes (dense %s: %d bytes)" % (dirname, entry["occupancy"], entry["nbytes"], packed.format,
+                                                                              entry["dense_nbytes"]))
 
 
 class DeviceScores(object):
@@ -170,11 +185,12 @@ class DeviceScores(object):
 
 
 def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_outputs, output_dir, dirname,
-               which_color_pred="blend_psv", jitter_pose=None, msi_format=None, scorer=None, scene=None, recon=False):
+               which_color_pred="blend_psv", jitter_pose=None, msi_format=None, scorer=None, scene=None, recon=False, sparse_log=None):
     """One iteration of the loop at test.py:199-281.  images = (ref, src, tgt) float [H,W,3] in [0,1]
     (image order ref, src, tgt: data_loader.py:134-136).  msi_format ('rgba8' | 'rgba16f'): the sample's inference also
     emits the packed stack, saved as msi_<dirname>.npz; every other output is unchanged.  recon (--recon_score; needs scorer):
-    both input eyes rendered back from the MSI in one launch, written as recon_ref_* / recon_src_* and scored."""
+    both input eyes rendered back from the MSI in one launch, written as recon_ref_* / recon_src_* and scored.  sparse_log (--msi_sparse):
+    see save_packed_msi."""
     import torch
     ref, src, tgt = (torch.from_numpy(np.ascontiguousarray(x[None])) for x in images)
     eye = np.eye(4, dtype=np.float32)[None]
@@ -255,7 +271,7 @@ def run_sample(model, images, baseline, tgt_pos, planes, num_planes, ngf, test_o
             write_image(os.path.join(output_dir, "output_ptgt%d_%s.png" % (vw, dirname)),
                         model.deprocess_image(o)[0].cpu().numpy())
     write_layer_outputs(outs, jouts, src, ref, num_planes, test_outputs, output_dir, dirname, which_color_pred)
-    save_packed_msi(outs, output_dir, dirname)
+    save_packed_msi(outs, output_dir, dirname, model, sparse_log)
     if deferred:
         raise deferred[0]
     return outs
@@ -357,6 +373,10 @@ def main(argv=None):
                     help="also save each sample's MSI as a compact layer stack msi_<dir>.npz (PackedLayers.save, planes included), "
                          "emitted by the same launch that writes the fp32 layers (with --test_type high_res also the high-res "
                          "stack, msi_hres_<dir>.npz); default: off")
+    ap.add_argument("--msi_sparse", action="store_true",
+                    help="with --msi_format, ODS inputs: save msi_<dir>.npz as a SparseLayers (only the occupied 4 x 16 tiles; --height %% 4 == 0 "
+                         "and --width %% 16 == 0) and write each sample's occupancy and bytes to <experiment>/sparse.json; the high-res stack of "
+                         "--test_type high_res (msi_hres_<dir>.npz) is not sparsified and stays dense, and high_res_only is refused; default: off")
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--hres_height", type=int, default=2048, help="loader.py:34")
@@ -400,6 +420,14 @@ def main(argv=None):
         ap.error("--recon_score needs --score")
     if args.recon_score and args.input_type != "ODS":
         ap.error("--recon_score renders ODS eyes: --input_type ODS only")
+    if args.msi_sparse and args.msi_format is None:
+        ap.error("--msi_sparse needs --msi_format")
+    if args.msi_sparse and args.input_type != "ODS":
+        ap.error("--msi_sparse keeps sphere stacks (the planar viewer does not read sparse stacks): --input_type ODS only")
+    if args.msi_sparse and (args.height % 4 or args.width % 16):
+        ap.error("--msi_sparse needs --height % 4 == 0 and --width % 16 == 0")
+    if args.msi_sparse and "high_res_only" in args.test_type:
+        ap.error("--msi_sparse sparsifies the low-res stacks only: --test_type high_res_only has none (the high-res stack stays dense)")
     if args.num_psv_planes != args.num_msi_planes:
         raise SystemExit("--num_psv_planes must equal --num_msi_planes (msi.py:138 indexes the source volume with num_msi_planes)")
     if "high_res" in args.test_type and args.input_type != "ODS":
@@ -427,6 +455,7 @@ def main(argv=None):
     exp_dir = os.path.join(args.output_root, args.experiment_name)
     os.makedirs(exp_dir, exist_ok=True)
     scorer = DeviceScores(model, keep_frames="on_video" in args.test_type) if args.score else None
+    sparse_log = [] if args.msi_sparse else None
     samples = list(parse_camera_files(args.cameras_glob, args.input_type))
     if args.num_runs >= 0:
         samples = samples[:args.num_runs]
@@ -453,7 +482,7 @@ def main(argv=None):
                         jitter = poses.random_rotation(args.rot_factor, args.tr_factor, jitter_rng)
                     run_sample(model, images, cam[0], cam[1:4], planes, d, args.ngf, args.test_outputs, out_dir, dirname,
                                which_color_pred=args.which_color_pred, jitter_pose=jitter, msi_format=args.msi_format,
-                               scorer=scorer, scene=scene, recon=args.recon_score)
+                               scorer=scorer, scene=scene, recon=args.recon_score, sparse_log=sparse_log)
                 model.render_status()        # raises if a render's ray origin was outside the innermost sphere
             except (MsiError, ValueError) as e:
                 # a sample whose statistics leave the LayerNorm window (a heuristic built from the weights) or whose target lies
@@ -474,6 +503,12 @@ def main(argv=None):
             dirname = sample_dirname(scene, ids, args.test_type, args.prefix)
             run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname, msi_format=args.msi_format)
             n += "high_res_only" in args.test_type
+    if sparse_log is not None:
+        from .sparse import TILE_H, TILE_W
+        with open(os.path.join(exp_dir, "sparse.json"), "w") as f:
+            json.dump(dict(format=args.msi_format, tile=[TILE_H, TILE_W], samples=sparse_log,
+                           mean_occupancy=float(np.mean([e["occupancy"] for e in sparse_log])) if sparse_log else None), f)
+        print("Occupancies written to %s" % os.path.join(exp_dir, "sparse.json"))
     if scorer is not None:
         with open(os.path.join(exp_dir, "scores.json"), "w") as f:
             json.dump(scorer.table(), f)

@@ -21,6 +21,7 @@ import torch
 from . import _native as N
 from . import nets
 from .packed import FORMATS as PACKED_FORMATS, PackedLayers
+from .sparse import SparseLayers, TILE_H, TILE_W
 
 
 def _ptr(t):
@@ -467,6 +468,9 @@ class MSI(object):
 
     # ------------------------------------------------------------------ msi.py:384-452
     def _native_layers(self, rgba_layers):
+        if isinstance(rgba_layers, SparseLayers):
+            raise TypeError("this method does not read sparse stacks: render a SparseLayers with render_views or render_ods_pair "
+                            "(MSI), or expand it with densify_layers first")
         if isinstance(rgba_layers, PackedLayers):
             raise TypeError("this method reads fp32 layer stacks only: render a PackedLayers with render_views (MSI) or "
                             "mpi_render_views (MPI), or expand it with unpack_layers first")
@@ -685,7 +689,11 @@ class MSI(object):
         circle inside); device-side ones are flagged through render_status().
         rgba_layers may be a PackedLayers (pack_layers; msi_render_views_packed): the kernel gathers from the compact stack
         itself and the outputs are bit-identical to rendering unpack_layers(rgba_layers).  planes=None then takes the planes
-        the PackedLayers carries (ValueError when it carries none); for an fp32 stack planes is required."""
+        the PackedLayers carries (ValueError when it carries none); for an fp32 stack planes is required.
+        rgba_layers may be a SparseLayers (sparsify_layers; msi_render_views_sparse), for all three cameras: every output element
+        compares == to the render of the PackedLayers it was made from and of densify_layers(rgba_layers) -- the same bits, except
+        that a zero may differ in sign -- provided colours are finite where alpha is zero (always so for rgba8).  planes=None
+        takes the planes it carries."""
         if camera not in self.CAMERAS:
             raise ValueError("camera must be 'equirect', 'pinhole' or 'ods', not %r" % (camera,))
         if camera != 'ods' and (eye is not None or baseline is not None):
@@ -694,8 +702,16 @@ class MSI(object):
             raise ValueError("render_views: camera='ods' needs eye (+1 / 'left' or -1 / 'right', or an array [V] / [B,V])")
         if not (want_rgb or want_depth):
             raise ValueError("render_views: want_rgb and want_depth are both False")
-        native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "render_views")
-        b, d, h, w, _ = native.shape
+        sparse = rgba_layers if isinstance(rgba_layers, SparseLayers) else None
+        if sparse is not None:
+            sparse = sparse if sparse.pool.device == self.device else sparse.to(self.device)
+            planes = sparse.planes if planes is None else planes
+            if planes is None:
+                raise ValueError("render_views: planes is required (this SparseLayers carries none)")
+            (b, h, w, d), fmt = sparse.shape, self.LAYER_FORMATS[sparse.format]
+        else:
+            native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "render_views")
+            b, d, h, w, _ = native.shape
         if camera != 'ods':
             self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
         pose, pos, v = self._view_poses("tgt_pose_rt", tgt_pose_rt, tgt_pos, b)
@@ -709,6 +725,9 @@ class MSI(object):
             self._ods_domain_guard(tgt_pos, tgt_pose_rt, planes, radius)
             radius = self._f32(radius).reshape(b * v)
             rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
+            if sparse is not None:
+                return self._render_sparse(sparse, fmt, pose, pos, None, radius, depths, self._trig(oh, ow), v, N.MSI_CAMERA_EQUIRECT,
+                                           oh, ow, rgb, dep)
             N.check(N.lib.msi_render_ods_views(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(), radius.data_ptr(),
                                                depths.data_ptr(), self._trig(oh, ow).data_ptr(), b, v, h, w, d, oh, ow,
                                                _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream()),
@@ -723,6 +742,8 @@ class MSI(object):
             oh, ow = int(size[0]), int(size[1])
             intr = self._pinhole_intrinsics(intrinsics, b, v)
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
+        if sparse is not None:
+            return self._render_sparse(sparse, fmt, pose, pos, intr, None, depths, trig, v, self.CAMERAS[camera], oh, ow, rgb, dep)
         if packed is not None:
             N.check(N.lib.msi_render_views_packed(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(),
                                                   _ptr(intr), depths.data_ptr(), _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow,
@@ -732,6 +753,14 @@ class MSI(object):
         N.check(N.lib.msi_render_views_f32(native.data_ptr(), pose.data_ptr(), pos.data_ptr(), _ptr(intr), depths.data_ptr(),
                                            _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep),
                                            self._render_status.data_ptr(), self._stream()), "msi_render_views_f32")
+        return rgb, dep
+
+    def _render_sparse(self, sparse, fmt, pose, pos, intr, radius, depths, trig, v, camera, oh, ow, rgb, dep):
+        b, h, w, d = sparse.shape
+        N.check(N.lib.msi_render_views_sparse(sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(), fmt,
+                                              pose.data_ptr(), pos.data_ptr(), _ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig),
+                                              b, v, h, w, d, camera, oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(),
+                                              self._stream()), "msi_render_views_sparse")
         return rgb, dep
 
     EYES = {'left': 1.0, 'right': -1.0}
@@ -799,7 +828,7 @@ class MSI(object):
         top -- the delivery format of 360 players, without a copy."""
         if layout not in ('views', 'top_bottom'):
             raise ValueError("layout must be 'views' or 'top_bottom', not %r" % (layout,))
-        b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]
+        b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]     # (SparseLayers.shape is (B, H, W, D))
 
         def per_view(x, default, tail):
             if x is None:
@@ -841,10 +870,55 @@ class MSI(object):
                 "msi_pack_layers")
         return PackedLayers(data, format, planes)
 
+    def sparsify_layers(self, layers, format='rgba8', planes=None):
+        """A stack -> SparseLayers (matryodshka_amd/sparse.py: only the 4 x 16 tiles a sphere render can see are stored).  `layers` is
+        an fp32 stack [B,H,W,D,4], packed first with pack_layers(layers, format), or a PackedLayers, whose own format is kept.
+        H % 4 == 0 and W % 16 == 0 are required (ValueError).  `planes`, or else the planes a PackedLayers carries, travel with the stack.
+        Three launches (msi_sparse_index_tiles: two, msi_sparse_gather_tiles) around one host synchronisation: the pool's size is
+        data-dependent.  The result is the same bytes every time and equals sparse.sparsify_np of the codes."""
+        if isinstance(layers, SparseLayers):
+            raise TypeError("sparsify_layers takes an fp32 stack or a PackedLayers, not a SparseLayers")
+        pk = layers if isinstance(layers, PackedLayers) else self.pack_layers(layers, format, planes)
+        planes = pk.planes if planes is None else planes
+        data = pk.data if pk.data.device == self.device else pk.data.to(self.device)
+        b, d, h, w, _ = data.shape
+        if planes is not None and len(planes) != d:
+            raise ValueError("len(planes) != number of layers")
+        if h % TILE_H or w % TILE_W:
+            raise ValueError("a sparse stack needs H %% %d == 0 and W %% %d == 0, not %d x %d" % (TILE_H, TILE_W, h, w))
+        fmt = self.LAYER_FORMATS[pk.format]
+        table = torch.empty((b, d, h // TILE_H, w // TILE_W), dtype=torch.int32, device=self.device)
+        counts = torch.empty((b * d,), dtype=torch.int32, device=self.device)
+        N.check(N.lib.msi_sparse_index_tiles(data.data_ptr(), fmt, b, d, h, w, table.data_ptr(), counts.data_ptr(), self._stream()),
+                "msi_sparse_index_tiles")
+        layer_start = torch.zeros((b * d + 1,), dtype=torch.int64, device=self.device)
+        if b * d:
+            layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(layer_start[-1].item())
+        pool = torch.empty((total, TILE_H, TILE_W, 4), dtype=data.dtype, device=self.device)
+        if total:
+            N.check(N.lib.msi_sparse_gather_tiles(data.data_ptr(), fmt, table.data_ptr(), layer_start.data_ptr(), b, d, h, w,
+                                                  pool.data_ptr(), self._stream()), "msi_sparse_gather_tiles")
+        return SparseLayers(table, layer_start, pool, pk.format, planes)
+
+    def densify_layers(self, sparse):
+        """SparseLayers -> the PackedLayers it stands for, all-zero bytes in dropped tiles (msi_sparse_expand)."""
+        if not isinstance(sparse, SparseLayers):
+            raise TypeError("densify_layers takes a SparseLayers")
+        sparse = sparse if sparse.pool.device == self.device else sparse.to(self.device)
+        b, h, w, d = sparse.shape
+        data = torch.empty((b, d, h, w, 4), dtype=sparse.pool.dtype, device=self.device)
+        if data.numel():
+            N.check(N.lib.msi_sparse_expand(sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(),
+                                            self.LAYER_FORMATS[sparse.format], b, d, h, w, data.data_ptr(), self._stream()),
+                    "msi_sparse_expand")
+        return PackedLayers(data, sparse.format, sparse.planes)
+
     def unpack_layers(self, packed):
         """PackedLayers -> fp32 [B,H,W,D,4], a permuted view of a new native [B,D,H,W,4] stack (msi_unpack_layers)."""
         if not isinstance(packed, PackedLayers):
-            raise TypeError("unpack_layers takes a PackedLayers")
+            raise TypeError("unpack_layers takes a PackedLayers" + (" (expand a SparseLayers with densify_layers first)"
+                                                                    if isinstance(packed, SparseLayers) else ""))
         data = packed.data if packed.data.device == self.device else packed.data.to(self.device)
         b, d, h, w, _ = data.shape
         native = torch.empty((b, d, h, w, 4), dtype=torch.float32, device=self.device)
