@@ -245,7 +245,12 @@ int msi_render_equirect_f32(const float *rgba_native, const float *tgt_pose_rt,
  *                        (fx, cx in row 0; fy, cy in row 1) (required); trig unused.  out size >= 2 x 2.
  *   out_rgb [B,V,out_height,out_width,3], out_depth [B,V,out_height,out_width] (ONE channel: the composited i / D of
  *   over_composite_depth); either may be NULL, not both.  status_device as above (may be NULL).
- * The grid runs sample -> view -> row: the views of one stack are rendered one after another. */
+ * The grid runs sample -> view -> row: the views of one stack are rendered one after another.
+ * Argument checks before any launch, in this order (the one order of every *_render_views entry point; each lists its own
+ * instance), MSI_E_BADARG: both outputs NULL; a NULL stack / pose / position / depths; unknown format (msi_render_views_packed);
+ * unknown camera; a NULL trig (equirect) / intrinsics (pinhole); batch < 0 or a non-positive height / width / num_planes ("bad
+ * dims"); views < 1; an output size below 1 x 1 (2 x 2 pinhole); H * W >= 2^24 (24-bit texel offsets); more than 2^31 - 8
+ * workgroups (64 output pixels of a row each).  batch = 0 then returns MSI_OK without a launch. */
 #define MSI_CAMERA_EQUIRECT 0
 #define MSI_CAMERA_PINHOLE 1
 int msi_render_views_f32(const float *rgba_native, const float *tgt_pose_rt, const float *tgt_pos,
@@ -310,7 +315,10 @@ int msi_render_views_packed(const void *layers, int32_t format, const float *tgt
  * status_device (may be NULL): the origin differs from pixel to pixel here, so MSI_RENDER_STATUS_ORIGIN_OUTSIDE is set when ANY
  * rendered pixel's origin is not strictly inside every sphere it is intersected with, or is NaN -- also when only a part of
  * the circle leaves the innermost sphere (every lane tests its own origin; one atomic OR per wavefront).  Pixels stay finite
- * (clamped discriminant), as in the other renders.  batch = 0 returns MSI_OK after validation, without a launch. */
+ * (clamped discriminant), as in the other renders.
+ * Argument checks before any launch, in this order, MSI_E_BADARG: both outputs NULL; a NULL input (every pointer but the outputs
+ * and status_device is required); unknown format; bad dims; views < 1; an output size below 1 x 1; H * W >= 2^24; the grid limit
+ * of msi_render_views_f32.  batch = 0 then returns MSI_OK without a launch. */
 int msi_render_ods_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
                          const float *eye_radius, const float *depths, const float *trig,
                          int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
@@ -427,9 +435,9 @@ int msi_mpi_render_f32(const float *rgba_native, const float *tgt_pose, const fl
  *          contributes zeros with its weight (no wrap-around): where every layer samples outside, rgb and depth are 0.
  *   packed stacks  Every tap is decoded by the rule of msi_unpack_layers, so the outputs are bit-identical to the same call
  *          on the msi_unpack_layers of the stack with MSI_LAYERS_F32.
- * Argument checks before any launch, MSI_E_BADARG unless noted: both outputs NULL; a NULL input; batch < 0 or a
- * non-positive height / width / num_planes ("bad dims"); views < 1; an output size below 1 x 1; an unknown format;
- * num_planes > 128 -> MSI_E_UNSUPPORTED; H * W >= 2^24 (24-bit texel offsets); more than 2^31 - 8 workgroups (64 x 4
+ * Argument checks before any launch, in this order, MSI_E_BADARG unless noted: both outputs NULL; a NULL input; an unknown
+ * format; batch < 0 or a non-positive height / width / num_planes ("bad dims"); num_planes > 128 -> MSI_E_UNSUPPORTED;
+ * views < 1; an output size below 1 x 1; H * W >= 2^24 (24-bit texel offsets); more than 2^31 - 8 workgroups (64 x 4
  * output pixels each).  batch = 0 then returns MSI_OK without a launch. */
 int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_pose, const float *intrinsics,
                          const float *tgt_intrinsics_inv, const float *depths, int32_t batch, int32_t views, int32_t height,
@@ -466,10 +474,11 @@ int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_po
  * stack.  status_device as in msi_render_views_f32: MSI_RENDER_STATUS_ORIGIN_OUTSIDE when a view's origin is not strictly
  * inside the innermost shell (max |o_k| >= min depths, or NaN); its pixels are finite for finite inputs.  Every texel address
  * is in range by construction for any input.
- * Argument checks before any launch, MSI_E_BADARG unless noted: both outputs NULL; a NULL input (trig / tgt_intrinsics only
- * for their camera); unknown format or camera; batch < 0 or non-positive face_size / num_planes ("bad dims"); views < 1; an
- * output size below 1 x 1 (2 x 2 for the pinhole camera); num_planes > 128 -> MSI_E_UNSUPPORTED; a sample whose six face
- * stacks reach 2^31 bytes (32-bit per-lane offsets); more than 2^31 - 8 workgroups.  batch = 0 returns MSI_OK, no launch. */
+ * Argument checks before any launch, in this order, MSI_E_BADARG unless noted: both outputs NULL; a NULL stack / pose /
+ * position / stack_intrinsics / depths; unknown format; unknown camera; a NULL trig (equirect) / tgt_intrinsics (pinhole);
+ * batch < 0 or non-positive face_size / num_planes ("bad dims"); num_planes > 128 -> MSI_E_UNSUPPORTED; views < 1; an output
+ * size below 1 x 1 (2 x 2 for the pinhole camera); a sample whose six face stacks reach 2^31 bytes (32-bit per-lane offsets);
+ * more than 2^31 - 8 workgroups.  batch = 0 returns MSI_OK, no launch. */
 int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
                           const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
                           int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,

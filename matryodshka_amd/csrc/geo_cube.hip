@@ -47,7 +47,7 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
   const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;                 // (no barrier below; lane (0, 0) of a workgroup is always inside)
 
-  ViewRay r = view_ray<CAMERA>(intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);
+  ViewRay r = view_ray<CAMERA>(intrinsics, nullptr, trig, tgt_pos, bv, i, j, out_h, out_w);
   apply_pose(pose_rt + (size_t)bv * 16, r);
   // render frame -> cube frame: x <-> z
   const float dx = r.rz, dy = r.ry, dz = r.rx;
@@ -180,26 +180,21 @@ int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_p
                           int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
                           int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
                           msi_stream_t stream) {
-  MSI_REQUIRE(out_rgb || out_depth, "cube_render_views: both outputs are NULL");
-  MSI_REQUIRE(layers && tgt_pose_rt && tgt_pos && stack_intrinsics && depths, "cube_render_views: null pointer");
-  MSI_REQUIRE(format == MSI_LAYERS_F32 || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F,
-              "cube_render_views: unknown format %d", format);
-  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || camera == MSI_CAMERA_PINHOLE, "cube_render_views: unknown camera %d", camera);
-  MSI_REQUIRE(camera != MSI_CAMERA_EQUIRECT || trig, "cube_render_views: null pointer (equirect camera needs trig)");
-  MSI_REQUIRE(camera != MSI_CAMERA_PINHOLE || tgt_intrinsics, "cube_render_views: null pointer (pinhole camera needs intrinsics)");
-  MSI_REQUIRE(batch >= 0 && face_size > 0 && num_planes > 0, "cube_render_views: bad dims");
-  MSI_REQUIRE(views >= 1, "cube_render_views: views must be >= 1 (got %d)", views);
-  const int min_out = camera == MSI_CAMERA_PINHOLE ? 2 : 1;
-  MSI_REQUIRE(out_height >= min_out && out_width >= min_out, "cube_render_views: bad output size %d x %d", out_height, out_width);
-  if (num_planes > DEPTH_FRAC_MAX)
-    return msi::fail(MSI_E_UNSUPPORTED, "cube_render_views: at most %d planes", DEPTH_FRAC_MAX);
+  const ViewArgs a = {"cube_render_views", out_rgb, out_depth, layers && tgt_pose_rt && tgt_pos && stack_intrinsics && depths, format, ANY_FORMAT, "",
+                      &camera, trig, tgt_intrinsics, nullptr, batch >= 0 && face_size > 0 && num_planes > 0, 0, views, batch, out_height, out_width, 4};
+  const auto planes = [&] {
+    return num_planes <= DEPTH_FRAC_MAX ? (int)MSI_OK : msi::fail(MSI_E_UNSUPPORTED, "cube_render_views: at most %d planes", DEPTH_FRAC_MAX);
+  };
   // the per-sample descriptor: the six faces' stacks are addressed with one 32-bit byte offset per lane
-  const int texel_bytes = format == MSI_LAYERS_F32 ? 16 : format == MSI_LAYERS_RGBA16F ? 8 : 4;
-  MSI_REQUIRE(face_size < (1 << 15) && (long)face_size * face_size * 6 * num_planes * texel_bytes < (1L << 31),   // (< 2^30 * 6 * 128 * 16)
-              "cube_render_views: a sample's six face stacks (6 x %d x %d x %d texels of %d bytes) reach 2^31 bytes (32-bit offsets)",
-              num_planes, face_size, face_size, texel_bytes);
+  const auto sample_bytes = [&] {
+    const int texel_bytes = format == MSI_LAYERS_F32 ? 16 : format == MSI_LAYERS_RGBA16F ? 8 : 4;
+    MSI_REQUIRE(face_size < (1 << 15) && (long)face_size * face_size * 6 * num_planes * texel_bytes < (1L << 31),   // (< 2^30 * 6 * 128 * 16)
+                "cube_render_views: a sample's six face stacks (6 x %d x %d x %d texels of %d bytes) reach 2^31 bytes (32-bit offsets)",
+                num_planes, face_size, face_size, texel_bytes);
+    return (int)MSI_OK;
+  };
   unsigned grid;
-  if (const int e = view_grid("cube_render_views", (long)((out_width + 63) / 64) * ((out_height + 3) / 4), views, batch, &grid)) return e;
+  if (const int e = check_views(a, planes, sample_bytes, &grid)) return e;
   if (batch == 0) return MSI_OK;
   const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);

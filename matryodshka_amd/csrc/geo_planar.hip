@@ -536,18 +536,14 @@ int msi_mpi_render_views(const void *layers, int32_t format, const float *tgt_po
                          const float *tgt_intrinsics_inv, const float *depths, int32_t batch, int32_t views, int32_t height,
                          int32_t width, int32_t num_planes, int32_t out_height, int32_t out_width, float *out_rgb,
                          float *out_depth, msi_stream_t stream) {
-  MSI_REQUIRE(out_rgb || out_depth, "mpi_render_views: both outputs are NULL");
-  MSI_REQUIRE(layers && tgt_pose && intrinsics && tgt_intrinsics_inv && depths, "mpi_render_views: null pointer");
-  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "mpi_render_views: bad dims");
-  MSI_REQUIRE(views >= 1, "mpi_render_views: views must be >= 1 (got %d)", views);
-  MSI_REQUIRE(out_height >= 1 && out_width >= 1, "mpi_render_views: bad output size %d x %d", out_height, out_width);
-  MSI_REQUIRE(format == MSI_LAYERS_F32 || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F,
-              "mpi_render_views: unknown format %d", format);
-  if (num_planes > MPI_MAX_PLANES)
-    return msi::fail(MSI_E_UNSUPPORTED, "mpi_render_views: at most %d planes", MPI_MAX_PLANES);
-  MSI_REQUIRE((long)height * width < (1L << 24), "mpi_render_views: layers of more than 2^24 texels (24-bit texel offsets)");
+  const ViewArgs a = {"mpi_render_views", out_rgb, out_depth, layers && tgt_pose && intrinsics && tgt_intrinsics_inv && depths, format, ANY_FORMAT, "",
+                      nullptr, nullptr, nullptr, nullptr, batch >= 0 && height > 0 && width > 0 && num_planes > 0, (long)height * width,
+                      views, batch, out_height, out_width, 4};
+  const auto planes = [&] {
+    return num_planes <= MPI_MAX_PLANES ? (int)MSI_OK : msi::fail(MSI_E_UNSUPPORTED, "mpi_render_views: at most %d planes", MPI_MAX_PLANES);
+  };
   unsigned grid;
-  if (const int e = view_grid("mpi_render_views", (long)((out_width + 63) / 64) * ((out_height + 3) / 4), views, batch, &grid)) return e;
+  if (const int e = check_views(a, planes, no_check, &grid)) return e;
   if (batch == 0) return MSI_OK;
   const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);

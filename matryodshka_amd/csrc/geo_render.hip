@@ -7,7 +7,7 @@ namespace {
 
 // ------------------------------------------------------------------------ K4
 // The kernels are built from the sphere-render pieces of geometry_device.h (SphereBlock: the workgroup shape and the XCD-aware grid; apply_pose,
-// sphere_quad, SphereStack::layer: the per-layer step; over_step; sphere_combine: the segment combine); each supplies its rays and its stores.
+// sphere_quad, sphere_uv: the per-layer geometry; SphereStack::layer: the per-layer step; over_step; sphere_combine: the segment combine).
 // ray model of the TARGET view: equirect (spherical.intersect_sphere, spherical.py:268-326),
 // ODS eye (intersect_ods, :328-365) or the hard-coded perspective crop (intersect_perspective, :367-401)
 enum RayModel { RAY_EQUIRECT = 0, RAY_ODS = 1, RAY_PERSPECTIVE = 2 };
@@ -57,8 +57,8 @@ render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt
   apply_pose(pose_rt + (size_t)b * 16, r);
   const SphereQuad q = sphere_quad(r);
 
-  // The per-layer step and the over-composite step are this kernel's own text (SphereStack::layer and over_step are the same arithmetic): written with
-  // them, not every instantiation keeps the instruction stream that bench.py times (profiles/shared_render_pieces_isa.txt).
+  // The gathers and the over-composite step are this kernel's own text (SphereStack::layer's and over_step's arithmetic): written with them, not
+  // every instantiation keeps the instruction stream that bench.py times (profiles/shared_render_pieces_isa.txt).
   const size_t hw = (size_t)height * width;             // source layer size
   const int layer_bytes = (int)(hw * 16);                // (H * W < 2^24, checked on the host)
   const size_t ohw = (size_t)R.out_h * R.out_w;          // target size
@@ -69,31 +69,9 @@ render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt
 
 #pragma unroll 4
   for (int d = d_lo; d < d_hi; ++d) {
-    const float radius = depths[d];
-    const float qc = q.cc - radius * radius;
-    qc_max = fmaxf(qc_max, qc);
-    const float disc = q.qb2 - q.fa * qc;
-#if MSI_FAST_TAIL
-    const float num = t_sqrt(fmaxf(disc, 0.0f)) - q.qb;
-    const float tq = num * q.inv_ta;
-    const float t = __builtin_fmaf(__builtin_fmaf(-tq, q.ta, num), q.inv_ta, tq);
-#else
-    const float t = t_div(-q.qb + t_sqrt(fmaxf(disc, 0.0f)), q.ta);
-#endif
-    const float x = r.cx + t * r.rx;
-    const float y = r.cy + t * r.ry;
-    const float z = r.cz + t * r.rz;
-    float theta, phi;
-    t_angles(x, y, z, radius, theta, phi);
-#if MSI_FAST_TAIL
-    const float u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
-    const float v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
-#else
-    const float u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
-    const float v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
-#endif
-
-    const TapsR tp4 = make_taps_ranged(u, v, width, height);
+    const SphereUv p = sphere_uv(depths[d], r, q, K);
+    qc_max = fmaxf(qc_max, p.qc);
+    const TapsR tp4 = make_taps_ranged(p.u, p.v, width, height);
     const __amdgpu_buffer_rsrc_t L = __builtin_amdgcn_make_buffer_rsrc((void *)(rgba + ((size_t)b * nd + d) * hw), 0, layer_bytes, 0x00020000);
     typedef unsigned u32x4_g __attribute__((ext_vector_type(4)));
     const float4 A = __builtin_bit_cast(float4, (u32x4_g)__builtin_amdgcn_raw_buffer_load_b128(L, tp4.oa << 4, 0, 0));
@@ -147,46 +125,16 @@ render_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt
   });
 }
 
-// Many views of one stack per launch (msi_render_views_f32 / msi_render_views_packed): render_kernel's per-layer arithmetic for V target cameras
-// per sample, view_ray's cameras, from a stack in texel format FMT.  A workgroup is one (sample, view, target row, 64-pixel block).  Outputs
-// rgb [B,V,h,w,3] and depth [B,V,h,w].  One body, two kernel names: the fp32 kernel keeps the name the profiles know it by.
-template <int MODE, int CAMERA, int FMT>
-__device__ __forceinline__ void render_views_body(const void *layers, const float *pose_rt, const float *tgt_pos, const float *intrinsics,
-                                                  const float *depths, const float *trig, int batch, int views, int height, int width, int nd,
-                                                  int out_h, int out_w, float *out_rgb, float *out_depth, const PixConsts &K, const DepthFrac &F,
-                                                  int *status) {
-  SphereBlock s(out_h, out_w, views, batch);
-  if (s.past_end()) return;
-  s.decode(views, out_w);
-  const unsigned bv = s.bv;
-  ViewRay r = view_ray<CAMERA>(intrinsics, trig, tgt_pos, bv, s.i, s.j, out_h, out_w);
-  apply_pose(pose_rt + (size_t)bv * 16, r);
-  const SphereQuad q = sphere_quad(r);
-  const SphereStack<FMT> S(layers, depths, s.b, nd, height, width);
-  const size_t pix = (size_t)bv * out_h * out_w + (size_t)s.i * out_w + s.j;
-  float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f, tr = 1.f;
-  float qc_max = -1.0f;
-#pragma unroll 4
-  for (int d = S.first(s.seg); d < S.end(s.seg); ++d) {
-    const auto t = S.layer(d, r, q, K, qc_max);
-    qc_max = t.qc_max;
-    const Composite n = over_step<MODE>(o0, o1, o2, od, tr, d, t.c, [&] { return depth_frac(F, d, nd); });
-    o0 = n.o0; o1 = n.o1; o2 = n.o2; od = n.od; tr = n.tr;
-  }
-  // (one lane per wave: the origin is a property of the view)
-  if (status != nullptr && threadIdx.x == 0 && (!(qc_max < 0.0f) || q.cc != q.cc)) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
-  sphere_combine(s, o0, o1, o2, od, tr,
-                 [&](float o0, float o1, float o2, float od) { store_pixel<MODE>(out_rgb, out_depth, pix, o0, o1, o2, od); });
-}
-
+// Many views of one stack per launch (msi_render_views_f32 / msi_render_views_packed): render_views_body (geometry_device.h) under two kernel
+// names; the fp32 kernel keeps the name the profiles know it by.
 template <int MODE, int CAMERA>
 __global__ void __launch_bounds__(256)
 render_views_kernel(const float4 *__restrict__ rgba, const float *__restrict__ pose_rt, const float *__restrict__ tgt_pos,
                     const float *__restrict__ intrinsics, const float *__restrict__ depths, const float *__restrict__ trig,
                     int batch, int views, int height, int width, int nd, int out_h, int out_w, float *__restrict__ out_rgb,
                     float *__restrict__ out_depth, PixConsts K, DepthFrac F, int *__restrict__ status) {
-  render_views_body<MODE, CAMERA, MSI_LAYERS_F32>(rgba, pose_rt, tgt_pos, intrinsics, depths, trig, batch, views, height, width, nd, out_h, out_w,
-                                                  out_rgb, out_depth, K, F, status);
+  render_views_body<MODE, CAMERA, MSI_LAYERS_F32>(rgba, pose_rt, tgt_pos, intrinsics, nullptr, depths, trig, batch, views, height, width, nd, out_h,
+                                                  out_w, out_rgb, out_depth, K, F, status);
 }
 
 // FMT = MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F (the formats and their exact rule are in msi_hip.h)
@@ -196,7 +144,7 @@ render_views_packed_kernel(const void *__restrict__ layers, const float *__restr
                            const float *__restrict__ intrinsics, const float *__restrict__ depths, const float *__restrict__ trig,
                            int batch, int views, int height, int width, int nd, int out_h, int out_w, float *__restrict__ out_rgb,
                            float *__restrict__ out_depth, PixConsts K, DepthFrac F, int *__restrict__ status) {
-  render_views_body<MODE, CAMERA, FMT>(layers, pose_rt, tgt_pos, intrinsics, depths, trig, batch, views, height, width, nd, out_h, out_w,
+  render_views_body<MODE, CAMERA, FMT>(layers, pose_rt, tgt_pos, intrinsics, nullptr, depths, trig, batch, views, height, width, nd, out_h, out_w,
                                        out_rgb, out_depth, K, F, status);
 }
 
@@ -254,25 +202,17 @@ int msi_render_equirect_f32(const float *rgba_native, const float *tgt_pose_rt,
                        width, num_planes, same_size(height, width), out_rgb, out_depth, nullptr, status_device, stream);
 }
 
-// msi_render_views_f32 and msi_render_views_packed: one set of checks and one launch table (`who` names the entry point in the
-// error text; `format` is one of MSI_LAYERS_*, already validated by the caller).
+// msi_render_views_f32 and msi_render_views_packed: one launch table behind the checks of every many-views entry point (`who` names the entry
+// point in the error text).
 static int render_views_launch(const char *who, const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
                                const float *intrinsics, const float *depths, const float *trig,
                                int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
                                int32_t camera, int32_t out_height, int32_t out_width,
                                float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream) {
-  MSI_REQUIRE(out_rgb || out_depth, "%s: both outputs are NULL", who);
-  MSI_REQUIRE(layers && tgt_pose_rt && tgt_pos && depths, "%s: null pointer", who);
-  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || camera == MSI_CAMERA_PINHOLE, "%s: unknown camera %d", who, camera);
-  MSI_REQUIRE(camera != MSI_CAMERA_EQUIRECT || trig, "%s: null pointer (equirect camera needs trig)", who);
-  MSI_REQUIRE(camera != MSI_CAMERA_PINHOLE || intrinsics, "%s: null pointer (pinhole camera needs intrinsics)", who);
-  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "%s: bad dims", who);
-  MSI_REQUIRE(views >= 1, "%s: views must be >= 1 (got %d)", who, views);
-  const int min_out = camera == MSI_CAMERA_PINHOLE ? 2 : 1;
-  MSI_REQUIRE(out_height >= min_out && out_width >= min_out, "%s: bad output size %d x %d", who, out_height, out_width);
-  MSI_REQUIRE((long)height * width < (1L << 24), "%s: layers of more than 2^24 texels (24-bit texel offsets)", who);
+  const ViewArgs a = {who, out_rgb, out_depth, layers && tgt_pose_rt && tgt_pos && depths, format, ANY_FORMAT, "", &camera, trig, intrinsics, nullptr,
+                      batch >= 0 && height > 0 && width > 0 && num_planes > 0, (long)height * width, views, batch, out_height, out_width, 1};
   unsigned grid;
-  if (const int e = view_grid(who, (long)((out_width + 63) / 64) * out_height, views, batch, &grid)) return e;
+  if (const int e = check_views(a, no_check, no_check, &grid)) return e;
   if (batch == 0) return MSI_OK;
   const dim3 block(64, RENDER_SEGS);
   const PixConsts K = make_consts(height, width);
@@ -304,8 +244,6 @@ int msi_render_views_packed(const void *layers, int32_t format, const float *tgt
                             int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
                             int32_t camera, int32_t out_height, int32_t out_width,
                             float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream) {
-  MSI_REQUIRE(format == MSI_LAYERS_F32 || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F,
-              "render_views_packed: unknown format %d", format);
   return render_views_launch("render_views_packed", layers, format, tgt_pose_rt, tgt_pos, intrinsics, depths, trig, batch, views,
                              height, width, num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
 }

@@ -146,10 +146,8 @@ __device__ __forceinline__ float blend4(const TapsS &t, float a, float b, float 
 // The sparse sibling of SphereStack: layer d of sample b is two buffer resources -- its row of the table ([H/4, W/16] int32) and its kept tiles in
 // the pool (base = pool + layer_start * tile bytes, num_records = the layer's kept bytes: a texel offset idx * 64 + (y & 3) * 16 + (x & 15) stays
 // below H * W < 2^24 whatever the pool's size, and an offset past the layer's tiles reads zeros instead of another layer).  The per-layer step is
-// split where the memory round trips are: lookup() is SphereStack::layer up to the taps, op for op, plus the table loads of the tap tiles;
+// split where the memory round trips are: lookup() is SphereStack::layer up to the taps (sphere_uv) plus the table loads of the tap tiles;
 // gather() is its four taps and blends for the lanes whose tap tiles are all present.
-constexpr int CAMERA_ODS = 2;   // (this unit's kernels only: not a camera code of the ABI)
-
 template <int FMT> struct SparseStack {
   const char *pool;
   const int *table;
@@ -170,30 +168,9 @@ template <int FMT> struct SparseStack {
   };
   __device__ __forceinline__ Look lookup(int d, const ViewRay &r, const SphereQuad &q, const PixConsts &K, float qc_max) const {
     Look s;
-    const float radius = depths[d];
-    const float qc = q.cc - radius * radius;
-    s.qc_max = fmaxf(qc_max, qc);
-    const float disc = q.qb2 - q.fa * qc;
-#if MSI_FAST_TAIL
-    const float num = t_sqrt(fmaxf(disc, 0.0f)) - q.qb;
-    const float tq = num * q.inv_ta;
-    const float t = __builtin_fmaf(__builtin_fmaf(-tq, q.ta, num), q.inv_ta, tq);
-#else
-    const float t = t_div(-q.qb + t_sqrt(fmaxf(disc, 0.0f)), q.ta);
-#endif
-    const float x = r.cx + t * r.rx;
-    const float y = r.cy + t * r.ry;
-    const float z = r.cz + t * r.rz;
-    float theta, phi;
-    t_angles(x, y, z, radius, theta, phi);
-#if MSI_FAST_TAIL
-    const float u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
-    const float v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
-#else
-    const float u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
-    const float v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
-#endif
-    s.tp = make_taps_sparse(u, v, width, height);
+    const SphereUv p = sphere_uv(depths[d], r, q, K);
+    s.qc_max = fmaxf(qc_max, p.qc);
+    s.tp = make_taps_sparse(p.u, p.v, width, height);
     const size_t l = (size_t)b * nd + d;
     const __amdgpu_buffer_rsrc_t T = __builtin_amdgcn_make_buffer_rsrc((void *)(table + l * (size_t)(table_bytes >> 2)), 0, table_bytes, 0x00020000);
     const unsigned r0 = __umul24(s.tp.y0 >> 2, (unsigned)tx_n), r1 = __umul24(s.tp.y1 >> 2, (unsigned)tx_n);
@@ -232,7 +209,7 @@ template <int FMT> struct SparseStack {
   }
 };
 
-// The body of render_views_kernel (CAMERA = MSI_CAMERA_EQUIRECT / _PINHOLE) and of render_ods_views_kernel (CAMERA_ODS) from a sparse stack.  The layers
+// render_views_body (geometry_device.h) with view_ray's three cameras, from a sparse stack: the same pieces around another layer loop.  The layers
 // of a segment go in groups of GROUP: first the geometry and the table lookups of the whole group (the lookups are a second dependent memory round
 // trip in front of every gather: issued together they overlap), then per layer the gathers and the over step -- for the lanes whose four tap tiles
 // are present; when the wave has none the gathers are not issued.  A lane with a dropped tap tile leaves o, od, tr as they are: in the dense render
@@ -251,18 +228,7 @@ render_views_sparse_kernel(const void *__restrict__ pool, const int *__restrict_
   if (s.past_end()) return;
   s.decode(views, out_w);
   const unsigned bv = s.bv;
-  ViewRay r;
-  if constexpr (CAMERA == CAMERA_ODS) {           // (render_ods_views_kernel's origin, op for op)
-    const int i = s.i, j = s.j;
-    const float cs = trig[j], ss = trig[out_w + j];
-    const float ct = trig[2 * out_w + i], st = trig[2 * out_w + out_h + i];
-    r.rx = cs * ct; r.ry = st; r.rz = ss * ct;
-    const float *tp = tgt_pos + (size_t)bv * 3;
-    const float e = eye_radius[bv];
-    r.cx = tp[2] + ss * e; r.cy = tp[1]; r.cz = tp[0] + (-cs) * e;
-  } else {
-    r = view_ray<CAMERA>(intrinsics, trig, tgt_pos, bv, s.i, s.j, out_h, out_w);
-  }
+  ViewRay r = view_ray<CAMERA>(intrinsics, eye_radius, trig, tgt_pos, bv, s.i, s.j, out_h, out_w);
   apply_pose(pose_rt + (size_t)bv * 16, r);
   const SphereQuad q = sphere_quad(r);
   const SparseStack<FMT> S(pool, table, layer_start, depths, s.b, nd, height, width);
@@ -372,22 +338,15 @@ int msi_render_views_sparse(const void *pool, const int32_t *table, const int64_
                             int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
                             msi_stream_t stream) {
   const char *who = "render_views_sparse";
-  MSI_REQUIRE(out_rgb || out_depth, "%s: both outputs are NULL", who);
-  MSI_REQUIRE(pool && table && layer_start && tgt_pose_rt && tgt_pos && depths, "%s: null pointer", who);
-  MSI_REQUIRE(format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F, "%s: unknown format %d (a sparse stack is rgba8 or rgba16f)", who, format);
-  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || camera == MSI_CAMERA_PINHOLE, "%s: unknown camera %d", who, camera);
-  MSI_REQUIRE(camera != MSI_CAMERA_EQUIRECT || trig, "%s: null pointer (equirect camera needs trig)", who);
-  MSI_REQUIRE(camera != MSI_CAMERA_PINHOLE || intrinsics, "%s: null pointer (pinhole camera needs intrinsics)", who);
-  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || !eye_radius, "%s: eye_radius (the ODS camera) goes with MSI_CAMERA_EQUIRECT", who);
-  MSI_REQUIRE(batch >= 0 && height > 0 && width > 0 && num_planes > 0, "%s: bad dims", who);
-  if (height % TILE_H != 0 || width % TILE_W != 0)
-    return msi::fail(MSI_E_UNSUPPORTED, "%s: a sparse stack needs H %% %d == 0 and W %% %d == 0 (got %d x %d)", who, TILE_H, TILE_W, height, width);
-  MSI_REQUIRE(views >= 1, "%s: views must be >= 1 (got %d)", who, views);
-  const int min_out = camera == MSI_CAMERA_PINHOLE ? 2 : 1;
-  MSI_REQUIRE(out_height >= min_out && out_width >= min_out, "%s: bad output size %d x %d", who, out_height, out_width);
-  MSI_REQUIRE((long)height * width < (1L << 24), "%s: layers of more than 2^24 texels (24-bit texel offsets)", who);
+  const ViewArgs a = {who, out_rgb, out_depth, pool && table && layer_start && tgt_pose_rt && tgt_pos && depths, format,
+                      1u << MSI_LAYERS_RGBA8 | 1u << MSI_LAYERS_RGBA16F, " (a sparse stack is rgba8 or rgba16f)", &camera, trig, intrinsics, eye_radius,
+                      batch >= 0 && height > 0 && width > 0 && num_planes > 0, (long)height * width, views, batch, out_height, out_width, 1};
   unsigned grid;
-  if (const int e = view_grid(who, (long)((out_width + 63) / 64) * out_height, views, batch, &grid)) return e;
+  const auto tiles = [&] {
+    if (height % TILE_H == 0 && width % TILE_W == 0) return (int)MSI_OK;
+    return msi::fail(MSI_E_UNSUPPORTED, "%s: a sparse stack needs H %% %d == 0 and W %% %d == 0 (got %d x %d)", who, TILE_H, TILE_W, height, width);
+  };
+  if (const int e = check_views(a, tiles, no_check, &grid)) return e;
   if (batch == 0) return MSI_OK;
   const dim3 block(64, RENDER_SEGS);
   const PixConsts K = make_consts(height, width);

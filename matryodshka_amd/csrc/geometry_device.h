@@ -416,18 +416,27 @@ template <int ROWS> struct ViewBlock {
   }
 };
 
-// A ray of a target view: direction r, origin c.  view_ray gives both BEFORE the pose for the cameras of render_views and cube_render_views
-// (pose, origin and K of a view are wave-uniform: scalar loads):
+// A ray of a target view: direction r, origin c.  view_ray gives both BEFORE the pose for the cameras of the many-views renders (pose, origin,
+// K and e of a view are wave-uniform: scalar loads; a camera reads its own table only, the others may be nullptr):
 //   MSI_CAMERA_EQUIRECT  (cos S cos T, sin T, sin S cos T) on the lat-long grid of the OUTPUT size (trig = its table)
 //   MSI_CAMERA_PINHOLE   (1, (i + 0.5 - cy) / fy, (j + 0.5 - cx) / fx): forward +x, image-down +y, image-right +z -- the
 //                        orientation of the equirect render around its centre pixel (IEEE divides: per pixel, not per layer)
-// with the origin (tgt_pos[2], tgt_pos[1], tgt_pos[0]) for both; apply_pose is r <- pose[:3,:3] r, c <- pose (c, 1) of every render
-// (spherical.py:303-310 / transform_ray :70-94), terms summed left to right.
+// with the origin (tgt_pos[2], tgt_pos[1], tgt_pos[0]) for both, and
+//   CAMERA_ODS           the equirect camera with the origin moved onto the viewing circle of the view:
+//                          direction  r = (cos S cos T, sin T, sin S cos T)
+//                          origin     c = (tgt_pos[2] + sin S * e, tgt_pos[1], tgt_pos[0] + (-cos S) * e)   -- e = eye_radius[b*V + v], signed:
+//                                                                                             e > 0 the left eye (the reference's order = +1)
+//                        (sin S, 0, -cos S) . r = 0: the ray is tangent to the circle of radius |e| around the head position.  With e = 0 the
+//                        origin is tgt_pos + (+-0) and the render has the bits of the equirect camera.  Column j is column W-1-j of
+//                        render_kernel<RAY_ODS>'s image (msi_render_ods_f32 keeps the reference's mirrored order), i.e. this one is upright
+//                        like every other render here.  The origin -- and with it cc, qb and qc -- is per LANE: see the status word below.
+// apply_pose is r <- pose[:3,:3] r, c <- pose (c, 1) of every render (spherical.py:303-310 / transform_ray :70-94), terms summed left to right.
+constexpr int CAMERA_ODS = 2;   // (the kernels' third camera, chosen by a non-NULL eye_radius: not a camera code of the ABI)
 struct ViewRay { float rx, ry, rz, cx, cy, cz; };
 
 template <int CAMERA>
-__device__ __forceinline__ ViewRay view_ray(const float *intrinsics, const float *trig, const float *tgt_pos, unsigned bv, int i, int j, int out_h,
-                                            int out_w) {
+__device__ __forceinline__ ViewRay view_ray(const float *intrinsics, const float *eye_radius, const float *trig, const float *tgt_pos, unsigned bv,
+                                            int i, int j, int out_h, int out_w) {
   ViewRay r;
   if (CAMERA == MSI_CAMERA_PINHOLE) {
     const float *Kv = intrinsics + (size_t)bv * 9;      // fx . cx / . fy cy
@@ -438,6 +447,12 @@ __device__ __forceinline__ ViewRay view_ray(const float *intrinsics, const float
     const float cs = trig[j], ss = trig[out_w + j];
     const float ct = trig[2 * out_w + i], st = trig[2 * out_w + out_h + i];
     r.rx = cs * ct; r.ry = st; r.rz = ss * ct;
+    if constexpr (CAMERA == CAMERA_ODS) {
+      const float *tp = tgt_pos + (size_t)bv * 3;
+      const float e = eye_radius[bv];
+      r.cx = tp[2] + ss * e; r.cy = tp[1]; r.cz = tp[0] + (-cs) * e;
+      return r;
+    }
   }
   const float *tp = tgt_pos + (size_t)bv * 3;
   r.cx = tp[2]; r.cy = tp[1]; r.cz = tp[0];
@@ -507,8 +522,9 @@ __device__ __forceinline__ void store_pixel(float *out_rgb, float *out_depth, si
 // from the strictly sequential form by ~1e-7).  One thread per pixel left the chip with 3 200 wavefronts for 8 192 wave slots and a 32-deep chain
 // of dependent-latency gathers per thread.  The ray/sphere quadratic's a and b do not depend on the layer, so per layer only sqrt, one divide
 // and the two angles remain; every texel of the D x H x W x 4 stack is fetched from HBM once.
-// What a kernel keeps for itself: where its ray comes from, the status word, and what it stores; render_kernel also keeps its own text of the
-// per-layer step and the over step (as pieces they change some of its instantiations: profiles/shared_render_pieces_isa.txt).
+// The many-views kernels of the three units are ONE body, render_views_body below, for view_ray's three cameras and a stack in any texel format;
+// render_views_sparse_kernel (geo_sparse.hip) runs the same pieces around its own layer loop.  render_kernel keeps its three ray models, its
+// stores and its own text of the gathers and the over step (as pieces they change some of its instantiations: profiles/shared_render_pieces_isa.txt).
 constexpr int RENDER_SEGS = 4;   // layer segments per pixel (threads in y)
 
 struct SphereBlock : ViewBlock<1> {
@@ -528,7 +544,13 @@ struct SphereBlock : ViewBlock<1> {
 // The status word of a sphere render: qc_max, the max over a thread's layers of |origin|^2 - radius^2, is >= 0 when the ray origin (cc = |origin|^2)
 // is not inside every sphere it was intersected with, and cc is NaN for a NaN pose / target position (fmaxf drops NaNs and leaves qc_max at -1 --
 // tested separately): outside the reference's domain (spherical.py:316-318 takes the square root of a negative number there).  The clamp
-// in SphereStack::layer kept the pixels finite; each kernel ORs MSI_RENDER_STATUS_ORIGIN_OUTSIDE into *status on `!(qc_max < 0.0f) || cc != cc`.
+// in sphere_uv kept the pixels finite; each kernel ORs MSI_RENDER_STATUS_ORIGIN_OUTSIDE into *status on `!(qc_max < 0.0f) || cc != cc`, one
+// atomicOr per wave at the most.  Who speaks for the wave depends on the camera: the origin of an equirect or pinhole view is a property of the
+// view, so all lanes agree and lane 0 tests its own.  The origin of an ODS view is a property of the LANE (a point of the viewing circle): a
+// circle that crosses the innermost sphere is outside the domain for some columns only, so every lane tests its own, the wave votes, and lane 0
+// issues the atomicOr.  (Lanes past the row end vote with the last pixel's origin, which a stored lane of this row has too.)  The choice is two
+// lines under `if constexpr (CAMERA == CAMERA_ODS)` in render_views_body and in render_views_sparse_kernel: as one function it changes the
+// instruction counts of both (profiles/ods_camera_pieces_isa.txt).
 
 // the layer-independent part of the ray/sphere quadratic |c + t r|^2 = radius^2 of ray r (after the pose)
 struct SphereQuad { float qb, cc, qb2, fa, ta, inv_ta; };
@@ -542,6 +564,41 @@ __device__ __forceinline__ SphereQuad sphere_quad(const ViewRay &r) {
   q.fa = 4.0f * qa; q.ta = 2.0f * qa;
   q.inv_ta = __builtin_amdgcn_rcpf(q.ta);
   return q;
+}
+
+// The per-layer geometry of every sphere render: where ray r meets the sphere of this radius, as pixel coordinates (u, v) of the layer, and
+// qc = |origin|^2 - radius^2 for the caller's qc_max (the status word above).
+struct SphereUv { float u, v, qc; };
+
+__device__ __forceinline__ SphereUv sphere_uv(float radius, const ViewRay &r, const SphereQuad &q, const PixConsts &K) {
+  SphereUv p;
+  p.qc = q.cc - radius * radius;
+  const float disc = q.qb2 - q.fa * p.qc;
+  // disc >= 0 whenever the ray origin is inside the sphere (the documented domain; the host-side guard of the MSI class
+  // enforces it for host inputs).  Outside it the reference takes sqrt of a negative number and casts NaN to int
+  // (undefined); the clamp keeps device-side inputs finite and changes nothing inside the domain.
+  // (no branch of the reference depends on these values: the whole chain is continuous -> 1-ulp primitives)
+#if MSI_FAST_TAIL
+  const float num = t_sqrt(fmaxf(disc, 0.0f)) - q.qb;           // t = num / ta with the pixel's 1 / ta (one correction step: <= 1 ulp)
+  const float tq = num * q.inv_ta;
+  const float t = __builtin_fmaf(__builtin_fmaf(-tq, q.ta, num), q.inv_ta, tq);
+#else
+  const float t = t_div(-q.qb + t_sqrt(fmaxf(disc, 0.0f)), q.ta);
+#endif
+  const float x = r.cx + t * r.rx;
+  const float y = r.cy + t * r.ry;
+  const float z = r.cz + t * r.rz;
+  // project_spherical (spherical.py:243-246) + theta_phi_to_pixels (:54-68); the point lies on the layer's sphere: |P| = radius
+  float theta, phi;
+  t_angles(x, y, z, radius, theta, phi);
+#if MSI_FAST_TAIL
+  p.u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
+  p.v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
+#else
+  p.u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
+  p.v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
+#endif
+  return p;
 }
 
 // (i / len) of projector.py:242 for layer d, tabulated up to DEPTH_FRAC_MAX layers
@@ -566,35 +623,9 @@ template <int FMT> struct SphereStack {
   struct Step { float4 c; float qc_max; };
   __device__ __forceinline__ Step layer(int d, const ViewRay &r, const SphereQuad &q, const PixConsts &K, float qc_max) const {
     Step s;
-    const float radius = depths[d];
-    const float qc = q.cc - radius * radius;
-    s.qc_max = fmaxf(qc_max, qc);
-    const float disc = q.qb2 - q.fa * qc;
-    // disc >= 0 whenever the ray origin is inside the sphere (the documented domain; the host-side guard of the MSI class
-    // enforces it for host inputs).  Outside it the reference takes sqrt of a negative number and casts NaN to int
-    // (undefined); the clamp keeps device-side inputs finite and changes nothing inside the domain.
-    // (no branch of the reference depends on these values: the whole chain is continuous -> 1-ulp primitives)
-#if MSI_FAST_TAIL
-    const float num = t_sqrt(fmaxf(disc, 0.0f)) - q.qb;           // t = num / ta with the pixel's 1 / ta (one correction step: <= 1 ulp)
-    const float tq = num * q.inv_ta;
-    const float t = __builtin_fmaf(__builtin_fmaf(-tq, q.ta, num), q.inv_ta, tq);
-#else
-    const float t = t_div(-q.qb + t_sqrt(fmaxf(disc, 0.0f)), q.ta);
-#endif
-    const float x = r.cx + t * r.rx;
-    const float y = r.cy + t * r.ry;
-    const float z = r.cz + t * r.rz;
-    // project_spherical (spherical.py:243-246) + theta_phi_to_pixels (:54-68); the point lies on the layer's sphere: |P| = radius
-    float theta, phi;
-    t_angles(x, y, z, radius, theta, phi);
-#if MSI_FAST_TAIL
-    const float u = ((theta + K.pi) - K.pi_over_w) * K.u_scale;
-    const float v = ((phi + K.half_pi) - K.half_pi_over_h) * K.v_scale;
-#else
-    const float u = (((theta + K.pi) - K.pi_over_w) / K.u_den) * K.wm1;
-    const float v = (((phi + K.half_pi) - K.half_pi_over_h) / K.v_den) * K.hm1;
-#endif
-    const TapsR tp4 = make_taps_ranged(u, v, width, height);
+    const SphereUv p = sphere_uv(depths[d], r, q, K);
+    s.qc_max = fmaxf(qc_max, p.qc);
+    const TapsR tp4 = make_taps_ranged(p.u, p.v, width, height);
     // one descriptor per layer (scalar work)
     const __amdgpu_buffer_rsrc_t L = StackTexel<FMT>::layer(layers, b, nd, d, hw, layer_bytes);
     const float4 A = StackTexel<FMT>::tap(L, tp4.oa), Bv = StackTexel<FMT>::tap(L, tp4.ob), C = StackTexel<FMT>::tap(L, tp4.oc), Dv = StackTexel<FMT>::tap(L, tp4.od);
@@ -624,6 +655,44 @@ __device__ __forceinline__ void sphere_combine(const SphereBlock &s, float o0, f
   store(o0, o1, o2, od);
 }
 
+// Many views of one stack per launch (msi_render_views_f32 / _packed: geo_render.hip; msi_render_ods_views: geo_ods.hip): render_kernel's
+// per-layer arithmetic for V target cameras per sample, view_ray's cameras, from a stack in texel format FMT.  A workgroup is one (sample, view,
+// target row, 64-pixel block).  Outputs rgb [B,V,h,w,3] and depth [B,V,h,w].  One body, three kernel names, the ones the profiles know them by.
+template <int MODE, int CAMERA, int FMT>
+__device__ __forceinline__ void render_views_body(const void *layers, const float *pose_rt, const float *tgt_pos, const float *intrinsics,
+                                                  const float *eye_radius, const float *depths, const float *trig, int batch, int views,
+                                                  int height, int width, int nd, int out_h, int out_w, float *out_rgb, float *out_depth,
+                                                  const PixConsts &K, const DepthFrac &F, int *status) {
+  SphereBlock s(out_h, out_w, views, batch);
+  if (s.past_end()) return;
+  s.decode(views, out_w);
+  const unsigned bv = s.bv;
+  ViewRay r = view_ray<CAMERA>(intrinsics, eye_radius, trig, tgt_pos, bv, s.i, s.j, out_h, out_w);
+  apply_pose(pose_rt + (size_t)bv * 16, r);
+  const SphereQuad q = sphere_quad(r);
+  const SphereStack<FMT> S(layers, depths, s.b, nd, height, width);
+  const size_t pix = (size_t)bv * out_h * out_w + (size_t)s.i * out_w + s.j;
+  float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f, tr = 1.f;
+  float qc_max = -1.0f;
+#pragma unroll 4
+  for (int d = S.first(s.seg); d < S.end(s.seg); ++d) {
+    const auto t = S.layer(d, r, q, K, qc_max);
+    qc_max = t.qc_max;
+    const Composite n = over_step<MODE>(o0, o1, o2, od, tr, d, t.c, [&] { return depth_frac(F, d, nd); });
+    o0 = n.o0; o1 = n.o1; o2 = n.o2; od = n.od; tr = n.tr;
+  }
+  if (status != nullptr) {
+    if constexpr (CAMERA == CAMERA_ODS) {         // (the wave votes)
+      const bool any = __builtin_amdgcn_ballot_w64(!(qc_max < 0.0f) || q.cc != q.cc) != 0;   // (wave-uniform)
+      if (any && threadIdx.x == 0) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+    } else {                                      // (lane 0 speaks for the wave)
+      if (threadIdx.x == 0 && (!(qc_max < 0.0f) || q.cc != q.cc)) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+    }
+  }
+  sphere_combine(s, o0, o1, o2, od, tr,
+                 [&](float o0, float o1, float o2, float od) { store_pixel<MODE>(out_rgb, out_depth, pix, o0, o1, o2, od); });
+}
+
 // ---- host helpers -------------------------------------------------------------------------------------------------------------
 // every family with a 1-D grid-stride kernel (prep, layers)
 int grid_1d(size_t n) {
@@ -648,6 +717,50 @@ int view_grid(const char *who, long blocks_per_view, int views, int batch, unsig
   MSI_REQUIRE(nblk < lim, "%s: too many target pixels for one launch", who);
   *grid = (unsigned)((nblk + 7) / 8 * 8);
   return MSI_OK;
+}
+
+// render, ods, sparse, planar, cube: the argument checks of the five *_render_views entry points, in ONE order (msi_hip.h states each entry point's
+// instance of it).  The entry point fills in what it has; its own checks are the two callables, made at their place in the order, each returning
+// MSI_OK or the result of msi::fail.  Returns the grid; the caller returns MSI_OK without a launch when batch == 0.
+constexpr unsigned ANY_FORMAT = 1u << MSI_LAYERS_F32 | 1u << MSI_LAYERS_RGBA8 | 1u << MSI_LAYERS_RGBA16F;
+struct ViewArgs {
+  const char *who;                              // names the entry point in the error text
+  const void *out_rgb, *out_depth;
+  bool inputs;                                  // every input the entry point requires is non-NULL
+  int format;
+  unsigned formats;                             // bit f: format f is allowed
+  const char *format_note;                      // appended to "unknown format %d"
+  const int32_t *camera;                        // nullptr: an entry point without a camera code (ods, mpi)
+  const void *trig, *intrinsics, *eye_radius;   // the tables of the equirect and pinhole cameras; sparse: the ODS camera's, which goes with equirect
+  bool dims;                                    // batch >= 0 and every stack dimension > 0
+  long texels;                                  // H * W of a layer, 0 where no 24-bit texel offset is used (cube)
+  int views, batch, out_h, out_w;
+  int rows;                                     // target rows per workgroup (ViewBlock<ROWS>)
+};
+
+inline int no_check() { return MSI_OK; }
+
+template <class Unsupported, class Limits>
+int check_views(const ViewArgs &a, Unsupported unsupported, Limits limits, unsigned *grid) {
+  const char *who = a.who;
+  MSI_REQUIRE(a.out_rgb || a.out_depth, "%s: both outputs are NULL", who);
+  MSI_REQUIRE(a.inputs, "%s: null pointer", who);
+  MSI_REQUIRE(a.format >= 0 && a.format < 32 && ((a.formats >> a.format) & 1u), "%s: unknown format %d%s", who, a.format, a.format_note);
+  const int camera = a.camera ? *a.camera : MSI_CAMERA_EQUIRECT;
+  MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || camera == MSI_CAMERA_PINHOLE, "%s: unknown camera %d", who, camera);
+  if (a.camera) {
+    MSI_REQUIRE(camera != MSI_CAMERA_EQUIRECT || a.trig, "%s: null pointer (equirect camera needs trig)", who);
+    MSI_REQUIRE(camera != MSI_CAMERA_PINHOLE || a.intrinsics, "%s: null pointer (pinhole camera needs intrinsics)", who);
+    MSI_REQUIRE(camera == MSI_CAMERA_EQUIRECT || !a.eye_radius, "%s: eye_radius (the ODS camera) goes with MSI_CAMERA_EQUIRECT", who);
+  }
+  MSI_REQUIRE(a.dims, "%s: bad dims", who);
+  if (const int e = unsupported()) return e;    // shapes the kernels do not support (MSI_E_UNSUPPORTED)
+  MSI_REQUIRE(a.views >= 1, "%s: views must be >= 1 (got %d)", who, a.views);
+  const int min_out = camera == MSI_CAMERA_PINHOLE ? 2 : 1;
+  MSI_REQUIRE(a.out_h >= min_out && a.out_w >= min_out, "%s: bad output size %d x %d", who, a.out_h, a.out_w);
+  MSI_REQUIRE(a.texels < (1L << 24), "%s: layers of more than 2^24 texels (24-bit texel offsets)", who);
+  if (const int e = limits()) return e;         // the entry point's own addressing limits
+  return view_grid(who, (long)((a.out_w + 63) / 64) * ((a.out_h + a.rows - 1) / a.rows), a.views, a.batch, grid);
 }
 
 DepthFrac depth_fractions(int num_planes) {

@@ -43,8 +43,9 @@ def _on_own_device(cls):
                 return fn(self, *args, **kwargs)
         return inner
 
+    inner = ("inv_depths", "_depths", "_current_poses", "_net_input", "_net_plan")     # no device work, or only ever called from a wrapped method
     for name, fn in list(vars(cls).items()):
-        if callable(fn) and not name.startswith("__") and not isinstance(fn, (staticmethod, classmethod)) and name != "inv_depths":
+        if callable(fn) and not name.startswith("__") and not isinstance(fn, (staticmethod, classmethod)) and name not in inner:
             setattr(cls, name, wrap(fn))
     return cls
 
@@ -115,6 +116,29 @@ class MSI(object):
             self._planes_cache[key] = t
         return t
 
+    def _depths(self, planes, d):
+        """The planes of a stack of d layers on the device."""
+        depths = self._planes(planes)
+        if depths.numel() != d:
+            raise ValueError("len(planes) != number of layers")
+        return depths
+
+    def _current_poses(self, ref_pose, src_pose, ref_pose_inv, b, jitter_pose_inv=None):
+        """curr_pose = pose @ ref_pose_inv of the reference and the source image, [2,B,4,4], in one launch (msi.py:1125); a missing
+        ref_pose_inv is computed on the host (pass it explicitly to avoid the round trip); jitter: msi.py:1120."""
+        if ref_pose_inv is None:
+            ref_pose_inv = torch.linalg.inv(torch.as_tensor(ref_pose, dtype=torch.float32).cpu().double()).float()   # test.py:111
+        ref_pose, src_pose, ref_pose_inv = self._f32(ref_pose), self._f32(src_pose), self._f32(ref_pose_inv)
+        if jitter_pose_inv is not None:
+            ref_pose_inv = self._compose(ref_pose_inv, jitter_pose_inv)
+        if ref_pose_inv.shape[0] != b:
+            ref_pose_inv = ref_pose_inv.reshape(-1, 4, 4).expand(b, 4, 4).contiguous()
+        cur = torch.empty((2, b, 4, 4), dtype=torch.float32, device=self.device)
+        N.check(N.lib.msi_compose_pose_pair_f32(ref_pose.data_ptr(), src_pose.data_ptr(), ref_pose_inv.data_ptr(),
+                                                cur[0].data_ptr(), cur[1].data_ptr(), b, self._stream()),
+                "msi_compose_pose_pair_f32")
+        return cur
+
     def load_weights(self, weights):
         """weights: dict TF-variable-name -> array (see nets.variable_shapes)."""
         try:
@@ -132,7 +156,8 @@ class MSI(object):
         self._blob_cache.clear()
         self._packed_cache.clear()
 
-    def _net(self, batch, height, width, in_channels, num_outputs, ngf):
+    def _net_plan(self, batch, height, width, in_channels, num_outputs, ngf):
+        """(descriptor, packed weights, workspace, plan) of a network shape, each made once and cached."""
         if self._weights is None:
             raise RuntimeError("MSI: no network weights loaded (load_weights / weights=...)")
         key = (batch, height, width, in_channels, num_outputs, ngf, self.coord_net, self.dtype)
@@ -154,7 +179,20 @@ class MSI(object):
             ws = torch.empty(plan.workspace_bytes(), dtype=torch.uint8, device=self.device)
             pw = (plan, ws)
             self._ws_cache[key] = pw
-        return desc, packed, pw[1]
+        return desc, packed, pw[1], pw[0]
+
+    def _net(self, *shape):          # (what tests and tools unpack: descriptor, packed weights, workspace)
+        return self._net_plan(*shape)[:3]
+
+    def _plan(self, *shape):
+        return self._net_plan(*shape)[3]
+
+    def _net_input(self, net_input):
+        """net_input as the plans of this model read it: contiguous, bf16 for a bf16 model."""
+        want = torch.bfloat16 if self.dtype == 'bf16' else torch.float32
+        if net_input.dtype != want or not net_input.is_contiguous():
+            net_input = net_input.to(want).contiguous()
+        return net_input
 
     def network_status(self):
         """msi_net_plan_status of the LAST network forward of this model: raises MsiError (MSI_E_RANGE) when a LayerNorm
@@ -177,11 +215,8 @@ class MSI(object):
         b, h, w, cin = net_input.shape
         if num_outputs is None:
             num_outputs = cin // 3          # blend_psv: 6 D -> 2 D
-        desc, packed, ws = self._net(b, h, w, cin, num_outputs, ngf)
-        want = torch.bfloat16 if self.dtype == 'bf16' else torch.float32
-        if net_input.dtype != want or not net_input.is_contiguous():
-            net_input = net_input.to(want).contiguous()
-        plan = self._plan(b, h, w, cin, num_outputs, ngf)
+        _, packed, ws, plan = self._net_plan(b, h, w, cin, num_outputs, ngf)
+        net_input = self._net_input(net_input)
         changed = N.c_int32(0)
         N.check(N.lib.msi_net_plan_calibrate(plan.handle, packed.data_ptr(), net_input.data_ptr(), ws.data_ptr(), ws.numel(), self._stream(),
                                              N.ctypes.byref(changed)), "msi_net_plan_calibrate")
@@ -199,12 +234,6 @@ class MSI(object):
             raise ValueError("a render's ray origin (pose @ tgt_pos) was not inside the innermost sphere: the reference takes "
                              "sqrt of a negative number there (spherical.py:316-318); the pixels of that call are not defined")
         return bits
-
-    def _plan(self, batch, height, width, in_channels, num_outputs, ngf):
-        self._net(batch, height, width, in_channels, num_outputs, ngf)
-        key = (batch, height, width, in_channels, num_outputs, ngf, self.coord_net, self.dtype) \
-            + tuple(sorted(self.net_options.items()))
-        return self._ws_cache[key][0]
 
     # ------------------------------------------------------------------ msi.py:1196-1217
     def inv_depths(self, start_depth, end_depth, num_depths):
@@ -294,26 +323,14 @@ class MSI(object):
         b, h, w, c = ref_image.shape
         if c != 3 or src_image.shape != ref_image.shape:
             raise ValueError("format_network_input: images must be [B,H,W,3] and agree")
-        # a missing ref_pose_inv is computed on the host (pass it explicitly to avoid the round trip)
-        if ref_pose_inv is None:
-            ref_pose_inv = torch.linalg.inv(torch.as_tensor(ref_pose, dtype=torch.float32).cpu().double()).float()   # test.py:111
-        ref_pose, src_pose, ref_pose_inv = self._f32(ref_pose), self._f32(src_pose), self._f32(ref_pose_inv)
-        if jitter_pose_inv is not None:
-            ref_pose_inv = self._compose(ref_pose_inv, jitter_pose_inv)          # msi.py:1120
+        cur = self._current_poses(ref_pose, src_pose, ref_pose_inv, b, jitter_pose_inv)
         depths = self._planes(planes)
         nd = depths.numel()
         intr = self._f32(intrinsics)
         trig = self._trig(h, w)
         bf16 = (dtype or self.dtype) == 'bf16'
         psv = torch.empty((b, h, w, 6 * nd), dtype=torch.bfloat16 if bf16 else torch.float32, device=self.device)
-        # order = +1 for the reference image (i = 0), -1 for the source (i = 1), msi.py:1127;
-        # curr_pose = pose @ ref_pose_inv for both sources in one launch (msi.py:1125)
-        if ref_pose_inv.shape[0] != b:
-            ref_pose_inv = ref_pose_inv.reshape(-1, 4, 4).expand(b, 4, 4).contiguous()
-        cur = torch.empty((2, b, 4, 4), dtype=torch.float32, device=self.device)
-        N.check(N.lib.msi_compose_pose_pair_f32(ref_pose.data_ptr(), src_pose.data_ptr(), ref_pose_inv.data_ptr(),
-                                                cur[0].data_ptr(), cur[1].data_ptr(), b, self._stream()),
-                "msi_compose_pose_pair_f32")
+        # order = +1 for the reference image (i = 0), -1 for the source (i = 1), msi.py:1127
         if self.input_type == 'ODS':
             N.check(N.lib.msi_ods_sweep_volume(ref_image.data_ptr(), src_image.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(),
                                                intr.data_ptr(), depths.data_ptr(), trig.data_ptr(), b, h, w, nd,
@@ -347,20 +364,22 @@ class MSI(object):
         net_input = self.format_network_input(ref_image, src_image, ref_pose, src_pose, psv_planes,
                                               intrinsics, ref_pose_inv=ref_pose_inv, jitter_pose_inv=jitter_pose_inv)
         pred = self.infer_layers(net_input, num_msi_planes, ngf, extra_outputs, which_color_pred, layer_format=layer_format)
+        return self._carrying(pred, psv_planes), net_input
+
+    @staticmethod
+    def _carrying(pred, planes):
+        """pred with `planes` attached to its PackedLayers, where it has one."""
         if 'packed_layers' in pred:
             pk = pred['packed_layers']
-            pred['packed_layers'] = PackedLayers(pk.data, pk.format, psv_planes)
-        return pred, net_input
+            pred['packed_layers'] = PackedLayers(pk.data, pk.format, planes)
+        return pred
 
     def run_net(self, net_input, num_outputs, ngf=64):
         """msi_net(net_input, num_outputs) (msi.py:95-125): [B,H,W,Cin] -> [B,H,W,num_outputs]."""
         b, h, w, cin = net_input.shape
-        desc, packed, ws = self._net(b, h, w, cin, num_outputs, ngf)
-        want = torch.bfloat16 if self.dtype == 'bf16' else torch.float32
-        if net_input.dtype != want or not net_input.is_contiguous():
-            net_input = net_input.to(want).contiguous()
+        _, packed, ws, plan = self._net_plan(b, h, w, cin, num_outputs, ngf)
+        net_input = self._net_input(net_input)
         pred = torch.empty((b, h, w, num_outputs), dtype=torch.float32, device=self.device)
-        plan = self._plan(b, h, w, cin, num_outputs, ngf)
         N.check(N.lib.msi_net_plan_forward(plan.handle, packed.data_ptr(), net_input.data_ptr(), pred.data_ptr(),
                                            ws.data_ptr(), ws.numel(), self._stream()), "msi_net_plan_forward")
         self._last_forward = (plan, ws)
@@ -411,8 +430,7 @@ class MSI(object):
                 if not want_f32:
                     del pred['rgba_layers']
             return pred
-        desc, packed, ws = self._net(b, h, w, cin, 2 * d, ngf)
-        plan = self._plan(b, h, w, cin, 2 * d, ngf)
+        _, packed, ws, plan = self._net_plan(b, h, w, cin, 2 * d, ngf)
         new = lambda: torch.empty((b, h, w, d), dtype=torch.float32, device=self.device)
         rgba = torch.empty((b, d, h, w, 4), dtype=torch.float32, device=self.device) if want_f32 else None
         bw = new() if 'blend_weights' in extra_outputs else None
@@ -515,9 +533,7 @@ class MSI(object):
         pos = self._f32(tgt_pos).reshape(-1, 3)
         if pose.shape[0] != b or pos.shape[0] != b:
             raise ValueError("tgt_pose_rt / tgt_pos batch must match rgba_layers")
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
+        depths = self._depths(planes, d)
         return native, pose, pos, depths, self._trig(h, w), (b, d, h, w)
 
     def msi_render_equirect_view(self, rgba_layers, tgt_pose_rt, tgt_pos, planes, intrinsics):
@@ -570,9 +586,7 @@ class MSI(object):
         intr = self._f32(intrinsics).reshape(-1, 3, 3)
         if pose.shape[0] != b or intr.shape[0] != b:
             raise ValueError("jitter_pose / intrinsics batch must match rgba_layers")
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
+        depths = self._depths(planes, d)
         out = torch.empty((b, h, w, 3), dtype=torch.float32, device=self.device)
         N.check(N.lib.msi_render_ods_f32(native.data_ptr(), pose.data_ptr(), intr.data_ptr(), depths.data_ptr(),
                                          self._trig(h, w).data_ptr(), b, h, w, d, int(order), out.data_ptr(),
@@ -603,9 +617,7 @@ class MSI(object):
         pos = self._f32(tgt_pos).reshape(-1, 3)
         if pos.shape[0] != b:
             raise ValueError("tgt_pos batch must match rgba_layers")
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
+        depths = self._depths(planes, d)
         out = torch.empty((b, psp_height, psp_width, 3), dtype=torch.float32, device=self.device)
         N.check(N.lib.msi_render_perspective_f32(native.data_ptr(), pose.data_ptr(), pos.data_ptr(), depths.data_ptr(),
                                                  b, h, w, d, psp_height, psp_width, out.data_ptr(),
@@ -715,52 +727,40 @@ class MSI(object):
         if camera != 'ods':
             self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
         pose, pos, v = self._view_poses("tgt_pose_rt", tgt_pose_rt, tgt_pos, b)
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
-        intr, trig = None, None
-        if camera == 'ods':
-            oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
-            radius = self._eye_radius(eye, baseline, intrinsics, b, v)
-            self._ods_domain_guard(tgt_pos, tgt_pose_rt, planes, radius)
-            radius = self._f32(radius).reshape(b * v)
-            rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
-            if sparse is not None:
-                return self._render_sparse(sparse, fmt, pose, pos, None, radius, depths, self._trig(oh, ow), v, N.MSI_CAMERA_EQUIRECT,
-                                           oh, ow, rgb, dep)
-            N.check(N.lib.msi_render_ods_views(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(), radius.data_ptr(),
-                                               depths.data_ptr(), self._trig(oh, ow).data_ptr(), b, v, h, w, d, oh, ow,
-                                               _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream()),
-                    "msi_render_ods_views")
-            return rgb, dep
-        if camera == 'equirect':
-            oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
-            trig = self._trig(oh, ow)
-        else:
+        depths = self._depths(planes, d)
+        intr = trig = radius = None
+        if camera == 'pinhole':
             if size is None or intrinsics is None:
                 raise ValueError("camera='pinhole' needs size=(h, w) and intrinsics")
             oh, ow = int(size[0]), int(size[1])
             intr = self._pinhole_intrinsics(intrinsics, b, v)
+        else:
+            oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
+            if camera == 'ods':
+                radius = self._eye_radius(eye, baseline, intrinsics, b, v)
+                self._ods_domain_guard(tgt_pos, tgt_pose_rt, planes, radius)
+                radius = self._f32(radius).reshape(b * v)
+            trig = self._trig(oh, ow)
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
+        # four entry points, one argument list: they differ in the stack, the camera's tables and whether there is a camera code ('ods' has none;
+        # from a sparse stack it is the equirect code with an eye_radius table)
+        views = (pose.data_ptr(), pos.data_ptr())
+        shape, code = (b, v, h, w, d), (self.CAMERAS[camera],)
+        out = (oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream())
         if sparse is not None:
-            return self._render_sparse(sparse, fmt, pose, pos, intr, None, depths, trig, v, self.CAMERAS[camera], oh, ow, rgb, dep)
-        if packed is not None:
-            N.check(N.lib.msi_render_views_packed(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(),
-                                                  _ptr(intr), depths.data_ptr(), _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow,
-                                                  _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream()),
-                    "msi_render_views_packed")
-            return rgb, dep
-        N.check(N.lib.msi_render_views_f32(native.data_ptr(), pose.data_ptr(), pos.data_ptr(), _ptr(intr), depths.data_ptr(),
-                                           _ptr(trig), b, v, h, w, d, self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep),
-                                           self._render_status.data_ptr(), self._stream()), "msi_render_views_f32")
-        return rgb, dep
-
-    def _render_sparse(self, sparse, fmt, pose, pos, intr, radius, depths, trig, v, camera, oh, ow, rgb, dep):
-        b, h, w, d = sparse.shape
-        N.check(N.lib.msi_render_views_sparse(sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(), fmt,
-                                              pose.data_ptr(), pos.data_ptr(), _ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig),
-                                              b, v, h, w, d, camera, oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(),
-                                              self._stream()), "msi_render_views_sparse")
+            name = "msi_render_views_sparse"
+            args = (sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(), fmt) + views \
+                + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
+        elif camera == 'ods':
+            name = "msi_render_ods_views"
+            args = (native.data_ptr(), fmt) + views + (radius.data_ptr(), depths.data_ptr(), trig.data_ptr()) + shape
+        elif packed is not None:
+            name = "msi_render_views_packed"
+            args = (native.data_ptr(), fmt) + views + (_ptr(intr), depths.data_ptr(), _ptr(trig)) + shape + code
+        else:
+            name = "msi_render_views_f32"
+            args = (native.data_ptr(),) + views + (_ptr(intr), depths.data_ptr(), _ptr(trig)) + shape + code
+        N.check(getattr(N.lib, name)(*(args + out)), name)
         return rgb, dep
 
     EYES = {'left': 1.0, 'right': -1.0}
@@ -945,23 +945,13 @@ class MSI(object):
         if bw.dim() != 4 or bw.shape != al.shape:
             raise ValueError("hres_layers: blend_weights and alphas must be [B,H,W,D] and agree")
         b, h, w, d = bw.shape
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
+        depths = self._depths(planes, d)
         hres_ref = self.preprocess_image(raw_hres_ref_image)
         hres_src = self.preprocess_image(raw_hres_src_image)
         if hres_ref.shape[0] != b or hres_ref.shape[3] != 3 or hres_src.shape != hres_ref.shape:
             raise ValueError("hres_layers: images must be [B,Hh,Wh,3], agree, and have the batch of blend_weights")
         hh, hw = hres_ref.shape[1], hres_ref.shape[2]
-        if ref_pose_inv is None:
-            ref_pose_inv = torch.linalg.inv(torch.as_tensor(ref_pose, dtype=torch.float32).cpu().double()).float()   # test.py:111
-        ref_pose, src_pose, ref_pose_inv = self._f32(ref_pose), self._f32(src_pose), self._f32(ref_pose_inv)
-        if ref_pose_inv.shape[0] != b:
-            ref_pose_inv = ref_pose_inv.reshape(-1, 4, 4).expand(b, 4, 4).contiguous()
-        cur = torch.empty((2, b, 4, 4), dtype=torch.float32, device=self.device)
-        N.check(N.lib.msi_compose_pose_pair_f32(ref_pose.data_ptr(), src_pose.data_ptr(), ref_pose_inv.data_ptr(),
-                                                cur[0].data_ptr(), cur[1].data_ptr(), b, self._stream()),
-                "msi_compose_pose_pair_f32")
+        cur = self._current_poses(ref_pose, src_pose, ref_pose_inv, b)
         intr, trig = self._f32(intrinsics), self._trig(hh, hw)
         rgba = torch.empty((b, d, hh, hw, 4), dtype=torch.float32, device=self.device) if want_f32 else None
         codes = None
@@ -1026,9 +1016,7 @@ class MSI(object):
         intr_inv = self._f32(intrinsics_inv).reshape(-1, 3, 3)
         if pose.shape[0] != b or intr.shape[0] != b or intr_inv.shape[0] != b:
             raise ValueError("tgt_pose / intrinsics batch must match rgba_layers")
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
+        depths = self._depths(planes, d)
         out = torch.empty((b, h, w, 3), dtype=torch.float32, device=self.device)
         N.check(N.lib.msi_mpi_render_f32(native.data_ptr(), pose.data_ptr(), intr.data_ptr(), intr_inv.data_ptr(),
                                          depths.data_ptr(), b, h, w, d, out.data_ptr(), self._stream()),
@@ -1084,9 +1072,7 @@ class MSI(object):
             k_t = self._view_intrinsics(intrinsics if tgt_intrinsics is None else tgt_intrinsics, b, v, "tgt_intrinsics")
             k_inv = torch.linalg.inv(k_t.cpu().double()).float()
         k_inv = self._f32(k_inv.contiguous())
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
+        depths = self._depths(planes, d)
         oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
         N.check(N.lib.msi_mpi_render_views(native.data_ptr(), fmt, pose.data_ptr(), intr.data_ptr(), k_inv.data_ptr(),
@@ -1153,9 +1139,7 @@ class MSI(object):
             cubemap.check_origin_inside(np.asarray(torch.as_tensor(tgt_pos)), np.asarray(torch.as_tensor(tgt_pose_rt)),
                                         np.asarray(torch.as_tensor(planes)))
         pose, pos = self._f32(tgt_pose_rt).reshape(b * v, 4, 4), self._f32(tgt_pos).reshape(b * v, 3)
-        depths = self._planes(planes)
-        if depths.numel() != d:
-            raise ValueError("len(planes) != number of layers")
+        depths = self._depths(planes, d)
         ks = self._f32(cubemap.default_face_intrinsics(s) if stack_intrinsics is None else stack_intrinsics).reshape(-1, 3, 3)
         if ks.shape[0] == 1 and b > 1:
             ks = ks.expand(b, 3, 3)
@@ -1209,10 +1193,7 @@ class MSI(object):
         kf = kf.expand(b, 3, 3)[:, None].expand(b, 6, 3, 3).reshape(6 * b, 3, 3).contiguous()
         net_input = self.format_network_input(ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye)
         pred = self.infer_layers(net_input, d, ngf, extra_outputs, which_color_pred, layer_format=layer_format)
-        if 'packed_layers' in pred:
-            pk = pred['packed_layers']
-            pred['packed_layers'] = PackedLayers(pk.data, pk.format, planes)
-        return pred
+        return self._carrying(pred, planes)
 
     # ------------------------------------------------------------------ image scores (eval.py:127-174 on the device)
     SCORE_TRANSFORMS = {'raw': N.MSI_SCORE_RAW, 'image': N.MSI_SCORE_IMAGE, 'depth': N.MSI_SCORE_DEPTH}

@@ -3,14 +3,11 @@ with the signatures the header declares (ABI still 9: new entry points change no
 reject bad calls with the documented code before any launch, and the shape rules and the host-side domain guard of
 MSI.cube_render_views (matryodshka_amd.cubemap) raise without a device.  No kernel is launched here: every native call below
 fails its validation, or has an empty batch, before it could reach a device (the dummy pointers are never dereferenced)."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import check_binding
+
 MSI_E_BADARG, MSI_E_UNSUPPORTED = -1, -3
 F32, RGBA8, RGBA16F = 0, 1, 2
 EQUIRECT, PINHOLE = 0, 1
@@ -33,22 +30,7 @@ def test_exported_and_bound(native_lib, name):
 
 @pytest.mark.parametrize("name", sorted(NAMES))
 def test_header_and_binding_agree_on_the_signature(native_lib, name):
-    header = open(os.path.join(ROOT, "include", "msi_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, header, flags=re.S)
-    assert m, "%s is not declared in include/msi_hip.h" % name
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    kinds = []
-    for p in params:
-        if "*" in p or p.startswith("msi_stream_t"):
-            kinds.append(ctypes.c_void_p)
-        else:
-            assert p.startswith("int32_t "), p
-            kinds.append(ctypes.c_int32)
-    res, args = native_lib.SIGNATURES[name]
-    assert res is ctypes.c_int32
-    assert args == kinds
-    assert [p.replace("*", " ").split()[-1] for p in params] == NAMES[name]
+    assert check_binding(native_lib, name, int32_and_pointers=True) == NAMES[name]
 
 
 def test_the_unit_is_a_geometry_unit():

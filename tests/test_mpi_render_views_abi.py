@@ -2,13 +2,10 @@
 the header declares (ABI still 9: a new entry point changes no existing signature), and its argument checks reject bad calls
 with the documented code before any launch.  No kernel is launched here: every call below fails its validation, or has an
 empty batch, before it could reach a device (the non-zero dummy pointers are never dereferenced)."""
-import ctypes
-import os
-import re
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import check_binding
+
 MSI_E_BADARG, MSI_E_UNSUPPORTED = -1, -3
 F32, RGBA8, RGBA16F = 0, 1, 2
 
@@ -21,22 +18,7 @@ def test_mpi_render_views_is_exported_and_bound(native_lib):
 
 
 def test_header_and_binding_agree_on_the_signature(native_lib):
-    header = open(os.path.join(ROOT, "include", "msi_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    m = re.search(r"\bint\s+msi_mpi_render_views\s*\((.*?)\)\s*;", header, flags=re.S)
-    assert m, "msi_mpi_render_views is not declared in include/msi_hip.h"
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    kinds = []
-    for p in params:
-        if "*" in p or p.startswith("msi_stream_t"):
-            kinds.append(ctypes.c_void_p)
-        else:
-            assert p.startswith("int32_t "), p
-            kinds.append(ctypes.c_int32)
-    res, args = native_lib.SIGNATURES["msi_mpi_render_views"]
-    assert res is ctypes.c_int32
-    assert args == kinds
-    names = [p.replace("*", " ").split()[-1] for p in params]
+    names = check_binding(native_lib, "msi_mpi_render_views", int32_and_pointers=True)
     assert names == ["layers", "format", "tgt_pose", "intrinsics", "tgt_intrinsics_inv", "depths", "batch", "views", "height",
                      "width", "num_planes", "out_height", "out_width", "out_rgb", "out_depth", "stream"]
 

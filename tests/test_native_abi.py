@@ -10,19 +10,35 @@ import pytest
 
 from oracle import geometry as G
 from oracle import nets as onets
+from tests.util import check_binding, header_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_every_header_symbol_is_exported(native_lib):
-    header = open(os.path.join(ROOT, "include", "msi_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    declared = set(re.findall(r"\b(msi_[a-z0-9_]+)\s*\(", header))
+    declared = set(re.findall(r"\b(msi_[a-z0-9_]+)\s*\(", header_text()))
     assert len(declared) >= 17
     assert declared == set(native_lib.SIGNATURES), declared ^ set(native_lib.SIGNATURES)
     for name in declared:
         assert hasattr(native_lib.lib, name), name
     assert native_lib.lib.msi_version().startswith(b"msi_hip")
+
+
+def _signature_names():
+    """(collection time: the names from the binding's source text, not from an import of it, which needs the built library)"""
+    text = open(os.path.join(ROOT, "matryodshka_amd", "_native.py")).read()
+    return re.findall(r'^    "(msi_[a-z0-9_]+)": \(', text[text.index("SIGNATURES = {"):], flags=re.M)
+
+
+def test_the_signature_test_covers_every_binding(native_lib):
+    assert sorted(_signature_names()) == sorted(native_lib.SIGNATURES) and len(_signature_names()) >= 60
+
+
+@pytest.mark.parametrize("name", _signature_names())
+def test_header_and_binding_agree_on_every_signature(native_lib, name):
+    """The return type and every parameter of _native.SIGNATURES[name] against the header's declaration (tests.util.declared): a
+    scalar as its ctype, a pointer as the typed pointer or as c_void_p."""
+    check_binding(native_lib, name)
 
 
 def test_library_has_no_high_half_to_low_lane_packed_operand(native_lib):
@@ -433,3 +449,45 @@ def test_plan_options_and_raw_layer_bookkeeping(native_lib):
         assert lib.msi_net_plan_set_option(h, opt, bad) == -1
     assert lib.msi_net_plan_layer_is_normalized(h, 17) == -1 and lib.msi_net_plan_layer_is_normalized(None, 0) == -1
     lib.msi_net_plan_destroy(h)
+
+
+# ---- the ONE order of the argument checks of the *_render_views entry points (include/msi_hip.h lists each one's instance): two faults at once,
+# the earlier one is reported.  No launch: every call fails its validation (the dummy pointers are never dereferenced).
+def _view_call(lib, name, out=True, fmt=1, views=2, size=16, planes=4, out_h=16, out_w=32, big=False):
+    """`size`: the layer height (cube: the face size); big: a 4096 x 4096 layer (cube: six 4096 x 4096 fp32 faces, beyond 2^31 bytes)."""
+    p = [4096 * (k + 1) for k in range(12)]
+    o = (p[10], p[11]) if out else (None, None)
+    h, w = (4096, 4096) if big else (size, 32)
+    if name == "msi_render_views_f32":
+        return lib.msi_render_views_f32(p[0], p[1], p[2], p[3], p[4], p[5], 2, views, h, w, planes, 0, out_h, out_w, o[0], o[1], None, None)
+    if name == "msi_render_views_packed":
+        return lib.msi_render_views_packed(p[0], fmt, p[1], p[2], p[3], p[4], p[5], 2, views, h, w, planes, 0, out_h, out_w, o[0], o[1], None, None)
+    if name == "msi_render_ods_views":
+        return lib.msi_render_ods_views(p[0], fmt, p[1], p[2], p[3], p[4], p[5], 2, views, h, w, planes, out_h, out_w, o[0], o[1], None, None)
+    if name == "msi_render_views_sparse":
+        return lib.msi_render_views_sparse(p[0], p[1], p[2], fmt, p[3], p[4], p[5], None, p[6], p[7], 2, views, h, w, planes, 0, out_h, out_w,
+                                           o[0], o[1], None, None)
+    if name == "msi_cube_render_views":
+        return lib.msi_cube_render_views(p[0], 0 if big else fmt, p[1], p[2], p[3], p[4], p[5], p[6], 2, views, h, planes, 0, out_h, out_w,
+                                         o[0], o[1], None, None)
+    return lib.msi_mpi_render_views(p[0], fmt, p[1], p[2], p[3], p[4], 2, views, h, w, planes, out_h, out_w, o[0], o[1], None)
+
+
+@pytest.mark.parametrize("name", ["msi_render_views_f32", "msi_render_views_packed", "msi_render_ods_views", "msi_render_views_sparse",
+                                  "msi_cube_render_views", "msi_mpi_render_views"])
+def test_view_entry_points_check_their_arguments_in_one_order(native_lib, name):
+    def reports(text, code=-1, **kw):
+        assert _view_call(native_lib.lib, name, **kw) == code, (name, kw)
+        msg = native_lib.last_error()
+        assert name[len("msi_"):].replace("_f32", "") + ":" in msg and text in msg, (name, kw, msg)
+
+    has_format = name != "msi_render_views_f32"                      # (it takes fp32 stacks only: no format to be unknown)
+    reports("both outputs are NULL", out=False, fmt=7, size=0 if not has_format else 16)
+    if has_format:
+        reports("unknown format 7", fmt=7, size=0)
+    reports("bad dims", size=0, views=0)
+    reports("views must be >= 1", views=0, out_h=0)
+    reports("bad output size", out_h=0, big=True)
+    reports("2^31 bytes" if name == "msi_cube_render_views" else "2^24", big=True)   # (control: the layer alone IS refused)
+    if name in ("msi_cube_render_views", "msi_mpi_render_views"):
+        reports("at most 128 planes", code=-3, planes=129, views=0)

@@ -3,13 +3,13 @@ still 9: a new entry point changes no existing signature), defined in exactly on
 checks reject bad calls with the documented text before any launch.  The ODS camera is an entry point of its own: camera code 2
 is still unknown to the three *_render_views functions.  No kernel is launched here: every native call below fails its
 validation, or has an empty batch, before it could reach a device (the dummy pointers are never dereferenced)."""
-import ctypes
 import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import check_binding, header_text
+
 MSI_E_BADARG = -1
 F32, RGBA8, RGBA16F = 0, 1, 2
 NAME = "msi_render_ods_views"
@@ -25,23 +25,8 @@ def test_exported_and_bound(native_lib):
 
 
 def test_header_and_binding_agree_on_the_signature(native_lib):
-    header = open(os.path.join(ROOT, "include", "msi_hip.h")).read()
-    assert "#define MSI_ABI_VERSION 9" in header
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % NAME, header, flags=re.S)
-    assert m, "%s is not declared in include/msi_hip.h" % NAME
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    kinds = []
-    for p in params:
-        if "*" in p or p.startswith("msi_stream_t"):
-            kinds.append(ctypes.c_void_p)
-        else:
-            assert p.startswith("int32_t "), p
-            kinds.append(ctypes.c_int32)
-    res, args = native_lib.SIGNATURES[NAME]
-    assert res is ctypes.c_int32
-    assert args == kinds
-    assert [p.replace("*", " ").split()[-1] for p in params] == PARAMS
+    assert "#define MSI_ABI_VERSION 9" in header_text()
+    assert check_binding(native_lib, NAME, int32_and_pointers=True) == PARAMS
 
 
 def test_defined_once_in_a_geometry_unit():

@@ -19,9 +19,9 @@ def test_symbols_are_exported_and_bound(native_lib):
 
 
 def test_header_defines_the_format_constants():
-    import os
     import re
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "msi_hip.h")).read()
+    from tests.util import header_text
+    header = header_text()
     for name, value in (("MSI_LAYERS_F32", 0), ("MSI_LAYERS_RGBA8", 1), ("MSI_LAYERS_RGBA16F", 2), ("MSI_ABI_VERSION", 9)):
         assert re.search(r"#define\s+%s\s+%d\b" % (name, value), header), name
 

@@ -3,47 +3,29 @@ signatures the header declares (ABI still 9), every argument error comes back as
 workspace query is non-zero and monotone.  No kernel is launched: every msi_score_images call below fails its validation, which
 is decided before any HIP call (the non-zero dummy pointers are never dereferenced)."""
 import ctypes
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import check_binding, declared, header_text, untyped
+
 MSI_E_BADARG, MSI_E_WORKSPACE = -1, -4
 F32, U8 = 0, 1
 RAW, IMAGE, DEPTH = 0, 1, 2
 MSE, MAE, SSIM = 1, 2, 4
 
 
-def _declared(name):
-    header = open(os.path.join(ROOT, "include", "msi_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    m = re.search(r"\b(int|size_t)\s+%s\s*\((.*?)\)\s*;" % name, header, flags=re.S)
-    assert m, "%s is not declared in include/msi_hip.h" % name
-    return m.group(1), [" ".join(p.split()) for p in m.group(2).split(",")]
-
-
-def _ctype(param):
-    if "*" in param or param.startswith("msi_stream_t"):
-        return ctypes.c_void_p
-    for prefix, kind in (("int32_t ", ctypes.c_int32), ("uint32_t ", ctypes.c_uint32), ("size_t ", ctypes.c_size_t), ("double ", ctypes.c_double)):
-        if param.startswith(prefix):
-            return kind
-    raise AssertionError(param)
-
-
 def test_both_symbols_are_exported_and_bound_with_the_declared_signature(native_lib):
     assert native_lib.MSI_ABI_VERSION == 9 and native_lib.lib.msi_abi_version() == 9
     for name, restype in (("msi_score_workspace_bytes", ctypes.c_size_t), ("msi_score_images", ctypes.c_int32)):
         assert name in native_lib.SIGNATURES and hasattr(native_lib.lib, name)
-        ret, params = _declared(name)
+        names = check_binding(native_lib, name)
         res, args = native_lib.SIGNATURES[name]
-        assert res is restype and ret == {ctypes.c_size_t: "size_t", ctypes.c_int32: "int"}[restype]
-        assert args == [_ctype(p) for p in params], name
-    names = [p.replace("*", " ").split()[-1] for p in _declared("msi_score_images")[1]]
+        assert res is restype
+        assert args == [untyped(kind) for kind, _ in declared(name)[1]], name
     assert names == ["pred", "target", "dtype", "transform", "quantize", "n_pairs", "group", "height", "width", "channels", "row_weights",
                      "max_val", "metrics", "out", "workspace", "workspace_bytes", "stream"]
-    header = open(os.path.join(ROOT, "include", "msi_hip.h")).read()
+    header = header_text()
     for macro, value in (("MSI_SCORE_F32", "0"), ("MSI_SCORE_U8", "1"), ("MSI_SCORE_RAW", "0"), ("MSI_SCORE_IMAGE", "1"), ("MSI_SCORE_DEPTH", "2"),
                          ("MSI_SCORE_MSE", "1u"), ("MSI_SCORE_MAE", "2u"), ("MSI_SCORE_SSIM", "4u")):
         assert re.search(r"#define\s+%s\s+%s\b" % (macro, value), header), macro

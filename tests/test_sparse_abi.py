@@ -6,11 +6,12 @@ Python level: an MSI object cannot be constructed without a device (MSI.__init__
 every method runs under the model's device), so the TypeError / ValueError paths of MSI.sparsify_layers, densify_layers and
 render_views on a SparseLayers are in tests/test_gpu_sparse_layers.py (test_6); what needs no device is here: the package export,
 the harness's --msi_sparse argument refusals and its --help, and (tests/test_sparse_cpu.py) SparseLayers' own refusals."""
-import ctypes
 import os
 import re
 
 import pytest
+
+from tests.util import check_binding, header_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MSI_E_BADARG, MSI_E_UNSUPPORTED = -1, -3
@@ -36,23 +37,8 @@ def test_exported_and_bound(native_lib):
 
 @pytest.mark.parametrize("name", sorted(PARAMS))
 def test_header_and_binding_agree_on_the_signature(native_lib, name):
-    header = open(os.path.join(ROOT, "include", "msi_hip.h")).read()
-    assert "#define MSI_ABI_VERSION 9" in header
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, header, flags=re.S)
-    assert m, "%s is not declared in include/msi_hip.h" % name
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    kinds = []
-    for p in params:
-        if "*" in p or p.startswith("msi_stream_t"):
-            kinds.append(ctypes.c_void_p)
-        else:
-            assert p.startswith("int32_t "), p
-            kinds.append(ctypes.c_int32)
-    res, args = native_lib.SIGNATURES[name]
-    assert res is ctypes.c_int32
-    assert args == kinds
-    assert [p.replace("*", " ").split()[-1] for p in params] == PARAMS[name]
+    assert "#define MSI_ABI_VERSION 9" in header_text()
+    assert check_binding(native_lib, name, int32_and_pointers=True) == PARAMS[name]
 
 
 def test_defined_once_in_a_geometry_unit():

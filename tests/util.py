@@ -6,6 +6,71 @@ import numpy as np
 from matryodshka_amd.synthetic import smooth_noise, make_inputs, random_rgba, pp_inputs  # noqa: F401,E402
 
 
+# ---- include/msi_hip.h as the ABI tests read it
+def header_text(comments=False):
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "msi_hip.h")).read()
+    return text if comments else re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def declared(name):
+    """(restype, [(ctype, parameter name)]) of function `name` as include/msi_hip.h declares it.  Scalars are the ctypes of
+    matryodshka_amd/_native.py and msi_stream_t is c_void_p; a pointer is POINTER(what it points to) -- the binding's Structure
+    for msi_net_desc / msi_layer_info -- and c_void_p for `void *` and the opaque msi_net_plan; a `const char *` return is
+    c_char_p, a `void` return None.  A binding may spell any pointer c_void_p: untyped() of the ctype."""
+    import ctypes as C
+    import re
+    from matryodshka_amd import _native as N
+    m = re.search(r"(?:^|[;}\n])\s*((?:const\s+)?\w+[\s*]+)%s\s*\((.*?)\)\s*;" % name, header_text(), flags=re.S)
+    assert m, "%s is not declared in include/msi_hip.h" % name
+    scalars = {"int": C.c_int32, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "uint8_t": C.c_uint8,
+               "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double, "char": C.c_char, "msi_stream_t": C.c_void_p,
+               "msi_net_desc": N.NetDesc, "msi_layer_info": N.LayerInfo}
+
+    def ctype(words, ret=False):
+        words = [w for w in words if w != "const"]
+        base, stars = words[0], words.count("*")
+        assert len(words) == 1 + stars, words
+        if ret and (base, stars) == ("char", 1):
+            return C.c_char_p
+        if base in ("void", "msi_net_plan"):            # (`void` itself: a return type only; nothing takes a msi_net_plan by value)
+            assert stars or (ret and base == "void"), words
+            kind, stars = (C.c_void_p if stars else None), stars - 1
+        else:
+            assert base in scalars, words
+            kind = scalars[base]
+        for _ in range(max(stars, 0)):
+            kind = C.POINTER(kind)
+        return kind
+
+    params = [p.replace("*", " * ").split() for p in m.group(2).split(",")]
+    params = [] if params in ([["void"]], [[]]) else params
+    return ctype(m.group(1).replace("*", " * ").split(), ret=True), [(ctype(p[:-1]), p[-1]) for p in params]
+
+
+def check_binding(native_lib, name, int32_and_pointers=False):
+    """Asserts that _native.SIGNATURES[name] is the header's declaration of `name` -- the return type, and every parameter as its
+    ctype or, a pointer, as c_void_p; with int32_and_pointers, that it returns int32 and takes nothing but int32_t and pointers
+    bound as c_void_p -- and returns the declared parameter names."""
+    import ctypes
+    ret, params = declared(name)
+    res, args = native_lib.SIGNATURES[name]
+    assert res is ret, (name, res, ret)
+    assert len(args) == len(params), (name, len(args), len(params))
+    for k, (arg, (kind, pname)) in enumerate(zip(args, params)):
+        assert arg in (kind, untyped(kind)), (name, k, pname, arg, kind)
+    if int32_and_pointers:
+        assert res is ctypes.c_int32 and set(args) <= {ctypes.c_void_p, ctypes.c_int32}, name
+    return [pname for _, pname in params]
+
+
+def untyped(kind):
+    """c_void_p for a ctypes pointer type, `kind` itself otherwise: how most of _native.SIGNATURES spells a pointer."""
+    import ctypes
+    return ctypes.c_void_p if isinstance(kind, type) and issubclass(kind, ctypes._Pointer) else kind
+
+
 # ---- stratified dense sample set of the full-size fixtures (tests/golden/make_golden.py writes the values, the -m gpu
 # tests regenerate the SAME indices from (shape, extra pixels, seed): only values and the oracle-derived pixels are stored)
 def stratified_rows(h):
