@@ -473,6 +473,7 @@ ods_sweep_lds_kernel(const float *__restrict__ image0, const float *__restrict__
 
 extern "C" {
 
+// (which form a shape takes, restated on the host: sweep_form in tests/sweep_cases.py -- its case table reaches every form; keep the two in step)
 static int sweep_common(const float *image, const float *image1, const float *pose, const float *pose1,
                         const float *intrinsics,
                         const float *depths, const float *trig, int32_t batch,

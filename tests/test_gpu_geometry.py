@@ -394,7 +394,7 @@ def _rot(ax, ay, az):
 
 
 @pytest.mark.parametrize("bf16", [False, True])
-@pytest.mark.parametrize("h,w,d,b", [(24, 64, 16, 5), (40, 64, 32, 3), (16, 32, 64, 2), (24, 128, 8, 19)])
+@pytest.mark.parametrize("h,w,d,b", [(24, 64, 16, 5), (40, 64, 32, 3), (16, 32, 64, 2), (24, 128, 8, 19), (24, 64, 16, 19)])      # (how many blocks of each stage: tests/test_sweep_cases_cpu.py)
 def test_lds_staged_sweep_is_bit_identical_to_the_gather_kernel(gpu, h, w, d, b, bf16):
     """Round 6: ods_sweep_lds_kernel stages the source patch a block's samples fall into in LDS and gathers from there; blocks whose box
     does not fit keep gathering from memory.  Taken for the double volume at batch >= 2 when blocks are full ((W * D / 2) % 256 == 0).  It must reproduce, bit for
