@@ -65,7 +65,8 @@ const char *msi_version(void);
  *   8: msi_probe_matrix_rate (round 6)
  *   9: msi_perspective_sweep_volume_bf16
  *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images; msi_cube_render_views,
- *      msi_equirect_to_cube_f32; msi_sparse_index_tiles, msi_sparse_gather_tiles, msi_sparse_expand, msi_render_views_sparse) */
+ *      msi_equirect_to_cube_f32; msi_sparse_index_tiles, msi_sparse_gather_tiles, msi_sparse_expand, msi_render_views_sparse;
+ *      msi_hres_index_tiles, msi_hres_layers_sparse) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -367,6 +368,35 @@ int msi_render_views_sparse(const void *pool, const int32_t *table, const int64_
                             const float *depths, const float *trig, int32_t batch, int32_t views, int32_t height, int32_t width,
                             int32_t num_planes, int32_t camera, int32_t out_height, int32_t out_width, float *out_rgb,
                             float *out_depth, int32_t *status_device, msi_stream_t stream);
+/* The high-res stack of msi_hres_layers built sparse (MSI.hres_layers_sparse): the dense stack is never written.
+ * RULE: msi_hres_layers stores a texel's alpha as the align-corners bilinear resize of the low-res alphas, encoded; it does not
+ * depend on the images.  So the keep rule above is applied to the alphas the dense stack WOULD hold -- the same resize
+ * expression and the same encoder, in the geometry units compiled without contraction -- and the table is known before any texel
+ * is computed: a NaN, a negative, a > 1, a too-small (rgba8: rounds to code 0; rgba16f: underflows to +-0) or a -0.0 alpha
+ * lands on the side the stored code would put it.
+ *   msi_hres_index_tiles    alphas [B,h,w,D] -> table_out [B,D,Hh/4,Wh/16] (final: index or -1) and counts_out [B*D], equal to
+ *                           msi_sparse_index_tiles of msi_hres_layers' codes of `format` (two launches, the second is
+ *                           msi_sparse_index_tiles' scan).  The prefix sum and the allocation of the pool are the caller's.
+ *   msi_hres_layers_sparse  msi_hres_layers' inputs, the table and layer_start -> pool_out: every texel of every kept tile,
+ *                           the empty ones too, with the bits of the dense stack (the one texel definition both kernels
+ *                           call); for a dropped tile no sample position is computed, no image memory is read and nothing is
+ *                           stored.  The result equals msi_sparse_gather_tiles of msi_hres_layers' stack.  One launch.  The
+ *                           pool's bytes decide between plain and non-temporal stores, as msi_hres_layers decides for its
+ *                           stack: where the DENSE stack would exceed 256 MiB (a smaller one bounds the pool), one 8-byte read
+ *                           of layer_start[B*D] and a wait for `stream` come first.  Pool offsets are 64-bit.
+ * Argument checks before any HIP call, in this order: msi_hres_layers' (a NULL pointer -> MSI_E_BADARG, bad dims,
+ * num_planes % 4 -> MSI_E_UNSUPPORTED, Hh * Wh >= 2^24 / Hh or B > 65535, h * w * D >= 2^31), then the tile entry points'
+ * (unknown format, MSI_LAYERS_F32 included -> MSI_E_BADARG; Hh % 4 or Wh % 16 -> MSI_E_UNSUPPORTED).  Error texts name
+ * hres_index_tiles / hres_layers_sparse.  batch = 0 returns MSI_OK after validation.  table, layer_start and the pool must
+ * belong together; msi_hres_layers_sparse refuses a layer_start that ends beyond the table's tiles. */
+int msi_hres_index_tiles(const float *alphas, int32_t format, int32_t batch, int32_t low_height, int32_t low_width,
+                         int32_t height, int32_t width, int32_t num_planes,
+                         int32_t *table_out, int32_t *counts_out, msi_stream_t stream);
+int msi_hres_layers_sparse(const float *ref_image, const float *src_image, const float *ref_curr_pose, const float *src_curr_pose,
+                           const float *intrinsics, const float *depths, const float *trig, const float *blend_weights,
+                           const float *alphas, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
+                           int32_t num_planes, const int32_t *table, const int64_t *layer_start, void *pool_out, int32_t format,
+                           msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -89,6 +89,8 @@ SIGNATURES = {
     "msi_sparse_gather_tiles": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "msi_sparse_expand": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "msi_render_views_sparse": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "msi_hres_index_tiles": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "msi_hres_layers_sparse": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "msi_project_layers_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "msi_render_ods_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_render_perspective_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),

@@ -3,16 +3,7 @@
 // their C ABI entry points below.
 #include "geometry_device.h"
 
-// tuning macros of hres_layers_kernel
-// Layers per group (one G-float vector per low-res corner; the group is unrolled) and the waves per SIMD the register allocation aims at.  What hides the gathers'
-// latency is the independent samples a lane has in flight, not the wave count (same-box A/B, DESIGN.md section 4, profiles/hres_layers_variants.txt): G = 4 at four waves
-// (101-103 VGPRs) 2.3 ms at 4096x2048x32, G = 2 at five waves the same there and 1.9 x slower at 1280x640, G = 1 at six waves 1.7 x / 2.8 x slower; G = 4 at five waves spills.
-#ifndef MSI_HRES_GROUP   // (tuning: -DMSI_HRES_GROUP=1 / 2 / 4)
-#define MSI_HRES_GROUP 4
-#endif
-#ifndef MSI_HRES_WAVES   // (tuning: -DMSI_HRES_WAVES=4 / 5)
-#define MSI_HRES_WAVES 4
-#endif
+// (the tuning macros of hres_layers_kernel, MSI_HRES_GROUP and MSI_HRES_WAVES: geometry_device.h, with the texel that geo_sparse.hip shares)
 
 namespace {
 
@@ -216,18 +207,7 @@ unpack_layers_kernel(const void *__restrict__ in, float4 *__restrict__ out, size
   }
 }
 
-// tf.image.resize(..., BILINEAR, align_corners=True) [TF-knowledge: resize_bilinear_op]:
-// src = dst * (in-1)/(out-1); lower = floor(src), upper = min(ceil(src), in-1), lerp = src - lower;
-// top = tl + (tr - tl)*xl; bottom = bl + (br - bl)*xl; out = top + (bottom - top)*yl.
-// Used by the high-res re-render to upsample blend weights / alphas (test.py:319-325).
-// The ONE definition of that expression, for a float (resize_bilinear_kernel, per component) or a vector of layers (hres_layers_kernel, elementwise).
-template <typename T>
-__device__ __forceinline__ T lerp2(T tl, T tr, T bl, T br, float xl, float yl) {
-  const T top = tl + (tr - tl) * xl;
-  const T bot = bl + (br - bl) * xl;
-  return top + (bot - top) * yl;
-}
-
+// tf.image.resize(..., BILINEAR, align_corners=True): the expression is lerp2 of geometry_device.h, per component.
 __global__ void resize_bilinear_kernel(const float4 *__restrict__ in, float4 *__restrict__ out, size_t n,
                                        int in_h, int in_w, int c4, int out_h, int out_w, float sy, float sx) {
   size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -268,29 +248,12 @@ __global__ void resize_bilinear_kernel(const float4 *__restrict__ in, float4 *__
 // FMT: MSI_LAYERS_F32 (no packed output), MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F; WITH_F32: the fp32 stack is written (too);
 // NT: bit 0 / bit 1 = non-temporal stores of the fp32 / the packed stack (the host sets a bit when that destination is larger
 // than the 256-MiB Infinity Cache; a template argument, as in pack_layers_kernel).
-constexpr int HRES_G = MSI_HRES_GROUP;
-typedef float hres_vec __attribute__((ext_vector_type(HRES_G)));
-__device__ __forceinline__ hres_vec hres_lerp(const float *__restrict__ p, unsigned tl, unsigned tr, unsigned bl, unsigned br, float xl, float yl) {
-  const hres_vec a = *reinterpret_cast<const hres_vec *>(p + tl), b = *reinterpret_cast<const hres_vec *>(p + tr);
-  const hres_vec c = *reinterpret_cast<const hres_vec *>(p + bl), d = *reinterpret_cast<const hres_vec *>(p + br);
-  return lerp2(a, b, c, d, xl, yl);             // (elementwise: the resize's expression)
-}
-
-template <int FMT, int NT>
-__device__ __forceinline__ void hres_store_packed(void *__restrict__ base, size_t texel, const float4 &t) {
-  if constexpr (FMT == MSI_LAYERS_RGBA8) {
-    unsigned *p = static_cast<unsigned *>(base) + texel;
-    const unsigned q = rgba8_encode(t);
-    if (NT) __builtin_nontemporal_store(q, p); else *p = q;
-  } else {
-    u32x2_g *p = static_cast<u32x2_g *>(base) + texel;
-    const u32x2_g q = rgba16f_encode(t);
-    if (NT) __builtin_nontemporal_store(q, p); else *p = q;
-  }
-}
-
+// The texel itself -- hres_pixel, hres_corners / hres_lerp, hres_texel, hres_store_packed -- is in geometry_device.h: hres_layers_sparse_kernel
+// (geo_sparse.hip) writes the same texels into a pool of kept tiles.
 template <int FMT, int WITH_F32, int NT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSI_HRES_WAVES, 8)))
+// (waves_per_eu with the maximum at MSI_HRES_WAVES too: with the texel in shared device functions the allocator settles at 93-95 VGPRs, which
+// would run five waves, and at five the launch is 5 % slower at 1280x640 -- same-process A/B in profiles/hres_sparse_isa.txt)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSI_HRES_WAVES, MSI_HRES_WAVES)))
 hres_layers_kernel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
                    const float *__restrict__ pose1, const float *__restrict__ intrinsics, const float *__restrict__ depths,
                    const float *__restrict__ trig, const float *__restrict__ blend_weights, const float *__restrict__ alphas,
@@ -301,56 +264,19 @@ hres_layers_kernel(const float *__restrict__ image0, const float *__restrict__ i
   if (j >= width) return;
   const int i = blockIdx.y, b = blockIdx.z;
 
-  // the sweep's per-pixel constants (ods_sweep_kernel)
-  const float cs = trig[j], ss = trig[width + j];
-  const float ct = trig[2 * width + i], st = trig[2 * width + height + i];
-  const float csct = cs * ct, ssct = ss * ct;
-  const int img_bytes = height * width * 12;
-  const float *P0 = pose0 + (size_t)b * 16, *P1 = pose1 + (size_t)b * 16;
-  const __amdgpu_buffer_rsrc_t img0 = __builtin_amdgcn_make_buffer_rsrc((void *)(image0 + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t img1 = __builtin_amdgcn_make_buffer_rsrc((void *)(image1 + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
-  const float r = intrinsics[(size_t)b * 9];
-  bool same = true;                             // both sources share the quadratic when their poses are equal
-#pragma unroll
-  for (int k = 0; k < 12; ++k) same = same && (P0[k] == P1[k]);
-
-  // the resize's corners and fractions (resize_bilinear_kernel; sy, sx from the host as in msi_resize_bilinear_f32)
-  const float fy = (float)i * sy, fx = (float)j * sx;
-  const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-  const int y1 = min((int)ceilf(fy), low_h - 1), x1 = min((int)ceilf(fx), low_w - 1);
-  const float yl = fy - (float)y0, xl = fx - (float)x0;
+  const HresPixel px = hres_pixel(image0, image1, pose0, pose1, intrinsics, trig, b, i, j, height, width);
+  const HresCorners k = hres_corners(i, j, sy, sx, low_h, low_w, nd);
   const size_t low_base = (size_t)b * low_h * low_w * nd;          // (h * w * D < 2^31: checked on the host)
   const float *bw = blend_weights + low_base, *al = alphas + low_base;
-  const unsigned o_tl = (unsigned)(y0 * low_w + x0) * (unsigned)nd, o_tr = (unsigned)(y0 * low_w + x1) * (unsigned)nd;
-  const unsigned o_bl = (unsigned)(y1 * low_w + x0) * (unsigned)nd, o_br = (unsigned)(y1 * low_w + x1) * (unsigned)nd;
 
   const size_t hw = (size_t)height * width;
   size_t texel = (size_t)b * nd * hw + (size_t)i * width + j;      // layer 0 of this pixel in the [B,D,H,W] stack
   for (int d0 = 0; d0 < nd; d0 += HRES_G) {                        // (nd % 4 == 0: checked on the host)
-    const hres_vec wv = hres_lerp(bw + d0, o_tl, o_tr, o_bl, o_br, xl, yl);
-    const hres_vec av = hres_lerp(al + d0, o_tl, o_tr, o_bl, o_br, xl, yl);
+    const hres_vec wv = hres_lerp(bw + d0, k);
+    const hres_vec av = hres_lerp(al + d0, k);
 #pragma unroll
     for (int q = 0; q < HRES_G; ++q) {
-      const float depth = depths[d0 + q];
-      float u, v, fg[3], bg[3];
-      const OdsQuad q0 = ods_quad(P0, r, depth, csct, st, ssct);
-      ods_tail(q0, 1.0f, K, u, v);
-      gather3(img0, make_taps_bytes(u, v, width, height), fg);
-      if (same) {
-        ods_tail(q0, -1.0f, K, u, v);
-      } else {
-        const OdsQuad q1 = ods_quad(P1, r, depth, csct, st, ssct);
-        ods_tail(q1, -1.0f, K, u, v);
-      }
-      gather3(img1, make_taps_bytes(u, v, width, height), bg);
-      // assemble_kernel, COLOR_BLEND_PSV with pred_scaled
-      const float w = wv[q];
-      const float omw = 1.0f - w;
-      float4 o;
-      o.x = w * fg[0] + omw * bg[0];
-      o.y = w * fg[1] + omw * bg[1];
-      o.z = w * fg[2] + omw * bg[2];
-      o.w = av[q];
+      const float4 o = hres_texel(px, depths[d0 + q], K, width, height, wv[q], av[q]);
       if (WITH_F32) sweep_store16(reinterpret_cast<uint4 *>(rgba + texel), __builtin_bit_cast(uint4, o), NT & 1);
       if constexpr (FMT != MSI_LAYERS_F32) hres_store_packed<FMT, (NT >> 1) & 1>(packed, texel, o);
       texel += hw;
@@ -445,18 +371,10 @@ int msi_hres_layers(const float *ref_image, const float *src_image, const float 
                     int32_t num_planes, float *rgba_native, void *layers_out, int32_t format, msi_stream_t stream) {
   MSI_REQUIRE(!layers_out || format == MSI_LAYERS_RGBA8 || format == MSI_LAYERS_RGBA16F, "hres_layers: unknown format %d", format);
   MSI_REQUIRE(rgba_native || layers_out, "hres_layers: null pointer (both outputs are NULL)");
-  MSI_REQUIRE(ref_image && src_image && ref_curr_pose && src_curr_pose && intrinsics && depths && trig && blend_weights && alphas,
-              "hres_layers: null pointer");
-  MSI_REQUIRE(batch >= 0 && low_height > 0 && low_width > 0 && height > 0 && width > 0 && num_planes > 0, "hres_layers: bad dims");
-  if (num_planes % 4 != 0)
-    return msi::fail(MSI_E_UNSUPPORTED, "hres_layers: num_planes=%d must be a multiple of 4", num_planes);
-  MSI_REQUIRE(height <= 65535 && batch <= 65535 && (long)height * width < (1L << 24),
-              "hres_layers: problem too large (24-bit pixel offsets: H * W < 2^24, H <= 65535)");
-  MSI_REQUIRE((long)low_height * low_width * num_planes < (1L << 31), "hres_layers: low-res tensors too large (h * w * D < 2^31)");
+  if (const int e = hres_check("hres_layers", ref_image && src_image && ref_curr_pose && src_curr_pose && intrinsics && depths && trig &&
+                               blend_weights && alphas, batch, low_height, low_width, height, width, num_planes)) return e;
   if (batch == 0) return MSI_OK;
-  // the scales of msi_resize_bilinear_f32
-  const float sy = height > 1 ? (float)(low_height - 1) / (float)(height - 1) : 0.0f;
-  const float sx = width > 1 ? (float)(low_width - 1) / (float)(width - 1) : 0.0f;
+  const float sy = hres_scale(low_height, height), sx = hres_scale(low_width, width);
   const int fmt = layers_out ? format : MSI_LAYERS_F32;
   // non-temporal stores for a destination that cannot stay in the Infinity Cache (as msi_pack_layers)
   const size_t texels = (size_t)batch * num_planes * height * width;

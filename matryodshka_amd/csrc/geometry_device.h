@@ -4,7 +4,8 @@
 //   geo_layers.hip  K3 RGBA assembly, bilinear resize, the fused high-res layer stack, pack / unpack of the compact stacks
 //   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed form
 //   geo_ods.hip     K4 with the ODS stereo camera: render_ods_views_kernel (both eyes of a stack per launch, fp32 or packed stacks)
-//   geo_sparse.hip  K4 from a sparse stack: the tile index / gather / expand kernels and render_views_sparse_kernel (the cameras of render and ods)
+//   geo_sparse.hip  K4 from a sparse stack: the tile index / gather / expand kernels and render_views_sparse_kernel (the cameras of render and ods);
+//                   the high-res stack built sparse (hres_keep_kernel, hres_layers_sparse_kernel)
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
@@ -305,14 +306,164 @@ __device__ __forceinline__ TapsB make_taps_bytes(float u, float v, int width, in
 __device__ __forceinline__ float blend4(const TapsB &t, float a, float b, float c, float d) {
   return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;   // tf.add_n order (sampling.py:187-190)
 }
-__device__ __forceinline__ void gather3(__amdgpu_buffer_rsrc_t img, const TapsB &t, float *out) {
-  const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oa, 0, 0));
-  const f32x3_g b = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.ob, 0, 0));
-  const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oc, 0, 0));
-  const f32x3_g d = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.od, 0, 0));
-  out[0] = blend4(t, a.x, b.x, c.x, d.x);
-  out[1] = blend4(t, a.y, b.y, c.y, d.y);
-  out[2] = blend4(t, a.z, b.z, c.z, d.z);
+// (the four loads and the three blends apart: hres_layers_sparse_kernel keeps the loads of one layer in flight while it blends another)
+struct Rgb4 { f32x3_g a, b, c, d; };
+__device__ __forceinline__ Rgb4 gather3_load(__amdgpu_buffer_rsrc_t img, const TapsB &t) {
+  Rgb4 g;
+  g.a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oa, 0, 0));
+  g.b = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.ob, 0, 0));
+  g.c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.oc, 0, 0));
+  g.d = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, t.od, 0, 0));
+  return g;
+}
+__device__ __forceinline__ void gather3_blend(const TapsB &t, const Rgb4 &g, float *out) {
+  out[0] = blend4(t, g.a.x, g.b.x, g.c.x, g.d.x);
+  out[1] = blend4(t, g.a.y, g.b.y, g.c.y, g.d.y);
+  out[2] = blend4(t, g.a.z, g.b.z, g.c.z, g.d.z);
+}
+__device__ __forceinline__ void gather3(__amdgpu_buffer_rsrc_t img, const TapsB &t, float *out) { gather3_blend(t, gather3_load(img, t), out); }
+
+// ---- layers (hres_layers_kernel) and sparse (hres_keep_kernel, hres_layers_sparse_kernel): ONE definition of a texel of the high-res stack, so the
+// tiles a sparse stack keeps and the codes in them are the dense stack's, bit for bit.  The texel is the sweep's functions above, the resize's
+// expression and the assembly's blend in the order of the three launches the dense kernel replaced (geo_layers.hip tells that story).
+// Layers per group (one G-float vector per low-res corner; the group is unrolled) and the waves per SIMD the register allocation aims at.  What hides the gathers'
+// latency is the independent samples a lane has in flight, not the wave count (same-box A/B, DESIGN.md section 4, profiles/hres_layers_variants.txt): G = 4 at four waves
+// (101-103 VGPRs) 2.3 ms at 4096x2048x32, G = 2 at five waves the same there and 1.9 x slower at 1280x640, G = 1 at six waves 1.7 x / 2.8 x slower; G = 4 at five waves spills.
+#ifndef MSI_HRES_GROUP   // (tuning: -DMSI_HRES_GROUP=1 / 2 / 4)
+#define MSI_HRES_GROUP 4
+#endif
+#ifndef MSI_HRES_WAVES   // (tuning: -DMSI_HRES_WAVES=4 / 5)
+#define MSI_HRES_WAVES 4
+#endif
+
+// tf.image.resize(..., BILINEAR, align_corners=True) [TF-knowledge: resize_bilinear_op]:
+// src = dst * (in-1)/(out-1); lower = floor(src), upper = min(ceil(src), in-1), lerp = src - lower;
+// top = tl + (tr - tl)*xl; bottom = bl + (br - bl)*xl; out = top + (bottom - top)*yl.
+// Used by the high-res re-render to upsample blend weights / alphas (test.py:319-325).
+// The ONE definition of that expression, for a float (resize_bilinear_kernel, per component) or a vector of layers (the hres kernels, elementwise).
+template <typename T>
+__device__ __forceinline__ T lerp2(T tl, T tr, T bl, T br, float xl, float yl) {
+  const T top = tl + (tr - tl) * xl;
+  const T bot = bl + (br - bl) * xl;
+  return top + (bot - top) * yl;
+}
+
+constexpr int HRES_G = MSI_HRES_GROUP;
+typedef float hres_vec __attribute__((ext_vector_type(HRES_G)));
+
+// the resize's corners (element offsets of layer 0 in a [h,w,D] low-res tensor) and fractions of high-res pixel (i, j) (resize_bilinear_kernel; sy, sx
+// from the host as in msi_resize_bilinear_f32)
+struct HresAxis {   // along one axis: the two low-res coordinates a high-res coordinate lies between (both non-decreasing in it) and the fraction
+  int lo, hi;
+  float frac;
+};
+__device__ __forceinline__ HresAxis hres_axis(int i, float s, int low_n) {
+  HresAxis a;
+  const float f = (float)i * s;
+  a.lo = (int)floorf(f);
+  a.hi = min((int)ceilf(f), low_n - 1);
+  a.frac = f - (float)a.lo;
+  return a;
+}
+struct HresCorners {
+  unsigned tl, tr, bl, br;
+  float xl, yl;
+};
+__device__ __forceinline__ HresCorners hres_corners(int i, int j, float sy, float sx, int low_h, int low_w, int nd) {
+  HresCorners c;
+  const HresAxis y = hres_axis(i, sy, low_h), x = hres_axis(j, sx, low_w);
+  c.yl = y.frac; c.xl = x.frac;
+  c.tl = (unsigned)(y.lo * low_w + x.lo) * (unsigned)nd; c.tr = (unsigned)(y.lo * low_w + x.hi) * (unsigned)nd;      // (h * w * D < 2^31: checked on the host)
+  c.bl = (unsigned)(y.hi * low_w + x.lo) * (unsigned)nd; c.br = (unsigned)(y.hi * low_w + x.hi) * (unsigned)nd;
+  return c;
+}
+// HRES_G layers of a low-res tensor (p = its sample + the group's first layer) at those corners
+__device__ __forceinline__ hres_vec hres_lerp(const float *__restrict__ p, const HresCorners &k) {
+  const hres_vec a = *reinterpret_cast<const hres_vec *>(p + k.tl), b = *reinterpret_cast<const hres_vec *>(p + k.tr);
+  const hres_vec c = *reinterpret_cast<const hres_vec *>(p + k.bl), d = *reinterpret_cast<const hres_vec *>(p + k.br);
+  return lerp2(a, b, c, d, k.xl, k.yl);         // (elementwise: the resize's expression)
+}
+
+template <int FMT, int NT>
+__device__ __forceinline__ void hres_store_packed(void *__restrict__ base, size_t texel, const float4 &t) {
+  if constexpr (FMT == MSI_LAYERS_RGBA8) {
+    unsigned *p = static_cast<unsigned *>(base) + texel;
+    const unsigned q = rgba8_encode(t);
+    if (NT) __builtin_nontemporal_store(q, p); else *p = q;
+  } else {
+    u32x2_g *p = static_cast<u32x2_g *>(base) + texel;
+    const u32x2_g q = rgba16f_encode(t);
+    if (NT) __builtin_nontemporal_store(q, p); else *p = q;
+  }
+}
+
+// what a pixel (b, i, j) of the high-res stack has for all its layers: the sweep's per-pixel constants (ods_sweep_kernel), the two images, the two poses
+struct HresPixel {
+  const float *P0, *P1;
+  __amdgpu_buffer_rsrc_t img0, img1;
+  float r, csct, st, ssct;
+  bool same;                                    // both sources share the quadratic when their poses are equal
+};
+__device__ __forceinline__ HresPixel hres_pixel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
+                                                const float *__restrict__ pose1, const float *__restrict__ intrinsics,
+                                                const float *__restrict__ trig, int b, int i, int j, int height, int width) {
+  HresPixel p;
+  const float cs = trig[j], ss = trig[width + j];
+  const float ct = trig[2 * width + i];
+  p.st = trig[2 * width + height + i];
+  p.csct = cs * ct; p.ssct = ss * ct;
+  const int img_bytes = height * width * 12;
+  p.P0 = pose0 + (size_t)b * 16; p.P1 = pose1 + (size_t)b * 16;
+  p.img0 = __builtin_amdgcn_make_buffer_rsrc((void *)(image0 + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
+  p.img1 = __builtin_amdgcn_make_buffer_rsrc((void *)(image1 + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
+  p.r = intrinsics[(size_t)b * 9];
+  p.same = true;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) p.same = p.same && (p.P0[k] == p.P1[k]);
+  return p;
+}
+
+// A texel in three steps, each a function of the one before: where its two samples lie (ods_quad / ods_tail / make_taps_bytes; the shared quadratic
+// for equal poses), their eight texels (gather3_load), and the blend (gather3_blend; assemble_kernel, COLOR_BLEND_PSV with pred_scaled).  hres_texel is
+// the three in a row, the dense kernel's texel; the sparse kernel calls the steps.
+struct HresTaps { TapsB fg, bg; };
+struct HresRgb { Rgb4 fg, bg; };
+__device__ __forceinline__ HresTaps hres_taps(const HresPixel &p, float depth, const PixConsts &K, int width, int height) {
+  HresTaps t;
+  float u, v;
+  const OdsQuad q0 = ods_quad(p.P0, p.r, depth, p.csct, p.st, p.ssct);
+  ods_tail(q0, 1.0f, K, u, v);
+  t.fg = make_taps_bytes(u, v, width, height);
+  if (p.same) {
+    ods_tail(q0, -1.0f, K, u, v);
+  } else {
+    const OdsQuad q1 = ods_quad(p.P1, p.r, depth, p.csct, p.st, p.ssct);
+    ods_tail(q1, -1.0f, K, u, v);
+  }
+  t.bg = make_taps_bytes(u, v, width, height);
+  return t;
+}
+__device__ __forceinline__ HresRgb hres_fetch(const HresPixel &p, const HresTaps &t) {
+  HresRgb g;
+  g.fg = gather3_load(p.img0, t.fg);
+  g.bg = gather3_load(p.img1, t.bg);
+  return g;
+}
+__device__ __forceinline__ float4 hres_blend(const HresTaps &t, const HresRgb &g, float w, float alpha) {
+  float fg[3], bg[3];
+  gather3_blend(t.fg, g.fg, fg);
+  gather3_blend(t.bg, g.bg, bg);
+  const float omw = 1.0f - w;
+  float4 o;
+  o.x = w * fg[0] + omw * bg[0];
+  o.y = w * fg[1] + omw * bg[1];
+  o.z = w * fg[2] + omw * bg[2];
+  o.w = alpha;
+  return o;
+}
+__device__ __forceinline__ float4 hres_texel(const HresPixel &p, float depth, const PixConsts &K, int width, int height, float w, float alpha) {
+  const HresTaps t = hres_taps(p, depth, K, width, height);
+  return hres_blend(t, hres_fetch(p, t), w, alpha);
 }
 
 // ---- sweep, layers (pack / unpack / hres) and planar: the 16-byte store of every streaming kernel; its host side is beyond_infinity_cache below.
@@ -704,6 +855,20 @@ int grid_1d(size_t n) {
 
 // sweep, layers, planar: non-temporal stores (sweep_store16 and its siblings) for a destination that cannot stay in the 256-MiB Infinity Cache anyway
 bool beyond_infinity_cache(size_t bytes) { return bytes > ((size_t)256 << 20); }
+
+// layers (msi_hres_layers) and sparse (msi_hres_index_tiles, msi_hres_layers_sparse): the checks every entry point of the high-res stack makes of
+// its inputs and sizes, in ONE order, and the scales of msi_resize_bilinear_f32
+int hres_check(const char *who, bool inputs, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width, int32_t num_planes) {
+  MSI_REQUIRE(inputs, "%s: null pointer", who);
+  MSI_REQUIRE(batch >= 0 && low_height > 0 && low_width > 0 && height > 0 && width > 0 && num_planes > 0, "%s: bad dims", who);
+  if (num_planes % 4 != 0)
+    return msi::fail(MSI_E_UNSUPPORTED, "%s: num_planes=%d must be a multiple of 4", who, num_planes);
+  MSI_REQUIRE(height <= 65535 && batch <= 65535 && (long)height * width < (1L << 24),
+              "%s: problem too large (24-bit pixel offsets: H * W < 2^24, H <= 65535)", who);
+  MSI_REQUIRE((long)low_height * low_width * num_planes < (1L << 31), "%s: low-res tensors too large (h * w * D < 2^31)", who);
+  return MSI_OK;
+}
+float hres_scale(int low, int high) { return high > 1 ? (float)(low - 1) / (float)(high - 1) : 0.0f; }
 
 // render, ods, planar, cube: the grid of a many-views launch (ViewBlock), blocks_per_view x views x batch workgroups rounded up to a multiple of 8; each
 // factor is < 2^31 and every product is checked before the next

@@ -22,6 +22,10 @@ MSI.render_views; in the high_res modes the high-res stack is kept the same way,
 only the 4 x 16 tiles a sphere render can see; SparseLayers.load reads it, MSI.render_views renders from it with the dense
 render's pixels), prints each sample's occupancy and bytes and writes them to <output_root>/<experiment>/sparse.json -- how sparse
 the stacks of real content are is read off here.  The high-res stack of `--test_type high_res` (`msi_hres_<dir>.npz`) is not sparsified.
+`--msi_hres_sparse` (with --msi_format and a high_res mode; --hres_height % 4 == 0, --hres_width % 16 == 0) saves `msi_hres_<dir>.npz` as a
+SparseLayers built directly (MSI.hres_layers_sparse: the kept tiles follow from the low-res alphas, only their texels are computed
+and the dense high-res stack is never allocated) and writes each sample's occupancy and bytes to <experiment>/hres_sparse.json; the
+images are the bytes of a run without the flag.
 `--checkpoint` reads a TF V2 checkpoint directly (tf_checkpoint.py), `--weights` an .npz of the TF variables
 (see nets.variable_shapes); without either Xavier-initialised
 weights are used (there is no network access for the pretrained checkpoint), step.txt then says 0.
@@ -318,14 +322,16 @@ def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, n
     return outs
 
 
-def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, dirname, msi_format=None):
+def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, dirname, msi_format=None, hres_sparse_log=None):
     """The high-res pass of test.py:283-394 for one sample: the low-res blend weights / alphas the first pass saved
     (blend_weights.npy, alphas.npy, test.py:264-271) are upsampled (align_corners), the layers re-assembled from the
     high-res sweep volume and rendered -- one fused device pass (MSI.msi_render_equirect_hres) instead of the
     reference's per-plane sess.run + numpy composite -- and written as test.py:383-394 does: (x + 1) / 2 * 255 and
     depth * 255, clipped and truncated to uint8 by write_image.  msi_format ('rgba8' | 'rgba16f'): the launch that builds the
     high-res stack (MSI.hres_layers) also emits it packed, saved with its planes as msi_hres_<dirname>.npz; the images are
-    the same bytes either way."""
+    the same bytes either way.  hres_sparse_log (--msi_hres_sparse; a list, needs msi_format): msi_hres_<dirname>.npz is the
+    SparseLayers of MSI.hres_layers_sparse instead -- the dense packed stack is never built --, the sample's occupancy and bytes
+    are appended to the list, and the images come from the fp32 stack as in a run without any of these flags."""
     import torch
     bw_path, al_path = os.path.join(output_dir, "blend_weights.npy"), os.path.join(output_dir, "alphas.npy")
     if not (os.path.exists(bw_path) and os.path.exists(al_path)):
@@ -337,7 +343,16 @@ def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, d
     intr = np.array([[[baseline, 0, 0], [0, 1, 0], [0, 0, 1]]], dtype=np.float32)
     pos = np.asarray(tgt_pos, dtype=np.float32)[None]
     packed = None
-    if msi_format is None:
+    if hres_sparse_log is not None:
+        rgb, dep = model.msi_render_equirect_hres(bw, al, ref, src, eye, eye, eye, pos, planes, intr)
+        packed = model.hres_layers_sparse(bw, al, ref, src, eye, eye, planes, intr, layer_format=msi_format)["sparse_layers"]
+        b, hh, hw, d = packed.shape
+        entry = dict(name=dirname, occupancy=packed.occupancy, nbytes=packed.nbytes,
+                     dense_nbytes=b * d * hh * hw * packed.pool.element_size() * 4)
+        hres_sparse_log.append(entry)
+        print("Sparse high-res MSI of %s: occupancy %.4f, %d bytes (dense %s: %d bytes, never allocated)" % (
+            dirname, entry["occupancy"], entry["nbytes"], msi_format, entry["dense_nbytes"]))
+    elif msi_format is None:
         rgb, dep = model.msi_render_equirect_hres(bw, al, ref, src, eye, eye, eye, pos, planes, intr)
     else:
         layers = model.hres_layers(bw, al, ref, src, eye, eye, planes, intr, layer_format=("f32", msi_format))
@@ -379,6 +394,11 @@ def main(argv=None):
                          "--test_type high_res (msi_hres_<dir>.npz) is not sparsified and stays dense, and high_res_only is refused; default: off")
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--msi_hres_sparse", action="store_true",
+                    help="with --msi_format and a high_res --test_type: save the high-res stack msi_hres_<dir>.npz as a SparseLayers built "
+                         "directly from the low-res alphas and the high-res images (MSI.hres_layers_sparse: the dense high-res stack is "
+                         "never allocated; --hres_height %% 4 == 0 and --hres_width %% 16 == 0) and write each sample's occupancy and bytes to "
+                         "<experiment>/hres_sparse.json; the images are the bytes of a run without the flag; default: off")
     ap.add_argument("--hres_height", type=int, default=2048, help="loader.py:34")
     ap.add_argument("--hres_width", type=int, default=4096, help="loader.py:35")
     ap.add_argument("--num_msi_planes", type=int, default=32)
@@ -428,6 +448,12 @@ def main(argv=None):
         ap.error("--msi_sparse needs --height % 4 == 0 and --width % 16 == 0")
     if args.msi_sparse and "high_res_only" in args.test_type:
         ap.error("--msi_sparse sparsifies the low-res stacks only: --test_type high_res_only has none (the high-res stack stays dense)")
+    if args.msi_hres_sparse and args.msi_format is None:
+        ap.error("--msi_hres_sparse needs --msi_format")
+    if args.msi_hres_sparse and "high_res" not in args.test_type:
+        ap.error("--msi_hres_sparse builds the high-res stack: it needs a high_res --test_type")
+    if args.msi_hres_sparse and (args.hres_height % 4 or args.hres_width % 16):
+        ap.error("--msi_hres_sparse needs --hres_height % 4 == 0 and --hres_width % 16 == 0")
     if args.num_psv_planes != args.num_msi_planes:
         raise SystemExit("--num_psv_planes must equal --num_msi_planes (msi.py:138 indexes the source volume with num_msi_planes)")
     if "high_res" in args.test_type and args.input_type != "ODS":
@@ -456,6 +482,7 @@ def main(argv=None):
     os.makedirs(exp_dir, exist_ok=True)
     scorer = DeviceScores(model, keep_frames="on_video" in args.test_type) if args.score else None
     sparse_log = [] if args.msi_sparse else None
+    hres_sparse_log = [] if args.msi_hres_sparse else None
     samples = list(parse_camera_files(args.cameras_glob, args.input_type))
     if args.num_runs >= 0:
         samples = samples[:args.num_runs]
@@ -501,8 +528,15 @@ def main(argv=None):
             hres = [load_image(os.path.join(args.hres_image_dir, "%s_pos%s.jpeg" % (scene, i)), args.hres_height, args.hres_width)
                     for i in ids[:2]]
             dirname = sample_dirname(scene, ids, args.test_type, args.prefix)
-            run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname, msi_format=args.msi_format)
+            run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname, msi_format=args.msi_format,
+                            hres_sparse_log=hres_sparse_log)
             n += "high_res_only" in args.test_type
+    if hres_sparse_log is not None:
+        from .sparse import TILE_H, TILE_W
+        with open(os.path.join(exp_dir, "hres_sparse.json"), "w") as f:
+            json.dump(dict(format=args.msi_format, tile=[TILE_H, TILE_W], samples=hres_sparse_log,
+                           mean_occupancy=float(np.mean([e["occupancy"] for e in hres_sparse_log])) if hres_sparse_log else None), f)
+        print("High-res occupancies written to %s" % os.path.join(exp_dir, "hres_sparse.json"))
     if sparse_log is not None:
         from .sparse import TILE_H, TILE_W
         with open(os.path.join(exp_dir, "sparse.json"), "w") as f:

@@ -927,6 +927,24 @@ class MSI(object):
         return native.permute(0, 2, 3, 1, 4)
 
     # ------------------------------------------------------------------ test.py:283-394
+    def _hres_inputs(self, who, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics,
+                     ref_pose_inv):
+        """What hres_layers and hres_layers_sparse hand to their launches, checked: (bw, al, hres_ref, hres_src, cur, intr, depths, trig)."""
+        if self.input_type != 'ODS':
+            raise ValueError("%s: the fused high-res assembly is built for input_type='ODS' models" % who)
+        bw, al = self._f32(blend_weights), self._f32(alphas)
+        if bw.dim() != 4 or bw.shape != al.shape:
+            raise ValueError("%s: blend_weights and alphas must be [B,H,W,D] and agree" % who)
+        b, h, w, d = bw.shape
+        depths = self._depths(planes, d)
+        hres_ref = self.preprocess_image(raw_hres_ref_image)
+        hres_src = self.preprocess_image(raw_hres_src_image)
+        if hres_ref.shape[0] != b or hres_ref.shape[3] != 3 or hres_src.shape != hres_ref.shape:
+            raise ValueError("%s: images must be [B,Hh,Wh,3], agree, and have the batch of blend_weights" % who)
+        cur = self._current_poses(ref_pose, src_pose, ref_pose_inv, b)
+        intr, trig = self._f32(intrinsics), self._trig(hres_ref.shape[1], hres_ref.shape[2])
+        return bw, al, hres_ref, hres_src, cur, intr, depths, trig
+
     def hres_layers(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
                     intrinsics, ref_pose_inv=None, layer_format='f32'):
         """The high-res layer stack of test.py:283-394 in ONE launch (msi_hres_layers): the high-res ODS sweep of both images,
@@ -937,22 +955,13 @@ class MSI(object):
         into render_views; ('f32', packed) writes both in the same launch.  The fp32 stack has the bits of format_network_input
         -> msi_resize_bilinear_f32 -> msi_assemble_rgba_scaled_f32, the packed one those of pack_layers of it; a packed-only
         request allocates nothing but the packed stack.  ODS models only (fp32 or bf16: the high-res colours are fp32 either
-        way).  Poses as in format_network_input (ref_pose_inv computed on the host when absent)."""
+        way).  Poses as in format_network_input (ref_pose_inv computed on the host when absent).  hres_layers_sparse builds the
+        packed stack sparse, without the dense one."""
         want_f32, pfmt = self._layer_formats(layer_format)
-        if self.input_type != 'ODS':
-            raise ValueError("hres_layers: the fused high-res assembly is built for input_type='ODS' models")
-        bw, al = self._f32(blend_weights), self._f32(alphas)
-        if bw.dim() != 4 or bw.shape != al.shape:
-            raise ValueError("hres_layers: blend_weights and alphas must be [B,H,W,D] and agree")
+        bw, al, hres_ref, hres_src, cur, intr, depths, trig = self._hres_inputs(
+            "hres_layers", blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics, ref_pose_inv)
         b, h, w, d = bw.shape
-        depths = self._depths(planes, d)
-        hres_ref = self.preprocess_image(raw_hres_ref_image)
-        hres_src = self.preprocess_image(raw_hres_src_image)
-        if hres_ref.shape[0] != b or hres_ref.shape[3] != 3 or hres_src.shape != hres_ref.shape:
-            raise ValueError("hres_layers: images must be [B,Hh,Wh,3], agree, and have the batch of blend_weights")
         hh, hw = hres_ref.shape[1], hres_ref.shape[2]
-        cur = self._current_poses(ref_pose, src_pose, ref_pose_inv, b)
-        intr, trig = self._f32(intrinsics), self._trig(hh, hw)
         rgba = torch.empty((b, d, hh, hw, 4), dtype=torch.float32, device=self.device) if want_f32 else None
         codes = None
         if pfmt is not None:
@@ -967,6 +976,44 @@ class MSI(object):
         if codes is not None:
             out['packed_layers'] = PackedLayers(codes, pfmt, planes)
         return out
+
+    def hres_layers_sparse(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
+                           intrinsics, ref_pose_inv=None, layer_format='rgba8'):
+        """hres_layers' packed stack as a SparseLayers, without the dense stack: the arguments of hres_layers, layer_format 'rgba8'
+        or 'rgba16f' alone (fp32 pools are not built), Hh % 4 == 0 and Wh % 16 == 0 (else ValueError) -> {'sparse_layers':
+        SparseLayers} that carries `planes`: the table, layer_start and pool that sparsify_layers(hres_layers(...)['packed_layers'])
+        has for the same request, bit for bit; it goes straight into render_views / render_ods_pair, save and densify_layers.
+        A texel's alpha is the resized low-res alpha, whatever the images hold, so msi_hres_index_tiles decides the kept tiles
+        from `alphas` alone; after the one host synchronisation sparsify_layers has too (the pool's size is data-dependent)
+        msi_hres_layers_sparse computes the texels of kept tiles only, straight into the pool.  Only table, counts, layer_start
+        and pool are allocated.  ODS models only."""
+        want_f32, pfmt = self._layer_formats(layer_format)
+        if want_f32 or pfmt is None:
+            raise ValueError("hres_layers_sparse takes layer_format 'rgba8' or 'rgba16f' alone (fp32 pools are not built), not %r"
+                             % (layer_format,))
+        bw, al, hres_ref, hres_src, cur, intr, depths, trig = self._hres_inputs(
+            "hres_layers_sparse", blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics,
+            ref_pose_inv)
+        b, h, w, d = bw.shape
+        hh, hw = hres_ref.shape[1], hres_ref.shape[2]
+        if hh % TILE_H or hw % TILE_W:
+            raise ValueError("a sparse stack needs H %% %d == 0 and W %% %d == 0, not %d x %d" % (TILE_H, TILE_W, hh, hw))
+        fmt = self.LAYER_FORMATS[pfmt]
+        table = torch.empty((b, d, hh // TILE_H, hw // TILE_W), dtype=torch.int32, device=self.device)
+        counts = torch.empty((b * d,), dtype=torch.int32, device=self.device)
+        N.check(N.lib.msi_hres_index_tiles(al.data_ptr(), fmt, b, h, w, hh, hw, d, table.data_ptr(), counts.data_ptr(), self._stream()),
+                "msi_hres_index_tiles")
+        layer_start = torch.zeros((b * d + 1,), dtype=torch.int64, device=self.device)
+        if b * d:
+            layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(layer_start[-1].item())
+        pool = torch.empty((total, TILE_H, TILE_W, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+        if total:
+            N.check(N.lib.msi_hres_layers_sparse(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(),
+                                                 intr.data_ptr(), depths.data_ptr(), trig.data_ptr(), bw.data_ptr(), al.data_ptr(),
+                                                 b, h, w, hh, hw, d, table.data_ptr(), layer_start.data_ptr(), pool.data_ptr(), fmt,
+                                                 self._stream()), "msi_hres_layers_sparse")
+        return {'sparse_layers': SparseLayers(table, layer_start, pool, pfmt, planes)}
 
     def msi_render_equirect_hres(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image,
                                  ref_pose, src_pose, tgt_pose_rt, tgt_pos, planes, intrinsics,
