@@ -66,7 +66,8 @@ const char *msi_version(void);
  *   9: msi_perspective_sweep_volume_bf16
  *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images; msi_cube_render_views,
  *      msi_equirect_to_cube_f32; msi_sparse_index_tiles, msi_sparse_gather_tiles, msi_sparse_expand, msi_render_views_sparse;
- *      msi_hres_index_tiles, msi_hres_layers_sparse) */
+ *      msi_hres_index_tiles, msi_hres_layers_sparse; msi_sparse_index_tiles_edge, msi_mpi_render_views_sparse,
+ *      msi_cube_render_views_sparse) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -368,6 +369,46 @@ int msi_render_views_sparse(const void *pool, const int32_t *table, const int64_
                             const float *depths, const float *trig, int32_t batch, int32_t views, int32_t height, int32_t width,
                             int32_t num_planes, int32_t camera, int32_t out_height, int32_t out_width, float *out_rgb,
                             float *out_depth, int32_t *status_device, msi_stream_t stream);
+/* Sparse stacks for surfaces that do not wrap (MSI.sparsify_layers(border='edge'); MSI.mpi_render_views / cube_render_views on a
+ * SparseLayers): the planar render zero-pads -- a tap outside [0,W) x [0,H) is masked to zero -- and the cube render clamps to the
+ * edge of the chosen face; neither ever reads the opposite border.  So the EDGE keep rule is the rule above with the tile's 6 x 18
+ * window CLIPPED to the image instead of wrapped: tile (ty, tx) of layer d is kept iff d == 0 or some texel of the clipped window is
+ * not empty.  Then a footprint with any in-range tap in a dropped tile has all in-range alphas zero.  Tile, "empty", table,
+ * layer_start, pool and layer 0 kept whole are unchanged; the kept set is a subset of the wrap rule's.  A stack records the rule
+ * it was made with: the sphere renders are correct on wrap-rule stacks only, these two read edge-rule stacks (the Python layer
+ * refuses a mismatch; the C entry points trust their caller).
+ *   msi_sparse_index_tiles_edge   msi_sparse_index_tiles with the edge rule: the same arguments, checks, launches and outputs.
+ *                                 msi_sparse_gather_tiles and msi_sparse_expand do not depend on the rule.
+ *   msi_mpi_render_views_sparse   msi_mpi_render_views with (pool, table, layer_start, format) in place of the stack.  Per layer a
+ *                                 lane looks up the tiles of its IN-RANGE taps only (a masked tap is never absent; its value is zero);
+ *                                 a pixel that samples outside (-1, W) x (-1, H) is present with every tap masked.
+ *   msi_cube_render_views_sparse  msi_cube_render_views likewise; table [6B,D,S/4,S/16].  S % 16 == 0 is required
+ *                                 (MSI_E_UNSUPPORTED).  Clamped taps never leave the face: all four are looked up.  The status word
+ *                                 is msi_cube_render_views'.  A sample's six DENSE face stacks must stay below 2^31 bytes, as there
+ *                                 (they bound its kept tiles, which one descriptor addresses).
+ * Both follow msi_render_views_sparse's contract: with every tap tile present a lane loads and blends exactly as the dense kernel
+ * does, otherwise the layer's step is skipped (and when no lane of a wavefront is present the texel loads are not issued); with
+ * finite colours under zero alphas every output element compares == to msi_mpi_render_views / msi_cube_render_views on the dense
+ * packed stack and on msi_sparse_expand's output (a zero may differ in sign).
+ * Argument checks before any HIP call, in this order, MSI_E_BADARG unless noted.  msi_sparse_index_tiles_edge: the tile entry
+ * points'.  msi_mpi_render_views_sparse: both outputs NULL; a NULL input; unknown format (MSI_LAYERS_F32 included); bad dims; more
+ * than 128 planes, then H % 4 or W % 16 -> MSI_E_UNSUPPORTED; views < 1; output size below 1 x 1; H * W >= 2^24; the grid limit.
+ * msi_cube_render_views_sparse: both outputs NULL; a NULL pool / table / layer_start / pose / position / stack_intrinsics / depths;
+ * unknown format; unknown camera; a NULL trig (equirect) / tgt_intrinsics (pinhole); bad dims; more than 128 planes, then S % 16 ->
+ * MSI_E_UNSUPPORTED; views < 1; output size below 1 x 1 (2 x 2 pinhole); the 2^31-byte limit; the grid limit.  batch = 0 returns
+ * MSI_OK after validation, without a launch. */
+int msi_sparse_index_tiles_edge(const void *layers, int32_t format, int32_t batch, int32_t num_planes, int32_t height, int32_t width,
+                                int32_t *table_out, int32_t *counts_out, msi_stream_t stream);
+int msi_mpi_render_views_sparse(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format,
+                                const float *tgt_pose, const float *intrinsics, const float *tgt_intrinsics_inv, const float *depths,
+                                int32_t batch, int32_t views, int32_t height, int32_t width, int32_t num_planes,
+                                int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, msi_stream_t stream);
+int msi_cube_render_views_sparse(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format,
+                                 const float *tgt_pose_rt, const float *tgt_pos, const float *tgt_intrinsics,
+                                 const float *stack_intrinsics, const float *depths, const float *trig,
+                                 int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
+                                 int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                                 msi_stream_t stream);
 /* The high-res stack of msi_hres_layers built sparse (MSI.hres_layers_sparse): the dense stack is never written.
  * RULE: msi_hres_layers stores a texel's alpha as the align-corners bilinear resize of the low-res alphas, encoded; it does not
  * depend on the images.  So the keep rule above is applied to the alphas the dense stack WOULD hold -- the same resize

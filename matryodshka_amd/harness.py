@@ -22,6 +22,9 @@ MSI.render_views; in the high_res modes the high-res stack is kept the same way,
 only the 4 x 16 tiles a sphere render can see; SparseLayers.load reads it, MSI.render_views renders from it with the dense
 render's pixels), prints each sample's occupancy and bytes and writes them to <output_root>/<experiment>/sparse.json -- how sparse
 the stacks of real content are is read off here.  The high-res stack of `--test_type high_res` (`msi_hres_<dir>.npz`) is not sparsified.
+`--msi_pp_sparse` (with --msi_format and --input_type PP; --height % 4 == 0, --width % 16 == 0) is its counterpart for planar stacks: `msi_<dir>.npz`
+is an edge-rule SparseLayers (MSI.sparsify_layers(border='edge'): the tiles a render that never reads the opposite border can see), which
+MSI.mpi_render_views renders with the dense render's pixels; occupancies and bytes go to <experiment>/pp_sparse.json, with sparse.json's keys.
 `--msi_hres_sparse` (with --msi_format and a high_res mode; --hres_height % 4 == 0, --hres_width % 16 == 0) saves `msi_hres_<dir>.npz` as a
 SparseLayers built directly (MSI.hres_layers_sparse: the kept tiles follow from the low-res alphas, only their texels are computed
 and the dense high-res stack is never allocated) and writes each sample's occupancy and bytes to <experiment>/hres_sparse.json; the
@@ -119,16 +122,17 @@ def write_layer_outputs(outs, jouts, src, ref, num_planes, test_outputs, output_
                 write_image(os.path.join(output_dir, "jitter_msi_rgb_%.2d.png" % i), (jr[0, :, :, i, :3] + 1.) / 2. * 255)
 
 
-def save_packed_msi(outs, output_dir, dirname, model=None, sparse_log=None):
-    """--msi_format: the sample's packed stack (with its planes) as msi_<dirname>.npz next to its other files.  sparse_log (--msi_sparse; a
-    list, needs model): the file is the stack's SparseLayers instead, and the sample's occupancy and bytes are appended to the list."""
+def save_packed_msi(outs, output_dir, dirname, model=None, sparse_log=None, border='wrap'):
+    """--msi_format: the sample's packed stack (with its planes) as msi_<dirname>.npz next to its other files.  sparse_log (--msi_sparse, or
+    --msi_pp_sparse with border='edge'; a list, needs model): the file is the stack's SparseLayers instead, made with the keep rule `border`, and
+    the sample's occupancy and bytes are appended to the list."""
     if "packed_layers" not in outs:
         return
     packed = outs["packed_layers"]
     if sparse_log is None:
         packed.save(os.path.join(output_dir, "msi_%s.npz" % dirname))
         return
-    sparse = model.sparsify_layers(packed)
+    sparse = model.sparsify_layers(packed, border=border)
     sparse.save(os.path.join(output_dir, "msi_%s.npz" % dirname))
     entry = dict(name=dirname, occupancy=sparse.occupancy, nbytes=sparse.nbytes, dense_nbytes=packed.nbytes)
     sparse_log.append(entry)
@@ -291,11 +295,12 @@ def sample_dirname(scene, ids, test_type="", prefix=""):
 
 
 def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, ngf, test_outputs, output_dir, dirname,
-                  which_color_pred="blend_psv", msi_format=None, scorer=None, scene=None):
+                  which_color_pred="blend_psv", msi_format=None, scorer=None, scene=None, sparse_log=None):
     """input_type=PP (test.py:51; data_loader.py:205-226): perspective pair, source camera shifted by -input_offset along
     x, target by -tgt_offset, intrinsics fx = cx = W/2, fy = cy = H/2; plane-sweep volume at the slerp mid-point pose
     (train.py:118-121), target view by mpi_render_view through tgt_pose @ interp_pose_inv (msi.py:644-646).  The MPI path
-    has no depth render (the reference has none either).  msi_format: as in run_sample."""
+    has no depth render (the reference has none either).  msi_format: as in run_sample.  sparse_log (--msi_pp_sparse): the saved stack
+    is an edge-rule SparseLayers, which MSI.mpi_render_views reads; see save_packed_msi."""
     import torch
     from . import poses
     ref, src, tgt = (torch.from_numpy(np.ascontiguousarray(x[None])) for x in images)
@@ -318,7 +323,7 @@ def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, n
         if scorer is not None:
             scorer.add(dirname, scene, tgt[0].numpy() * 255.0, rgb8)
     write_layer_outputs(outs, None, src, ref, num_planes, test_outputs, output_dir, dirname, which_color_pred)
-    save_packed_msi(outs, output_dir, dirname)
+    save_packed_msi(outs, output_dir, dirname, model, sparse_log, border='edge')
     return outs
 
 
@@ -394,6 +399,11 @@ def main(argv=None):
                          "--test_type high_res (msi_hres_<dir>.npz) is not sparsified and stays dense, and high_res_only is refused; default: off")
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--msi_pp_sparse", action="store_true",
+                    help="with --msi_format and --input_type PP: save msi_<dir>.npz as an edge-rule SparseLayers (the occupied 4 x 16 tiles a "
+                         "render that never reads the opposite border can see: MSI.mpi_render_views reads it; --height %% 4 == 0 and "
+                         "--width %% 16 == 0) and write each sample's occupancy and bytes to <experiment>/pp_sparse.json; the images are the "
+                         "bytes of a run without the flag; default: off")
     ap.add_argument("--msi_hres_sparse", action="store_true",
                     help="with --msi_format and a high_res --test_type: save the high-res stack msi_hres_<dir>.npz as a SparseLayers built "
                          "directly from the low-res alphas and the high-res images (MSI.hres_layers_sparse: the dense high-res stack is "
@@ -448,6 +458,12 @@ def main(argv=None):
         ap.error("--msi_sparse needs --height % 4 == 0 and --width % 16 == 0")
     if args.msi_sparse and "high_res_only" in args.test_type:
         ap.error("--msi_sparse sparsifies the low-res stacks only: --test_type high_res_only has none (the high-res stack stays dense)")
+    if args.msi_pp_sparse and args.msi_format is None:
+        ap.error("--msi_pp_sparse needs --msi_format")
+    if args.msi_pp_sparse and args.input_type != "PP":
+        ap.error("--msi_pp_sparse keeps planar stacks: it needs --input_type PP (ODS inputs: --msi_sparse)")
+    if args.msi_pp_sparse and (args.height % 4 or args.width % 16):
+        ap.error("--msi_pp_sparse needs --height % 4 == 0 and --width % 16 == 0")
     if args.msi_hres_sparse and args.msi_format is None:
         ap.error("--msi_hres_sparse needs --msi_format")
     if args.msi_hres_sparse and "high_res" not in args.test_type:
@@ -483,6 +499,7 @@ def main(argv=None):
     scorer = DeviceScores(model, keep_frames="on_video" in args.test_type) if args.score else None
     sparse_log = [] if args.msi_sparse else None
     hres_sparse_log = [] if args.msi_hres_sparse else None
+    pp_sparse_log = [] if args.msi_pp_sparse else None
     samples = list(parse_camera_files(args.cameras_glob, args.input_type))
     if args.num_runs >= 0:
         samples = samples[:args.num_runs]
@@ -500,7 +517,8 @@ def main(argv=None):
             try:
                 if args.input_type == "PP":
                     run_sample_pp(model, images, cam[0], cam[1], planes, d, args.ngf, args.test_outputs, out_dir, dirname,
-                                  which_color_pred=args.which_color_pred, msi_format=args.msi_format, scorer=scorer, scene=scene)
+                                  which_color_pred=args.which_color_pred, msi_format=args.msi_format, scorer=scorer, scene=scene,
+                                  sparse_log=pp_sparse_log)
                     model.network_status()   # raises if a LayerNorm statistic left the range the kernels resolve
                 else:
                     jitter = None
@@ -537,6 +555,12 @@ def main(argv=None):
             json.dump(dict(format=args.msi_format, tile=[TILE_H, TILE_W], samples=hres_sparse_log,
                            mean_occupancy=float(np.mean([e["occupancy"] for e in hres_sparse_log])) if hres_sparse_log else None), f)
         print("High-res occupancies written to %s" % os.path.join(exp_dir, "hres_sparse.json"))
+    if pp_sparse_log is not None:
+        from .sparse import TILE_H, TILE_W
+        with open(os.path.join(exp_dir, "pp_sparse.json"), "w") as f:
+            json.dump(dict(format=args.msi_format, tile=[TILE_H, TILE_W], samples=pp_sparse_log,
+                           mean_occupancy=float(np.mean([e["occupancy"] for e in pp_sparse_log])) if pp_sparse_log else None), f)
+        print("PP occupancies written to %s" % os.path.join(exp_dir, "pp_sparse.json"))
     if sparse_log is not None:
         from .sparse import TILE_H, TILE_W
         with open(os.path.join(exp_dir, "sparse.json"), "w") as f:

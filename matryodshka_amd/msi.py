@@ -21,7 +21,7 @@ import torch
 from . import _native as N
 from . import nets
 from .packed import FORMATS as PACKED_FORMATS, PackedLayers
-from .sparse import SparseLayers, TILE_H, TILE_W
+from .sparse import BORDERS, SparseLayers, TILE_H, TILE_W
 
 
 def _ptr(t):
@@ -488,7 +488,8 @@ class MSI(object):
     def _native_layers(self, rgba_layers):
         if isinstance(rgba_layers, SparseLayers):
             raise TypeError("this method does not read sparse stacks: render a SparseLayers with render_views or render_ods_pair "
-                            "(MSI), or expand it with densify_layers first")
+                            "(MSI; border='wrap') or with mpi_render_views / cube_render_views (border='edge'), or expand it with "
+                            "densify_layers first")
         if isinstance(rgba_layers, PackedLayers):
             raise TypeError("this method reads fp32 layer stacks only: render a PackedLayers with render_views (MSI) or "
                             "mpi_render_views (MPI), or expand it with unpack_layers first")
@@ -643,6 +644,21 @@ class MSI(object):
             raise ValueError("%s: planes is required (only a PackedLayers that carries its planes may leave it out)" % who)
         return native, packed, planes, self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
 
+    def _sparse_arg(self, rgba_layers, planes, who, border):
+        """A SparseLayers made with the keep rule `border` -> (the stack on this device, planes); None when rgba_layers is no
+        SparseLayers.  A stack made for the other kind of surface is refused: an edge-rule stack misses tiles a sphere render
+        reads across the border, and a sphere stack in a planar viewer is almost always a mistake."""
+        if not isinstance(rgba_layers, SparseLayers):
+            return None, planes
+        if rgba_layers.border != border:
+            raise TypeError("%s reads SparseLayers made with border=%r, not %r: expand this one with densify_layers and "
+                            "sparsify_layers(..., border=%r) the result" % (who, border, rgba_layers.border, border))
+        sparse = rgba_layers if rgba_layers.pool.device == self.device else rgba_layers.to(self.device)
+        planes = sparse.planes if planes is None else planes
+        if planes is None:
+            raise ValueError("%s: planes is required (this SparseLayers carries none)" % who)
+        return sparse, planes
+
     def _view_poses(self, name, tgt_pose, tgt_pos, b):
         """Per-view poses [B,V,4,4] and, where the camera has them, positions [B,V,3] ([V,4,4] / [V,3] when B = 1) -> fp32
         (pose, pos, V)."""
@@ -705,7 +721,7 @@ class MSI(object):
         rgba_layers may be a SparseLayers (sparsify_layers; msi_render_views_sparse), for all three cameras: every output element
         compares == to the render of the PackedLayers it was made from and of densify_layers(rgba_layers) -- the same bits, except
         that a zero may differ in sign -- provided colours are finite where alpha is zero (always so for rgba8).  planes=None
-        takes the planes it carries."""
+        takes the planes it carries.  Only a stack made with border='wrap' (the default) is accepted: TypeError otherwise."""
         if camera not in self.CAMERAS:
             raise ValueError("camera must be 'equirect', 'pinhole' or 'ods', not %r" % (camera,))
         if camera != 'ods' and (eye is not None or baseline is not None):
@@ -714,12 +730,8 @@ class MSI(object):
             raise ValueError("render_views: camera='ods' needs eye (+1 / 'left' or -1 / 'right', or an array [V] / [B,V])")
         if not (want_rgb or want_depth):
             raise ValueError("render_views: want_rgb and want_depth are both False")
-        sparse = rgba_layers if isinstance(rgba_layers, SparseLayers) else None
+        sparse, planes = self._sparse_arg(rgba_layers, planes, "render_views", 'wrap')
         if sparse is not None:
-            sparse = sparse if sparse.pool.device == self.device else sparse.to(self.device)
-            planes = sparse.planes if planes is None else planes
-            if planes is None:
-                raise ValueError("render_views: planes is required (this SparseLayers carries none)")
             (b, h, w, d), fmt = sparse.shape, self.LAYER_FORMATS[sparse.format]
         else:
             native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "render_views")
@@ -870,14 +882,19 @@ class MSI(object):
                 "msi_pack_layers")
         return PackedLayers(data, format, planes)
 
-    def sparsify_layers(self, layers, format='rgba8', planes=None):
-        """A stack -> SparseLayers (matryodshka_amd/sparse.py: only the 4 x 16 tiles a sphere render can see are stored).  `layers` is
+    def sparsify_layers(self, layers, format='rgba8', planes=None, border='wrap'):
+        """A stack -> SparseLayers (matryodshka_amd/sparse.py: only the 4 x 16 tiles a render can see are stored).  border='wrap': the
+        tiles a sphere render can see (render_views, render_ods_pair; msi_sparse_index_tiles); border='edge': those a render that
+        never reads the opposite border can see -- mpi_render_views on a [B,H,W,D,4] MPI and cube_render_views on [6B,S,S,D,4] cube
+        faces (msi_sparse_index_tiles_edge).  `layers` is
         an fp32 stack [B,H,W,D,4], packed first with pack_layers(layers, format), or a PackedLayers, whose own format is kept.
         H % 4 == 0 and W % 16 == 0 are required (ValueError).  `planes`, or else the planes a PackedLayers carries, travel with the stack.
         Three launches (msi_sparse_index_tiles: two, msi_sparse_gather_tiles) around one host synchronisation: the pool's size is
         data-dependent.  The result is the same bytes every time and equals sparse.sparsify_np of the codes."""
         if isinstance(layers, SparseLayers):
             raise TypeError("sparsify_layers takes an fp32 stack or a PackedLayers, not a SparseLayers")
+        if border not in BORDERS:
+            raise ValueError("border must be one of %s, not %r" % (BORDERS, border))
         pk = layers if isinstance(layers, PackedLayers) else self.pack_layers(layers, format, planes)
         planes = pk.planes if planes is None else planes
         data = pk.data if pk.data.device == self.device else pk.data.to(self.device)
@@ -889,8 +906,8 @@ class MSI(object):
         fmt = self.LAYER_FORMATS[pk.format]
         table = torch.empty((b, d, h // TILE_H, w // TILE_W), dtype=torch.int32, device=self.device)
         counts = torch.empty((b * d,), dtype=torch.int32, device=self.device)
-        N.check(N.lib.msi_sparse_index_tiles(data.data_ptr(), fmt, b, d, h, w, table.data_ptr(), counts.data_ptr(), self._stream()),
-                "msi_sparse_index_tiles")
+        index = "msi_sparse_index_tiles" if border == 'wrap' else "msi_sparse_index_tiles_edge"
+        N.check(getattr(N.lib, index)(data.data_ptr(), fmt, b, d, h, w, table.data_ptr(), counts.data_ptr(), self._stream()), index)
         layer_start = torch.zeros((b * d + 1,), dtype=torch.int64, device=self.device)
         if b * d:
             layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
@@ -899,10 +916,10 @@ class MSI(object):
         if total:
             N.check(N.lib.msi_sparse_gather_tiles(data.data_ptr(), fmt, table.data_ptr(), layer_start.data_ptr(), b, d, h, w,
                                                   pool.data_ptr(), self._stream()), "msi_sparse_gather_tiles")
-        return SparseLayers(table, layer_start, pool, pk.format, planes)
+        return SparseLayers(table, layer_start, pool, pk.format, planes, border=border)
 
     def densify_layers(self, sparse):
-        """SparseLayers -> the PackedLayers it stands for, all-zero bytes in dropped tiles (msi_sparse_expand)."""
+        """SparseLayers (of either keep rule) -> the PackedLayers it stands for, all-zero bytes in dropped tiles (msi_sparse_expand)."""
         if not isinstance(sparse, SparseLayers):
             raise TypeError("densify_layers takes a SparseLayers")
         sparse = sparse if sparse.pool.device == self.device else sparse.to(self.device)
@@ -1096,15 +1113,22 @@ class MSI(object):
         tgt_intrinsics ([B,V,3,3], [B,3,3] or [3,3]; inverted on the host in fp64 and rounded to fp32, as mpi_render_view
         does) OR intrinsics_inv (same shapes, used as given); neither means inverse(intrinsics), both is a ValueError.
         size = (h, w), shared by every view, default (H, W); the target camera is in pixels of that size.  At size (H, W)
-        with the same intrinsics_inv, rgb[:, v] is bit-identical to mpi_render_view with tgt_pose[:, v]."""
+        with the same intrinsics_inv, rgb[:, v] is bit-identical to mpi_render_view with tgt_pose[:, v].
+        rgba_layers may be a SparseLayers made with border='edge' (sparsify_layers; msi_mpi_render_views_sparse): every output
+        element compares == to the render of the PackedLayers it was made from (a zero may differ in sign), provided colours
+        are finite where alpha is zero; planes=None takes the planes it carries.  A border='wrap' stack is refused (TypeError)."""
         if not (want_rgb or want_depth):
             raise ValueError("mpi_render_views: want_rgb and want_depth are both False")
         if tgt_intrinsics is not None and intrinsics_inv is not None:
             raise ValueError("mpi_render_views: pass tgt_intrinsics or intrinsics_inv, not both")
         if intrinsics is None:
             raise ValueError("mpi_render_views: intrinsics (the stack's camera) is required")
-        native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "mpi_render_views")
-        b, d, h, w, _ = native.shape
+        sparse, planes = self._sparse_arg(rgba_layers, planes, "mpi_render_views", 'edge')
+        if sparse is not None:
+            (b, h, w, d), fmt = sparse.shape, self.LAYER_FORMATS[sparse.format]
+        else:
+            native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "mpi_render_views")
+            b, d, h, w, _ = native.shape
         pose, _, v = self._view_poses("tgt_pose", tgt_pose, None, b)
         pose = pose.contiguous()
         intr = self._f32(intrinsics).reshape(-1, 3, 3)
@@ -1122,9 +1146,13 @@ class MSI(object):
         depths = self._depths(planes, d)
         oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
-        N.check(N.lib.msi_mpi_render_views(native.data_ptr(), fmt, pose.data_ptr(), intr.data_ptr(), k_inv.data_ptr(),
-                                           depths.data_ptr(), b, v, h, w, d, oh, ow, _ptr(rgb), _ptr(dep), self._stream()),
-                "msi_mpi_render_views")
+        tail = (pose.data_ptr(), intr.data_ptr(), k_inv.data_ptr(), depths.data_ptr(), b, v, h, w, d, oh, ow, _ptr(rgb), _ptr(dep),
+                self._stream())
+        if sparse is not None:
+            N.check(N.lib.msi_mpi_render_views_sparse(sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(),
+                                                      fmt, *tail), "msi_mpi_render_views_sparse")
+        else:
+            N.check(N.lib.msi_mpi_render_views(native.data_ptr(), fmt, *tail), "msi_mpi_render_views")
         return rgb, dep
 
     # ------------------------------------------------------------------ cube-map viewer of the PP path (cubemap.py has the conventions)
@@ -1173,15 +1201,25 @@ class MSI(object):
         swapping x and z, so the centre of an equirect output looks at the centre of face 0 and one set of arguments renders
         an MSI and a cube stack of one scene.  size = (h, w) is required for both cameras.
         Host-side poses and positions are checked before the launch (ValueError when an origin is not strictly inside the
-        innermost shell: max |o_k| >= min planes); device-side ones are flagged through render_status()."""
+        innermost shell: max |o_k| >= min planes); device-side ones are flagged through render_status().
+        rgba_layers may be a SparseLayers of the faces made with border='edge' (sparsify_layers of the [6B,S,S,D,4] stack;
+        msi_cube_render_views_sparse; whole tiles make S % 16 == 0, sparsify_layers refuses other sizes): every output element compares == to the render of the
+        PackedLayers it was made from (a zero may differ in sign), provided colours are finite where alpha is zero, and the
+        status word is the same; planes=None takes the planes it carries.  A border='wrap' stack is refused (TypeError)."""
         from . import cubemap
         if camera not in ('equirect', 'pinhole'):
             raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
         if not (want_rgb or want_depth):
             raise ValueError("cube_render_views: want_rgb and want_depth are both False")
-        native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "cube_render_views")
+        sparse, planes = self._sparse_arg(rgba_layers, planes, "cube_render_views", 'edge')
+        if sparse is not None:
+            (faces, sh, sw, sd), fmt = sparse.shape, self.LAYER_FORMATS[sparse.format]
+            native_shape = (faces, sd, sh, sw, 4)          # (square faces of whole tiles: S % 16 == 0)
+        else:
+            native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "cube_render_views")
+            native_shape = native.shape
         shape = lambda t: tuple(t.shape) if hasattr(t, "shape") else tuple(np.asarray(t).shape)
-        b, v, s, d, oh, ow = cubemap.cube_view_shapes(native.shape, shape(tgt_pose_rt), shape(tgt_pos), size)
+        b, v, s, d, oh, ow = cubemap.cube_view_shapes(native_shape, shape(tgt_pose_rt), shape(tgt_pos), size)
         if not any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, tgt_pose_rt, planes)):
             cubemap.check_origin_inside(np.asarray(torch.as_tensor(tgt_pos)), np.asarray(torch.as_tensor(tgt_pose_rt)),
                                         np.asarray(torch.as_tensor(planes)))
@@ -1201,9 +1239,13 @@ class MSI(object):
                 raise ValueError("camera='pinhole' needs intrinsics")
             intr = self._pinhole_intrinsics(intrinsics, b, v)
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
-        N.check(N.lib.msi_cube_render_views(native.data_ptr(), fmt, pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(),
-                                            depths.data_ptr(), _ptr(trig), b, v, s, d, self.CAMERAS[camera], oh, ow, _ptr(rgb),
-                                            _ptr(dep), self._render_status.data_ptr(), self._stream()), "msi_cube_render_views")
+        tail = (pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(), depths.data_ptr(), _ptr(trig), b, v, s, d,
+                self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream())
+        if sparse is not None:
+            N.check(N.lib.msi_cube_render_views_sparse(sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(),
+                                                       fmt, *tail), "msi_cube_render_views_sparse")
+        else:
+            N.check(N.lib.msi_cube_render_views(native.data_ptr(), fmt, *tail), "msi_cube_render_views")
         return rgb, dep
 
     def infer_cube(self, raw_src_equirect, raw_ref_equirect, src_pose, face_size, planes, face_intrinsics=None,

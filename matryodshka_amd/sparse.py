@@ -21,6 +21,10 @@ The rule (include/msi_hip.h states it for the C ABI):
   table        int32 [B,D,H/4,W/16]: the tile's index among the kept tiles of its own layer (b, d), row-major, or -1.
   layer_start  int64 [B*D+1]: exclusive prefix sum of the kept tiles per layer; layer_start[-1] = T.
   pool         [T,4,16,4] codes (uint8 / float16); tile k of layer (b, d) is pool[layer_start[b*D+d] + k].
+  border       which surface the stack was made for.  'wrap' is the rule above, for the sphere renders.  'edge' is for samplers that never
+               read the opposite border -- the planar viewer zero-pads, the cube viewer clamps to the edge of the face --: the same rule
+               with the 6 x 18 window CLIPPED to the image instead of wrapped.  An edge stack keeps a subset of the wrap stack's tiles;
+               a sphere render of it would be wrong, so the viewers accept only the rule they were made for.
 """
 import numpy as np
 import torch
@@ -28,7 +32,14 @@ import torch
 from .packed import FORMATS, PackedLayers, _NP_DTYPE, _TORCH_DTYPE, _check_format
 
 TILE_H, TILE_W = 4, 16
-LAYOUT_VERSION = 1            # of the .npz written by SparseLayers.save
+LAYOUT_VERSION = 1            # of the .npz written by SparseLayers.save for a 'wrap' stack
+EDGE_LAYOUT_VERSION = 2       # ... for an 'edge' stack: version 1 plus a `border` key (a reader written for 1 refuses it)
+BORDERS = ('wrap', 'edge')
+
+
+def _check_border(border):
+    if border not in BORDERS:
+        raise ValueError("border must be one of %s, not %r" % (BORDERS, border))
 
 
 def _check_tiles(h, w):
@@ -51,24 +62,38 @@ def _tiles(q):
     return q.reshape(b, d, h // TILE_H, TILE_H, w // TILE_W, TILE_W, 4).transpose(0, 1, 2, 4, 3, 5, 6)
 
 
-def keep_np(codes, format):
+def _shift_clipped(a, dy, dx):
+    """`a` [B,D,H,W] moved by (dy, dx) along (H, W), False moved in: np.roll without the wrap."""
+    out = np.zeros_like(a)
+    h, w = a.shape[2], a.shape[3]
+    ys, yd = (slice(0, h - dy), slice(dy, h)) if dy >= 0 else (slice(-dy, h), slice(0, h + dy))
+    xs, xd = (slice(0, w - dx), slice(dx, w)) if dx >= 0 else (slice(-dx, w), slice(0, w + dx))
+    out[:, :, yd, xd] = a[:, :, ys, xs]
+    return out
+
+
+def keep_np(codes, format, border='wrap'):
     """bool [B,D,H/4,W/16]: the keep rule."""
+    _check_border(border)
     q = _codes(codes, format)
     b, d, h, w, _ = q.shape
     occupied = q[..., 3] != 0                                       # (-0.0 != 0 is False: both zeros of a half are empty)
     near = np.zeros_like(occupied)
     for dy in (-1, 0, 1):
         for dx in (-1, 0, 1):
-            near |= np.roll(occupied, (dy, dx), axis=(2, 3))        # the torus: both axes wrap
+            if border == 'wrap':
+                near |= np.roll(occupied, (dy, dx), axis=(2, 3))    # the torus: both axes wrap
+            else:
+                near |= _shift_clipped(occupied, dy, dx)            # the window is clipped to the image
     keep = near.reshape(b, d, h // TILE_H, TILE_H, w // TILE_W, TILE_W).any(axis=(3, 5))
     keep[:, 0] = True
     return keep
 
 
-def sparsify_np(codes, format):
+def sparsify_np(codes, format, border='wrap'):
     """codes [B,D,H,W,4] (uint8 / float16) -> (table int32 [B,D,H/4,W/16], layer_start int64 [B*D+1], pool [T,4,16,4])."""
     q = _codes(codes, format)
-    keep = keep_np(q, format)
+    keep = keep_np(q, format, border)
     b, d, ty, tx = keep.shape
     flat = keep.reshape(b * d, ty * tx)
     table = np.where(flat, np.cumsum(flat, axis=1) - 1, -1).astype(np.int32).reshape(b, d, ty, tx)
@@ -110,6 +135,8 @@ class SparseLayers(object):
     format       'rgba8' | 'rgba16f'
     shape        (B, H, W, D): the [B,H,W,D,4] stack it stands for
     planes       the sphere radii the stack was made for (tuple of floats, far -> near), or None
+    border       'wrap' (a sphere stack: render_views, render_ods_pair) | 'edge' (a planar or cube-face stack: mpi_render_views,
+                 cube_render_views)
     tile         (4, 16)
     table        torch int32 [B,D,H/4,W/16]
     layer_start  torch int64 [B*D+1]
@@ -117,8 +144,9 @@ class SparseLayers(object):
     nbytes       bytes of the three arrays
     occupancy    T / number of tiles"""
 
-    def __init__(self, table, layer_start, pool, format, planes=None, tile=(TILE_H, TILE_W)):
+    def __init__(self, table, layer_start, pool, format, planes=None, tile=(TILE_H, TILE_W), border='wrap'):
         _check_format(format)
+        _check_border(border)
         if tuple(int(t) for t in tile) != (TILE_H, TILE_W):
             raise ValueError("tile must be %r, not %r" % ((TILE_H, TILE_W), tuple(tile)))
         as_tensor = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
@@ -139,6 +167,7 @@ class SparseLayers(object):
             raise ValueError("table, layer_start and pool do not belong together")
         self.table, self.layer_start, self.pool = table.contiguous(), layer_start.contiguous(), pool.contiguous()
         self.format = format
+        self.border = border
         self.tile = (TILE_H, TILE_W)
         if planes is not None:
             if torch.is_tensor(planes):
@@ -149,12 +178,12 @@ class SparseLayers(object):
         self.planes = planes
 
     @classmethod
-    def from_codes(cls, codes, format, planes=None):
+    def from_codes(cls, codes, format, planes=None, border='wrap'):
         """The numpy rule on host-side codes [B,D,H,W,4] (or a host-side PackedLayers)."""
         if isinstance(codes, PackedLayers):
             codes, format, planes = codes.data.cpu().numpy(), codes.format, codes.planes if planes is None else planes
-        table, layer_start, pool = sparsify_np(codes, format)
-        return cls(table, layer_start, pool, format, planes)
+        table, layer_start, pool = sparsify_np(codes, format, border)
+        return cls(table, layer_start, pool, format, planes, border=border)
 
     @property
     def shape(self):
@@ -170,20 +199,23 @@ class SparseLayers(object):
         return self.pool.shape[0] / float(max(self.table.numel(), 1))
 
     def to(self, device):
-        return SparseLayers(self.table.to(device), self.layer_start.to(device), self.pool.to(device), self.format, self.planes)
+        return SparseLayers(self.table.to(device), self.layer_start.to(device), self.pool.to(device), self.format, self.planes,
+                            border=self.border)
 
     def expand_np(self):
         """The dense codes [B,D,H,W,4] (numpy), dropped tiles zeroed."""
         return expand_np(self.table.cpu().numpy(), self.layer_start.cpu().numpy(), self.pool.cpu().numpy(), self.format)
 
     def save(self, path):
-        """One .npz (no pickle): table, layer_start, pool, format, tile, planes, layout_version."""
+        """One .npz (no pickle): table, layer_start, pool, format, tile, planes, layout_version -- version 1 for a 'wrap' stack; an 'edge'
+        stack is version 2 with a `border` key, so that a reader written for version 1 refuses it instead of rendering it on a sphere."""
         planes = np.zeros(0, np.float64) if self.planes is None else np.asarray(self.planes, np.float64)
+        edge = dict(border=np.array(self.border)) if self.border == 'edge' else {}
         with open(path, "wb") as f:
-            np.savez(f, sparse_layout_version=np.int64(LAYOUT_VERSION), format=np.array(self.format),
+            np.savez(f, sparse_layout_version=np.int64(EDGE_LAYOUT_VERSION if edge else LAYOUT_VERSION), format=np.array(self.format),
                      tile_h=np.int64(TILE_H), tile_w=np.int64(TILE_W), table=self.table.cpu().numpy(),
                      layer_start=self.layer_start.cpu().numpy(), pool=self.pool.cpu().numpy(),
-                     has_planes=np.bool_(self.planes is not None), planes=planes)
+                     has_planes=np.bool_(self.planes is not None), planes=planes, **edge)
 
     @classmethod
     def load(cls, path, device=None):
@@ -191,8 +223,14 @@ class SparseLayers(object):
             if "sparse_layout_version" not in z.files:
                 raise ValueError("%s: not a SparseLayers file (no sparse_layout_version)" % path)
             version = int(z["sparse_layout_version"])
-            if version != LAYOUT_VERSION:
-                raise ValueError("%s: sparse layout version %d, this reader is written for %d" % (path, version, LAYOUT_VERSION))
+            if version not in (LAYOUT_VERSION, EDGE_LAYOUT_VERSION):
+                raise ValueError("%s: sparse layout version %d, this reader is written for %d and %d"
+                                 % (path, version, LAYOUT_VERSION, EDGE_LAYOUT_VERSION))
+            border = 'wrap'
+            if version == EDGE_LAYOUT_VERSION:
+                if "border" not in z.files or str(z["border"]) != 'edge':
+                    raise ValueError("%s: a version %d file must say border = 'edge'" % (path, EDGE_LAYOUT_VERSION))
+                border = 'edge'
             format = str(z["format"])
             if format not in FORMATS:
                 raise ValueError("%s: unknown format %r (known: %s)" % (path, format, FORMATS))
@@ -207,5 +245,5 @@ class SparseLayers(object):
             raise ValueError("%s: table / layer_start stored as %s / %s" % (path, table.dtype, layer_start.dtype))
         if not consistent_np(table, layer_start, pool.shape[0]):
             raise ValueError("%s: table, layer_start and pool do not belong together" % path)
-        out = cls(table, layer_start, pool, format, planes)
+        out = cls(table, layer_start, pool, format, planes, border=border)
         return out if device is None else out.to(device)
