@@ -3,7 +3,7 @@
 // their C ABI entry points below.
 #include "geometry_device.h"
 
-// (the tuning macros of hres_layers_kernel, MSI_HRES_GROUP and MSI_HRES_WAVES: geometry_device.h, with the texel that geo_sparse.hip shares)
+// (the tuning macros of hres_layers_kernel, MSI_HRES_GROUP and MSI_HRES_WAVES: geometry_device.h, with the texel that geo_sparse_hres.hip shares)
 
 namespace {
 
@@ -249,7 +249,7 @@ __global__ void resize_bilinear_kernel(const float4 *__restrict__ in, float4 *__
 // NT: bit 0 / bit 1 = non-temporal stores of the fp32 / the packed stack (the host sets a bit when that destination is larger
 // than the 256-MiB Infinity Cache; a template argument, as in pack_layers_kernel).
 // The texel itself -- hres_pixel, hres_corners / hres_lerp, hres_texel, hres_store_packed -- is in geometry_device.h: hres_layers_sparse_kernel
-// (geo_sparse.hip) writes the same texels into a pool of kept tiles.
+// (geo_sparse_hres.hip) writes the same texels into a pool of kept tiles.
 template <int FMT, int WITH_F32, int NT>
 // (waves_per_eu with the maximum at MSI_HRES_WAVES too: with the texel in shared device functions the allocator settles at 93-95 VGPRs, which
 // would run five waves, and at five the launch is 5 % slower at 1280x640 -- same-process A/B in profiles/hres_sparse_isa.txt)

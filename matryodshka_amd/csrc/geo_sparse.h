@@ -1,0 +1,59 @@
+// Shared by the three units of the sparse layer stacks -- a packed [B,D,H,W] stack (rgba8 / rgba16f) that stores only the 4 x 16 tiles a render can
+// see: a table [B,D,H/4,W/16] of indices into a pool of kept tiles, and layer_start [B D + 1], each layer's first tile:
+//   geo_sparse.hip        the format: the keep rule (both borders), the scan, the copies between a dense stack and a pool
+//   geo_sparse_hres.hip   the high-res stack built sparse: hres_keep_kernel, hres_layers_sparse_kernel
+//   geo_sparse_views.hip  the viewers reading such a stack: render_views_sparse_kernel, mpi_render_views_sparse_kernel, cube_render_views_sparse_kernel
+// Here: ONLY what more than one of them uses.  The format and the keep rule are stated in msi_hip.h and, in numpy, in matryodshka_amd/sparse.py.
+#pragma once
+#include "geometry_device.h"
+
+namespace {
+
+constexpr int TILE_H = 4, TILE_W = 16;             // texels; a tile row is one 64-byte (rgba8) / 128-byte (rgba16f) run
+constexpr int TILE_TEXELS = TILE_H * TILE_W;
+
+// ---- the keep rule's test (format, hres) ----------------------------------------------------------------------------------------
+// "alpha decodes to zero" on the raw codes: rgba8 alpha is the top byte of the texel's word; an rgba16f alpha is the top half of the texel's second
+// word, and +0 / -0 both decode to zero (a NaN or a denormal does not).  nonzero-result <=> some texel is NOT empty.
+template <int FMT> constexpr unsigned ALPHA_MASK = FMT == MSI_LAYERS_RGBA8 ? 0xff000000u : 0x7fff0000u;   // of the texel's word that holds alpha
+// the same bits of the code an alpha WOULD be stored as: the encoder of msi_common.h itself on a texel whose only live channel is alpha (the
+// compiler drops the colours), so a NaN, a negative, a > 1, a denormal-half or a -0.0 alpha lands where the stored code puts it
+template <int FMT> __device__ __forceinline__ unsigned alpha_bits_of(float alpha) {
+  const float4 t = make_float4(0.0f, 0.0f, 0.0f, alpha);
+  if constexpr (FMT == MSI_LAYERS_RGBA8) return rgba8_encode(t) & ALPHA_MASK<FMT>;
+  else return rgba16f_encode(t).y & ALPHA_MASK<FMT>;
+}
+
+// ---- buffer resources (hres, views) -----------------------------------------------------------------------------------------------
+constexpr unsigned NO_TEXEL = 0x80000000u;       // a byte offset past any image or resource here (each is below 2^31 bytes): a load of it reads zeros
+
+// `bytes` of a table (rows of the tile table, entries of layer_start) from `first`
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_rsrc(const void *first, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(first), 0, bytes, 0x00020000);
+}
+// `tiles` kept tiles from tile `first` of the pool (a layer's: a texel offset idx * 64 + (y & 3) * 16 + (x & 15) stays below H * W < 2^24 whatever
+// the pool's size, and an offset past the layer's tiles reads zeros instead of another layer)
+template <int FMT> __device__ __forceinline__ __amdgpu_buffer_rsrc_t pool_rsrc(const char *pool, long long first, long long tiles) {
+  constexpr int SH = StackTexel<FMT>::shift;
+  const long long bytes = tiles * (long long)(TILE_TEXELS << SH);
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(pool + (((size_t)first * TILE_TEXELS) << SH)), 0, (int)(bytes < 0x7fffffffLL ? bytes : 0x7fffffffLL),
+                                           0x00020000);
+}
+
+// ---- host helpers ---------------------------------------------------------------------------------------------------------------
+constexpr unsigned SPARSE_FORMATS = 1u << MSI_LAYERS_RGBA8 | 1u << MSI_LAYERS_RGBA16F;
+constexpr const char *SPARSE_FORMATS_NOTE = " (a sparse stack is rgba8 or rgba16f)";
+
+inline int whole_tiles(const char *who, int height, int width) {
+  if (height % TILE_H == 0 && width % TILE_W == 0) return MSI_OK;
+  return msi::fail(MSI_E_UNSUPPORTED, "%s: a sparse stack needs H %% %d == 0 and W %% %d == 0 (got %d x %d)", who, TILE_H, TILE_W, height, width);
+}
+
+inline const long long *tile_starts(const int64_t *layer_start) { return reinterpret_cast<const long long *>(layer_start); }   // (the kernels' type)
+
+}  // namespace
+
+// Defined in geo_sparse.hip.  sparse_dims: the checks every tile entry point makes; *tiles = B * D * (H / 4) * (W / 16).  scan_tiles: the second
+// launch of every index entry point, 0 / 1 flags -> indices and counts.
+extern int sparse_dims(const char *who, int32_t format, int32_t batch, int32_t num_planes, int32_t height, int32_t width, size_t *tiles);
+extern int scan_tiles(const char *who, int32_t *table, int32_t *counts, int32_t batch, int32_t num_planes, int32_t height, int32_t width, hipStream_t s);

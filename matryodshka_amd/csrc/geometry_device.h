@@ -4,8 +4,9 @@
 //   geo_layers.hip  K3 RGBA assembly, bilinear resize, the fused high-res layer stack, pack / unpack of the compact stacks
 //   geo_render.hip  K4 fused reprojection + wrap-around bilinear gather + over-composite: render_kernel, render_views_kernel and its packed form
 //   geo_ods.hip     K4 with the ODS stereo camera: render_ods_views_kernel (both eyes of a stack per launch, fp32 or packed stacks)
-//   geo_sparse.hip  K4 from a sparse stack: the tile index / gather / expand kernels and render_views_sparse_kernel (the cameras of render and ods);
-//                   the high-res stack built sparse (hres_keep_kernel, hres_layers_sparse_kernel)
+//   geo_sparse.hip  the sparse layer stacks' format: the tile index (both keep rules) / gather / expand kernels.  geo_sparse.h: what the three sparse units share
+//   geo_sparse_hres.hip   the high-res stack built sparse (hres_keep_kernel, hres_layers_sparse_kernel)
+//   geo_sparse_views.hip  K4 from a sparse stack: render_views_sparse_kernel (the cameras of render and ods); the planar and cube renders from one
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
@@ -674,7 +675,7 @@ __device__ __forceinline__ void store_pixel(float *out_rgb, float *out_depth, si
 // of dependent-latency gathers per thread.  The ray/sphere quadratic's a and b do not depend on the layer, so per layer only sqrt, one divide
 // and the two angles remain; every texel of the D x H x W x 4 stack is fetched from HBM once.
 // The many-views kernels of the three units are ONE body, render_views_body below, for view_ray's three cameras and a stack in any texel format;
-// render_views_sparse_kernel (geo_sparse.hip) runs the same pieces around its own layer loop.  render_kernel keeps its three ray models, its
+// render_views_sparse_kernel (geo_sparse_views.hip) runs the same pieces around its own layer loop.  render_kernel keeps its three ray models, its
 // stores and its own text of the gathers and the over step (as pieces they change some of its instantiations: profiles/shared_render_pieces_isa.txt).
 constexpr int RENDER_SEGS = 4;   // layer segments per pixel (threads in y)
 

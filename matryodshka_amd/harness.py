@@ -372,6 +372,15 @@ def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, d
     return rgb, dep
 
 
+def write_occupancy_log(path, msi_format, samples, what):
+    """The occupancy log of a sparse run (sparse.json, pp_sparse.json, hres_sparse.json: one set of keys)."""
+    from .sparse import TILE_H, TILE_W
+    with open(path, "w") as f:
+        json.dump(dict(format=msi_format, tile=[TILE_H, TILE_W], samples=samples,
+                       mean_occupancy=float(np.mean([e["occupancy"] for e in samples])) if samples else None), f)
+    print("%s written to %s" % (what, path))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cameras_glob", default="glob/test/ods/*.txt")
@@ -549,24 +558,10 @@ def main(argv=None):
             run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname, msi_format=args.msi_format,
                             hres_sparse_log=hres_sparse_log)
             n += "high_res_only" in args.test_type
-    if hres_sparse_log is not None:
-        from .sparse import TILE_H, TILE_W
-        with open(os.path.join(exp_dir, "hres_sparse.json"), "w") as f:
-            json.dump(dict(format=args.msi_format, tile=[TILE_H, TILE_W], samples=hres_sparse_log,
-                           mean_occupancy=float(np.mean([e["occupancy"] for e in hres_sparse_log])) if hres_sparse_log else None), f)
-        print("High-res occupancies written to %s" % os.path.join(exp_dir, "hres_sparse.json"))
-    if pp_sparse_log is not None:
-        from .sparse import TILE_H, TILE_W
-        with open(os.path.join(exp_dir, "pp_sparse.json"), "w") as f:
-            json.dump(dict(format=args.msi_format, tile=[TILE_H, TILE_W], samples=pp_sparse_log,
-                           mean_occupancy=float(np.mean([e["occupancy"] for e in pp_sparse_log])) if pp_sparse_log else None), f)
-        print("PP occupancies written to %s" % os.path.join(exp_dir, "pp_sparse.json"))
-    if sparse_log is not None:
-        from .sparse import TILE_H, TILE_W
-        with open(os.path.join(exp_dir, "sparse.json"), "w") as f:
-            json.dump(dict(format=args.msi_format, tile=[TILE_H, TILE_W], samples=sparse_log,
-                           mean_occupancy=float(np.mean([e["occupancy"] for e in sparse_log])) if sparse_log else None), f)
-        print("Occupancies written to %s" % os.path.join(exp_dir, "sparse.json"))
+    for log, name, what in ((hres_sparse_log, "hres_sparse.json", "High-res occupancies"), (pp_sparse_log, "pp_sparse.json", "PP occupancies"),
+                            (sparse_log, "sparse.json", "Occupancies")):
+        if log is not None:
+            write_occupancy_log(os.path.join(exp_dir, name), args.msi_format, log, what)
     if scorer is not None:
         with open(os.path.join(exp_dir, "scores.json"), "w") as f:
             json.dump(scorer.table(), f)

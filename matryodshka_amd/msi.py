@@ -630,9 +630,24 @@ class MSI(object):
     # ('ods' is not a camera code of the native library: it has its own entry point, msi_render_ods_views)
     CAMERAS = {'equirect': N.MSI_CAMERA_EQUIRECT, 'pinhole': N.MSI_CAMERA_PINHOLE, 'ods': None}
 
-    def _stack_args(self, rgba_layers, planes, who):
-        """A stack [B,H,W,D,4] or a PackedLayers -> (native stack on this device, the PackedLayers or None, planes, native format
-        code); planes=None takes the planes a PackedLayers carries."""
+    def _view_stack(self, rgba_layers, planes, who, border):
+        """What a viewer's launch takes from its stack -- a stack [B,H,W,D,4], a PackedLayers or a SparseLayers made with the keep
+        rule `border` -> (the entry point's leading arguments: (pool, table, layer_start, format) or (layers, format); the suffix
+        of its name: '_sparse', '_packed' or '_f32'; (b, d, h, w); planes; the stack on this device, which the caller holds until
+        the launch).  planes=None takes the planes a PackedLayers or SparseLayers carries.  A sparse stack made for the other kind
+        of surface is refused: an edge-rule stack misses tiles a sphere render reads across the border, and a sphere stack in a
+        planar viewer is almost always a mistake."""
+        if isinstance(rgba_layers, SparseLayers):
+            if rgba_layers.border != border:
+                raise TypeError("%s reads SparseLayers made with border=%r, not %r: expand this one with densify_layers and "
+                                "sparsify_layers(..., border=%r) the result" % (who, border, rgba_layers.border, border))
+            sparse = rgba_layers if rgba_layers.pool.device == self.device else rgba_layers.to(self.device)
+            planes = sparse.planes if planes is None else planes
+            if planes is None:
+                raise ValueError("%s: planes is required (this SparseLayers carries none)" % who)
+            b, h, w, d = sparse.shape
+            lead = (sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(), self.LAYER_FORMATS[sparse.format])
+            return lead, "_sparse", (b, d, h, w), planes, sparse
         packed = rgba_layers if isinstance(rgba_layers, PackedLayers) else None
         if packed is not None:
             native = packed.data if packed.data.device == self.device else packed.data.to(self.device)
@@ -642,22 +657,8 @@ class MSI(object):
             native = self._native_layers(rgba_layers)
         if planes is None:
             raise ValueError("%s: planes is required (only a PackedLayers that carries its planes may leave it out)" % who)
-        return native, packed, planes, self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
-
-    def _sparse_arg(self, rgba_layers, planes, who, border):
-        """A SparseLayers made with the keep rule `border` -> (the stack on this device, planes); None when rgba_layers is no
-        SparseLayers.  A stack made for the other kind of surface is refused: an edge-rule stack misses tiles a sphere render
-        reads across the border, and a sphere stack in a planar viewer is almost always a mistake."""
-        if not isinstance(rgba_layers, SparseLayers):
-            return None, planes
-        if rgba_layers.border != border:
-            raise TypeError("%s reads SparseLayers made with border=%r, not %r: expand this one with densify_layers and "
-                            "sparsify_layers(..., border=%r) the result" % (who, border, rgba_layers.border, border))
-        sparse = rgba_layers if rgba_layers.pool.device == self.device else rgba_layers.to(self.device)
-        planes = sparse.planes if planes is None else planes
-        if planes is None:
-            raise ValueError("%s: planes is required (this SparseLayers carries none)" % who)
-        return sparse, planes
+        fmt = self.LAYER_FORMATS[packed.format] if packed is not None else N.MSI_LAYERS_F32
+        return (native.data_ptr(), fmt), "_packed" if packed is not None else "_f32", tuple(native.shape[:4]), planes, native
 
     def _view_poses(self, name, tgt_pose, tgt_pos, b):
         """Per-view poses [B,V,4,4] and, where the camera has them, positions [B,V,3] ([V,4,4] / [V,3] when B = 1) -> fp32
@@ -730,12 +731,7 @@ class MSI(object):
             raise ValueError("render_views: camera='ods' needs eye (+1 / 'left' or -1 / 'right', or an array [V] / [B,V])")
         if not (want_rgb or want_depth):
             raise ValueError("render_views: want_rgb and want_depth are both False")
-        sparse, planes = self._sparse_arg(rgba_layers, planes, "render_views", 'wrap')
-        if sparse is not None:
-            (b, h, w, d), fmt = sparse.shape, self.LAYER_FORMATS[sparse.format]
-        else:
-            native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "render_views")
-            b, d, h, w, _ = native.shape
+        lead, suffix, (b, d, h, w), planes, _keep = self._view_stack(rgba_layers, planes, "render_views", 'wrap')   # (_keep: alive until the launch)
         if camera != 'ods':
             self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
         pose, pos, v = self._view_poses("tgt_pose_rt", tgt_pose_rt, tgt_pos, b)
@@ -759,19 +755,15 @@ class MSI(object):
         views = (pose.data_ptr(), pos.data_ptr())
         shape, code = (b, v, h, w, d), (self.CAMERAS[camera],)
         out = (oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream())
-        if sparse is not None:
-            name = "msi_render_views_sparse"
-            args = (sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(), fmt) + views \
-                + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
+        name = "msi_render_views" + suffix
+        if suffix == "_sparse":
+            args = lead + views + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape \
+                + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
         elif camera == 'ods':
             name = "msi_render_ods_views"
-            args = (native.data_ptr(), fmt) + views + (radius.data_ptr(), depths.data_ptr(), trig.data_ptr()) + shape
-        elif packed is not None:
-            name = "msi_render_views_packed"
-            args = (native.data_ptr(), fmt) + views + (_ptr(intr), depths.data_ptr(), _ptr(trig)) + shape + code
-        else:
-            name = "msi_render_views_f32"
-            args = (native.data_ptr(),) + views + (_ptr(intr), depths.data_ptr(), _ptr(trig)) + shape + code
+            args = lead + views + (radius.data_ptr(), depths.data_ptr(), trig.data_ptr()) + shape
+        else:                                     # (msi_render_views_f32 takes no format code)
+            args = lead[:1 if suffix == "_f32" else 2] + views + (_ptr(intr), depths.data_ptr(), _ptr(trig)) + shape + code
         N.check(getattr(N.lib, name)(*(args + out)), name)
         return rgb, dep
 
@@ -1123,12 +1115,7 @@ class MSI(object):
             raise ValueError("mpi_render_views: pass tgt_intrinsics or intrinsics_inv, not both")
         if intrinsics is None:
             raise ValueError("mpi_render_views: intrinsics (the stack's camera) is required")
-        sparse, planes = self._sparse_arg(rgba_layers, planes, "mpi_render_views", 'edge')
-        if sparse is not None:
-            (b, h, w, d), fmt = sparse.shape, self.LAYER_FORMATS[sparse.format]
-        else:
-            native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "mpi_render_views")
-            b, d, h, w, _ = native.shape
+        lead, suffix, (b, d, h, w), planes, _keep = self._view_stack(rgba_layers, planes, "mpi_render_views", 'edge')
         pose, _, v = self._view_poses("tgt_pose", tgt_pose, None, b)
         pose = pose.contiguous()
         intr = self._f32(intrinsics).reshape(-1, 3, 3)
@@ -1148,11 +1135,8 @@ class MSI(object):
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
         tail = (pose.data_ptr(), intr.data_ptr(), k_inv.data_ptr(), depths.data_ptr(), b, v, h, w, d, oh, ow, _ptr(rgb), _ptr(dep),
                 self._stream())
-        if sparse is not None:
-            N.check(N.lib.msi_mpi_render_views_sparse(sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(),
-                                                      fmt, *tail), "msi_mpi_render_views_sparse")
-        else:
-            N.check(N.lib.msi_mpi_render_views(native.data_ptr(), fmt, *tail), "msi_mpi_render_views")
+        name = "msi_mpi_render_views" + (suffix if suffix == "_sparse" else "")
+        N.check(getattr(N.lib, name)(*(lead + tail)), name)
         return rgb, dep
 
     # ------------------------------------------------------------------ cube-map viewer of the PP path (cubemap.py has the conventions)
@@ -1211,15 +1195,9 @@ class MSI(object):
             raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
         if not (want_rgb or want_depth):
             raise ValueError("cube_render_views: want_rgb and want_depth are both False")
-        sparse, planes = self._sparse_arg(rgba_layers, planes, "cube_render_views", 'edge')
-        if sparse is not None:
-            (faces, sh, sw, sd), fmt = sparse.shape, self.LAYER_FORMATS[sparse.format]
-            native_shape = (faces, sd, sh, sw, 4)          # (square faces of whole tiles: S % 16 == 0)
-        else:
-            native, packed, planes, fmt = self._stack_args(rgba_layers, planes, "cube_render_views")
-            native_shape = native.shape
+        lead, suffix, native_shape, planes, _keep = self._view_stack(rgba_layers, planes, "cube_render_views", 'edge')
         shape = lambda t: tuple(t.shape) if hasattr(t, "shape") else tuple(np.asarray(t).shape)
-        b, v, s, d, oh, ow = cubemap.cube_view_shapes(native_shape, shape(tgt_pose_rt), shape(tgt_pos), size)
+        b, v, s, d, oh, ow = cubemap.cube_view_shapes(native_shape + (4,), shape(tgt_pose_rt), shape(tgt_pos), size)
         if not any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, tgt_pose_rt, planes)):
             cubemap.check_origin_inside(np.asarray(torch.as_tensor(tgt_pos)), np.asarray(torch.as_tensor(tgt_pose_rt)),
                                         np.asarray(torch.as_tensor(planes)))
@@ -1241,11 +1219,8 @@ class MSI(object):
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
         tail = (pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(), depths.data_ptr(), _ptr(trig), b, v, s, d,
                 self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream())
-        if sparse is not None:
-            N.check(N.lib.msi_cube_render_views_sparse(sparse.pool.data_ptr(), sparse.table.data_ptr(), sparse.layer_start.data_ptr(),
-                                                       fmt, *tail), "msi_cube_render_views_sparse")
-        else:
-            N.check(N.lib.msi_cube_render_views(native.data_ptr(), fmt, *tail), "msi_cube_render_views")
+        name = "msi_cube_render_views" + (suffix if suffix == "_sparse" else "")
+        N.check(getattr(N.lib, name)(*(lead + tail)), name)
         return rgb, dep
 
     def infer_cube(self, raw_src_equirect, raw_ref_equirect, src_pose, face_size, planes, face_intrinsics=None,

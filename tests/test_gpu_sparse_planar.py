@@ -19,6 +19,7 @@ BITS = {'rgba8': np.uint8, 'rgba16f': np.uint16}
 B, V, D = 2, 2, 4
 STACKS = [(8, 32), (12, 48)]                       # 2 x 2 and 3 x 3 tiles
 MODES = [(True, True), (True, False), (False, True)]
+ODD_D = 5                                          # an odd layer count: the planar render's last group of two runs past the end
 CUBE_D = 3
 CUBE_PLANES = [50.0, 5.0, 1.0]
 
@@ -59,14 +60,18 @@ def _colours(seed, shape):
 
 # ------------------------------------------------------------------------------------------------ the planar stacks
 @functools.lru_cache(maxsize=None)
-def planar_stack(h, w):
-    """fp32 [B,H,W,D,4], read-only: layer 0 all alpha 0 (its colour counts anyway), layer 1 empty (no kept tile), layer 2 a 2 x 6 block in a
-    corner of the image (the top-left one in sample 0, the bottom-right one in sample 1: it touches the outer ring), layer 3 full."""
-    x = _colours(900 + h, (B, h, w, D))
-    mask = np.zeros((B, h, w, D), F)
+def planar_stack(h, w, d=D):
+    """fp32 [B,H,W,d,4], read-only: layer 0 all alpha 0 (its colour counts anyway), layer 1 empty (no kept tile), layer 2 a 2 x 6 block in a
+    corner of the image (the top-left one in sample 0, the bottom-right one in sample 1: it touches the outer ring), layer 3 full; with
+    d = ODD_D, layer 4 is layer 2's block in the opposite corner."""
+    x = _colours(900 + h, (B, h, w, d))
+    mask = np.zeros((B, h, w, d), F)
     mask[0, :2, :6, 2] = 1
     mask[1, h - 2:, w - 6:, 2] = 1
     mask[..., 3] = 1
+    if d == ODD_D:
+        mask[0, h - 2:, w - 6:, 4] = 1
+        mask[1, :2, :6, 4] = 1
     x[..., 3] *= mask
     x.setflags(write=False)
     return x
@@ -165,6 +170,9 @@ def test_0_the_masks_drop_and_keep_tiles(fmt):
     h, w = STACKS[0]
     per_layer = S.keep_np(P.encode_np(_native(planar_stack(h, w)), fmt), fmt, 'edge').reshape(B, D, -1).sum(-1)
     assert np.array_equal(per_layer, [[4, 0, 1, 4]] * B)               # whole, empty, one tile, full
+    odd = S.keep_np(P.encode_np(_native(planar_stack(h, w, ODD_D)), fmt), fmt, 'edge')
+    assert np.array_equal(odd.reshape(B, ODD_D, -1).sum(-1), [[4, 0, 1, 4, 1]] * B)      # the fifth layer: one tile kept, three dropped
+    assert not np.array_equal(odd[:, 2], odd[:, 4])                                      # (in the opposite corner)
 
 
 # 1 ---------------------------------------------------------------------------------------------------------------------
@@ -240,6 +248,28 @@ def test_2_planar_render_from_sparse_equals_the_dense_render(gpu, fmt, own_size,
     assert not np.array_equal(_np(m.mpi_render_views(pk, pose, want_depth=False, **kw)[0]), _np(r_bg))   # kept layers matter
     back = m.densify_layers(sp)
     assert torch.equal(m.mpi_render_views(back, pose, **kw)[0], m.mpi_render_views(sp, pose, **kw)[0])
+
+
+@pytest.mark.parametrize("want_rgb,want_depth", MODES)
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_2_planar_render_with_an_odd_layer_count_equals_the_dense_render(gpu, fmt, want_rgb, want_depth):
+    """D = 5 in groups of two layers: the last group's second lookup is past the end (the last layer's again, its step skipped)."""
+    torch, m = gpu
+    h, w = STACKS[0]
+    pk = m.pack_layers(torch.from_numpy(planar_stack(h, w, ODD_D)).cuda(), fmt, planes=_planes(m, ODD_D))
+    sp = m.sparsify_layers(pk, border='edge')
+    assert sp.shape == (B, h, w, ODD_D) and np.array_equal(np.diff(_np(sp.layer_start)).reshape(B, ODD_D), [[4, 0, 1, 4, 1]] * B)
+    kw = dict(intrinsics=_cam(h, w), want_rgb=want_rgb, want_depth=want_depth)
+    for out_s, out_d in zip(m.mpi_render_views(sp, planar_poses(), **kw), m.mpi_render_views(pk, planar_poses(), **kw)):
+        assert (out_s is None) == (out_d is None)
+        if out_s is not None:
+            assert tuple(out_s.shape)[:4] == (B, V, h, w) and np.array_equal(_np(out_s), _np(out_d))
+    # the fifth layer is composited: without it the render differs
+    if want_rgb:
+        four = np.array(planar_stack(h, w, ODD_D))
+        four[..., 4, 3] = 0
+        r4 = m.mpi_render_views(m.pack_layers(torch.from_numpy(four).cuda(), fmt, planes=_planes(m, ODD_D)), planar_poses(), **kw)[0]
+        assert not np.array_equal(_np(r4), _np(m.mpi_render_views(sp, planar_poses(), **kw)[0]))
 
 
 # 3 ---------------------------------------------------------------------------------------------------------------------

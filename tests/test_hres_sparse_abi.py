@@ -64,10 +64,10 @@ def test_the_texel_and_the_tile_are_each_defined_once():
     from matryodshka_amd import build
     texts = {u: open(os.path.join(build.CSRC, u)).read() for u in os.listdir(build.CSRC) if u.endswith((".hip", ".h", ".cpp", ".inc"))}
     for pattern, where in ((r"float4 hres_texel\(", "geometry_device.h"), (r"HresTaps hres_taps\(", "geometry_device.h"),
-                           (r"constexpr int TILE_H = ", "geo_sparse.hip"), (r"\nsparse_scan_kernel\(", "geo_sparse.hip"),
+                           (r"constexpr int TILE_H = ", "geo_sparse.h"), (r"\nsparse_scan_kernel\(", "geo_sparse.hip"),
                            (r"\nint sparse_dims\(", "geo_sparse.hip")):
         assert {u: len(re.findall(pattern, t)) for u, t in texts.items() if re.search(pattern, t)} == {where: 1}, pattern
-    for unit, kernel in (("geo_layers.hip", "hres_layers_kernel"), ("geo_sparse.hip", "hres_layers_sparse_kernel")):
+    for unit, kernel in (("geo_layers.hip", "hres_layers_kernel"), ("geo_sparse_hres.hip", "hres_layers_sparse_kernel")):
         body = texts[unit][texts[unit].index("\n%s(" % kernel):]
         body = body[:body.index("\n}\n")]
         assert re.search(r"hres_texel\(|hres_taps\(", body) and "ods_quad" not in body and "gather3(" not in body, unit

@@ -1,5 +1,5 @@
 """CPU-only checks of the plumbing of the edge-rule sparse stacks: msi_sparse_index_tiles_edge, msi_mpi_render_views_sparse and
-msi_cube_render_views_sparse are exported, bound and declared with one signature (ABI still 9), defined once, in geo_sparse.hip, and
+msi_cube_render_views_sparse are exported, bound and declared with one signature (ABI still 9), defined once, in geo_sparse.hip / geo_sparse_views.hip, and
 their argument checks reject bad calls with the documented code and text before any HIP call.  No kernel is launched here: every
 native call below fails its validation, or has an empty batch, before it could reach a device (the dummy pointers are never
 dereferenced).  The harness's --msi_pp_sparse refusals and its --help need no device either; the TypeError / ValueError paths of the
@@ -50,6 +50,7 @@ def test_the_sparse_forms_take_the_dense_entry_points_arguments(native_lib):
 def test_defined_once_in_geo_sparse():
     from matryodshka_amd import build
     for name in PARAMS:
+        where = "geo_sparse.hip" if name == "msi_sparse_index_tiles_edge" else "geo_sparse_views.hip"
         pattern = re.compile(r"^int\s+%s\(" % name, re.M)
         hits = {}
         for unit in sorted(os.listdir(build.CSRC)):
@@ -58,7 +59,7 @@ def test_defined_once_in_geo_sparse():
                     n = len(pattern.findall(f.read()))
                 if n:
                     hits[unit] = n
-        assert hits == {"geo_sparse.hip": 1}, name
+        assert hits == {where: 1}, name
 
 
 # ------------------------------------------------------------------------------------------------ msi_sparse_index_tiles_edge
