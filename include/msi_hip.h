@@ -67,7 +67,7 @@ const char *msi_version(void);
  *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images; msi_cube_render_views,
  *      msi_equirect_to_cube_f32; msi_sparse_index_tiles, msi_sparse_gather_tiles, msi_sparse_expand, msi_render_views_sparse;
  *      msi_hres_index_tiles, msi_hres_layers_sparse; msi_sparse_index_tiles_edge, msi_mpi_render_views_sparse,
- *      msi_cube_render_views_sparse) */
+ *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -478,6 +478,33 @@ int msi_perspective_sweep_volume_bf16(const float *ref_image, const float *src_i
                                       const float *src_curr_pose, const float *intrinsics, const float *depths,
                                       int32_t batch, int32_t height, int32_t width, int32_t num_depths,
                                       void *psv_bf16, msi_stream_t stream);
+/* The high-res layer stack of the PP path in ONE launch (MSI.mpi_hres_layers): msi_hres_layers for perspective images.  Two
+ * msi_perspective_plane_sweep_f32 of the high-res images (ref = foreground, src = background; poses as
+ * msi_perspective_sweep_volume_bf16, intrinsics [B,3,3] those of the HIGH-RES images), msi_resize_bilinear_f32 of the low-res
+ * blend_weights / alphas [B,h,w,D] and msi_assemble_rgba_scaled_f32, without the [B,Hh,Wh,6D] volume or the upsampled tensor:
+ * rgba_native [B,D,Hh,Wh,4] has the bits of those launches, layers_out those of msi_pack_layers of it.  Parameters, outputs
+ * (either may be NULL, not both), formats, store policy and checks are msi_hres_layers' without `trig`; in addition Hh > 1,
+ * Wh > 1 and Hh * Wh * 12 < 2^31 (MSI_E_BADARG), the sweep's own.  Error texts name pp_hres_layers.  batch = 0 returns MSI_OK
+ * after validation. */
+int msi_pp_hres_layers(const float *ref_image, const float *src_image, const float *ref_curr_pose, const float *src_curr_pose,
+                       const float *intrinsics, const float *depths, const float *blend_weights, const float *alphas, int32_t batch,
+                       int32_t low_height, int32_t low_width, int32_t height, int32_t width, int32_t num_planes, float *rgba_native,
+                       void *layers_out, int32_t format, msi_stream_t stream);
+/* msi_pp_hres_layers' packed stack built sparse for the viewers that never read the opposite border (MSI.mpi_hres_layers_sparse;
+ * msi_mpi_render_views_sparse, msi_cube_render_views_sparse), as msi_hres_index_tiles / msi_hres_layers_sparse build the sphere's:
+ *   msi_hres_index_tiles_edge  msi_hres_index_tiles with msi_sparse_index_tiles_edge's keep rule (a tile's 6 x 18 window clipped
+ *                              to the image): equal to msi_sparse_index_tiles_edge of msi_pp_hres_layers' codes of `format`.
+ *   msi_pp_hres_layers_sparse  msi_hres_layers_sparse without `trig`, with msi_pp_hres_layers' texel: equal to
+ *                              msi_sparse_gather_tiles of msi_pp_hres_layers' stack.
+ * Checks: their siblings', then Hh > 1, Wh > 1 and Hh * Wh * 12 < 2^31 ahead of the tile entry points' checks.  Error texts
+ * name hres_index_tiles_edge / pp_hres_layers_sparse. */
+int msi_hres_index_tiles_edge(const float *alphas, int32_t format, int32_t batch, int32_t low_height, int32_t low_width,
+                              int32_t height, int32_t width, int32_t num_planes,
+                              int32_t *table_out, int32_t *counts_out, msi_stream_t stream);
+int msi_pp_hres_layers_sparse(const float *ref_image, const float *src_image, const float *ref_curr_pose, const float *src_curr_pose,
+                              const float *intrinsics, const float *depths, const float *blend_weights, const float *alphas,
+                              int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width, int32_t num_planes,
+                              const int32_t *table, const int64_t *layer_start, void *pool_out, int32_t format, msi_stream_t stream);
 /* MSI.mpi_render_view (msi.py:527-548): pj.projective_forward_homography (projector.py:343-373) ->
  * homography.planar_transform (homography.py:35-157) -> tf.contrib.resampler (zero padding) ->
  * pj.over_composite.  intrinsics_inv [B,3,3] replaces the hidden graph input `intrinsics_inv:0`

@@ -1,8 +1,9 @@
 // Shared by the three units of the sparse layer stacks -- a packed [B,D,H,W] stack (rgba8 / rgba16f) that stores only the 4 x 16 tiles a render can
 // see: a table [B,D,H/4,W/16] of indices into a pool of kept tiles, and layer_start [B D + 1], each layer's first tile:
 //   geo_sparse.hip        the format: the keep rule (both borders), the scan, the copies between a dense stack and a pool
-//   geo_sparse_hres.hip   the high-res stack built sparse: hres_keep_kernel, hres_layers_sparse_kernel
+//   geo_sparse_hres.hip   the high-res stack built sparse: hres_keep_kernel (both borders), hres_layers_sparse_kernel
 //   geo_sparse_views.hip  the viewers reading such a stack: render_views_sparse_kernel, mpi_render_views_sparse_kernel, cube_render_views_sparse_kernel
+// and by geo_planar_hres.hip, whose pp_hres_layers_sparse_kernel writes the PP high-res stack into such a pool.
 // Here: ONLY what more than one of them uses.  The format and the keep rule are stated in msi_hip.h and, in numpy, in matryodshka_amd/sparse.py.
 #pragma once
 #include "geometry_device.h"
@@ -11,6 +12,11 @@ namespace {
 
 constexpr int TILE_H = 4, TILE_W = 16;             // texels; a tile row is one 64-byte (rgba8) / 128-byte (rgba16f) run
 constexpr int TILE_TEXELS = TILE_H * TILE_W;
+
+// ---- the keep rule's two borders (format: sparse_keep_kernel; hres: hres_keep_kernel) ---------------------------------------------------
+// BORDER_WRAP takes a tile's 6 x 18 window modulo the image (the sphere renders wrap); BORDER_EDGE clips it to the image (the planar render zero-pads
+// and the cube render clamps to the edge of the face: neither reads the opposite border).
+constexpr int BORDER_WRAP = 0, BORDER_EDGE = 1;
 
 // ---- the keep rule's test (format, hres) ----------------------------------------------------------------------------------------
 // "alpha decodes to zero" on the raw codes: rgba8 alpha is the top byte of the texel's word; an rgba16f alpha is the top half of the texel's second

@@ -31,8 +31,7 @@ template <int FMT> __device__ __forceinline__ unsigned alpha_bits1(const char *p
 // One thread per tile: 1 where the tile is kept -- layer 0, or a texel of the tile's 6 x 18 window is not empty --, else 0.  BORDER_WRAP takes the
 // window's x modulo W and y modulo H (the sphere renders wrap); BORDER_EDGE clips it to the image (the planar render zero-pads and the cube render
 // clamps to the edge of the face: neither reads the opposite border).  Adjacent windows overlap by their borders only, so a texel is read ~1.7
-// times, once from HBM.
-constexpr int BORDER_WRAP = 0, BORDER_EDGE = 1;
+// times, once from HBM.  (BORDER_WRAP / BORDER_EDGE: geo_sparse.h, with hres_keep_kernel)
 
 template <int FMT, int BORDER>
 __global__ void __launch_bounds__(256)

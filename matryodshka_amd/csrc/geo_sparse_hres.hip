@@ -1,4 +1,4 @@
-// The high-res stack, built sparse (msi_hres_index_tiles, msi_hres_layers_sparse): the keep rule of geo_sparse.hip from the low-res alphas, and
+// The high-res stack, built sparse (msi_hres_index_tiles / _index_tiles_edge, msi_hres_layers_sparse): the keep rule of geo_sparse.hip from the low-res alphas, and
 // hres_layers_kernel's texel (geo_layers.hip) for kept tiles only.
 // hres_layers_kernel stores o.w = the resized alpha: a texel's alpha -- and with it the keep rule -- is a function of the low-res
 // alphas alone.  So the table comes first, from [B,h,w,D] alphas, and the texels of kept tiles go straight into the pool; the dense stack never exists.
@@ -30,11 +30,14 @@ __device__ __forceinline__ void window_run(int k, int tile_index, int tile, int 
   else { first = 0; last = t0 + tile == n ? 0 : -1; }
 }
 
-template <int FMT>
+// BORDER (geo_sparse.h): BORDER_WRAP is the window above; BORDER_EDGE applies sparse_keep_kernel<..., BORDER_EDGE>'s rule -- the window clipped to the
+// image: run 0 alone in the proof, no wrapped row or column in the walk (the stacks of the planar and cube renders, geo_planar_hres.hip).
+template <int FMT, int BORDER>
 __global__ void __launch_bounds__(256)
 hres_keep_kernel(const float *__restrict__ alphas, int low_h, int low_w, int height, int width, int nd, float sy, float sx, size_t groups,
                  int *__restrict__ table) {
   constexpr unsigned ALL = (1u << HRES_G) - 1u;
+  constexpr int RUNS = BORDER == BORDER_WRAP ? 3 : 1;         // runs of window_run per axis
   const int tx_n = width / TILE_W, ty_n = height / TILE_H;
   const size_t per_layer = (size_t)tx_n * ty_n, dg_n = (size_t)(nd / HRES_G);
   for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
@@ -50,12 +53,12 @@ hres_keep_kernel(const float *__restrict__ alphas, int low_h, int low_w, int hei
     unsigned nan = 0u;
 #pragma unroll
     for (int q = 0; q < HRES_G; ++q) { lo[q] = INFINITY; hi[q] = -INFINITY; }
-    for (int ky = 0; ky < 3; ++ky) {
+    for (int ky = 0; ky < RUNS; ++ky) {
       int ya, yb;
       window_run(ky, ty, TILE_H, height, ya, yb);
       if (yb < ya) continue;
       const int ly0 = hres_axis(ya, sy, low_h).lo, ly1 = hres_axis(yb, sy, low_h).hi;
-      for (int kx = 0; kx < 3; ++kx) {
+      for (int kx = 0; kx < RUNS; ++kx) {
         int xa, xb;
         window_run(kx, tx, TILE_W, width, xa, xb);
         if (xb < xa) continue;
@@ -77,10 +80,12 @@ hres_keep_kernel(const float *__restrict__ alphas, int low_h, int low_w, int hei
 
     for (int r = -1; r <= TILE_H && (found | proven) != ALL; ++r) {
       int y = ty * TILE_H + r;
-      y = y < 0 ? height - 1 : (y >= height ? 0 : y);
+      if constexpr (BORDER == BORDER_WRAP) y = y < 0 ? height - 1 : (y >= height ? 0 : y);
+      else if (y < 0 || y >= height) continue;                 // (clipped: the row outside the image is not in the window)
       for (int c = -1; c <= TILE_W && (found | proven) != ALL; ++c) {
         int x = tx * TILE_W + c;
-        x = x < 0 ? width - 1 : (x >= width ? 0 : x);
+        if constexpr (BORDER == BORDER_WRAP) x = x < 0 ? width - 1 : (x >= width ? 0 : x);
+        else if (x < 0 || x >= width) continue;
         const hres_vec av = hres_lerp(al, hres_corners(y, x, sy, sx, low_h, low_w, nd));
 #pragma unroll
         for (int q = 0; q < HRES_G; ++q) found |= alpha_bits_of<FMT>(av[q]) ? 1u << q : 0u;
@@ -155,22 +160,43 @@ hres_layers_sparse_kernel(const float *__restrict__ image0, const float *__restr
 
 extern "C" {
 
-int msi_hres_index_tiles(const float *alphas, int32_t format, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
-                         int32_t num_planes, int32_t *table_out, int32_t *counts_out, msi_stream_t stream) {
-  const char *who = "hres_index_tiles";
+// both keep rules: the checks, the keep kernel of `border`, the scan
+static int hres_index_tiles(const char *who, int border, const float *alphas, int32_t format, int32_t batch, int32_t low_height, int32_t low_width,
+                            int32_t height, int32_t width, int32_t num_planes, int32_t *table_out, int32_t *counts_out, msi_stream_t stream) {
   if (const int e = hres_check(who, alphas && table_out && counts_out, batch, low_height, low_width, height, width, num_planes)) return e;
+  if (border == BORDER_EDGE)
+    if (const int e = pp_hres_check(who, height, width)) return e;
   size_t tiles;
   if (const int e = sparse_dims(who, format, batch, num_planes, height, width, &tiles)) return e;
   if (batch == 0) return MSI_OK;
   hipStream_t s = msi::as_stream(stream);
   const size_t groups = tiles / HRES_G;
+  const float sy = hres_scale(low_height, height), sx = hres_scale(low_width, width);
   for_format(format, [&](auto FMT) {
-    if constexpr (decltype(FMT)::value != MSI_LAYERS_F32)
-      hipLaunchKernelGGL((hres_keep_kernel<decltype(FMT)::value>), dim3(grid_1d(groups)), dim3(256), 0, s, alphas, low_height, low_width, height,
-                         width, num_planes, hres_scale(low_height, height), hres_scale(low_width, width), groups, table_out);
+    constexpr int fmt = decltype(FMT)::value;
+    if constexpr (fmt != MSI_LAYERS_F32) {
+      if (border == BORDER_EDGE)
+        hipLaunchKernelGGL((hres_keep_kernel<fmt, BORDER_EDGE>), dim3(grid_1d(groups)), dim3(256), 0, s, alphas, low_height, low_width, height, width,
+                           num_planes, sy, sx, groups, table_out);
+      else
+        hipLaunchKernelGGL((hres_keep_kernel<fmt, BORDER_WRAP>), dim3(grid_1d(groups)), dim3(256), 0, s, alphas, low_height, low_width, height, width,
+                           num_planes, sy, sx, groups, table_out);
+    }
   });
   if (const int e = msi::check_launch(who)) return e;
   return scan_tiles(who, table_out, counts_out, batch, num_planes, height, width, s);
+}
+
+int msi_hres_index_tiles(const float *alphas, int32_t format, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
+                         int32_t num_planes, int32_t *table_out, int32_t *counts_out, msi_stream_t stream) {
+  return hres_index_tiles("hres_index_tiles", BORDER_WRAP, alphas, format, batch, low_height, low_width, height, width, num_planes, table_out, counts_out,
+                          stream);
+}
+
+int msi_hres_index_tiles_edge(const float *alphas, int32_t format, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
+                              int32_t num_planes, int32_t *table_out, int32_t *counts_out, msi_stream_t stream) {
+  return hres_index_tiles("hres_index_tiles_edge", BORDER_EDGE, alphas, format, batch, low_height, low_width, height, width, num_planes, table_out,
+                          counts_out, stream);
 }
 
 int msi_hres_layers_sparse(const float *ref_image, const float *src_image, const float *ref_curr_pose, const float *src_curr_pose,

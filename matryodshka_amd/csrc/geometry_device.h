@@ -8,6 +8,7 @@
 //   geo_sparse_hres.hip   the high-res stack built sparse (hres_keep_kernel, hres_layers_sparse_kernel)
 //   geo_sparse_views.hip  K4 from a sparse stack: render_views_sparse_kernel (the cameras of render and ods); the planar and cube renders from one
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
+//   geo_planar_hres.hip   the PP high-res stack in one pass, dense or sparse: pp_hres_layers_kernel, pp_hres_layers_sparse_kernel
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
 // sharing is a contract.  What a single family uses lives in that family's unit.
@@ -467,6 +468,91 @@ __device__ __forceinline__ float4 hres_texel(const HresPixel &p, float depth, co
   return hres_blend(t, hres_fetch(p, t), w, alpha);
 }
 
+// ---- planar-hres (pp_hres_layers_kernel, pp_hres_layers_sparse_kernel: geo_planar_hres.hip): ONE definition of a texel of the PP high-res stack.  It is
+// pp_sweep_kernel's arithmetic (geo_planar.hip), op for op -- S and T of uv_grid, backproject_planar with its two divides, apply_pose, M = K4 @ pose with
+// the padded column's 0 * pose[3][c], rows 0..2 of M, u = pr0 / pr2, v = pr1 / pr2, make_taps, blend4 -- once per source image (ref = foreground,
+// src = background), then the steps the ODS texel above ends with (hres_corners / hres_lerp, hres_blend, hres_store_packed): the bits of
+// msi_perspective_plane_sweep_f32 x 2 -> msi_resize_bilinear_f32 -> msi_assemble_rgba_scaled_f32.  No reciprocal, no fused multiply-add, no reassociation.
+// K, both poses and both M depend on the sample alone: they are made wave-uniform (pp_uniform) so that they live in SGPRs, not in 60 VGPRs of every lane.
+__device__ __forceinline__ float pp_uniform(float v) {   // (v is the same in every lane: a function of blockIdx.z)
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+struct PpHresSource {
+  __amdgpu_buffer_rsrc_t img;
+  const float *P;      // pose [4,4] of this source
+  float m[12];         // rows 0..2 of K4 @ pose
+};
+struct PpHresPixel {
+  PpHresSource s0, s1;
+  float S, T, fx, fy, cx, cy;
+  bool same;           // equal poses: both sources sample the same position
+};
+__device__ __forceinline__ PpHresSource pp_hres_source(const float *__restrict__ image, const float *__restrict__ pose, const float *Kb, int b, int height,
+                                                       int width) {
+  PpHresSource s;
+  s.P = pose + (size_t)b * 16;
+  s.img = __builtin_amdgcn_make_buffer_rsrc((void *)(image + (size_t)b * height * width * 3), 0, height * width * 12, 0x00020000);   // (H * W * 12 < 2^31: checked on the host)
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      s.m[r * 4 + c] = pp_uniform(((Kb[r * 3 + 0] * s.P[c] + Kb[r * 3 + 1] * s.P[4 + c]) + Kb[r * 3 + 2] * s.P[8 + c]) + 0.0f * s.P[12 + c]);
+  return s;
+}
+__device__ __forceinline__ PpHresPixel pp_hres_pixel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
+                                                     const float *__restrict__ pose1, const float *__restrict__ intrinsics, int b, int i, int j, int height,
+                                                     int width, float s0, float sstep, float t0, float tstep) {
+  PpHresPixel p;
+  const float *Kb = intrinsics + (size_t)b * 9;
+  p.fx = Kb[0]; p.fy = Kb[4]; p.cx = Kb[2]; p.cy = Kb[5];
+  p.S = s0 + sstep * (float)j; p.T = t0 + tstep * (float)i;
+  p.s0 = pp_hres_source(image0, pose0, Kb, b, height, width);
+  p.s1 = pp_hres_source(image1, pose1, Kb, b, height, width);
+  p.same = true;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) p.same = p.same && (p.s0.P[k] == p.s1.P[k]);   // (row 3 too: M has 0 * pose[3][c], which is NaN for an infinite entry)
+  return p;
+}
+// where the plane point (x, y, z) of backproject_planar lands in one source: apply_pose, project_perspective, the wrap-around taps as byte offsets
+__device__ __forceinline__ TapsB pp_hres_source_taps(const PpHresSource &s, float x, float y, float z, int width, int height) {
+  const float *P = s.P;
+  const float ax = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
+  const float ay = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
+  const float az = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
+  float pr[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) pr[r] = ((s.m[r * 4 + 0] * ax + s.m[r * 4 + 1] * ay) + s.m[r * 4 + 2] * az) + s.m[r * 4 + 3] * 1.0f;
+  const float u = pr[0] / pr[2], v = pr[1] / pr[2];
+  const Taps t = make_taps(u, v, width, height);      // (wrapped indices lie inside the image whatever u and v are)
+  TapsB r;
+  r.oa = (unsigned)(t.y0 * width + t.x0) * 12u; r.ob = (unsigned)(t.y0 * width + t.x1) * 12u;
+  r.oc = (unsigned)(t.y1 * width + t.x0) * 12u; r.od = (unsigned)(t.y1 * width + t.x1) * 12u;
+  r.wa = t.wa; r.wb = t.wb; r.wc = t.wc; r.wd = t.wd;
+  return r;
+}
+// The PP texel in the ODS texel's three steps: pp_hres_taps -> pp_hres_fetch -> hres_blend (the blend is the same function); pp_hres_texel is the three in a row.
+__device__ __forceinline__ HresTaps pp_hres_taps(const PpHresPixel &p, float depth, int width, int height) {
+  HresTaps t;
+  // backproject_planar (spherical.py:146-148)
+  const float x = ((depth * p.S) * p.cx) / p.fx;
+  const float y = ((depth * p.T) * p.cy) / p.fy;
+  const float z = depth * 1.0f;
+  t.fg = pp_hres_source_taps(p.s0, x, y, z, width, height);
+  if (p.same) t.bg = t.fg;
+  else t.bg = pp_hres_source_taps(p.s1, x, y, z, width, height);
+  return t;
+}
+__device__ __forceinline__ HresRgb pp_hres_fetch(const PpHresPixel &p, const HresTaps &t) {
+  HresRgb g;
+  g.fg = gather3_load(p.s0.img, t.fg);
+  g.bg = gather3_load(p.s1.img, t.bg);
+  return g;
+}
+__device__ __forceinline__ float4 pp_hres_texel(const PpHresPixel &p, float depth, int width, int height, float w, float alpha) {
+  const HresTaps t = pp_hres_taps(p, depth, width, height);
+  return hres_blend(t, pp_hres_fetch(p, t), w, alpha);
+}
+
 // ---- sweep, layers (pack / unpack / hres) and planar: the 16-byte store of every streaming kernel; its host side is beyond_infinity_cache below.
 // The 16-byte pieces of a wave's whole-pixel strip.  nt != 0 (block-uniform; the host sets it when the volume is larger than the 256-MB Infinity Cache): non-temporal
 // stores -- a volume that cannot stay cached until conv1_1 reads it should not evict what can (r06, same-box A/B at configs[2]: sweep 1.07 -> 0.98 ms per 16 frames;
@@ -870,6 +956,13 @@ int hres_check(const char *who, bool inputs, int32_t batch, int32_t low_height, 
   return MSI_OK;
 }
 float hres_scale(int low, int high) { return high > 1 ? (float)(low - 1) / (float)(high - 1) : 0.0f; }
+// planar-hres (msi_pp_hres_layers, msi_pp_hres_layers_sparse) and sparse-hres (msi_hres_index_tiles_edge): after hres_check, what the perspective sweep
+// asks of an image (msi_perspective_plane_sweep_f32: uv_grid divides by n - 1; 32-bit byte offsets into one [H,W,3] image)
+int pp_hres_check(const char *who, int32_t height, int32_t width) {
+  MSI_REQUIRE(height > 1 && width > 1, "%s: bad dims (a perspective sweep needs H > 1 and W > 1)", who);
+  MSI_REQUIRE((long)height * width * 12 < 2147483647L, "%s: problem too large (H * W * 12 < 2^31)", who);
+  return MSI_OK;
+}
 
 // render, ods, planar, cube: the grid of a many-views launch (ViewBlock), blocks_per_view x views x batch workgroups rounded up to a multiple of 8; each
 // factor is < 2^31 and every product is checked before the next

@@ -937,10 +937,12 @@ class MSI(object):
 
     # ------------------------------------------------------------------ test.py:283-394
     def _hres_inputs(self, who, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics,
-                     ref_pose_inv):
-        """What hres_layers and hres_layers_sparse hand to their launches, checked: (bw, al, hres_ref, hres_src, cur, intr, depths, trig)."""
-        if self.input_type != 'ODS':
-            raise ValueError("%s: the fused high-res assembly is built for input_type='ODS' models" % who)
+                     ref_pose_inv, sweep='ODS'):
+        """What the high-res builders hand to their launches, checked: (bw, al, hres_ref, hres_src, cur, intr, depths, trig).  sweep='ODS'
+        (hres_layers, hres_layers_sparse): the model's own sweep, ODS models only; sweep='PP' (their mpi_ twins): the method names the
+        sweep, any model, trig is None and intr is [B,3,3]."""
+        if sweep == 'ODS' and self.input_type != 'ODS':
+            raise ValueError("%s sweeps the sphere (input_type='ODS' models); the perspective sweep is mpi_%s" % (who, who))
         bw, al = self._f32(blend_weights), self._f32(alphas)
         if bw.dim() != 4 or bw.shape != al.shape:
             raise ValueError("%s: blend_weights and alphas must be [B,H,W,D] and agree" % who)
@@ -951,8 +953,14 @@ class MSI(object):
         if hres_ref.shape[0] != b or hres_ref.shape[3] != 3 or hres_src.shape != hres_ref.shape:
             raise ValueError("%s: images must be [B,Hh,Wh,3], agree, and have the batch of blend_weights" % who)
         cur = self._current_poses(ref_pose, src_pose, ref_pose_inv, b)
-        intr, trig = self._f32(intrinsics), self._trig(hres_ref.shape[1], hres_ref.shape[2])
-        return bw, al, hres_ref, hres_src, cur, intr, depths, trig
+        intr = self._f32(intrinsics)
+        if sweep == 'ODS':
+            return bw, al, hres_ref, hres_src, cur, intr, depths, self._trig(hres_ref.shape[1], hres_ref.shape[2])
+        if intr.numel() != b * 9:
+            raise ValueError("%s: intrinsics (of the high-res images) must be [B,3,3] with B = %d" % (who, b))
+        if hres_ref.shape[1] < 2 or hres_ref.shape[2] < 2:
+            raise ValueError("%s: a perspective sweep needs images of at least 2 x 2" % who)
+        return bw, al, hres_ref, hres_src, cur, intr, depths, None
 
     def hres_layers(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
                     intrinsics, ref_pose_inv=None, layer_format='f32'):
@@ -966,25 +974,9 @@ class MSI(object):
         request allocates nothing but the packed stack.  ODS models only (fp32 or bf16: the high-res colours are fp32 either
         way).  Poses as in format_network_input (ref_pose_inv computed on the host when absent).  hres_layers_sparse builds the
         packed stack sparse, without the dense one."""
-        want_f32, pfmt = self._layer_formats(layer_format)
-        bw, al, hres_ref, hres_src, cur, intr, depths, trig = self._hres_inputs(
-            "hres_layers", blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics, ref_pose_inv)
-        b, h, w, d = bw.shape
-        hh, hw = hres_ref.shape[1], hres_ref.shape[2]
-        rgba = torch.empty((b, d, hh, hw, 4), dtype=torch.float32, device=self.device) if want_f32 else None
-        codes = None
-        if pfmt is not None:
-            codes = torch.empty((b, d, hh, hw, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
-        N.check(N.lib.msi_hres_layers(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(),
-                                      intr.data_ptr(), depths.data_ptr(), trig.data_ptr(), bw.data_ptr(), al.data_ptr(),
-                                      b, h, w, hh, hw, d, _ptr(rgba), _ptr(codes), self.LAYER_FORMATS.get(pfmt, N.MSI_LAYERS_F32),
-                                      self._stream()), "msi_hres_layers")
-        out = {}
-        if rgba is not None:
-            out['rgba_layers'] = rgba.permute(0, 2, 3, 1, 4)
-        if codes is not None:
-            out['packed_layers'] = PackedLayers(codes, pfmt, planes)
-        return out
+        formats = self._layer_formats(layer_format)
+        return self._hres_build("hres_layers", 'ODS', blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
+                                intrinsics, ref_pose_inv, *formats)
 
     def hres_layers_sparse(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
                            intrinsics, ref_pose_inv=None, layer_format='rgba8'):
@@ -996,33 +988,90 @@ class MSI(object):
         from `alphas` alone; after the one host synchronisation sparsify_layers has too (the pool's size is data-dependent)
         msi_hres_layers_sparse computes the texels of kept tiles only, straight into the pool.  Only table, counts, layer_start
         and pool are allocated.  ODS models only."""
-        want_f32, pfmt = self._layer_formats(layer_format)
-        if want_f32 or pfmt is None:
-            raise ValueError("hres_layers_sparse takes layer_format 'rgba8' or 'rgba16f' alone (fp32 pools are not built), not %r"
-                             % (layer_format,))
+        formats = self._layer_formats(layer_format)
+        return self._hres_build_sparse("hres_layers_sparse", 'ODS', blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose,
+                                       planes, intrinsics, ref_pose_inv, *formats)
+
+    def mpi_hres_layers(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
+                        intrinsics, ref_pose_inv=None, layer_format='f32'):
+        """hres_layers for perspective images, in ONE launch (msi_pp_hres_layers): the high-res perspective plane sweep of both
+        images (ref = foreground, src = background), the align_corners resize of the low-res blend_weights / alphas [B,H,W,D]
+        and the blend -> what hres_layers returns (result['rgba_layers'] [B,Hh,Wh,D,4] and / or result['packed_layers'], which
+        carries `planes`), for mpi_render_views and, with six faces per sample, cube_render_views.  `intrinsics` [B,3,3] are
+        those of the HIGH-RES images.  The fp32 stack has the bits of two msi_perspective_plane_sweep_f32 ->
+        msi_resize_bilinear_f32 -> msi_assemble_rgba_scaled_f32, the packed one those of pack_layers of it; the [B,Hh,Wh,6D]
+        volume and the upsampled tensor never exist, and a packed-only request allocates nothing but the packed stack.  Works on
+        any model, like mpi_render_views: the method names the sweep.  mpi_hres_layers_sparse builds the packed stack sparse."""
+        formats = self._layer_formats(layer_format)
+        return self._hres_build("mpi_hres_layers", 'PP', blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
+                                intrinsics, ref_pose_inv, *formats)
+
+    def mpi_hres_layers_sparse(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
+                               intrinsics, ref_pose_inv=None, layer_format='rgba8'):
+        """mpi_hres_layers' packed stack as a SparseLayers with border='edge', without the dense stack: layer_format 'rgba8' or
+        'rgba16f' alone, Hh % 4 == 0 and Wh % 16 == 0 (else ValueError) -> {'sparse_layers': SparseLayers} that carries `planes`:
+        the table, layer_start and pool of sparsify_layers(mpi_hres_layers(...)['packed_layers'], border='edge'), bit for bit; it
+        goes straight into mpi_render_views / cube_render_views.  msi_hres_index_tiles_edge decides the kept tiles from `alphas`
+        alone (a texel's alpha is the resized alpha), msi_pp_hres_layers_sparse computes the texels of kept tiles only.  Only
+        table, counts, layer_start and pool are allocated.  Any model."""
+        formats = self._layer_formats(layer_format)
+        return self._hres_build_sparse("mpi_hres_layers_sparse", 'PP', blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose,
+                                       src_pose, planes, intrinsics, ref_pose_inv, *formats)
+
+    def _hres_build(self, who, sweep, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics,
+                    ref_pose_inv, want_f32, pfmt):
+        """hres_layers (sweep='ODS': msi_hres_layers) and mpi_hres_layers (sweep='PP': msi_pp_hres_layers, the same parameters without trig);
+        (want_f32, pfmt) = _layer_formats of the caller's request."""
         bw, al, hres_ref, hres_src, cur, intr, depths, trig = self._hres_inputs(
-            "hres_layers_sparse", blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics,
-            ref_pose_inv)
+            who, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics, ref_pose_inv, sweep)
+        b, h, w, d = bw.shape
+        hh, hw = hres_ref.shape[1], hres_ref.shape[2]
+        rgba = torch.empty((b, d, hh, hw, 4), dtype=torch.float32, device=self.device) if want_f32 else None
+        codes = None
+        if pfmt is not None:
+            codes = torch.empty((b, d, hh, hw, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+        name = "msi_hres_layers" if sweep == 'ODS' else "msi_pp_hres_layers"
+        trig_arg = (trig.data_ptr(),) if sweep == 'ODS' else ()
+        N.check(getattr(N.lib, name)(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(), intr.data_ptr(),
+                                     depths.data_ptr(), *trig_arg, bw.data_ptr(), al.data_ptr(), b, h, w, hh, hw, d, _ptr(rgba), _ptr(codes),
+                                     self.LAYER_FORMATS.get(pfmt, N.MSI_LAYERS_F32), self._stream()), name)
+        out = {}
+        if rgba is not None:
+            out['rgba_layers'] = rgba.permute(0, 2, 3, 1, 4)
+        if codes is not None:
+            out['packed_layers'] = PackedLayers(codes, pfmt, planes)
+        return out
+
+    def _hres_build_sparse(self, who, sweep, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
+                           intrinsics, ref_pose_inv, want_f32, pfmt):
+        """hres_layers_sparse (sweep='ODS': msi_hres_index_tiles, msi_hres_layers_sparse, border 'wrap') and mpi_hres_layers_sparse
+        (sweep='PP': msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse, border 'edge'); (want_f32, pfmt) = _layer_formats of the
+        caller's request."""
+        if want_f32 or pfmt is None:
+            raise ValueError("%s takes layer_format 'rgba8' or 'rgba16f' alone (fp32 pools are not built)" % who)
+        bw, al, hres_ref, hres_src, cur, intr, depths, trig = self._hres_inputs(
+            who, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics, ref_pose_inv, sweep)
         b, h, w, d = bw.shape
         hh, hw = hres_ref.shape[1], hres_ref.shape[2]
         if hh % TILE_H or hw % TILE_W:
             raise ValueError("a sparse stack needs H %% %d == 0 and W %% %d == 0, not %d x %d" % (TILE_H, TILE_W, hh, hw))
         fmt = self.LAYER_FORMATS[pfmt]
+        index, fill, border = (("msi_hres_index_tiles", "msi_hres_layers_sparse", 'wrap') if sweep == 'ODS' else
+                               ("msi_hres_index_tiles_edge", "msi_pp_hres_layers_sparse", 'edge'))
         table = torch.empty((b, d, hh // TILE_H, hw // TILE_W), dtype=torch.int32, device=self.device)
         counts = torch.empty((b * d,), dtype=torch.int32, device=self.device)
-        N.check(N.lib.msi_hres_index_tiles(al.data_ptr(), fmt, b, h, w, hh, hw, d, table.data_ptr(), counts.data_ptr(), self._stream()),
-                "msi_hres_index_tiles")
+        N.check(getattr(N.lib, index)(al.data_ptr(), fmt, b, h, w, hh, hw, d, table.data_ptr(), counts.data_ptr(), self._stream()), index)
         layer_start = torch.zeros((b * d + 1,), dtype=torch.int64, device=self.device)
         if b * d:
             layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
         total = int(layer_start[-1].item())
         pool = torch.empty((total, TILE_H, TILE_W, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
         if total:
-            N.check(N.lib.msi_hres_layers_sparse(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(),
-                                                 intr.data_ptr(), depths.data_ptr(), trig.data_ptr(), bw.data_ptr(), al.data_ptr(),
-                                                 b, h, w, hh, hw, d, table.data_ptr(), layer_start.data_ptr(), pool.data_ptr(), fmt,
-                                                 self._stream()), "msi_hres_layers_sparse")
-        return {'sparse_layers': SparseLayers(table, layer_start, pool, pfmt, planes)}
+            trig_arg = (trig.data_ptr(),) if sweep == 'ODS' else ()
+            N.check(getattr(N.lib, fill)(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(), intr.data_ptr(),
+                                         depths.data_ptr(), *trig_arg, bw.data_ptr(), al.data_ptr(), b, h, w, hh, hw, d, table.data_ptr(),
+                                         layer_start.data_ptr(), pool.data_ptr(), fmt, self._stream()), fill)
+        return {'sparse_layers': SparseLayers(table, layer_start, pool, pfmt, planes, border=border)}
 
     def msi_render_equirect_hres(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image,
                                  ref_pose, src_pose, tgt_pose_rt, tgt_pos, planes, intrinsics,
@@ -1030,7 +1079,8 @@ class MSI(object):
         """High-res re-render of test.py:283-394 as two launches: the reference loops over the planes
         on the host (one sess.run + numpy composite per plane, to fit its GPU memory); here hres_layers
         builds the whole fp32 high-res stack in one kernel (no sweep volume in memory) and one render
-        composites it.  To keep the stack, or to get it packed, call hres_layers itself.
+        composites it (on an input_type='PP' model: mpi_hres_layers, the perspective sweep).  To keep the stack, or to get it
+        packed, call hres_layers / mpi_hres_layers itself.
         blend_weights / alphas: the low-res [B,H,W,D] outputs of infer_msi(extra_outputs=
         'blend_weights alphas') (test.py:264-271 saves them as .npy).  Returns (rgb, depth), both
         [B,Hh,Wh,3] float (rgb in [-1,1], depth = composited plane index / D as test.py:374-382)."""
@@ -1038,25 +1088,10 @@ class MSI(object):
             rgba_layers = self.hres_layers(blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose,
                                            planes, intrinsics, ref_pose_inv=ref_pose_inv, layer_format='f32')['rgba_layers']
             return self.msi_render_equirect_view_and_depth(rgba_layers, tgt_pose_rt, tgt_pos, planes, intrinsics)
-        # perspective inputs: sweep, resize and assembly as three launches
-        bw = self._f32(blend_weights)
-        al = self._f32(alphas)
-        b, h, w, d = bw.shape
-        hres_ref = self.preprocess_image(raw_hres_ref_image)
-        hres_src = self.preprocess_image(raw_hres_src_image)
-        hh, hw = hres_ref.shape[1], hres_ref.shape[2]
-        # the high-res volume feeds the fp32 assembly (not the network): fp32 also on a bf16 model
-        psv = self.format_network_input(hres_ref, hres_src, ref_pose, src_pose, planes, intrinsics,
-                                        ref_pose_inv=ref_pose_inv, dtype='f32')
-        low = torch.cat([bw, al], dim=-1).contiguous()
-        up = torch.empty((b, hh, hw, 2 * d), dtype=torch.float32, device=self.device)
-        N.check(N.lib.msi_resize_bilinear_f32(low.data_ptr(), up.data_ptr(), b, h, w, 2 * d, hh, hw, self._stream()),
-                "msi_resize_bilinear_f32")
-        rgba = torch.empty((b, d, hh, hw, 4), dtype=torch.float32, device=self.device)
-        N.check(N.lib.msi_assemble_rgba_scaled_f32(psv.data_ptr(), up.data_ptr(), rgba.data_ptr(), b, hh, hw, d,
-                                                   self._stream()), "msi_assemble_rgba_scaled_f32")
-        return self.msi_render_equirect_view_and_depth(rgba.permute(0, 2, 3, 1, 4), tgt_pose_rt, tgt_pos, planes,
-                                                       intrinsics)
+        # perspective inputs: the same two launches through the PP builder (the bits of the sweep, resize and assembly it replaced here)
+        rgba_layers = self.mpi_hres_layers(blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose,
+                                           planes, intrinsics, ref_pose_inv=ref_pose_inv, layer_format='f32')['rgba_layers']
+        return self.msi_render_equirect_view_and_depth(rgba_layers, tgt_pose_rt, tgt_pos, planes, intrinsics)
 
     # ------------------------------------------------------------------ msi.py:527-548
     def mpi_render_view(self, rgba_layers, tgt_pose, planes, intrinsics, intrinsics_inv=None):
@@ -1232,14 +1267,22 @@ class MSI(object):
         pred['packed_layers'], which carries `planes`) goes straight into cube_render_views.  Pure composition: no kernel of
         its own.  For input_type='PP' models only.  The panoramas are single-centre equirectangular images: the faces of an
         ODS panorama are not perspective images."""
-        from . import cubemap
         if self.input_type != 'PP':
             raise ValueError("infer_cube runs the perspective (PP) network on cube faces: build the model with input_type='PP'")
-        s = int(face_size)
-        d = len(planes)
         src, ref = self.preprocess_image(raw_src_equirect), self.preprocess_image(raw_ref_equirect)
+        src_faces, ref_faces, eye, face_src, kf = self._cube_faces("infer_cube", src, ref, src_pose, face_size, face_intrinsics)
+        net_input = self.format_network_input(ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye)
+        pred = self.infer_layers(net_input, len(planes), ngf, extra_outputs, which_color_pred, layer_format=layer_format)
+        return self._carrying(pred, planes)
+
+    def _cube_faces(self, who, src, ref, src_pose, face_size, face_intrinsics):
+        """What infer_cube and hres_cube_layers make of a pair of panoramas [B,H,W,3] (fp32, on the device): both cut into faces
+        [6B,S,S,3] (equirect_to_cube), ref_pose = I and src_pose = cubemap.face_poses(src_pose) per face [6B,4,4], and the face
+        camera per face [6B,3,3] -> (src_faces, ref_faces, eye, face_src, kf)."""
+        from . import cubemap
+        s = int(face_size)
         if src.dim() != 4 or src.shape[-1] != 3 or src.shape != ref.shape:
-            raise ValueError("infer_cube: the panoramas must be [B,H,W,3] and agree")
+            raise ValueError("%s: the panoramas must be [B,H,W,3] and agree" % who)
         b = src.shape[0]
         k = cubemap.default_face_intrinsics(s) if face_intrinsics is None else face_intrinsics
         src_faces = self.equirect_to_cube(src, s, k).reshape(6 * b, s, s, 3)
@@ -1248,16 +1291,32 @@ class MSI(object):
         if sp.shape[0] == 1 and b > 1:
             sp = sp.expand(b, 4, 4)
         if sp.shape[0] != b:
-            raise ValueError("infer_cube: src_pose must be [4,4] or [B,4,4] with B = %d" % b)
+            raise ValueError("%s: src_pose must be [4,4] or [B,4,4] with B = %d" % (who, b))
         face_src = cubemap.face_poses(sp).reshape(6 * b, 4, 4).contiguous()
         eye = torch.eye(4, dtype=torch.float32, device=self.device).expand(6 * b, 4, 4).contiguous()
         kf = self._f32(k).reshape(-1, 3, 3)
         if kf.shape[0] not in (1, b):
-            raise ValueError("infer_cube: face_intrinsics must be [3,3] or [B,3,3] with B = %d" % b)
+            raise ValueError("%s: face_intrinsics must be [3,3] or [B,3,3] with B = %d" % (who, b))
         kf = kf.expand(b, 3, 3)[:, None].expand(b, 6, 3, 3).reshape(6 * b, 3, 3).contiguous()
-        net_input = self.format_network_input(ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye)
-        pred = self.infer_layers(net_input, d, ngf, extra_outputs, which_color_pred, layer_format=layer_format)
-        return self._carrying(pred, planes)
+        return src_faces, ref_faces, eye, face_src, kf
+
+    def hres_cube_layers(self, blend_weights, alphas, raw_hres_src_equirect, raw_hres_ref_equirect, src_pose, face_size, planes,
+                         face_intrinsics=None, layer_format='rgba8', sparse=False):
+        """The high-res stack of a cube, for cube_render_views: blend_weights / alphas [6B,S,S,D] of infer_cube(extra_outputs=
+        'blend_weights alphas') and the pair of high-res panoramas [B,H,W,3] (uint8 [0,255] or float [0,1]) -> six face stacks of
+        face_size per sample.  Pure composition: the raw panoramas are cut into faces [6B,face_size,face_size,3] in [0,1]
+        (equirect_to_cube), with the face poses of infer_cube and face_intrinsics ([3,3] or [B,3,3], default
+        cubemap.default_face_intrinsics(face_size): those of the HIGH-RES faces), and mpi_hres_layers (sparse=False: its result
+        dict) or mpi_hres_layers_sparse (sparse=True: {'sparse_layers': SparseLayers}, face_size % 16 == 0) builds the stack of
+        batch 6B, which goes straight into cube_render_views.  layer_format as there.  Packed is the default here: the viewer
+        refuses a sample whose six fp32 face stacks reach 2^31 bytes (face_size > 836 at D = 32; 1182 in rgba16f, 1672 in rgba8).
+        Any model.  Faces are filtered one by one: nothing is fetched across a cube edge."""
+        to_unit = lambda x: (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(self.device)
+        src, ref = to_unit(raw_hres_src_equirect), to_unit(raw_hres_ref_equirect)
+        src, ref = (x.float() / 255.0 if x.dtype == torch.uint8 else x.float() for x in (src, ref))
+        src_faces, ref_faces, eye, face_src, kf = self._cube_faces("hres_cube_layers", src, ref, src_pose, face_size, face_intrinsics)
+        build = self.mpi_hres_layers_sparse if sparse else self.mpi_hres_layers
+        return build(blend_weights, alphas, ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye, layer_format=layer_format)
 
     # ------------------------------------------------------------------ image scores (eval.py:127-174 on the device)
     SCORE_TRANSFORMS = {'raw': N.MSI_SCORE_RAW, 'image': N.MSI_SCORE_IMAGE, 'depth': N.MSI_SCORE_DEPTH}
