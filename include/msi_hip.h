@@ -67,7 +67,8 @@ const char *msi_version(void);
  *      (additions since, no bump: msi_mpi_render_views; msi_score_workspace_bytes, msi_score_images; msi_cube_render_views,
  *      msi_equirect_to_cube_f32; msi_sparse_index_tiles, msi_sparse_gather_tiles, msi_sparse_expand, msi_render_views_sparse;
  *      msi_hres_index_tiles, msi_hres_layers_sparse; msi_sparse_index_tiles_edge, msi_mpi_render_views_sparse,
- *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse) */
+ *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse;
+ *      msi_cube_plane_sweep_f32, msi_cube_sweep_volume_bf16, msi_cube_hres_layers, msi_cube_hres_layers_sparse) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -588,6 +589,61 @@ int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_p
  * msi_build_trig_tables_host), bilinear, wrapping in u and clamping in v. */
 int msi_equirect_to_cube_f32(const float *image, const float *intrinsics, int32_t batch, int32_t height, int32_t width,
                              int32_t channels, int32_t face_size, float *out, msi_stream_t stream);
+
+/* ---- cube path, source half sampled from the source PANORAMA (MSI.format_cube_input; src_sampling='panorama' of
+ * MSI.infer_cube / MSI.hres_cube_layers; no reference counterpart) --------------------------------------------------------
+ * The face-wise cube path sweeps each face's own source image with the wrap-around sampler: a plane point that projects past
+ * the face's border gets texels from the opposite side of the SAME face.  These entry points take the source panorama itself
+ * and look every plane point up along its own direction, so such a point gets the neighbouring face's content.  They are the
+ * face-wise twins with that one change; `batch` is the number of CUBES B, every per-face array has 6 B entries (face f of cube
+ * b at 6 b + f, faces in the table above), faces are square (face_size = S).
+ * The sample position, shared by all four (one device function): for face f = n % 6 of entry n, pixel (i, j), plane depth d,
+ * P = face_pose[n] and K = intrinsics[n]:
+ *   X = backproject_planar and a = apply_pose(P, X) exactly as msi_perspective_plane_sweep_f32 computes them; Y = apply_pose(P, a)
+ *   (the reference applies the pose twice -- once in apply_pose, once inside project_perspective through K4 @ pose -- so the
+ *   face sweep samples K Y: Y is the direction it looks along wherever its (u, v) falls inside the face; no K enters Y);
+ *   dir = R_f Y (a signed permutation); lon = atan2(dir_x + 0, dir_z + 0), lat = asin(dir_y / |dir|) (the sweep's and render's
+ *   angle helpers, 1.3e-7 rad; libm with -DMSI_FAST_TAIL=0); u = (lon + pi) / 2pi Wp - 0.5, v = (lat + pi/2) / pi Hp - 0.5;
+ *   u clamped to [-0.5, Wp - 0.5] and wrapped, v clamped to [0, Hp - 1] (msi_equirect_to_cube_f32's sampler, its weights and
+ *   sum order).  A NaN coordinate (Y = 0, a non-finite pose) becomes the lower bound before the float -> int conversion:
+ *   every texel address lies inside the cube's own panorama for any input.
+ *
+ * msi_cube_plane_sweep_f32   msi_perspective_plane_sweep_f32 of one source: writes channels [channel_offset, channel_offset +
+ *                            3 D) of psv [6B,S,S,psv_channels] and nothing else.  panorama [B,Hp,Wp,3], face_pose [6B,4,4],
+ *                            intrinsics [6B,3,3], depths [D].  Both kernel forms and the store policy are the twin's, chosen by
+ *                            the twin's conditions.
+ * msi_cube_sweep_volume_bf16 msi_perspective_sweep_volume_bf16: the whole bf16 network input [6B,S,S,6D] in one launch.  The ref
+ *                            half [0,3D) comes from ref_faces [6B,S,S,3] with ref_face_pose and has that entry point's bits;
+ *                            the src half [3D,6D) is the round to nearest even of msi_cube_plane_sweep_f32 with
+ *                            src_face_pose, bit for bit.
+ * msi_cube_hres_layers       msi_pp_hres_layers with the background taps from the panorama: the bits of
+ *                            msi_perspective_plane_sweep_f32 (ref faces) + msi_cube_plane_sweep_f32 (panorama) at face_size ->
+ *                            msi_resize_bilinear_f32 of blend_weights / alphas [6B,s,s,D] (s = low_size) ->
+ *                            msi_assemble_rgba_scaled_f32; rgba_native [6B,D,S,S,4] and / or layers_out (msi_pack_layers of
+ *                            it); outputs, formats and store policy as msi_pp_hres_layers.
+ * msi_cube_hres_layers_sparse  msi_pp_hres_layers_sparse likewise: equal to msi_sparse_gather_tiles of msi_cube_hres_layers'
+ *                            stack; the table is msi_hres_index_tiles_edge's (batch 6B): alphas do not depend on the sweep.
+ * Checks before any launch, MSI_E_BADARG unless noted: (hres: unknown format, both outputs NULL;) a NULL pointer; (sweeps:
+ * num_depths < 1;) batch < 0 or face_size < 2; Hp < 2 or Wp < 2; Hp * Wp * 12 >= 2^31; 6 * batch or face_size above 65535;
+ * S * S * 12 >= 2^31; then the twin's own (the channel window; msi_hres_layers' checks with batch 6B, num_planes % 4 ->
+ * MSI_E_UNSUPPORTED; the tile entry points' checks).  batch = 0 then returns MSI_OK without a launch.  Error texts name
+ * cube_plane_sweep / cube_sweep_volume_bf16 / cube_hres_layers / cube_hres_layers_sparse. */
+int msi_cube_plane_sweep_f32(const float *panorama, const float *face_pose, const float *intrinsics, const float *depths,
+                             int32_t batch, int32_t pano_height, int32_t pano_width, int32_t face_size, int32_t num_depths,
+                             float *psv, int32_t psv_channels, int32_t channel_offset, msi_stream_t stream);
+int msi_cube_sweep_volume_bf16(const float *ref_faces, const float *src_panorama, const float *ref_face_pose,
+                               const float *src_face_pose, const float *intrinsics, const float *depths, int32_t batch,
+                               int32_t pano_height, int32_t pano_width, int32_t face_size, int32_t num_depths, void *psv_bf16,
+                               msi_stream_t stream);
+int msi_cube_hres_layers(const float *ref_faces, const float *src_panorama, const float *ref_face_pose, const float *src_face_pose,
+                         const float *intrinsics, const float *depths, const float *blend_weights, const float *alphas,
+                         int32_t batch, int32_t pano_height, int32_t pano_width, int32_t low_size, int32_t face_size,
+                         int32_t num_planes, float *rgba_native, void *layers_out, int32_t format, msi_stream_t stream);
+int msi_cube_hres_layers_sparse(const float *ref_faces, const float *src_panorama, const float *ref_face_pose,
+                                const float *src_face_pose, const float *intrinsics, const float *depths,
+                                const float *blend_weights, const float *alphas, int32_t batch, int32_t pano_height,
+                                int32_t pano_width, int32_t low_size, int32_t face_size, int32_t num_planes, const int32_t *table,
+                                const int64_t *layer_start, void *pool_out, int32_t format, msi_stream_t stream);
 
 /* ---- image scores --------------------------------------------------------------------
  * eval.py:127-174 (tf.image.ssim, tf.image.psnr with max_val 255; the mean absolute difference of consecutive frames) for

@@ -106,6 +106,10 @@ SIGNATURES = {
     "msi_mpi_render_views": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_cube_render_views": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_equirect_to_cube_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "msi_cube_plane_sweep_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "msi_cube_sweep_volume_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "msi_cube_hres_layers": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "msi_cube_hres_layers_sparse": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "msi_score_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),
     "msi_score_images": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, ctypes.c_double, ctypes.c_uint32, _P, _P, c_size_t, _P]),
     "msi_net_layer_info": (_I, [POINTER(NetDesc), _I, POINTER(LayerInfo)]),

@@ -10,6 +10,8 @@
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_planar_hres.hip   the PP high-res stack in one pass, dense or sparse: pp_hres_layers_kernel, pp_hres_layers_sparse_kernel
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
+//   geo_cube_sweep.hip    the cube path's source half sampled from the source PANORAMA, across face edges: cube_sweep_kernel, cube_sweep_volume_bf16_kernel,
+//                         cube_hres_layers_kernel, cube_hres_layers_sparse_kernel
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
 // sharing is a contract.  What a single family uses lives in that family's unit.
 //
@@ -551,6 +553,107 @@ __device__ __forceinline__ HresRgb pp_hres_fetch(const PpHresPixel &p, const Hre
 __device__ __forceinline__ float4 pp_hres_texel(const PpHresPixel &p, float depth, int width, int height, float w, float alpha) {
   const HresTaps t = pp_hres_taps(p, depth, width, height);
   return hres_blend(t, pp_hres_fetch(p, t), w, alpha);
+}
+
+// ---- cube-sweep (cube_sweep_kernel, cube_sweep_volume_bf16_kernel, cube_hres_layers_kernel, cube_hres_layers_sparse_kernel: geo_cube_sweep.hip): ONE definition
+// of where a plane point of a cube face lies in the source PANORAMA, so that the fp32 sweep, the bf16 volume and the high-res builders agree bit for bit.
+// (x, y, z) is apply_pose(P, backproject_planar) as pp_sweep_kernel has it; the face sweep goes on to pr = (K4 @ P) (x, y, z, 1) = K Y with
+// Y = apply_pose(P, (x, y, z)) -- the reference's doubled pose (geo_planar.hip) -- so Y is the direction the face sweep samples wherever its (u, v) falls
+// inside the face.  Here Y is looked up in the panorama along itself: R_f Y with equirect_to_cube_kernel's face table (a signed permutation; f is
+// workgroup-uniform), that kernel's lat-long mapping lon = atan2(x + 0, z + 0), lat = asin(y / |dir|) through t_angles (atan2(y, hypot(x, z)) is that
+// arcsine; -DMSI_FAST_TAIL=0: libm), u = (lon + pi) / 2pi W - 0.5, v = (lat + pi/2) / pi H - 0.5, and its sampler: u clamped to [-0.5, W - 0.5] and
+// wrapped, v clamped to [0, H - 1], fmaxf first so that a NaN (Y = 0, a non-finite pose) is the lower bound BEFORE the float -> int conversion; the
+// weights and blend4's order are that kernel's.  Every offset lies inside one sample's [H,W,3] panorama for any input (H * W * 12 < 2^31, checked on
+// the host); the range-checked descriptor is a second line.
+__device__ __forceinline__ TapsB cube_pano_taps(const float *__restrict__ P, int f, float x, float y, float z, int pano_h, int pano_w) {
+  // the pose once more: Y = apply_pose(P, a), rows 0..2
+  const float yx = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
+  const float yy = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
+  const float yz = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
+  float cx, cy, cz;                                                             // R_f Y
+  switch (f) {
+    case 0: cx = yx; cy = yy; cz = yz; break;
+    case 1: cx = yz; cy = yy; cz = -yx; break;
+    case 2: cx = -yx; cy = yy; cz = -yz; break;
+    case 3: cx = -yz; cy = yy; cz = yx; break;
+    case 4: cx = yx; cy = -yz; cz = yy; break;
+    default: cx = yx; cy = yz; cz = -yy; break;
+  }
+  // t_angles' (x, z) are the render frame's: cube (z, x); "+ 0.0f" turns -0 into +0 (one longitude at a pole, as equirect_to_cube_kernel)
+  float lon_neg, lat;
+  t_angles(cz + 0.0f, cy, cx + 0.0f, t_sqrt((cx * cx + cy * cy) + cz * cz), lon_neg, lat);
+  const float PI = 3.14159265358979323846f;
+  float u = ((PI - lon_neg) * ((float)pano_w * 0.15915494309189535f)) - 0.5f;   // (W / 2pi and H / pi: wave-uniform)
+  float v = ((lat + 0.5f * PI) * ((float)pano_h * 0.31830988618379069f)) - 0.5f;
+  u = fminf(fmaxf(u, -0.5f), (float)pano_w - 0.5f);
+  v = fminf(fmaxf(v, 0.0f), (float)(pano_h - 1));
+  const float fx0 = floorf(u), fy0 = floorf(v);
+  const float du = u - fx0, dv = v - fy0;
+  int x0 = min((int)fx0, pano_w - 1);                   // in [-1, W-1] ((float)W - 0.5f is W itself from 2^24 on)
+  const int y0 = min((int)fy0, pano_h - 1);             // in [0, H-1]
+  int x1 = x0 + 1;
+  const int y1 = min(y0 + 1, pano_h - 1);
+  x0 = x0 < 0 ? x0 + pano_w : x0;
+  x1 = x1 >= pano_w ? x1 - pano_w : x1;
+  TapsB t;
+  t.oa = (unsigned)(y0 * pano_w + x0) * 12u; t.ob = (unsigned)(y0 * pano_w + x1) * 12u;
+  t.oc = (unsigned)(y1 * pano_w + x0) * 12u; t.od = (unsigned)(y1 * pano_w + x1) * 12u;
+  t.wa = (1.0f - dv) * (1.0f - du); t.wb = (1.0f - dv) * du; t.wc = dv * (1.0f - du); t.wd = dv * du;
+  return t;
+}
+// one sample's panorama [H,W,3] as a range-checked buffer
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t cube_pano_rsrc(const float *__restrict__ panorama, int sample, int pano_h, int pano_w) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(panorama + (size_t)sample * pano_h * pano_w * 3), 0, pano_h * pano_w * 12, 0x00020000);
+}
+
+// The texel of the cube high-res stack: the PP texel above with its background taken from the source panorama.  Entry n of the [6B,...] batch is face
+// n % 6 of sample n / 6; the foreground (ref face, ref pose) is pp_hres_source / pp_hres_source_taps unchanged, and there is no equal-poses shortcut:
+// the two sources are different images.  Steps as there: cube_hres_taps -> cube_hres_fetch -> hres_blend.
+struct CubeHresPixel {
+  PpHresSource s0;                 // the ref face
+  __amdgpu_buffer_rsrc_t pano;     // the source panorama of this cube
+  const float *P1;                 // the face's source pose
+  float S, T, fx, fy, cx, cy;
+  int f, pano_h, pano_w;
+};
+__device__ __forceinline__ CubeHresPixel cube_hres_pixel(const float *__restrict__ ref_faces, const float *__restrict__ panorama,
+                                                         const float *__restrict__ pose0, const float *__restrict__ pose1,
+                                                         const float *__restrict__ intrinsics, int n, int i, int j, int height, int width, int pano_h,
+                                                         int pano_w, float s0, float sstep, float t0, float tstep) {
+  CubeHresPixel p;
+  const float *Kb = intrinsics + (size_t)n * 9;
+  p.fx = Kb[0]; p.fy = Kb[4]; p.cx = Kb[2]; p.cy = Kb[5];
+  p.S = s0 + sstep * (float)j; p.T = t0 + tstep * (float)i;
+  p.s0 = pp_hres_source(ref_faces, pose0, Kb, n, height, width);
+  const int sample = n / 6;
+  p.f = n - sample * 6; p.pano_h = pano_h; p.pano_w = pano_w;
+  p.pano = cube_pano_rsrc(panorama, sample, pano_h, pano_w);
+  p.P1 = pose1 + (size_t)n * 16;
+  return p;
+}
+__device__ __forceinline__ HresTaps cube_hres_taps(const CubeHresPixel &p, float depth, int width, int height) {
+  HresTaps t;
+  // backproject_planar (spherical.py:146-148)
+  const float x = ((depth * p.S) * p.cx) / p.fx;
+  const float y = ((depth * p.T) * p.cy) / p.fy;
+  const float z = depth * 1.0f;
+  t.fg = pp_hres_source_taps(p.s0, x, y, z, width, height);
+  const float *P = p.P1;   // apply_pose, as pp_hres_source_taps begins
+  const float ax = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
+  const float ay = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
+  const float az = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
+  t.bg = cube_pano_taps(P, p.f, ax, ay, az, p.pano_h, p.pano_w);
+  return t;
+}
+__device__ __forceinline__ HresRgb cube_hres_fetch(const CubeHresPixel &p, const HresTaps &t) {
+  HresRgb g;
+  g.fg = gather3_load(p.s0.img, t.fg);
+  g.bg = gather3_load(p.pano, t.bg);
+  return g;
+}
+__device__ __forceinline__ float4 cube_hres_texel(const CubeHresPixel &p, float depth, int width, int height, float w, float alpha) {
+  const HresTaps t = cube_hres_taps(p, depth, width, height);
+  return hres_blend(t, cube_hres_fetch(p, t), w, alpha);
 }
 
 // ---- sweep, layers (pack / unpack / hres) and planar: the 16-byte store of every streaming kernel; its host side is beyond_infinity_cache below.

@@ -1258,34 +1258,94 @@ class MSI(object):
         N.check(getattr(N.lib, name)(*(lead + tail)), name)
         return rgb, dep
 
+    SRC_SAMPLINGS = ('face', 'panorama')
+
+    def _src_sampling(self, who, src_sampling):
+        if src_sampling not in self.SRC_SAMPLINGS:
+            raise ValueError("%s: src_sampling must be one of %s, not %r" % (who, self.SRC_SAMPLINGS, src_sampling))
+        return src_sampling == 'panorama'
+
+    def _cube_sweep_inputs(self, who, ref_faces, src_panorama, face_src_poses, face_intrinsics):
+        """The checked fp32 inputs the panorama-sampling entry points share -> (ref_faces, panorama, eye, face_src, kf, B, S)."""
+        ref_faces, pano = self._f32(ref_faces), self._f32(src_panorama)
+        if ref_faces.dim() != 4 or ref_faces.shape[3] != 3 or ref_faces.shape[1] != ref_faces.shape[2] or ref_faces.shape[0] % 6:
+            raise ValueError("%s: ref_faces must be [6B,S,S,3], got %s" % (who, tuple(ref_faces.shape)))
+        b, s = ref_faces.shape[0] // 6, ref_faces.shape[1]
+        if pano.dim() != 4 or pano.shape[0] != b or pano.shape[3] != 3 or pano.shape[1] < 2 or pano.shape[2] < 2:
+            raise ValueError("%s: src_panorama must be [B,Hp,Wp,3] with B = %d and Hp, Wp >= 2, got %s" % (who, b, tuple(pano.shape)))
+        if s < 2:
+            raise ValueError("%s: a perspective sweep needs faces of at least 2 x 2" % who)
+        face_src, kf = self._f32(face_src_poses), self._f32(face_intrinsics)
+        if face_src.numel() != 6 * b * 16 or kf.numel() != 6 * b * 9:
+            raise ValueError("%s: face_src_poses must be [6B,4,4] and face_intrinsics [6B,3,3] with 6B = %d" % (who, 6 * b))
+        eye = torch.eye(4, dtype=torch.float32, device=self.device).expand(6 * b, 4, 4).contiguous()
+        return ref_faces, pano, eye, face_src, kf, b, s
+
+    def format_cube_input(self, ref_faces, src_panorama, face_src_poses, planes, face_intrinsics, dtype=None):
+        """format_network_input for a cube whose source half is sampled from the source PANORAMA: ref_faces [6B,S,S,3] and
+        src_panorama [B,Hp,Wp,3] (both preprocessed, [-1,1]), face_src_poses [6B,4,4] (cubemap.face_poses of the source pose),
+        face_intrinsics [6B,3,3] -> net_input [6B,S,S,6D].  The ref half is the perspective sweep of the ref faces with the
+        identity pose, as format_network_input computes it; in the src half a plane point of face f is looked up in the
+        panorama along its own direction (include/msi_hip.h states the sample position), so a point that projects past the
+        face's border gets the neighbouring face's content, not the opposite side of its own face.  The model's dtype decides
+        as in format_network_input (dtype='f32' forces fp32): bf16 is one launch (msi_cube_sweep_volume_bf16), fp32 is
+        msi_perspective_plane_sweep_f32 for the ref half and msi_cube_plane_sweep_f32 for the src half."""
+        ref_faces, pano, eye, face_src, kf, b, s = self._cube_sweep_inputs("format_cube_input", ref_faces, src_panorama, face_src_poses,
+                                                                          face_intrinsics)
+        depths = self._planes(planes)
+        nd = depths.numel()
+        hp, wp = pano.shape[1], pano.shape[2]
+        bf16 = (dtype or self.dtype) == 'bf16'
+        psv = torch.empty((6 * b, s, s, 6 * nd), dtype=torch.bfloat16 if bf16 else torch.float32, device=self.device)
+        if bf16:
+            N.check(N.lib.msi_cube_sweep_volume_bf16(ref_faces.data_ptr(), pano.data_ptr(), eye.data_ptr(), face_src.data_ptr(), kf.data_ptr(),
+                                                     depths.data_ptr(), b, hp, wp, s, nd, psv.data_ptr(), self._stream()),
+                    "msi_cube_sweep_volume_bf16")
+        else:
+            N.check(N.lib.msi_perspective_plane_sweep_f32(ref_faces.data_ptr(), eye.data_ptr(), kf.data_ptr(), depths.data_ptr(), 6 * b, s, s, nd,
+                                                          psv.data_ptr(), 6 * nd, 0, self._stream()), "msi_perspective_plane_sweep_f32")
+            N.check(N.lib.msi_cube_plane_sweep_f32(pano.data_ptr(), face_src.data_ptr(), kf.data_ptr(), depths.data_ptr(), b, hp, wp, s, nd,
+                                                   psv.data_ptr(), 6 * nd, 3 * nd, self._stream()), "msi_cube_plane_sweep_f32")
+        return psv
+
     def infer_cube(self, raw_src_equirect, raw_ref_equirect, src_pose, face_size, planes, face_intrinsics=None,
-                   layer_format='f32', ngf=64, extra_outputs='', which_color_pred='blend_psv'):
+                   layer_format='f32', ngf=64, extra_outputs='', which_color_pred='blend_psv', src_sampling='face'):
         """A 360-degree pair through the PP network, face by face: preprocess both panoramas [B,H,W,3], equirect_to_cube each,
         view the faces as a batch [6B,S,S,3], format_network_input with ref_pose = I and src_pose =
         cubemap.face_poses(src_pose) (src_pose [4,4] or [B,4,4]: the source camera in the cube frame = the reference
         camera's frame), then infer_layers.  Returns the pred dict; its stack (pred['rgba_layers'] [6B,S,S,D,4] and / or
-        pred['packed_layers'], which carries `planes`) goes straight into cube_render_views.  Pure composition: no kernel of
-        its own.  For input_type='PP' models only.  The panoramas are single-centre equirectangular images: the faces of an
-        ODS panorama are not perspective images."""
+        pred['packed_layers'], which carries `planes`) goes straight into cube_render_views.  For input_type='PP' models only.
+        The panoramas are single-centre equirectangular images: the faces of an ODS panorama are not perspective images.
+        src_sampling: 'face' (the default) sweeps each face's own source image with the reference's wrap-around sampler --
+        nothing is fetched across a cube edge: a plane point that projects past the face's border gets the opposite side of
+        the same face.  'panorama' fetches across edges: the source panorama is preprocessed and never cut into faces, and
+        format_cube_input samples it along every plane point's own direction (the interior of a face agrees with 'face' up to
+        the resampling of the cut)."""
         if self.input_type != 'PP':
             raise ValueError("infer_cube runs the perspective (PP) network on cube faces: build the model with input_type='PP'")
+        panorama = self._src_sampling("infer_cube", src_sampling)
         src, ref = self.preprocess_image(raw_src_equirect), self.preprocess_image(raw_ref_equirect)
-        src_faces, ref_faces, eye, face_src, kf = self._cube_faces("infer_cube", src, ref, src_pose, face_size, face_intrinsics)
-        net_input = self.format_network_input(ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye)
+        src_faces, ref_faces, eye, face_src, kf = self._cube_faces("infer_cube", src, ref, src_pose, face_size, face_intrinsics, cut_src=not panorama)
+        if panorama:
+            net_input = self.format_cube_input(ref_faces, src, face_src, planes, kf)
+        else:
+            net_input = self.format_network_input(ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye)
         pred = self.infer_layers(net_input, len(planes), ngf, extra_outputs, which_color_pred, layer_format=layer_format)
         return self._carrying(pred, planes)
 
-    def _cube_faces(self, who, src, ref, src_pose, face_size, face_intrinsics):
+    def _cube_faces(self, who, src, ref, src_pose, face_size, face_intrinsics, cut_src=True):
         """What infer_cube and hres_cube_layers make of a pair of panoramas [B,H,W,3] (fp32, on the device): both cut into faces
         [6B,S,S,3] (equirect_to_cube), ref_pose = I and src_pose = cubemap.face_poses(src_pose) per face [6B,4,4], and the face
-        camera per face [6B,3,3] -> (src_faces, ref_faces, eye, face_src, kf)."""
+        camera per face [6B,3,3] -> (src_faces, ref_faces, eye, face_src, kf).  Cut faces are what src_sampling='face' sweeps,
+        face by face, nothing fetched across a cube edge; src_sampling='panorama' fetches across edges from the source panorama
+        itself and passes cut_src=False: src_faces is None, the source panorama is not cut."""
         from . import cubemap
         s = int(face_size)
         if src.dim() != 4 or src.shape[-1] != 3 or src.shape != ref.shape:
             raise ValueError("%s: the panoramas must be [B,H,W,3] and agree" % who)
         b = src.shape[0]
         k = cubemap.default_face_intrinsics(s) if face_intrinsics is None else face_intrinsics
-        src_faces = self.equirect_to_cube(src, s, k).reshape(6 * b, s, s, 3)
+        src_faces = self.equirect_to_cube(src, s, k).reshape(6 * b, s, s, 3) if cut_src else None
         ref_faces = self.equirect_to_cube(ref, s, k).reshape(6 * b, s, s, 3)
         sp = self._f32(src_pose).reshape(-1, 4, 4)
         if sp.shape[0] == 1 and b > 1:
@@ -1301,7 +1361,7 @@ class MSI(object):
         return src_faces, ref_faces, eye, face_src, kf
 
     def hres_cube_layers(self, blend_weights, alphas, raw_hres_src_equirect, raw_hres_ref_equirect, src_pose, face_size, planes,
-                         face_intrinsics=None, layer_format='rgba8', sparse=False):
+                         face_intrinsics=None, layer_format='rgba8', sparse=False, src_sampling='face'):
         """The high-res stack of a cube, for cube_render_views: blend_weights / alphas [6B,S,S,D] of infer_cube(extra_outputs=
         'blend_weights alphas') and the pair of high-res panoramas [B,H,W,3] (uint8 [0,255] or float [0,1]) -> six face stacks of
         face_size per sample.  Pure composition: the raw panoramas are cut into faces [6B,face_size,face_size,3] in [0,1]
@@ -1310,13 +1370,67 @@ class MSI(object):
         dict) or mpi_hres_layers_sparse (sparse=True: {'sparse_layers': SparseLayers}, face_size % 16 == 0) builds the stack of
         batch 6B, which goes straight into cube_render_views.  layer_format as there.  Packed is the default here: the viewer
         refuses a sample whose six fp32 face stacks reach 2^31 bytes (face_size > 836 at D = 32; 1182 in rgba16f, 1672 in rgba8).
-        Any model.  Faces are filtered one by one: nothing is fetched across a cube edge."""
+        Any model.  src_sampling='face' (the default): the background comes from each face's own cut source image, face by face
+        -- nothing is fetched across a cube edge.  src_sampling='panorama' fetches across edges: the source panorama is not cut,
+        and the background taps of every texel come from the panorama along the plane point's own direction, in one launch
+        (msi_cube_hres_layers / msi_cube_hres_layers_sparse): the bits of format_cube_input at face_size ->
+        msi_resize_bilinear_f32 -> msi_assemble_rgba_scaled_f32, packed or sparse as in 'face' mode."""
+        panorama = self._src_sampling("hres_cube_layers", src_sampling)
         to_unit = lambda x: (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(self.device)
         src, ref = to_unit(raw_hres_src_equirect), to_unit(raw_hres_ref_equirect)
         src, ref = (x.float() / 255.0 if x.dtype == torch.uint8 else x.float() for x in (src, ref))
-        src_faces, ref_faces, eye, face_src, kf = self._cube_faces("hres_cube_layers", src, ref, src_pose, face_size, face_intrinsics)
+        src_faces, ref_faces, eye, face_src, kf = self._cube_faces("hres_cube_layers", src, ref, src_pose, face_size, face_intrinsics,
+                                                                   cut_src=not panorama)
+        if panorama:
+            return self._cube_hres_build(blend_weights, alphas, self.preprocess_image(ref_faces), self.preprocess_image(src), face_src, planes, kf,
+                                         sparse, *self._layer_formats(layer_format))
         build = self.mpi_hres_layers_sparse if sparse else self.mpi_hres_layers
         return build(blend_weights, alphas, ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye, layer_format=layer_format)
+
+    def _cube_hres_build(self, blend_weights, alphas, ref_faces, src_panorama, face_src_poses, planes, face_intrinsics, sparse, want_f32, pfmt):
+        """hres_cube_layers(src_sampling='panorama'): _hres_build / _hres_build_sparse with the cube entry points.  ref_faces [6B,S,S,3] and
+        src_panorama [B,Hp,Wp,3] are preprocessed ([-1,1]); (want_f32, pfmt) = _layer_formats of the caller's request."""
+        who = "hres_cube_layers"
+        ref_faces, pano, eye, face_src, kf, b, s = self._cube_sweep_inputs(who, ref_faces, src_panorama, face_src_poses, face_intrinsics)
+        bw, al = self._f32(blend_weights), self._f32(alphas)
+        if bw.dim() != 4 or bw.shape != al.shape or bw.shape[0] != 6 * b or bw.shape[1] != bw.shape[2]:
+            raise ValueError("%s: blend_weights and alphas must be [6B,s,s,D] with 6B = %d and agree" % (who, 6 * b))
+        low, d = bw.shape[1], bw.shape[3]
+        depths = self._depths(planes, d)
+        hp, wp = pano.shape[1], pano.shape[2]
+        head = (ref_faces.data_ptr(), pano.data_ptr(), eye.data_ptr(), face_src.data_ptr(), kf.data_ptr(), depths.data_ptr(), bw.data_ptr(),
+                al.data_ptr(), b, hp, wp, low, s, d)
+        if not sparse:
+            rgba = torch.empty((6 * b, d, s, s, 4), dtype=torch.float32, device=self.device) if want_f32 else None
+            codes = None
+            if pfmt is not None:
+                codes = torch.empty((6 * b, d, s, s, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+            N.check(N.lib.msi_cube_hres_layers(*head, _ptr(rgba), _ptr(codes), self.LAYER_FORMATS.get(pfmt, N.MSI_LAYERS_F32), self._stream()),
+                    "msi_cube_hres_layers")
+            out = {}
+            if rgba is not None:
+                out['rgba_layers'] = rgba.permute(0, 2, 3, 1, 4)
+            if codes is not None:
+                out['packed_layers'] = PackedLayers(codes, pfmt, planes)
+            return out
+        if want_f32 or pfmt is None:
+            raise ValueError("%s: sparse=True takes layer_format 'rgba8' or 'rgba16f' alone (fp32 pools are not built)" % who)
+        if s % TILE_H or s % TILE_W:
+            raise ValueError("a sparse stack needs H %% %d == 0 and W %% %d == 0, not %d x %d" % (TILE_H, TILE_W, s, s))
+        fmt = self.LAYER_FORMATS[pfmt]
+        table = torch.empty((6 * b, d, s // TILE_H, s // TILE_W), dtype=torch.int32, device=self.device)
+        counts = torch.empty((6 * b * d,), dtype=torch.int32, device=self.device)
+        N.check(N.lib.msi_hres_index_tiles_edge(al.data_ptr(), fmt, 6 * b, low, low, s, s, d, table.data_ptr(), counts.data_ptr(), self._stream()),
+                "msi_hres_index_tiles_edge")
+        layer_start = torch.zeros((6 * b * d + 1,), dtype=torch.int64, device=self.device)
+        if b * d:
+            layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(layer_start[-1].item())
+        pool = torch.empty((total, TILE_H, TILE_W, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+        if total:
+            N.check(N.lib.msi_cube_hres_layers_sparse(*head, table.data_ptr(), layer_start.data_ptr(), pool.data_ptr(), fmt, self._stream()),
+                    "msi_cube_hres_layers_sparse")
+        return {'sparse_layers': SparseLayers(table, layer_start, pool, pfmt, planes, border='edge')}
 
     # ------------------------------------------------------------------ image scores (eval.py:127-174 on the device)
     SCORE_TRANSFORMS = {'raw': N.MSI_SCORE_RAW, 'image': N.MSI_SCORE_IMAGE, 'depth': N.MSI_SCORE_DEPTH}
