@@ -248,8 +248,8 @@ __global__ void resize_bilinear_kernel(const float4 *__restrict__ in, float4 *__
 // FMT: MSI_LAYERS_F32 (no packed output), MSI_LAYERS_RGBA8 or MSI_LAYERS_RGBA16F; WITH_F32: the fp32 stack is written (too);
 // NT: bit 0 / bit 1 = non-temporal stores of the fp32 / the packed stack (the host sets a bit when that destination is larger
 // than the 256-MiB Infinity Cache; a template argument, as in pack_layers_kernel).
-// The texel itself -- hres_pixel, hres_corners / hres_lerp, hres_texel, hres_store_packed -- is in geometry_device.h: hres_layers_sparse_kernel
-// (geo_sparse_hres.hip) writes the same texels into a pool of kept tiles.
+// The texel (OdsHres, hres_texel) is in geometry_device.h: the PP and cube builders run this loop, restated, on their sources, and
+// hres_layers_sparse_kernel (geo_sparse_hres.hip) writes the same texels into a pool of kept tiles.
 template <int FMT, int WITH_F32, int NT>
 // (waves_per_eu with the maximum at MSI_HRES_WAVES too: with the texel in shared device functions the allocator settles at 93-95 VGPRs, which
 // would run five waves, and at five the launch is 5 % slower at 1280x640 -- same-process A/B in profiles/hres_sparse_isa.txt)
@@ -263,8 +263,7 @@ hres_layers_kernel(const float *__restrict__ image0, const float *__restrict__ i
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= width) return;
   const int i = blockIdx.y, b = blockIdx.z;
-
-  const HresPixel px = hres_pixel(image0, image1, pose0, pose1, intrinsics, trig, b, i, j, height, width);
+  const OdsHres px = ods_hres(image0, image1, pose0, pose1, intrinsics, trig, K, b, i, j, height, width);
   const HresCorners k = hres_corners(i, j, sy, sx, low_h, low_w, nd);
   const size_t low_base = (size_t)b * low_h * low_w * nd;          // (h * w * D < 2^31: checked on the host)
   const float *bw = blend_weights + low_base, *al = alphas + low_base;
@@ -276,7 +275,7 @@ hres_layers_kernel(const float *__restrict__ image0, const float *__restrict__ i
     const hres_vec av = hres_lerp(al + d0, k);
 #pragma unroll
     for (int q = 0; q < HRES_G; ++q) {
-      const float4 o = hres_texel(px, depths[d0 + q], K, width, height, wv[q], av[q]);
+      const float4 o = hres_texel(px, depths[d0 + q], wv[q], av[q]);
       if (WITH_F32) sweep_store16(reinterpret_cast<uint4 *>(rgba + texel), __builtin_bit_cast(uint4, o), NT & 1);
       if constexpr (FMT != MSI_LAYERS_F32) hres_store_packed<FMT, (NT >> 1) & 1>(packed, texel, o);
       texel += hw;
@@ -375,41 +374,14 @@ int msi_hres_layers(const float *ref_image, const float *src_image, const float 
                                blend_weights && alphas, batch, low_height, low_width, height, width, num_planes)) return e;
   if (batch == 0) return MSI_OK;
   const float sy = hres_scale(low_height, height), sx = hres_scale(low_width, width);
-  const int fmt = layers_out ? format : MSI_LAYERS_F32;
-  // non-temporal stores for a destination that cannot stay in the Infinity Cache (as msi_pack_layers)
-  const size_t texels = (size_t)batch * num_planes * height * width;
-  const int nt = (rgba_native && beyond_infinity_cache(texels * 16) ? 1 : 0) | (layers_out && beyond_infinity_cache(texels * (fmt == MSI_LAYERS_RGBA8 ? 4 : 8)) ? 2 : 0);
+  const PixConsts K = make_consts(height, width);
   const dim3 grid((unsigned)((width + 255) / 256), height, batch);
-#define MSI_LAUNCH_HRES(FMT, F32_, NT_)                                                                                              \
-  hipLaunchKernelGGL((hres_layers_kernel<FMT, F32_, NT_>), grid, dim3(256), 0, msi::as_stream(stream), ref_image, src_image,           \
-                     ref_curr_pose, src_curr_pose, intrinsics, depths, trig, blend_weights, alphas, low_height, low_width, height,   \
-                     width, num_planes, sy, sx, make_consts(height, width), reinterpret_cast<float4 *>(rgba_native), layers_out)
-#define MSI_LAUNCH_HRES_P(FMT)                                                                                             \
-  {                                                                                                                        \
-    if (rgba_native) {                                                                                                     \
-      switch (nt) {                                                                                                        \
-        case 0: MSI_LAUNCH_HRES(FMT, 1, 0); break;                                                                         \
-        case 1: MSI_LAUNCH_HRES(FMT, 1, 1); break;                                                                         \
-        case 2: MSI_LAUNCH_HRES(FMT, 1, 2); break;                                                                         \
-        default: MSI_LAUNCH_HRES(FMT, 1, 3); break;                                                                        \
-      }                                                                                                                    \
-    } else if (nt) {                                                                                                       \
-      MSI_LAUNCH_HRES(FMT, 0, 2);                                                                                          \
-    } else {                                                                                                               \
-      MSI_LAUNCH_HRES(FMT, 0, 0);                                                                                          \
-    }                                                                                                                      \
-  }
-  if (fmt == MSI_LAYERS_RGBA8) {
-    MSI_LAUNCH_HRES_P(MSI_LAYERS_RGBA8)
-  } else if (fmt == MSI_LAYERS_RGBA16F) {
-    MSI_LAUNCH_HRES_P(MSI_LAYERS_RGBA16F)
-  } else if (nt) {
-    MSI_LAUNCH_HRES(MSI_LAYERS_F32, 1, 1);
-  } else {
-    MSI_LAUNCH_HRES(MSI_LAYERS_F32, 1, 0);
-  }
-#undef MSI_LAUNCH_HRES_P
-#undef MSI_LAUNCH_HRES
+  hipStream_t s = msi::as_stream(stream);
+  hres_dense_launch(format, rgba_native, layers_out, (size_t)batch * num_planes * height * width, [&](auto FMT, auto F32, auto NT) {
+    hipLaunchKernelGGL((hres_layers_kernel<decltype(FMT)::value, decltype(F32)::value, decltype(NT)::value>), grid, dim3(256), 0, s, ref_image,
+                       src_image, ref_curr_pose, src_curr_pose, intrinsics, depths, trig, blend_weights, alphas, low_height, low_width, height, width,
+                       num_planes, sy, sx, K, reinterpret_cast<float4 *>(rgba_native), layers_out);
+  });
   return msi::check_launch("hres_layers");
 }
 

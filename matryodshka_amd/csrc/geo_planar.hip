@@ -16,98 +16,41 @@ namespace {
 // threads and broadcast through LDS instead of by every thread; (b) a corner is ONE 12-byte buffer load, not three dword loads behind 64-bit address arithmetic;
 // (c) a wave's 64 / D complete pixels leave through a wave-private LDS strip as 16-byte-per-lane stores of whole 3 D-float runs instead of 3 dword stores at a
 // 12-byte stride per lane; non-temporal when the volume exceeds the Infinity Cache (sweep_store16).  Measured at configs[4] (64 faces, two sweeps each): DESIGN.md section 4.
+// The arithmetic is geometry_device.h's (the steps of the planar sweep, sweep_body); here is where pp_sweep_kernel samples: image b through its own camera.
+struct PpSweepSource {
+  const float *image, *P;          // the [B,H,W,3] batch; the pose [4,4] of sample b
+  int b, height, width;
+  template <int FAST> __device__ __forceinline__ void sample(const float *Kb, const Vec3 &a, float *o) const {
+    if (FAST) {
+      __shared__ float s_m[12];
+      if (threadIdx.x < 12) s_m[threadIdx.x] = k4_pose(Kb, P, threadIdx.x >> 2, threadIdx.x & 3);
+      __syncthreads();
+      wrap_gather3(image_rsrc(image, b, height, width), project_rows(s_m, a), width, height, o);
+      return;
+    }
+    const Uv p = project_k4_pose(Kb, P, a);
+    const Taps t = make_taps(p.u, p.v, width, height);
+    const float *img = image + (size_t)b * height * width * 3;
+    const float *pa = img + ((size_t)t.y0 * width + t.x0) * 3;
+    const float *pb = img + ((size_t)t.y0 * width + t.x1) * 3;
+    const float *pc = img + ((size_t)t.y1 * width + t.x0) * 3;
+    const float *pd = img + ((size_t)t.y1 * width + t.x1) * 3;
+    o[0] = blend4(t, pa[0], pb[0], pc[0], pd[0]);
+    o[1] = blend4(t, pa[1], pb[1], pc[1], pd[1]);
+    o[2] = blend4(t, pa[2], pb[2], pc[2], pd[2]);
+  }
+};
+
 template <int FAST>
 __global__ void __launch_bounds__(256)
 pp_sweep_kernel(const float *__restrict__ image, const float *__restrict__ pose,
                 const float *__restrict__ intrinsics, const float *__restrict__ depths, int batch,
                 int height, int width, int nd, float s0, float sstep, float t0, float tstep,
                 float *__restrict__ psv, int channels, int coff, unsigned nd_magic, int nt) {
-  // grid = (ceil(W*D / 256), H, B): 32-bit index math only (64-bit div/mod are emulated in ~100
-  // VALU instructions each and used to dominate this kernel)
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (!FAST && idx >= width * nd) return;
-  int j, d;
-  if (FAST) {
-    unsigned jq = __umulhi((unsigned)idx, nd_magic);   // idx / nd by multiply-high (+ one correction)
-    if ((unsigned)idx - jq * (unsigned)nd >= (unsigned)nd) ++jq;
-    j = (int)jq; d = idx - j * nd;
-  } else {
-    j = idx / nd; d = idx - j * nd;
-  }
-  const int i = blockIdx.y, b = blockIdx.z;
-  const long p = ((long)b * height + i) * width + j;
-  const float S = s0 + sstep * (float)j, T = t0 + tstep * (float)i;
-  const float depth = depths[d];
-  const float *Kb = intrinsics + (size_t)b * 9;
-  const float fx = Kb[0], fy = Kb[4], cx = Kb[2], cy = Kb[5];
-  // backproject_planar (spherical.py:146-148): x = depth*S*cx/fx, y = depth*T*cy/fy, z = depth*1
-  float x = ((depth * S) * cx) / fx;
-  float y = ((depth * T) * cy) / fy;
-  float z = depth * 1.0f;
-  const float *P = pose + (size_t)b * 16;
-  {  // apply_pose (projector.py:275-291)
-    const float ax = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
-    const float ay = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
-    const float az = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
-    x = ax; y = ay; z = az;
-  }
-  // project_perspective: M = K4 @ pose, rows 0..2; the padded column contributes 0 * pose[3][c]
-  float pr[3];
-  __shared__ float s_m[12];
-  if (FAST) {
-    if (threadIdx.x < 12) {
-      const int r = threadIdx.x >> 2, c = threadIdx.x & 3;
-      s_m[threadIdx.x] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 3; ++r) pr[r] = ((s_m[r * 4 + 0] * x + s_m[r * 4 + 1] * y) + s_m[r * 4 + 2] * z) + s_m[r * 4 + 3] * 1.0f;
-  } else {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    float m[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      m[c] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
-    pr[r] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * 1.0f;
-  }
-  }
-  const float u = pr[0] / pr[2], v = pr[1] / pr[2];
-  const Taps t = make_taps(u, v, width, height);
-  if (FAST) {
-    const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void *)(image + (size_t)b * height * width * 3), 0, height * width * 12, 0x00020000);
-    const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x0) * 12u, 0, 0));
-    const f32x3_g bq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x1) * 12u, 0, 0));
-    const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x0) * 12u, 0, 0));
-    const f32x3_g dq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x1) * 12u, 0, 0));
-    const float o0 = blend4(t, a.x, bq.x, c.x, dq.x), o1 = blend4(t, a.y, bq.y, c.y, dq.y), o2 = blend4(t, a.z, bq.z, c.z, dq.z);
-    // whole-pixel runs through the wave's strip: lane = (pixel of the wave, depth); the wave's 64 / D pixels are consecutive, each owns 3 D contiguous floats at + coff
-    __shared__ __attribute__((aligned(16))) float s_out[4][192];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float *w = s_out[wave];
-    __builtin_amdgcn_wave_barrier();
-    w[lane * 3 + 0] = o0; w[lane * 3 + 1] = o1; w[lane * 3 + 2] = o2;      // (lane = pl * D + d: the strip IS the pixels' runs back to back)
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 48) {
-      const int vpp = (3 * nd) >> 2;                                         // 16-byte vectors per pixel run
-      unsigned plq = __umulhi((unsigned)lane, 0xffffffffu / (unsigned)vpp + 1u);
-      if ((unsigned)lane - plq * (unsigned)vpp >= (unsigned)vpp) --plq;      // (lane < 48, vpp >= 3: the estimate is exact or one too large)
-      const int pl = (int)plq, k = lane - pl * vpp;
-      const long pw0 = ((long)b * height + i) * width + (long)((blockIdx.x * 256 + wave * 64) / nd);
-      uint4 *dst = reinterpret_cast<uint4 *>(psv + (size_t)(pw0 + pl) * channels + coff) + k;
-      sweep_store16(dst, reinterpret_cast<const uint4 *>(w)[lane], nt);
-    }
-    return;
-  }
-  const float *img = image + (size_t)b * height * width * 3;
-  const float *pa = img + ((size_t)t.y0 * width + t.x0) * 3;
-  const float *pb = img + ((size_t)t.y0 * width + t.x1) * 3;
-  const float *pc = img + ((size_t)t.y1 * width + t.x0) * 3;
-  const float *pd = img + ((size_t)t.y1 * width + t.x1) * 3;
-  float *o = psv + (size_t)p * channels + coff + d * 3;
-  o[0] = blend4(t, pa[0], pb[0], pc[0], pd[0]);
-  o[1] = blend4(t, pa[1], pb[1], pc[1], pd[1]);
-  o[2] = blend4(t, pa[2], pb[2], pc[2], pd[2]);
+  // grid = (ceil(W*D / 256), H, B)
+  const int b = blockIdx.z;
+  sweep_body<FAST>(PpSweepSource{image, pose + (size_t)b * 16, b, height, width}, intrinsics, depths, height, width, nd, s0, sstep, t0, tstep, psv, channels,
+                   coff, nd_magic, nt);
 }
 
 // The whole bf16 PP network input of format_network_input (msi.py:1157-1161) in one launch: ref into channels [0, 3D), src into [3D, 6D)
@@ -123,112 +66,21 @@ pp_sweep_kernel(const float *__restrict__ image, const float *__restrict__ pose,
 // (H * W * 12 < 2^31, checked on the host) in both forms; make_taps' wrapped indices lie inside the image.  The kernel is VALU-bound
 // (DESIGN.md section 4).  NT is a template argument, not sweep_store16's runtime flag: with the packed value computed ahead of the
 // branch, hipcc merges the two stores into one plain store.
+// (the src half of sweep_volume_bf16_body: a second image of the ref half's camera)
+struct PpSecondImage {
+  static constexpr bool CAMERA = true;
+  const float *image, *P;          // the [B,H,W,3] batch; the pose of sample b
+};
+
 template <int FAST, int NT>
 __global__ void __launch_bounds__(256)
 pp_sweep_volume_bf16_kernel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
                             const float *__restrict__ pose1, const float *__restrict__ intrinsics, const float *__restrict__ depths,
                             int height, int width, int nd, int nd_shift, float s0, float sstep, float t0, float tstep,
                             unsigned short *__restrict__ psv) {
-  // grid = (ceil(W*D / 256), H, B): 32-bit index math only
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  const int i = blockIdx.y, b = blockIdx.z;
-  const float *Kb = intrinsics + (size_t)b * 9;
-  const float fx = Kb[0], fy = Kb[4], cx = Kb[2], cy = Kb[5];
-  const float T = t0 + tstep * (float)i;
-  __shared__ float s_m[2][12];
-  __shared__ float s_y[64];
-  if (FAST) {
-    // project_perspective's M = K4 @ pose (rows 0..2; the padded column contributes 0 * pose[3][c]) per source, and
-    // backproject_planar's y = depth*T*cy/fy per plane of this row
-    const int tid = threadIdx.x;
-    if (tid < 24) {
-      const int s = tid / 12, e = tid - s * 12, r = e >> 2, c = e & 3;
-      const float *P = (s ? pose1 : pose0) + (size_t)b * 16;
-      s_m[s][e] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
-    } else if (tid >= 64 && tid < 64 + nd) {
-      s_y[tid - 64] = ((depths[tid - 64] * T) * cy) / fy;
-    }
-    __syncthreads();
-    if (idx >= width * nd) return;   // (W * D) % 64 == 0: whole waves
-  } else {
-    if (idx >= width * nd) return;
-  }
-  const int j = FAST ? idx >> nd_shift : idx / nd;
-  const int d = FAST ? idx & (nd - 1) : idx - j * nd;
-  const float S = s0 + sstep * (float)j;
-  const float depth = depths[d];
-  // backproject_planar (spherical.py:146-148), shared by both sources
-  const float x0 = ((depth * S) * cx) / fx;
-  const float y0 = FAST ? s_y[d] : ((depth * T) * cy) / fy;
-  const float z0 = depth * 1.0f;
-  const int img_bytes = height * width * 12;
-  float out[2][3];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const float *P = (s ? pose1 : pose0) + (size_t)b * 16;
-    // apply_pose (projector.py:275-291)
-    const float x = ((P[0] * x0 + P[1] * y0) + P[2] * z0) + P[3] * 1.0f;
-    const float y = ((P[4] * x0 + P[5] * y0) + P[6] * z0) + P[7] * 1.0f;
-    const float z = ((P[8] * x0 + P[9] * y0) + P[10] * z0) + P[11] * 1.0f;
-    float pr[3];
-    if (FAST) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) pr[r] = ((s_m[s][r * 4 + 0] * x + s_m[s][r * 4 + 1] * y) + s_m[s][r * 4 + 2] * z) + s_m[s][r * 4 + 3] * 1.0f;
-    } else {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        float m[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          m[c] = ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
-        pr[r] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3] * 1.0f;
-      }
-    }
-    const float u = pr[0] / pr[2], v = pr[1] / pr[2];
-    const Taps t = make_taps(u, v, width, height);
-    const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void *)((s ? image1 : image0) + (size_t)b * height * width * 3), 0, img_bytes, 0x00020000);
-    const f32x3_g a = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x0) * 12u, 0, 0));
-    const f32x3_g bq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y0 * width + t.x1) * 12u, 0, 0));
-    const f32x3_g c = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x0) * 12u, 0, 0));
-    const f32x3_g dq = __builtin_bit_cast(f32x3_g, (u32x3_g)__builtin_amdgcn_raw_buffer_load_b96(img, (unsigned)(t.y1 * width + t.x1) * 12u, 0, 0));
-    out[s][0] = blend4(t, a.x, bq.x, c.x, dq.x);
-    out[s][1] = blend4(t, a.y, bq.y, c.y, dq.y);
-    out[s][2] = blend4(t, a.z, bq.z, c.z, dq.z);
-  }
-  const long p = ((long)b * height + i) * width + j;
-  if (FAST) {
-    // the wave's 64 / D pixels are consecutive and each owns 6 D contiguous channels: lane = pl * D + d writes its two triples into the
-    // strip at pl * 6 D + {0, 3 D} + 3 d, then lanes 0..47 each pack 8 of the 384 values into one 16-byte store
-    __shared__ __attribute__((aligned(16))) float s_out[4][384];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pl = lane >> nd_shift;
-    float *w = s_out[wave];
-    __builtin_amdgcn_wave_barrier();
-    const int e0 = pl * 6 * nd + 3 * d;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      w[e0 + c] = out[0][c];
-      w[e0 + 3 * nd + c] = out[1][c];
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 48) {
-      const float4 lo = reinterpret_cast<const float4 *>(w)[2 * lane], hi = reinterpret_cast<const float4 *>(w)[2 * lane + 1];
-      uint4 pk;
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.x) : "v"(lo.x), "v"(lo.y));
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.y) : "v"(lo.z), "v"(lo.w));
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.z) : "v"(hi.x), "v"(hi.y));
-      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.w) : "v"(hi.z), "v"(hi.w));
-      uint4 *dst = reinterpret_cast<uint4 *>(psv + (size_t)(p - pl) * (6 * nd)) + lane;   // (p - pl: the wave's first pixel)
-      sweep_store16(dst, pk, NT);
-    }
-    return;
-  }
-  unsigned short *o = psv + (size_t)p * (6 * nd) + 3 * d;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    o[c] = f32_to_bf16(out[0][c]);
-    o[3 * nd + c] = f32_to_bf16(out[1][c]);
-  }
+  // grid = (ceil(W*D / 256), H, B)
+  sweep_volume_bf16_body<FAST, NT>(image0, pose0 + (size_t)blockIdx.z * 16, PpSecondImage{image1, pose1 + (size_t)blockIdx.z * 16}, intrinsics, depths,
+                                   height, width, nd, nd_shift, s0, sstep, t0, tstep, psv);
 }
 
 // MSI.mpi_render_view (msi.py:527-548): pj.projective_forward_homography (projector.py:343-373) ->

@@ -1,10 +1,11 @@
 // The high-res layer stack of the PP path in ONE pass (msi_pp_hres_layers, msi_pp_hres_layers_sparse): what the planar viewer (msi_mpi_render_views)
 // and the cube-map viewer (msi_cube_render_views) read, fp32 or packed, dense or sparse.  The three-launch form -- pp_sweep_kernel twice (geo_planar.hip)
 // -> resize_bilinear_kernel -> assemble_kernel<0, COLOR_BLEND_PSV> (geo_layers.hip) -- writes and re-reads a [B,Hh,Wh,6D] volume and a [B,Hh,Wh,2D]
-// tensor; these kernels run the same arithmetic per texel (pp_hres_pixel / pp_hres_taps / pp_hres_fetch, then hres_corners / hres_lerp, hres_blend and
-// hres_store_packed of the ODS builder: geometry_device.h) without contraction, so every texel has the bits of the three launches.  The mapping, the
-// store policy and the sparse structure are hres_layers_kernel's (geo_layers.hip) and hres_layers_sparse_kernel's (geo_sparse_hres.hip); the table of a
-// sparse PP stack comes from msi_hres_index_tiles_edge (geo_sparse_hres.hip).  Kernels first, their C ABI entry points below.
+// tensor; these kernels run the same arithmetic per texel (the PP source PpHres: pp_hres, taps, fetch; then hres_corners / hres_lerp, hres_blend and
+// hres_store_packed: geometry_device.h) without contraction, so every texel has the bits of the three launches.  The mapping, the store policy and the
+// sparse structure are hres_layers_kernel's (geo_layers.hip: its loop, restated) and hres_layers_sparse_kernel's (geo_sparse_hres.hip: its
+// loop, restated), behind the same launchers (hres_dense_launch, hres_sparse_launch); the table of a sparse PP stack comes from
+// msi_hres_index_tiles_edge (geo_sparse_hres.hip).  Kernels first, their C ABI entry points below.
 #include "geometry_device.h"
 #include "geo_sparse.h"
 
@@ -14,7 +15,8 @@ namespace {
 
 // hres_layers_kernel's mapping: grid = (ceil(W / 256), H, B), a lane is one pixel of a 256-column run of row blockIdx.y and walks the layers; S, T and the
 // resize corners are per-pixel work done once, K, the poses and both M are per-sample (SGPRs), each layer's store is one contiguous run per wave.
-// FMT, WITH_F32, NT: as hres_layers_kernel.
+// FMT, WITH_F32, NT: as hres_layers_kernel.  (The loop is written per kernel: as one function under the three dense builders it missed the timing
+// margin, profiles/hres_bodies_isa.txt; written out, on the source type, each builder has the instructions it had before.)
 template <int FMT, int WITH_F32, int NT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSI_HRES_WAVES, MSI_HRES_WAVES)))
 pp_hres_layers_kernel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
@@ -24,8 +26,7 @@ pp_hres_layers_kernel(const float *__restrict__ image0, const float *__restrict_
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= width) return;
   const int i = blockIdx.y, b = blockIdx.z;
-
-  const PpHresPixel px = pp_hres_pixel(image0, image1, pose0, pose1, intrinsics, b, i, j, height, width, s0, sstep, t0, tstep);
+  const PpHres px = pp_hres(image0, image1, pose0, pose1, intrinsics, b, i, j, height, width, s0, sstep, t0, tstep);
   const HresCorners k = hres_corners(i, j, sy, sx, low_h, low_w, nd);
   const size_t low_base = (size_t)b * low_h * low_w * nd;          // (h * w * D < 2^31: checked on the host)
   const float *bw = blend_weights + low_base, *al = alphas + low_base;
@@ -37,7 +38,7 @@ pp_hres_layers_kernel(const float *__restrict__ image0, const float *__restrict_
     const hres_vec av = hres_lerp(al + d0, k);
 #pragma unroll
     for (int q = 0; q < HRES_G; ++q) {
-      const float4 o = pp_hres_texel(px, depths[d0 + q], width, height, wv[q], av[q]);
+      const float4 o = hres_texel(px, depths[d0 + q], wv[q], av[q]);
       if (WITH_F32) sweep_store16(reinterpret_cast<uint4 *>(rgba + texel), __builtin_bit_cast(uint4, o), NT & 1);
       if constexpr (FMT != MSI_LAYERS_F32) hres_store_packed<FMT, (NT >> 1) & 1>(packed, texel, o);
       texel += hw;
@@ -45,9 +46,10 @@ pp_hres_layers_kernel(const float *__restrict__ image0, const float *__restrict_
   }
 }
 
-// hres_layers_sparse_kernel's structure with the PP texel's steps: per layer a lane reads its tile's table entry; a lane of a dropped tile computes no
+// hres_layers_sparse_kernel's structure with the PP source's steps: per layer a lane reads its tile's table entry; a lane of a dropped tile computes no
 // sample position, blends nothing and stores nothing, and its eight loads carry NO_TEXEL (past the image: zeros, no memory access), so that the gathers
-// of layer q + 1 are in flight, unconditionally, while layer q is blended; pool offsets are 64-bit.
+// of layer q + 1 are in flight, unconditionally, while layer q is blended; pool offsets are 64-bit.  (The loop is written per kernel: shared as one
+// function it changes the instruction streams of all three sparse builders and missed the timing margin, profiles/hres_bodies_isa.txt.)
 template <int FMT, int NT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSI_HRES_WAVES, 8)))
 pp_hres_layers_sparse_kernel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
@@ -58,7 +60,7 @@ pp_hres_layers_sparse_kernel(const float *__restrict__ image0, const float *__re
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= width) return;
   const int i = blockIdx.y, b = blockIdx.z;
-  const PpHresPixel px = pp_hres_pixel(image0, image1, pose0, pose1, intrinsics, b, i, j, height, width, s0, sstep, t0, tstep);
+  const PpHres px = pp_hres(image0, image1, pose0, pose1, intrinsics, b, i, j, height, width, s0, sstep, t0, tstep);
   const HresCorners k = hres_corners(i, j, sy, sx, low_h, low_w, nd);
   const size_t low_base = (size_t)b * low_h * low_w * nd;
   const float *bw = blend_weights + low_base, *al = alphas + low_base;
@@ -80,8 +82,8 @@ pp_hres_layers_sparse_kernel(const float *__restrict__ image0, const float *__re
     HresRgb rgb[HRES_G];
     const auto stage = [&](int q) {
       tp[q].fg = tp[q].bg = TapsB{NO_TEXEL, NO_TEXEL, NO_TEXEL, NO_TEXEL, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (idx[q] >= 0) tp[q] = pp_hres_taps(px, depths[d0 + q], width, height);
-      rgb[q] = pp_hres_fetch(px, tp[q]);
+      if (idx[q] >= 0) tp[q] = px.taps(depths[d0 + q]);
+      rgb[q] = px.fetch(tp[q]);
     };
     const auto finish = [&](int q) {
       if (idx[q] >= 0) {
@@ -116,31 +118,12 @@ int msi_pp_hres_layers(const float *ref_image, const float *src_image, const flo
   if (batch == 0) return MSI_OK;
   const float sy = hres_scale(low_height, height), sx = hres_scale(low_width, width);
   const UvGrid gs = uv_grid(width), gt = uv_grid(height);
-  const int fmt = layers_out ? format : MSI_LAYERS_F32;
-  // non-temporal stores for a destination that cannot stay in the Infinity Cache (as msi_hres_layers)
-  const size_t texels = (size_t)batch * num_planes * height * width;
-  const int nt = (rgba_native && beyond_infinity_cache(texels * 16) ? 1 : 0) |
-                 (layers_out && beyond_infinity_cache(texels << (fmt == MSI_LAYERS_RGBA8 ? 2 : 3)) ? 2 : 0);
   const dim3 grid((unsigned)((width + 255) / 256), height, batch);
   hipStream_t s = msi::as_stream(stream);
-  const auto launch = [&](auto FMT, auto F32, auto NT) {
+  hres_dense_launch(format, rgba_native, layers_out, (size_t)batch * num_planes * height * width, [&](auto FMT, auto F32, auto NT) {
     hipLaunchKernelGGL((pp_hres_layers_kernel<decltype(FMT)::value, decltype(F32)::value, decltype(NT)::value>), grid, dim3(256), 0, s, ref_image,
                        src_image, ref_curr_pose, src_curr_pose, intrinsics, depths, blend_weights, alphas, low_height, low_width, height, width,
                        num_planes, sy, sx, gs.start, gs.step, gt.start, gt.step, reinterpret_cast<float4 *>(rgba_native), layers_out);
-  };
-  for_format(fmt, [&](auto FMT) {
-    if constexpr (decltype(FMT)::value == MSI_LAYERS_F32) {
-      if (nt) launch(FMT, Const<1>{}, Const<1>{}); else launch(FMT, Const<1>{}, Const<0>{});
-    } else if (rgba_native) {
-      switch (nt) {
-        case 0: launch(FMT, Const<1>{}, Const<0>{}); break;
-        case 1: launch(FMT, Const<1>{}, Const<1>{}); break;
-        case 2: launch(FMT, Const<1>{}, Const<2>{}); break;
-        default: launch(FMT, Const<1>{}, Const<3>{}); break;
-      }
-    } else {
-      if (nt) launch(FMT, Const<0>{}, Const<2>{}); else launch(FMT, Const<0>{}, Const<0>{});
-    }
   });
   return msi::check_launch(who);
 }
@@ -156,34 +139,15 @@ int msi_pp_hres_layers_sparse(const float *ref_image, const float *src_image, co
   size_t tiles;
   if (const int e = sparse_dims(who, format, batch, num_planes, height, width, &tiles)) return e;
   if (batch == 0) return MSI_OK;
-  hipStream_t s = msi::as_stream(stream);
-  // the store policy needs the pool's bytes, and only layer_start knows them (as msi_hres_layers_sparse: a pool is never larger than the dense
-  // stack, so layer_start's last entry comes back to the host only where that could leave the Infinity Cache; the caller has just waited for it)
-  const int shift = format == MSI_LAYERS_RGBA8 ? StackTexel<MSI_LAYERS_RGBA8>::shift : StackTexel<MSI_LAYERS_RGBA16F>::shift;
-  long long kept = (long long)tiles;
-  if (beyond_infinity_cache((tiles * TILE_TEXELS) << shift)) {
-    hipError_t e = hipMemcpyAsync(&kept, layer_start + (size_t)batch * num_planes, sizeof kept, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return msi::fail(MSI_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
-    MSI_REQUIRE(kept >= 0 && (size_t)kept <= tiles, "%s: layer_start ends at %lld tiles of %zu", who, kept, tiles);
-    if (kept == 0) return MSI_OK;
-  }
   const float sy = hres_scale(low_height, height), sx = hres_scale(low_width, width);
   const UvGrid gs = uv_grid(width), gt = uv_grid(height);
   const dim3 grid((unsigned)((width + 255) / 256), height, batch);
-  for_format(format, [&](auto FMT) {
-    constexpr int fmt = decltype(FMT)::value;
-    if constexpr (fmt != MSI_LAYERS_F32) {
-      auto launch = [&](auto NT) {
-        hipLaunchKernelGGL((pp_hres_layers_sparse_kernel<fmt, decltype(NT)::value>), grid, dim3(256), 0, s, ref_image, src_image, ref_curr_pose,
-                           src_curr_pose, intrinsics, depths, blend_weights, alphas, low_height, low_width, height, width, num_planes, sy, sx,
-                           gs.start, gs.step, gt.start, gt.step, table, tile_starts(layer_start), pool_out);
-      };
-      if (beyond_infinity_cache(((size_t)kept * TILE_TEXELS) << StackTexel<fmt>::shift)) launch(Const<1>{});
-      else launch(Const<0>{});
-    }
+  hipStream_t s = msi::as_stream(stream);
+  return hres_sparse_launch(who, format, tiles, layer_start, (size_t)batch * num_planes, s, [&](auto FMT, auto NT) {
+    hipLaunchKernelGGL((pp_hres_layers_sparse_kernel<decltype(FMT)::value, decltype(NT)::value>), grid, dim3(256), 0, s, ref_image, src_image,
+                       ref_curr_pose, src_curr_pose, intrinsics, depths, blend_weights, alphas, low_height, low_width, height, width, num_planes, sy,
+                       sx, gs.start, gs.step, gt.start, gt.step, table, tile_starts(layer_start), pool_out);
   });
-  return msi::check_launch(who);
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 //   geo_sparse.hip        the format: the keep rule (both borders), the scan, the copies between a dense stack and a pool
 //   geo_sparse_hres.hip   the high-res stack built sparse: hres_keep_kernel (both borders), hres_layers_sparse_kernel
 //   geo_sparse_views.hip  the viewers reading such a stack: render_views_sparse_kernel, mpi_render_views_sparse_kernel, cube_render_views_sparse_kernel
-// and by geo_planar_hres.hip, whose pp_hres_layers_sparse_kernel writes the PP high-res stack into such a pool.
+// and by geo_planar_hres.hip and geo_cube_sweep.hip, whose pp_ / cube_hres_layers_sparse_kernel write their high-res stacks into such a pool: the three
+// sparse builders share one launcher (hres_sparse_launch), here.
 // Here: ONLY what more than one of them uses.  The format and the keep rule are stated in msi_hip.h and, in numpy, in matryodshka_amd/sparse.py.
 #pragma once
 #include "geometry_device.h"
@@ -56,6 +57,31 @@ inline int whole_tiles(const char *who, int height, int width) {
 }
 
 inline const long long *tile_starts(const int64_t *layer_start) { return reinterpret_cast<const long long *>(layer_start); }   // (the kernels' type)
+
+// msi_hres_layers_sparse, msi_pp_hres_layers_sparse, msi_cube_hres_layers_sparse, after their checks (format: rgba8 or rgba16f, sparse_dims; `tiles` from
+// it; layers = B * D): ONE store policy for the sparse builders.  It needs the pool's bytes, and only layer_start knows them.  A pool is never larger
+// than the dense stack: where that stays within the Infinity Cache the answer is known; otherwise layer_start's last entry comes back to the host (the
+// caller has just waited for the same number to allocate the pool: the stream is idle).  launch(Const<FMT>, Const<NT>), NT = non-temporal stores,
+// unless nothing is kept.
+template <class Launch>
+int hres_sparse_launch(const char *who, int format, size_t tiles, const int64_t *layer_start, size_t layers, hipStream_t s, Launch launch) {
+  const int shift = format == MSI_LAYERS_RGBA8 ? StackTexel<MSI_LAYERS_RGBA8>::shift : StackTexel<MSI_LAYERS_RGBA16F>::shift;
+  long long kept = (long long)tiles;
+  if (beyond_infinity_cache((tiles * TILE_TEXELS) << shift)) {
+    hipError_t e = hipMemcpyAsync(&kept, layer_start + layers, sizeof kept, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return msi::fail(MSI_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
+    MSI_REQUIRE(kept >= 0 && (size_t)kept <= tiles, "%s: layer_start ends at %lld tiles of %zu", who, kept, tiles);
+    if (kept == 0) return MSI_OK;
+  }
+  for_format(format, [&](auto FMT) {
+    if constexpr (decltype(FMT)::value != MSI_LAYERS_F32) {
+      if (beyond_infinity_cache(((size_t)kept * TILE_TEXELS) << StackTexel<decltype(FMT)::value>::shift)) launch(FMT, Const<1>{});
+      else launch(FMT, Const<0>{});
+    }
+  });
+  return msi::check_launch(who);
+}
 
 }  // namespace
 

@@ -97,7 +97,7 @@ hres_keep_kernel(const float *__restrict__ alphas, int low_h, int low_w, int hei
 }
 
 // The texel pass: hres_layers_kernel's mapping (a lane is one pixel of a 256-column run of row blockIdx.y and walks the layers in groups of HRES_G) and
-// its texel (hres_taps -> hres_fetch -> hres_blend, geometry_device.h: the steps of hres_texel), written for kept tiles only, at
+// its texel (OdsHres::taps -> fetch -> hres_blend, geometry_device.h: the steps of hres_texel), written for kept tiles only, at
 // pool[(layer_start[b D + d] + index) * 64 + (i & 3) * 16 + (j & 15)]: a tile row is one 64- / 128-byte run from 16 lanes, every texel of a kept tile
 // is stored, the empty ones too, and pool offsets are 64-bit.  Per layer a lane reads its tile's table entry (16 lanes share it; the tile row is the
 // block's).  A lane of a dropped tile computes no sample position (when the wave has none the instructions are skipped), blends nothing and stores
@@ -115,7 +115,7 @@ hres_layers_sparse_kernel(const float *__restrict__ image0, const float *__restr
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= width) return;
   const int i = blockIdx.y, b = blockIdx.z;
-  const HresPixel px = hres_pixel(image0, image1, pose0, pose1, intrinsics, trig, b, i, j, height, width);
+  const OdsHres px = ods_hres(image0, image1, pose0, pose1, intrinsics, trig, K, b, i, j, height, width);
   const HresCorners k = hres_corners(i, j, sy, sx, low_h, low_w, nd);
   const size_t low_base = (size_t)b * low_h * low_w * nd;
   const float *bw = blend_weights + low_base, *al = alphas + low_base;
@@ -137,8 +137,8 @@ hres_layers_sparse_kernel(const float *__restrict__ image0, const float *__restr
     HresRgb rgb[HRES_G];
     const auto stage = [&](int q) {
       tp[q].fg = tp[q].bg = TapsB{NO_TEXEL, NO_TEXEL, NO_TEXEL, NO_TEXEL, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (idx[q] >= 0) tp[q] = hres_taps(px, depths[d0 + q], K, width, height);
-      rgb[q] = hres_fetch(px, tp[q]);
+      if (idx[q] >= 0) tp[q] = px.taps(depths[d0 + q]);
+      rgb[q] = px.fetch(tp[q]);
     };
     const auto finish = [&](int q) {
       if (idx[q] >= 0) {
@@ -209,36 +209,15 @@ int msi_hres_layers_sparse(const float *ref_image, const float *src_image, const
   size_t tiles;
   if (const int e = sparse_dims(who, format, batch, num_planes, height, width, &tiles)) return e;
   if (batch == 0) return MSI_OK;
-  hipStream_t s = msi::as_stream(stream);
-  // msi_hres_layers' store policy needs the pool's bytes, and only layer_start knows them.  A pool is never larger than the dense stack: where
-  // that stays within the Infinity Cache the answer is known; otherwise layer_start's last entry comes back to the host (the caller has just
-  // waited for the same number to allocate the pool: the stream is idle)
-  const int shift = format == MSI_LAYERS_RGBA8 ? StackTexel<MSI_LAYERS_RGBA8>::shift : StackTexel<MSI_LAYERS_RGBA16F>::shift;
-  long long kept = (long long)tiles;
-  if (beyond_infinity_cache((tiles * TILE_TEXELS) << shift)) {
-    hipError_t e = hipMemcpyAsync(&kept, layer_start + (size_t)batch * num_planes, sizeof kept, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return msi::fail(MSI_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
-    MSI_REQUIRE(kept >= 0 && (size_t)kept <= tiles, "%s: layer_start ends at %lld tiles of %zu", who, kept, tiles);
-    if (kept == 0) return MSI_OK;
-  }
   const float sy = hres_scale(low_height, height), sx = hres_scale(low_width, width);
   const PixConsts K = make_consts(height, width);
   const dim3 grid((unsigned)((width + 255) / 256), height, batch);
-  for_format(format, [&](auto FMT) {
-    constexpr int fmt = decltype(FMT)::value;
-    if constexpr (fmt != MSI_LAYERS_F32) {
-      auto launch = [&](auto NT) {
-        hipLaunchKernelGGL((hres_layers_sparse_kernel<fmt, decltype(NT)::value>), grid, dim3(256), 0, s, ref_image, src_image, ref_curr_pose,
-                           src_curr_pose, intrinsics, depths, trig, blend_weights, alphas, low_height, low_width, height, width, num_planes, sy, sx,
-                           K, table, tile_starts(layer_start), pool_out);
-      };
-      // non-temporal stores for a pool that cannot stay in the Infinity Cache (as msi_hres_layers)
-      if (beyond_infinity_cache(((size_t)kept * TILE_TEXELS) << StackTexel<fmt>::shift)) launch(Const<1>{});
-      else launch(Const<0>{});
-    }
+  hipStream_t s = msi::as_stream(stream);
+  return hres_sparse_launch(who, format, tiles, layer_start, (size_t)batch * num_planes, s, [&](auto FMT, auto NT) {
+    hipLaunchKernelGGL((hres_layers_sparse_kernel<decltype(FMT)::value, decltype(NT)::value>), grid, dim3(256), 0, s, ref_image, src_image,
+                       ref_curr_pose, src_curr_pose, intrinsics, depths, trig, blend_weights, alphas, low_height, low_width, height, width, num_planes,
+                       sy, sx, K, table, tile_starts(layer_start), pool_out);
   });
-  return msi::check_launch(who);
 }
 
 }  // extern "C"

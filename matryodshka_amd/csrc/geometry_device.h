@@ -327,6 +327,18 @@ __device__ __forceinline__ void gather3_blend(const TapsB &t, const Rgb4 &g, flo
 }
 __device__ __forceinline__ void gather3(__amdgpu_buffer_rsrc_t img, const TapsB &t, float *out) { gather3_blend(t, gather3_load(img, t), out); }
 
+// ---- sweep, layers (pack / unpack / hres) and planar: the 16-byte store of every streaming kernel; its host side is beyond_infinity_cache below.
+// The 16-byte pieces of a wave's whole-pixel strip.  nt != 0 (block-uniform; the host sets it when the volume is larger than the 256-MB Infinity Cache): non-temporal
+// stores -- a volume that cannot stay cached until conv1_1 reads it should not evict what can (r06, same-box A/B at configs[2]: sweep 1.07 -> 0.98 ms per 16 frames;
+// configs[3] -1 %; at batch 1 the 157-MB volume stays cached and keeps plain stores).
+__device__ __forceinline__ void sweep_store16(uint4 *dst, const uint4 &v, int nt) {
+  if (nt) {
+    __builtin_nontemporal_store(v.x, &dst->x); __builtin_nontemporal_store(v.y, &dst->y); __builtin_nontemporal_store(v.z, &dst->z); __builtin_nontemporal_store(v.w, &dst->w);
+  } else {
+    *dst = v;
+  }
+}
+
 // ---- layers (hres_layers_kernel) and sparse (hres_keep_kernel, hres_layers_sparse_kernel): ONE definition of a texel of the high-res stack, so the
 // tiles a sparse stack keeps and the codes in them are the dense stack's, bit for bit.  The texel is the sweep's functions above, the resize's
 // expression and the assembly's blend in the order of the three launches the dense kernel replaced (geo_layers.hip tells that story).
@@ -401,17 +413,51 @@ __device__ __forceinline__ void hres_store_packed(void *__restrict__ base, size_
   }
 }
 
-// what a pixel (b, i, j) of the high-res stack has for all its layers: the sweep's per-pixel constants (ods_sweep_kernel), the two images, the two poses
-struct HresPixel {
+// A texel in three steps, each a function of the one before: where its two samples lie (taps), their eight texels (fetch: gather3_load x 2), and the
+// blend (hres_blend: gather3_blend; assemble_kernel, COLOR_BLEND_PSV with pred_scaled).  The first two belong to the SOURCE of the stack -- the ODS
+// pair, the PP pair, a cube face and its panorama -- and every source is one type of the same shape:
+//   its members       what pixel (b, i, j) of an [B,D,height,width] stack has for all its layers (computed once, by the function that returns it)
+//   taps(depth)       the sample positions of the texel at that depth, as byte offsets and weights; a source's own shortcuts live here
+//   fetch(taps)       the eight 12-byte loads
+// hres_texel is the three in a row, the dense builders' texel; the sparse builders call the steps.
+struct HresTaps { TapsB fg, bg; };
+struct HresRgb { Rgb4 fg, bg; };
+
+// The ODS source (hres_layers_kernel, hres_layers_sparse_kernel): the sweep's per-pixel constants (ods_sweep_kernel), the two images, the two poses;
+// taps = ods_quad / ods_tail / make_taps_bytes per image.
+struct OdsHres {
+  int b, i, j, height, width;
+  const PixConsts &K;                           // the kernel's own argument (a copy moves its loads): K must outlive the source
   const float *P0, *P1;
   __amdgpu_buffer_rsrc_t img0, img1;
   float r, csct, st, ssct;
   bool same;                                    // both sources share the quadratic when their poses are equal
+  __device__ __forceinline__ HresTaps taps(float depth) const {
+    HresTaps t;
+    float u, v;
+    const OdsQuad q0 = ods_quad(P0, r, depth, csct, st, ssct);
+    ods_tail(q0, 1.0f, K, u, v);
+    t.fg = make_taps_bytes(u, v, width, height);
+    if (same) {
+      ods_tail(q0, -1.0f, K, u, v);
+    } else {
+      const OdsQuad q1 = ods_quad(P1, r, depth, csct, st, ssct);
+      ods_tail(q1, -1.0f, K, u, v);
+    }
+    t.bg = make_taps_bytes(u, v, width, height);
+    return t;
+  }
+  __device__ __forceinline__ HresRgb fetch(const HresTaps &t) const {
+    HresRgb g;
+    g.fg = gather3_load(img0, t.fg);
+    g.bg = gather3_load(img1, t.bg);
+    return g;
+  }
 };
-__device__ __forceinline__ HresPixel hres_pixel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
-                                                const float *__restrict__ pose1, const float *__restrict__ intrinsics,
-                                                const float *__restrict__ trig, int b, int i, int j, int height, int width) {
-  HresPixel p;
+__device__ __forceinline__ OdsHres ods_hres(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
+                                            const float *__restrict__ pose1, const float *__restrict__ intrinsics, const float *__restrict__ trig,
+                                            const PixConsts &K, int b, int i, int j, int height, int width) {
+  OdsHres p{b, i, j, height, width, K};
   const float cs = trig[j], ss = trig[width + j];
   const float ct = trig[2 * width + i];
   p.st = trig[2 * width + height + i];
@@ -427,32 +473,6 @@ __device__ __forceinline__ HresPixel hres_pixel(const float *__restrict__ image0
   return p;
 }
 
-// A texel in three steps, each a function of the one before: where its two samples lie (ods_quad / ods_tail / make_taps_bytes; the shared quadratic
-// for equal poses), their eight texels (gather3_load), and the blend (gather3_blend; assemble_kernel, COLOR_BLEND_PSV with pred_scaled).  hres_texel is
-// the three in a row, the dense kernel's texel; the sparse kernel calls the steps.
-struct HresTaps { TapsB fg, bg; };
-struct HresRgb { Rgb4 fg, bg; };
-__device__ __forceinline__ HresTaps hres_taps(const HresPixel &p, float depth, const PixConsts &K, int width, int height) {
-  HresTaps t;
-  float u, v;
-  const OdsQuad q0 = ods_quad(p.P0, p.r, depth, p.csct, p.st, p.ssct);
-  ods_tail(q0, 1.0f, K, u, v);
-  t.fg = make_taps_bytes(u, v, width, height);
-  if (p.same) {
-    ods_tail(q0, -1.0f, K, u, v);
-  } else {
-    const OdsQuad q1 = ods_quad(p.P1, p.r, depth, p.csct, p.st, p.ssct);
-    ods_tail(q1, -1.0f, K, u, v);
-  }
-  t.bg = make_taps_bytes(u, v, width, height);
-  return t;
-}
-__device__ __forceinline__ HresRgb hres_fetch(const HresPixel &p, const HresTaps &t) {
-  HresRgb g;
-  g.fg = gather3_load(p.img0, t.fg);
-  g.bg = gather3_load(p.img1, t.bg);
-  return g;
-}
 __device__ __forceinline__ float4 hres_blend(const HresTaps &t, const HresRgb &g, float w, float alpha) {
   float fg[3], bg[3];
   gather3_blend(t.fg, g.fg, fg);
@@ -465,16 +485,214 @@ __device__ __forceinline__ float4 hres_blend(const HresTaps &t, const HresRgb &g
   o.w = alpha;
   return o;
 }
-__device__ __forceinline__ float4 hres_texel(const HresPixel &p, float depth, const PixConsts &K, int width, int height, float w, float alpha) {
-  const HresTaps t = hres_taps(p, depth, K, width, height);
-  return hres_blend(t, hres_fetch(p, t), w, alpha);
+template <class Source>
+__device__ __forceinline__ float4 hres_texel(const Source &src, float depth, float w, float alpha) {
+  const HresTaps t = src.taps(depth);
+  return hres_blend(t, src.fetch(t), w, alpha);
+}
+
+
+// ---- planar (pp_sweep_kernel, pp_sweep_volume_bf16_kernel), planar-hres and cube-sweep: the steps of pj.perspective_plane_sweep (projector.py:221-223),
+// each written ONCE, so that the fp32 sweeps, the bf16 volumes and the high-res builders of the PP and the cube path agree bit for bit.  No reciprocal,
+// no fused multiply-add, no reassociation: the parentheses are the reference's order of operations.
+struct Vec3 { float x, y, z; };
+// backproject_planar (spherical.py:146-148): x = depth*S*cx/fx, y = depth*T*cy/fy, z = depth*1.  One axis (the bf16 sweeps stage y per plane) and the point.
+__device__ __forceinline__ float backproject_axis(float depth, float s, float c, float f) { return ((depth * s) * c) / f; }
+__device__ __forceinline__ Vec3 backproject_planar(float depth, float S, float T, float fx, float fy, float cx, float cy) {
+  return Vec3{backproject_axis(depth, S, cx, fx), backproject_axis(depth, T, cy, fy), depth * 1.0f};
+}
+// apply_pose (projector.py:275-291): rows 0..2 of pose @ (x, y, z, 1), terms summed left to right
+__device__ __forceinline__ Vec3 apply_pose(const float *P, const Vec3 &a) {
+  return Vec3{((P[0] * a.x + P[1] * a.y) + P[2] * a.z) + P[3] * 1.0f, ((P[4] * a.x + P[5] * a.y) + P[6] * a.z) + P[7] * 1.0f,
+              ((P[8] * a.x + P[9] * a.y) + P[10] * a.z) + P[11] * 1.0f};
+}
+// project_perspective (spherical.py:248-266): entry (r, c), r < 3, of M = K4 @ pose -- the 3x3 intrinsics Kb are zero-padded to 4x4 (projector.py:145-148),
+// so the padded column contributes 0 * pose[3][c] -- and (u, v) = (pr0 / pr2, pr1 / pr2) of pr = M (x, y, z, 1) from rows 0..2 of M (m[12], registers or LDS)
+__device__ __forceinline__ float k4_pose(const float *Kb, const float *P, int r, int c) {
+  return ((Kb[r * 3 + 0] * P[c] + Kb[r * 3 + 1] * P[4 + c]) + Kb[r * 3 + 2] * P[8 + c]) + 0.0f * P[12 + c];
+}
+struct Uv { float u, v; };
+__device__ __forceinline__ Uv project_rows(const float *m, const Vec3 &a) {
+  float pr[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) pr[r] = ((m[r * 4 + 0] * a.x + m[r * 4 + 1] * a.y) + m[r * 4 + 2] * a.z) + m[r * 4 + 3] * 1.0f;
+  return Uv{pr[0] / pr[2], pr[1] / pr[2]};
+}
+// make_taps' four corners as byte offsets into one [H,W,3] image (H * W * 12 < 2^31: checked on the host), for gather3
+__device__ __forceinline__ TapsB taps_bytes(const Taps &t, int width) {
+  TapsB r;
+  r.oa = (unsigned)(t.y0 * width + t.x0) * 12u; r.ob = (unsigned)(t.y0 * width + t.x1) * 12u;
+  r.oc = (unsigned)(t.y1 * width + t.x0) * 12u; r.od = (unsigned)(t.y1 * width + t.x1) * 12u;
+  r.wa = t.wa; r.wb = t.wb; r.wc = t.wc; r.wd = t.wd;
+  return r;
+}
+// (the form without staged rows: M computed by the thread that uses it)
+__device__ __forceinline__ Uv project_k4_pose(const float *Kb, const float *P, const Vec3 &a) {
+  float m[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) m[e] = k4_pose(Kb, P, e >> 2, e & 3);
+  return project_rows(m, a);
+}
+
+// ---- planar and cube-sweep: what the plane sweeps of an image and of a cube's panorama share around their samplers -- a thread is sample idx = j * nd + d of
+// row blockIdx.y of image blockIdx.z, grid = (ceil(W * D / 256), H, B) -- the decode and the stores.  FAST forms: full waves of complete pixels (the host decides).
+struct PixelPlane { int j, d; };
+// FAST: idx / nd by multiply-high with nd_magic = udiv_magic32(nd) (+ one correction); 32-bit index math only (64-bit div / mod are emulated in ~100 VALU
+// instructions each and used to dominate the sweep)
+template <int FAST> __device__ __forceinline__ PixelPlane sweep_pixel_plane(int idx, int nd, unsigned nd_magic) {
+  int j;
+  if (FAST) {
+    unsigned jq = __umulhi((unsigned)idx, nd_magic);
+    if ((unsigned)idx - jq * (unsigned)nd >= (unsigned)nd) ++jq;
+    j = (int)jq;
+  } else {
+    j = idx / nd;
+  }
+  return PixelPlane{j, idx - j * nd};
+}
+// The fp32 sweeps' FAST store: whole-pixel runs through the wave's strip.  lane = (pixel of the wave, depth); the wave's 64 / D pixels are consecutive from
+// row0 (the row's first pixel) + the wave's first, each owns 3 D contiguous floats at + coff: the strip IS the pixels' runs back to back, and lanes 0..47
+// store 16 bytes each (non-temporal when the volume exceeds the Infinity Cache: sweep_store16).
+__device__ __forceinline__ void sweep_strip_store(const float *o, long row0, int nd, float *__restrict__ psv, int channels, int coff, int nt) {
+  __shared__ __attribute__((aligned(16))) float s_out[4][192];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float *w = s_out[wave];
+  __builtin_amdgcn_wave_barrier();
+  w[lane * 3 + 0] = o[0]; w[lane * 3 + 1] = o[1]; w[lane * 3 + 2] = o[2];
+  __builtin_amdgcn_wave_barrier();
+  if (lane < 48) {
+    const int vpp = (3 * nd) >> 2;                                         // 16-byte vectors per pixel run
+    unsigned plq = __umulhi((unsigned)lane, 0xffffffffu / (unsigned)vpp + 1u);
+    if ((unsigned)lane - plq * (unsigned)vpp >= (unsigned)vpp) --plq;      // (lane < 48, vpp >= 3: the estimate is exact or one too large)
+    const int pl = (int)plq, k = lane - pl * vpp;
+    const long pw0 = row0 + (long)((blockIdx.x * 256 + wave * 64) / nd);
+    uint4 *dst = reinterpret_cast<uint4 *>(psv + (size_t)(pw0 + pl) * channels + coff) + k;
+    sweep_store16(dst, reinterpret_cast<const uint4 *>(w)[lane], nt);
+  }
+}
+// The bf16 volumes' store of pixel p, plane d: out[0] into channels [0, 3D), out[1] into [3D, 6D) of psv [.,6D].  FAST: the wave's 64 / D pixels are
+// consecutive and each owns 6 D contiguous channels: lane = pl * D + d writes its two triples into a wave-private fp32 strip at pl * 6 D + {0, 3 D} + 3 d, then
+// lanes 0..47 each pack 8 of the 384 values (v_cvt_pk_bf16_f32: round to nearest even, what f32_to_bf16 computes for the finite values stored here) into one
+// 16-byte store.  Generic: six bf16 halves per thread.  NT is a template argument, not sweep_store16's runtime flag: with the packed value computed
+// ahead of the branch, hipcc merges the two stores into one plain store.
+template <int FAST, int NT>
+__device__ __forceinline__ void sweep_volume_store_bf16(const float (&out)[2][3], long p, int d, int nd, int nd_shift, unsigned short *__restrict__ psv) {
+  if (FAST) {
+    __shared__ __attribute__((aligned(16))) float s_out[4][384];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pl = lane >> nd_shift;
+    float *w = s_out[wave];
+    __builtin_amdgcn_wave_barrier();
+    const int e0 = pl * 6 * nd + 3 * d;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      w[e0 + c] = out[0][c];
+      w[e0 + 3 * nd + c] = out[1][c];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 48) {
+      const float4 lo = reinterpret_cast<const float4 *>(w)[2 * lane], hi = reinterpret_cast<const float4 *>(w)[2 * lane + 1];
+      uint4 pk;
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.x) : "v"(lo.x), "v"(lo.y));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.y) : "v"(lo.z), "v"(lo.w));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.z) : "v"(hi.x), "v"(hi.y));
+      asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk.w) : "v"(hi.z), "v"(hi.w));
+      uint4 *dst = reinterpret_cast<uint4 *>(psv + (size_t)(p - pl) * (6 * nd)) + lane;   // (p - pl: the wave's first pixel)
+      sweep_store16(dst, pk, NT);
+    }
+    return;
+  }
+  unsigned short *o = psv + (size_t)p * (6 * nd) + 3 * d;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    o[c] = f32_to_bf16(out[0][c]);
+    o[3 * nd + c] = f32_to_bf16(out[1][c]);
+  }
+}
+// image b of an [B,H,W,3] batch as a range-checked buffer with 32-bit byte offsets (H * W * 12 < 2^31: checked on the host)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const float *__restrict__ images, int b, int height, int width) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(images + (size_t)b * height * width * 3), 0, height * width * 12, 0x00020000);
+}
+// the sample of an image at pixel coordinates p through the reference's wrap-around sampler: one 12-byte buffer load per corner
+__device__ __forceinline__ void wrap_gather3(__amdgpu_buffer_rsrc_t img, const Uv &p, int width, int height, float *out) {
+  gather3(img, taps_bytes(make_taps(p.u, p.v, width, height), width), out);
+}
+
+// The fp32 plane sweep of one source into its 3 D channel window of psv [B,H,W,C] (pp_sweep_kernel: geo_planar.hip, which tells the story;
+// cube_sweep_kernel: geo_cube_sweep.hip) is ONE body around the source's sampler: src.sample<FAST>(Kb, a, o) = the RGB of the source where the posed plane
+// point a lands (its own pose src.P applied once already).  FAST: whole pixels through the wave's strip.
+template <int FAST, class Source>
+__device__ __forceinline__ void sweep_body(const Source &src, const float *intrinsics, const float *depths, int height, int width, int nd, float s0,
+                                           float sstep, float t0, float tstep, float *psv, int channels, int coff, unsigned nd_magic, int nt) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (!FAST && idx >= width * nd) return;
+  const PixelPlane q = sweep_pixel_plane<FAST>(idx, nd, nd_magic);
+  const int i = blockIdx.y, b = blockIdx.z;
+  const float *Kb = intrinsics + (size_t)b * 9;
+  const long row0 = ((long)b * height + i) * width;
+  const float S = s0 + sstep * (float)q.j, T = t0 + tstep * (float)i;
+  float o[3];
+  src.template sample<FAST>(Kb, apply_pose(src.P, backproject_planar(depths[q.d], S, T, Kb[0], Kb[4], Kb[2], Kb[5])), o);
+  if (FAST) {
+    sweep_strip_store(o, row0, nd, psv, channels, coff, nt);
+    return;
+  }
+  float *dst = psv + (size_t)(row0 + q.j) * channels + coff + q.d * 3;
+  dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+}
+
+// The whole bf16 network input of a pair in one launch (pp_sweep_volume_bf16_kernel: geo_planar.hip, which tells the story;
+// cube_sweep_volume_bf16_kernel: geo_cube_sweep.hip): ONE body.  The ref half is image0 through its own camera; the src half is Src's -- Src::CAMERA: a
+// second image of the same camera (src.image, src.P: its M is staged next to the ref half's), else src.sample(a, o) as in sweep_body.  FAST
+// (64 % D == 0, (W * D) % 64 == 0): M per face and camera source and backproject_planar's y per plane of this row are staged in LDS.
+template <int FAST, int NT, class Src>
+__device__ __forceinline__ void sweep_volume_bf16_body(const float *image0, const float *P0, const Src &src,
+                                                       const float *intrinsics, const float *depths, int height, int width,
+                                                       int nd, int nd_shift, float s0, float sstep, float t0, float tstep,
+                                                       unsigned short *psv) {
+  constexpr int NM = Src::CAMERA ? 2 : 1;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int i = blockIdx.y, b = blockIdx.z;
+  const float *Kb = intrinsics + (size_t)b * 9;
+  const float fx = Kb[0], fy = Kb[4], cx = Kb[2], cy = Kb[5];
+  const float T = t0 + tstep * (float)i;
+  __shared__ float s_m[NM][12];
+  __shared__ float s_y[64];
+  if (FAST) {
+    const int tid = threadIdx.x;
+    if (tid < 12 * NM) {
+      const int s = tid / 12, e = tid - s * 12;
+      s_m[s][e] = k4_pose(Kb, s ? src.P : P0, e >> 2, e & 3);
+    } else if (tid >= 64 && tid < 64 + nd) {
+      s_y[tid - 64] = backproject_axis(depths[tid - 64], T, cy, fy);
+    }
+    __syncthreads();
+    if (idx >= width * nd) return;   // (W * D) % 64 == 0: whole waves
+  } else {
+    if (idx >= width * nd) return;
+  }
+  const int j = FAST ? idx >> nd_shift : idx / nd;
+  const int d = FAST ? idx & (nd - 1) : idx - j * nd;
+  const float S = s0 + sstep * (float)j;
+  const float depth = depths[d];
+  // backproject_planar, shared by both halves
+  const Vec3 point = Vec3{backproject_axis(depth, S, cx, fx), FAST ? s_y[d] : backproject_axis(depth, T, cy, fy), depth * 1.0f};
+  float out[2][3];
+  const auto camera = [&](int s, const float *image, const float *P) {
+    const Vec3 a = apply_pose(P, point);
+    wrap_gather3(image_rsrc(image, b, height, width), FAST ? project_rows(s_m[s], a) : project_k4_pose(Kb, P, a), width, height, out[s]);
+  };
+  camera(0, image0, P0);
+  if constexpr (Src::CAMERA) camera(1, src.image, src.P);
+  else src.template sample<FAST>(Kb, apply_pose(src.P, point), out[1]);
+  sweep_volume_store_bf16<FAST, NT>(out, ((long)b * height + i) * width + j, d, nd, nd_shift, psv);
 }
 
 // ---- planar-hres (pp_hres_layers_kernel, pp_hres_layers_sparse_kernel: geo_planar_hres.hip): ONE definition of a texel of the PP high-res stack.  It is
-// pp_sweep_kernel's arithmetic (geo_planar.hip), op for op -- S and T of uv_grid, backproject_planar with its two divides, apply_pose, M = K4 @ pose with
-// the padded column's 0 * pose[3][c], rows 0..2 of M, u = pr0 / pr2, v = pr1 / pr2, make_taps, blend4 -- once per source image (ref = foreground,
-// src = background), then the steps the ODS texel above ends with (hres_corners / hres_lerp, hres_blend, hres_store_packed): the bits of
-// msi_perspective_plane_sweep_f32 x 2 -> msi_resize_bilinear_f32 -> msi_assemble_rgba_scaled_f32.  No reciprocal, no fused multiply-add, no reassociation.
+// pp_sweep_kernel's arithmetic (geo_planar.hip), the steps above -- S and T of uv_grid, backproject_planar with its two divides, apply_pose, M = K4 @ pose,
+// u = pr0 / pr2, v = pr1 / pr2, make_taps, blend4 -- once per source image (ref = foreground, src = background), then the steps every source ends with
+// (hres_corners / hres_lerp, hres_blend, hres_store_packed): the bits of msi_perspective_plane_sweep_f32 x 2 -> msi_resize_bilinear_f32 ->
+// msi_assemble_rgba_scaled_f32.
 // K, both poses and both M depend on the sample alone: they are made wave-uniform (pp_uniform) so that they live in SGPRs, not in 60 VGPRs of every lane.
 __device__ __forceinline__ float pp_uniform(float v) {   // (v is the same in every lane: a function of blockIdx.z)
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
@@ -484,92 +702,85 @@ struct PpHresSource {
   const float *P;      // pose [4,4] of this source
   float m[12];         // rows 0..2 of K4 @ pose
 };
-struct PpHresPixel {
-  PpHresSource s0, s1;
-  float S, T, fx, fy, cx, cy;
-  bool same;           // equal poses: both sources sample the same position
-};
 __device__ __forceinline__ PpHresSource pp_hres_source(const float *__restrict__ image, const float *__restrict__ pose, const float *Kb, int b, int height,
                                                        int width) {
   PpHresSource s;
   s.P = pose + (size_t)b * 16;
-  s.img = __builtin_amdgcn_make_buffer_rsrc((void *)(image + (size_t)b * height * width * 3), 0, height * width * 12, 0x00020000);   // (H * W * 12 < 2^31: checked on the host)
+  s.img = image_rsrc(image, b, height, width);
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
-      s.m[r * 4 + c] = pp_uniform(((Kb[r * 3 + 0] * s.P[c] + Kb[r * 3 + 1] * s.P[4 + c]) + Kb[r * 3 + 2] * s.P[8 + c]) + 0.0f * s.P[12 + c]);
+    for (int c = 0; c < 4; ++c) s.m[r * 4 + c] = pp_uniform(k4_pose(Kb, s.P, r, c));
   return s;
 }
-__device__ __forceinline__ PpHresPixel pp_hres_pixel(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
-                                                     const float *__restrict__ pose1, const float *__restrict__ intrinsics, int b, int i, int j, int height,
-                                                     int width, float s0, float sstep, float t0, float tstep) {
-  PpHresPixel p;
+// where the plane point of backproject_planar lands in one source: apply_pose, project_perspective, the wrap-around taps as byte offsets
+__device__ __forceinline__ TapsB pp_hres_source_taps(const PpHresSource &s, const Vec3 &point, int width, int height) {
+  const Uv p = project_rows(s.m, apply_pose(s.P, point));
+  return taps_bytes(make_taps(p.u, p.v, width, height), width);      // (wrapped indices lie inside the image whatever u and v are)
+}
+// what the PP and the cube source share: pixel (b, i, j) of a stack of `height` x `width` images, its point S, T of uv_grid, the camera of sample b and
+// the foreground image (ref image, ref pose)
+struct PlanarHresPixel {
+  int b, i, j, height, width;
+  PpHresSource s0;
+  float S, T, fx, fy, cx, cy;
+  __device__ __forceinline__ Vec3 plane_point(float depth) const { return backproject_planar(depth, S, T, fx, fy, cx, cy); }
+};
+__device__ __forceinline__ PlanarHresPixel planar_hres_pixel(const float *__restrict__ image0, const float *__restrict__ pose0,
+                                                             const float *__restrict__ intrinsics, int b, int i, int j, int height, int width, float s0,
+                                                             float sstep, float t0, float tstep) {
+  PlanarHresPixel p;
+  p.b = b; p.i = i; p.j = j; p.height = height; p.width = width;
   const float *Kb = intrinsics + (size_t)b * 9;
   p.fx = Kb[0]; p.fy = Kb[4]; p.cx = Kb[2]; p.cy = Kb[5];
   p.S = s0 + sstep * (float)j; p.T = t0 + tstep * (float)i;
   p.s0 = pp_hres_source(image0, pose0, Kb, b, height, width);
-  p.s1 = pp_hres_source(image1, pose1, Kb, b, height, width);
+  return p;
+}
+// The PP source (pp_hres_layers_kernel, pp_hres_layers_sparse_kernel): the background is a second image of the same camera.  Equal poses: both sample
+// the same position, and the taps are copied.
+struct PpHres : PlanarHresPixel {
+  PpHresSource s1;
+  bool same;
+  __device__ __forceinline__ HresTaps taps(float depth) const {
+    HresTaps t;
+    const Vec3 point = plane_point(depth);
+    t.fg = pp_hres_source_taps(s0, point, width, height);
+    if (same) t.bg = t.fg;
+    else t.bg = pp_hres_source_taps(s1, point, width, height);
+    return t;
+  }
+  __device__ __forceinline__ HresRgb fetch(const HresTaps &t) const {
+    HresRgb g;
+    g.fg = gather3_load(s0.img, t.fg);
+    g.bg = gather3_load(s1.img, t.bg);
+    return g;
+  }
+};
+__device__ __forceinline__ PpHres pp_hres(const float *__restrict__ image0, const float *__restrict__ image1, const float *__restrict__ pose0,
+                                          const float *__restrict__ pose1, const float *__restrict__ intrinsics, int b, int i, int j, int height, int width,
+                                          float s0, float sstep, float t0, float tstep) {
+  PpHres p{planar_hres_pixel(image0, pose0, intrinsics, b, i, j, height, width, s0, sstep, t0, tstep)};
+  p.s1 = pp_hres_source(image1, pose1, intrinsics + (size_t)b * 9, b, height, width);
   p.same = true;
 #pragma unroll
   for (int k = 0; k < 16; ++k) p.same = p.same && (p.s0.P[k] == p.s1.P[k]);   // (row 3 too: M has 0 * pose[3][c], which is NaN for an infinite entry)
   return p;
 }
-// where the plane point (x, y, z) of backproject_planar lands in one source: apply_pose, project_perspective, the wrap-around taps as byte offsets
-__device__ __forceinline__ TapsB pp_hres_source_taps(const PpHresSource &s, float x, float y, float z, int width, int height) {
-  const float *P = s.P;
-  const float ax = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
-  const float ay = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
-  const float az = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
-  float pr[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) pr[r] = ((s.m[r * 4 + 0] * ax + s.m[r * 4 + 1] * ay) + s.m[r * 4 + 2] * az) + s.m[r * 4 + 3] * 1.0f;
-  const float u = pr[0] / pr[2], v = pr[1] / pr[2];
-  const Taps t = make_taps(u, v, width, height);      // (wrapped indices lie inside the image whatever u and v are)
-  TapsB r;
-  r.oa = (unsigned)(t.y0 * width + t.x0) * 12u; r.ob = (unsigned)(t.y0 * width + t.x1) * 12u;
-  r.oc = (unsigned)(t.y1 * width + t.x0) * 12u; r.od = (unsigned)(t.y1 * width + t.x1) * 12u;
-  r.wa = t.wa; r.wb = t.wb; r.wc = t.wc; r.wd = t.wd;
-  return r;
-}
-// The PP texel in the ODS texel's three steps: pp_hres_taps -> pp_hres_fetch -> hres_blend (the blend is the same function); pp_hres_texel is the three in a row.
-__device__ __forceinline__ HresTaps pp_hres_taps(const PpHresPixel &p, float depth, int width, int height) {
-  HresTaps t;
-  // backproject_planar (spherical.py:146-148)
-  const float x = ((depth * p.S) * p.cx) / p.fx;
-  const float y = ((depth * p.T) * p.cy) / p.fy;
-  const float z = depth * 1.0f;
-  t.fg = pp_hres_source_taps(p.s0, x, y, z, width, height);
-  if (p.same) t.bg = t.fg;
-  else t.bg = pp_hres_source_taps(p.s1, x, y, z, width, height);
-  return t;
-}
-__device__ __forceinline__ HresRgb pp_hres_fetch(const PpHresPixel &p, const HresTaps &t) {
-  HresRgb g;
-  g.fg = gather3_load(p.s0.img, t.fg);
-  g.bg = gather3_load(p.s1.img, t.bg);
-  return g;
-}
-__device__ __forceinline__ float4 pp_hres_texel(const PpHresPixel &p, float depth, int width, int height, float w, float alpha) {
-  const HresTaps t = pp_hres_taps(p, depth, width, height);
-  return hres_blend(t, pp_hres_fetch(p, t), w, alpha);
-}
 
 // ---- cube-sweep (cube_sweep_kernel, cube_sweep_volume_bf16_kernel, cube_hres_layers_kernel, cube_hres_layers_sparse_kernel: geo_cube_sweep.hip): ONE definition
 // of where a plane point of a cube face lies in the source PANORAMA, so that the fp32 sweep, the bf16 volume and the high-res builders agree bit for bit.
-// (x, y, z) is apply_pose(P, backproject_planar) as pp_sweep_kernel has it; the face sweep goes on to pr = (K4 @ P) (x, y, z, 1) = K Y with
-// Y = apply_pose(P, (x, y, z)) -- the reference's doubled pose (geo_planar.hip) -- so Y is the direction the face sweep samples wherever its (u, v) falls
+// a is apply_pose(P, backproject_planar) as pp_sweep_kernel has it; the face sweep goes on to pr = (K4 @ P) (a, 1) = K Y with
+// Y = apply_pose(P, a) -- the reference's doubled pose (geo_planar.hip) -- so Y is the direction the face sweep samples wherever its (u, v) falls
 // inside the face.  Here Y is looked up in the panorama along itself: R_f Y with equirect_to_cube_kernel's face table (a signed permutation; f is
 // workgroup-uniform), that kernel's lat-long mapping lon = atan2(x + 0, z + 0), lat = asin(y / |dir|) through t_angles (atan2(y, hypot(x, z)) is that
 // arcsine; -DMSI_FAST_TAIL=0: libm), u = (lon + pi) / 2pi W - 0.5, v = (lat + pi/2) / pi H - 0.5, and its sampler: u clamped to [-0.5, W - 0.5] and
 // wrapped, v clamped to [0, H - 1], fmaxf first so that a NaN (Y = 0, a non-finite pose) is the lower bound BEFORE the float -> int conversion; the
 // weights and blend4's order are that kernel's.  Every offset lies inside one sample's [H,W,3] panorama for any input (H * W * 12 < 2^31, checked on
 // the host); the range-checked descriptor is a second line.
-__device__ __forceinline__ TapsB cube_pano_taps(const float *__restrict__ P, int f, float x, float y, float z, int pano_h, int pano_w) {
-  // the pose once more: Y = apply_pose(P, a), rows 0..2
-  const float yx = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
-  const float yy = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
-  const float yz = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
+__device__ __forceinline__ TapsB cube_pano_taps(const float *__restrict__ P, int f, const Vec3 &a, int pano_h, int pano_w) {
+  const Vec3 Y = apply_pose(P, a);                                              // the pose once more
+  const float yx = Y.x, yy = Y.y, yz = Y.z;
   float cx, cy, cz;                                                             // R_f Y
   switch (f) {
     case 0: cx = yx; cy = yy; cz = yz; break;
@@ -601,71 +812,37 @@ __device__ __forceinline__ TapsB cube_pano_taps(const float *__restrict__ P, int
   t.wa = (1.0f - dv) * (1.0f - du); t.wb = (1.0f - dv) * du; t.wc = dv * (1.0f - du); t.wd = dv * du;
   return t;
 }
-// one sample's panorama [H,W,3] as a range-checked buffer
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cube_pano_rsrc(const float *__restrict__ panorama, int sample, int pano_h, int pano_w) {
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(panorama + (size_t)sample * pano_h * pano_w * 3), 0, pano_h * pano_w * 12, 0x00020000);
-}
 
 // The texel of the cube high-res stack: the PP texel above with its background taken from the source panorama.  Entry n of the [6B,...] batch is face
-// n % 6 of sample n / 6; the foreground (ref face, ref pose) is pp_hres_source / pp_hres_source_taps unchanged, and there is no equal-poses shortcut:
-// the two sources are different images.  Steps as there: cube_hres_taps -> cube_hres_fetch -> hres_blend.
-struct CubeHresPixel {
-  PpHresSource s0;                 // the ref face
+// n % 6 of sample n / 6 (b = n here); the foreground (ref face, ref pose) is PlanarHresPixel's, unchanged, and there is no equal-poses shortcut: the two
+// sources are different images.
+struct CubeHres : PlanarHresPixel {
   __amdgpu_buffer_rsrc_t pano;     // the source panorama of this cube
   const float *P1;                 // the face's source pose
-  float S, T, fx, fy, cx, cy;
   int f, pano_h, pano_w;
+  __device__ __forceinline__ HresTaps taps(float depth) const {
+    HresTaps t;
+    const Vec3 point = plane_point(depth);
+    t.fg = pp_hres_source_taps(s0, point, width, height);
+    t.bg = cube_pano_taps(P1, f, apply_pose(P1, point), pano_h, pano_w);
+    return t;
+  }
+  __device__ __forceinline__ HresRgb fetch(const HresTaps &t) const {
+    HresRgb g;
+    g.fg = gather3_load(s0.img, t.fg);
+    g.bg = gather3_load(pano, t.bg);
+    return g;
+  }
 };
-__device__ __forceinline__ CubeHresPixel cube_hres_pixel(const float *__restrict__ ref_faces, const float *__restrict__ panorama,
-                                                         const float *__restrict__ pose0, const float *__restrict__ pose1,
-                                                         const float *__restrict__ intrinsics, int n, int i, int j, int height, int width, int pano_h,
-                                                         int pano_w, float s0, float sstep, float t0, float tstep) {
-  CubeHresPixel p;
-  const float *Kb = intrinsics + (size_t)n * 9;
-  p.fx = Kb[0]; p.fy = Kb[4]; p.cx = Kb[2]; p.cy = Kb[5];
-  p.S = s0 + sstep * (float)j; p.T = t0 + tstep * (float)i;
-  p.s0 = pp_hres_source(ref_faces, pose0, Kb, n, height, width);
+__device__ __forceinline__ CubeHres cube_hres(const float *__restrict__ ref_faces, const float *__restrict__ panorama, const float *__restrict__ pose0,
+                                              const float *__restrict__ pose1, const float *__restrict__ intrinsics, int n, int i, int j, int face,
+                                              int pano_h, int pano_w, float s0, float sstep) {
+  CubeHres p{planar_hres_pixel(ref_faces, pose0, intrinsics, n, i, j, face, face, s0, sstep, s0, sstep)};
   const int sample = n / 6;
   p.f = n - sample * 6; p.pano_h = pano_h; p.pano_w = pano_w;
-  p.pano = cube_pano_rsrc(panorama, sample, pano_h, pano_w);
+  p.pano = image_rsrc(panorama, sample, pano_h, pano_w);
   p.P1 = pose1 + (size_t)n * 16;
   return p;
-}
-__device__ __forceinline__ HresTaps cube_hres_taps(const CubeHresPixel &p, float depth, int width, int height) {
-  HresTaps t;
-  // backproject_planar (spherical.py:146-148)
-  const float x = ((depth * p.S) * p.cx) / p.fx;
-  const float y = ((depth * p.T) * p.cy) / p.fy;
-  const float z = depth * 1.0f;
-  t.fg = pp_hres_source_taps(p.s0, x, y, z, width, height);
-  const float *P = p.P1;   // apply_pose, as pp_hres_source_taps begins
-  const float ax = ((P[0] * x + P[1] * y) + P[2] * z) + P[3] * 1.0f;
-  const float ay = ((P[4] * x + P[5] * y) + P[6] * z) + P[7] * 1.0f;
-  const float az = ((P[8] * x + P[9] * y) + P[10] * z) + P[11] * 1.0f;
-  t.bg = cube_pano_taps(P, p.f, ax, ay, az, p.pano_h, p.pano_w);
-  return t;
-}
-__device__ __forceinline__ HresRgb cube_hres_fetch(const CubeHresPixel &p, const HresTaps &t) {
-  HresRgb g;
-  g.fg = gather3_load(p.s0.img, t.fg);
-  g.bg = gather3_load(p.pano, t.bg);
-  return g;
-}
-__device__ __forceinline__ float4 cube_hres_texel(const CubeHresPixel &p, float depth, int width, int height, float w, float alpha) {
-  const HresTaps t = cube_hres_taps(p, depth, width, height);
-  return hres_blend(t, cube_hres_fetch(p, t), w, alpha);
-}
-
-// ---- sweep, layers (pack / unpack / hres) and planar: the 16-byte store of every streaming kernel; its host side is beyond_infinity_cache below.
-// The 16-byte pieces of a wave's whole-pixel strip.  nt != 0 (block-uniform; the host sets it when the volume is larger than the 256-MB Infinity Cache): non-temporal
-// stores -- a volume that cannot stay cached until conv1_1 reads it should not evict what can (r06, same-box A/B at configs[2]: sweep 1.07 -> 0.98 ms per 16 frames;
-// configs[3] -1 %; at batch 1 the 157-MB volume stays cached and keeps plain stores).
-__device__ __forceinline__ void sweep_store16(uint4 *dst, const uint4 &v, int nt) {
-  if (nt) {
-    __builtin_nontemporal_store(v.x, &dst->x); __builtin_nontemporal_store(v.y, &dst->y); __builtin_nontemporal_store(v.z, &dst->z); __builtin_nontemporal_store(v.w, &dst->w);
-  } else {
-    *dst = v;
-  }
 }
 
 // ---- render (render_views_packed_kernel) and layers (unpack_layers_kernel): ONE decode rule, so a render from a packed stack is bit-identical to
@@ -1153,6 +1330,31 @@ template <class F> void for_format(int format, F f) {
 template <class F> void for_camera(int camera, F f) {
   if (camera == MSI_CAMERA_PINHOLE) f(Const<MSI_CAMERA_PINHOLE>{});
   else f(Const<MSI_CAMERA_EQUIRECT>{});
+}
+
+// layers, planar-hres, cube-sweep (msi_hres_layers, msi_pp_hres_layers, msi_cube_hres_layers): ONE store policy and ONE table of instantiations for the
+// dense builders.  NT bit 0 / bit 1: non-temporal stores of the fp32 / the packed stack when that destination (texels x 16 / 8 / 4 bytes) cannot stay
+// in the Infinity Cache.  launch(Const<FMT>, Const<WITH_F32>, Const<NT>) is called for exactly one of: fp32 alone NT 0, 1; packed + fp32 NT 0..3;
+// packed alone NT 0, 2.  format: validated by the caller where layers_out is set.
+template <class Launch>
+void hres_dense_launch(int format, const void *rgba_native, const void *layers_out, size_t texels, Launch launch) {
+  const int fmt = layers_out ? format : MSI_LAYERS_F32;
+  const int nt = (rgba_native && beyond_infinity_cache(texels * 16) ? 1 : 0) |
+                 (layers_out && beyond_infinity_cache(texels << (fmt == MSI_LAYERS_RGBA8 ? 2 : 3)) ? 2 : 0);
+  for_format(fmt, [&](auto FMT) {
+    if constexpr (decltype(FMT)::value == MSI_LAYERS_F32) {
+      if (nt) launch(FMT, Const<1>{}, Const<1>{}); else launch(FMT, Const<1>{}, Const<0>{});
+    } else if (rgba_native) {
+      switch (nt) {
+        case 0: launch(FMT, Const<1>{}, Const<0>{}); break;
+        case 1: launch(FMT, Const<1>{}, Const<1>{}); break;
+        case 2: launch(FMT, Const<1>{}, Const<2>{}); break;
+        default: launch(FMT, Const<1>{}, Const<3>{}); break;
+      }
+    } else {
+      if (nt) launch(FMT, Const<0>{}, Const<2>{}); else launch(FMT, Const<0>{}, Const<0>{});
+    }
+  });
 }
 
 // render (RAY_PERSPECTIVE) and planar: spherical.uv_grid (spherical.py:46-48) = tf.linspace(-1 + 1/n, 1 - 1/n, n) with its fp32 semantics; v[i] = start + step * i

@@ -1026,21 +1026,46 @@ class MSI(object):
             who, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics, ref_pose_inv, sweep)
         b, h, w, d = bw.shape
         hh, hw = hres_ref.shape[1], hres_ref.shape[2]
-        rgba = torch.empty((b, d, hh, hw, 4), dtype=torch.float32, device=self.device) if want_f32 else None
-        codes = None
-        if pfmt is not None:
-            codes = torch.empty((b, d, hh, hw, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
         name = "msi_hres_layers" if sweep == 'ODS' else "msi_pp_hres_layers"
         trig_arg = (trig.data_ptr(),) if sweep == 'ODS' else ()
-        N.check(getattr(N.lib, name)(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(), intr.data_ptr(),
-                                     depths.data_ptr(), *trig_arg, bw.data_ptr(), al.data_ptr(), b, h, w, hh, hw, d, _ptr(rgba), _ptr(codes),
-                                     self.LAYER_FORMATS.get(pfmt, N.MSI_LAYERS_F32), self._stream()), name)
+        return self._hres_dense(name, (hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(), intr.data_ptr(),
+                                       depths.data_ptr(), *trig_arg, bw.data_ptr(), al.data_ptr(), b, h, w, hh, hw, d), (b, d, hh, hw), planes,
+                                want_f32, pfmt)
+
+    def _hres_dense(self, name, head, shape, planes, want_f32, pfmt):
+        """The dense high-res builders' outputs and launch: entry point `name` called with `head` (its inputs and sizes), the fp32 and / or packed
+        stack of `shape` = (B, D, H, W) allocated for it, and the result wrapped as hres_layers documents."""
+        rgba = torch.empty(shape + (4,), dtype=torch.float32, device=self.device) if want_f32 else None
+        codes = None
+        if pfmt is not None:
+            codes = torch.empty(shape + (4,), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+        N.check(getattr(N.lib, name)(*head, _ptr(rgba), _ptr(codes), self.LAYER_FORMATS.get(pfmt, N.MSI_LAYERS_F32), self._stream()), name)
         out = {}
         if rgba is not None:
             out['rgba_layers'] = rgba.permute(0, 2, 3, 1, 4)
         if codes is not None:
             out['packed_layers'] = PackedLayers(codes, pfmt, planes)
         return out
+
+    def _hres_sparse(self, index, fill, head, alphas, low, shape, planes, pfmt, border):
+        """The sparse high-res builders: the table of `shape` = (B, D, H, W) from the low-res alphas ([B,h,w,D], low = (h, w)) by entry point `index`,
+        layer_start by cumsum, the pool (one host synchronisation: its size is data-dependent), and entry point `fill` called with `head` (its
+        inputs and sizes) for the texels of kept tiles -> {'sparse_layers': SparseLayers}."""
+        b, d, hh, hw = shape
+        if hh % TILE_H or hw % TILE_W:
+            raise ValueError("a sparse stack needs H %% %d == 0 and W %% %d == 0, not %d x %d" % (TILE_H, TILE_W, hh, hw))
+        fmt = self.LAYER_FORMATS[pfmt]
+        table = torch.empty((b, d, hh // TILE_H, hw // TILE_W), dtype=torch.int32, device=self.device)
+        counts = torch.empty((b * d,), dtype=torch.int32, device=self.device)
+        N.check(getattr(N.lib, index)(alphas.data_ptr(), fmt, b, low[0], low[1], hh, hw, d, table.data_ptr(), counts.data_ptr(), self._stream()), index)
+        layer_start = torch.zeros((b * d + 1,), dtype=torch.int64, device=self.device)
+        if b * d:
+            layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(layer_start[-1].item())
+        pool = torch.empty((total, TILE_H, TILE_W, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
+        if total:
+            N.check(getattr(N.lib, fill)(*head, table.data_ptr(), layer_start.data_ptr(), pool.data_ptr(), fmt, self._stream()), fill)
+        return {'sparse_layers': SparseLayers(table, layer_start, pool, pfmt, planes, border=border)}
 
     def _hres_build_sparse(self, who, sweep, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
                            intrinsics, ref_pose_inv, want_f32, pfmt):
@@ -1053,25 +1078,12 @@ class MSI(object):
             who, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics, ref_pose_inv, sweep)
         b, h, w, d = bw.shape
         hh, hw = hres_ref.shape[1], hres_ref.shape[2]
-        if hh % TILE_H or hw % TILE_W:
-            raise ValueError("a sparse stack needs H %% %d == 0 and W %% %d == 0, not %d x %d" % (TILE_H, TILE_W, hh, hw))
-        fmt = self.LAYER_FORMATS[pfmt]
         index, fill, border = (("msi_hres_index_tiles", "msi_hres_layers_sparse", 'wrap') if sweep == 'ODS' else
                                ("msi_hres_index_tiles_edge", "msi_pp_hres_layers_sparse", 'edge'))
-        table = torch.empty((b, d, hh // TILE_H, hw // TILE_W), dtype=torch.int32, device=self.device)
-        counts = torch.empty((b * d,), dtype=torch.int32, device=self.device)
-        N.check(getattr(N.lib, index)(al.data_ptr(), fmt, b, h, w, hh, hw, d, table.data_ptr(), counts.data_ptr(), self._stream()), index)
-        layer_start = torch.zeros((b * d + 1,), dtype=torch.int64, device=self.device)
-        if b * d:
-            layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
-        total = int(layer_start[-1].item())
-        pool = torch.empty((total, TILE_H, TILE_W, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
-        if total:
-            trig_arg = (trig.data_ptr(),) if sweep == 'ODS' else ()
-            N.check(getattr(N.lib, fill)(hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(), intr.data_ptr(),
-                                         depths.data_ptr(), *trig_arg, bw.data_ptr(), al.data_ptr(), b, h, w, hh, hw, d, table.data_ptr(),
-                                         layer_start.data_ptr(), pool.data_ptr(), fmt, self._stream()), fill)
-        return {'sparse_layers': SparseLayers(table, layer_start, pool, pfmt, planes, border=border)}
+        trig_arg = (trig.data_ptr(),) if sweep == 'ODS' else ()
+        head = (hres_ref.data_ptr(), hres_src.data_ptr(), cur[0].data_ptr(), cur[1].data_ptr(), intr.data_ptr(), depths.data_ptr(), *trig_arg,
+                bw.data_ptr(), al.data_ptr(), b, h, w, hh, hw, d)
+        return self._hres_sparse(index, fill, head, al, (h, w), (b, d, hh, hw), planes, pfmt, border)
 
     def msi_render_equirect_hres(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image,
                                  ref_pose, src_pose, tgt_pose_rt, tgt_pos, planes, intrinsics,
@@ -1388,7 +1400,7 @@ class MSI(object):
         return build(blend_weights, alphas, ref_faces, src_faces, eye, face_src, planes, kf, ref_pose_inv=eye, layer_format=layer_format)
 
     def _cube_hres_build(self, blend_weights, alphas, ref_faces, src_panorama, face_src_poses, planes, face_intrinsics, sparse, want_f32, pfmt):
-        """hres_cube_layers(src_sampling='panorama'): _hres_build / _hres_build_sparse with the cube entry points.  ref_faces [6B,S,S,3] and
+        """hres_cube_layers(src_sampling='panorama'): _hres_dense / _hres_sparse with the cube entry points.  ref_faces [6B,S,S,3] and
         src_panorama [B,Hp,Wp,3] are preprocessed ([-1,1]); (want_f32, pfmt) = _layer_formats of the caller's request."""
         who = "hres_cube_layers"
         ref_faces, pano, eye, face_src, kf, b, s = self._cube_sweep_inputs(who, ref_faces, src_panorama, face_src_poses, face_intrinsics)
@@ -1401,36 +1413,10 @@ class MSI(object):
         head = (ref_faces.data_ptr(), pano.data_ptr(), eye.data_ptr(), face_src.data_ptr(), kf.data_ptr(), depths.data_ptr(), bw.data_ptr(),
                 al.data_ptr(), b, hp, wp, low, s, d)
         if not sparse:
-            rgba = torch.empty((6 * b, d, s, s, 4), dtype=torch.float32, device=self.device) if want_f32 else None
-            codes = None
-            if pfmt is not None:
-                codes = torch.empty((6 * b, d, s, s, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
-            N.check(N.lib.msi_cube_hres_layers(*head, _ptr(rgba), _ptr(codes), self.LAYER_FORMATS.get(pfmt, N.MSI_LAYERS_F32), self._stream()),
-                    "msi_cube_hres_layers")
-            out = {}
-            if rgba is not None:
-                out['rgba_layers'] = rgba.permute(0, 2, 3, 1, 4)
-            if codes is not None:
-                out['packed_layers'] = PackedLayers(codes, pfmt, planes)
-            return out
+            return self._hres_dense("msi_cube_hres_layers", head, (6 * b, d, s, s), planes, want_f32, pfmt)
         if want_f32 or pfmt is None:
             raise ValueError("%s: sparse=True takes layer_format 'rgba8' or 'rgba16f' alone (fp32 pools are not built)" % who)
-        if s % TILE_H or s % TILE_W:
-            raise ValueError("a sparse stack needs H %% %d == 0 and W %% %d == 0, not %d x %d" % (TILE_H, TILE_W, s, s))
-        fmt = self.LAYER_FORMATS[pfmt]
-        table = torch.empty((6 * b, d, s // TILE_H, s // TILE_W), dtype=torch.int32, device=self.device)
-        counts = torch.empty((6 * b * d,), dtype=torch.int32, device=self.device)
-        N.check(N.lib.msi_hres_index_tiles_edge(al.data_ptr(), fmt, 6 * b, low, low, s, s, d, table.data_ptr(), counts.data_ptr(), self._stream()),
-                "msi_hres_index_tiles_edge")
-        layer_start = torch.zeros((6 * b * d + 1,), dtype=torch.int64, device=self.device)
-        if b * d:
-            layer_start[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
-        total = int(layer_start[-1].item())
-        pool = torch.empty((total, TILE_H, TILE_W, 4), dtype=torch.uint8 if pfmt == 'rgba8' else torch.float16, device=self.device)
-        if total:
-            N.check(N.lib.msi_cube_hres_layers_sparse(*head, table.data_ptr(), layer_start.data_ptr(), pool.data_ptr(), fmt, self._stream()),
-                    "msi_cube_hres_layers_sparse")
-        return {'sparse_layers': SparseLayers(table, layer_start, pool, pfmt, planes, border='edge')}
+        return self._hres_sparse("msi_hres_index_tiles_edge", "msi_cube_hres_layers_sparse", head, al, (low, low), (6 * b, d, s, s), planes, pfmt, 'edge')
 
     # ------------------------------------------------------------------ image scores (eval.py:127-174 on the device)
     SCORE_TRANSFORMS = {'raw': N.MSI_SCORE_RAW, 'image': N.MSI_SCORE_IMAGE, 'depth': N.MSI_SCORE_DEPTH}

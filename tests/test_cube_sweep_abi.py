@@ -41,16 +41,25 @@ def test_defined_once_in_the_new_unit_and_one_sample_position():
         assert {u: n for u, n in hits.items() if n} == {"geo_cube_sweep.hip": 1}, (name, hits)
     assert {u: len(re.findall(r"TapsB cube_pano_taps\(", t)) for u, t in texts.items() if "TapsB cube_pano_taps(" in t} == {"geometry_device.h": 1}
     unit = texts["geo_cube_sweep.hip"]
-    for kernel, call in (("cube_sweep_kernel", "cube_pano_taps("), ("cube_sweep_volume_bf16_kernel", "cube_pano_taps("),
-                         ("cube_hres_layers_kernel", "cube_hres_texel("), ("cube_hres_layers_sparse_kernel", "cube_hres_taps(")):
+    # each sweep kernel names the one body of its kind, each builder the texel or its steps, and all the source type that samples the panorama
+    for kernel, body_name, source in (("cube_sweep_kernel", "sweep_body<", "cube_pano_source("),
+                                      ("cube_sweep_volume_bf16_kernel", "sweep_volume_bf16_body<", "cube_pano_source("),
+                                      ("cube_hres_layers_kernel", "hres_texel(px, ", "cube_hres("),
+                                      ("cube_hres_layers_sparse_kernel", "px.taps(", "cube_hres(")):
         body = unit[unit.index("\n%s(" % kernel):]
         body = body[:body.index("\n}\n")]
-        assert call in body and "atan2f" not in body and "asinf" not in body, kernel
-    # the high-res texel's background goes through the same function, and nothing else in the library computes the position
+        assert body_name in body and source in body and "atan2f" not in body and "asinf" not in body, kernel
+    # both source types go through the one function, and nothing else in the library computes the position
     header = texts["geometry_device.h"]
-    taps = header[header.index("HresTaps cube_hres_taps("):]
-    assert "cube_pano_taps(" in taps[:taps.index("\n}\n")]
-    assert sum(t.count("cube_pano_taps(") for t in texts.values()) == 4          # the definition and three callers
+    for text, struct, member in ((unit, "struct CubePanoSource {", "void sample("), (header, "struct CubeHres : ", "HresTaps taps(")):
+        assert text.count(struct) == 1
+        source = text[text.index(struct):]
+        source = source[:source.index("\n};\n")]
+        assert member in source and "cube_pano_taps(" in source and "atan2f" not in source and "asinf" not in source, struct
+    for pattern in (r"CubeHres cube_hres\(", r"void sweep_body\(", r"void sweep_volume_bf16_body\("):
+        assert {u: len(re.findall(pattern, t)) for u, t in texts.items() if re.search(pattern, t)} == {"geometry_device.h": 1}, pattern
+    # the definition and two callers: CubePanoSource::sample (both sweep kernels) and CubeHres::taps (both high-res builders)
+    assert sum(t.count("cube_pano_taps(") for t in texts.values()) == 3
 
 
 # ------------------------------------------------------------------------------------------------ the argument checks

@@ -15,6 +15,9 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 LOW, D = 8, 4
 PLANES = (100.0, 10.0, 3.0, 1.0)
+# D = 4 is ONE layer group of the builders (HRES_G = 4): their group loop runs once.  This case has two, with alpha blocks sparse enough that whole groups drop.
+SEED_TWO_GROUPS = 3       # (by the keep rule restated in numpy: 5 of the 24 tiles drop all of layers 4..7, 17 keep some of them, 2 keep all four)
+TWO_GROUPS = dict(s=16, b=1, d=8, planes=(100.0, 30.0, 10.0, 5.0, 3.0, 2.0, 1.5, 1.0), on=0.06, seed=SEED_TWO_GROUPS)
 FORMATS = ["f32", "rgba8", "rgba16f", ("f32", "rgba8")]
 CODE_DTYPE = {"rgba8": "uint8", "rgba16f": "float16"}
 SHAPES = [(16, 1), (16, 2), (32, 1), (32, 2)]          # (face size, cubes)
@@ -27,14 +30,14 @@ def model():
 
 
 @functools.lru_cache(maxsize=None)
-def _case(s, b):
-    """Low-res blend weights and alphas [6B,8,8,D] (alphas zero outside random 2 x 3-texel blocks, so that the sparse build drops tiles), a pair of raw
-    panoramas in [0, 1], and the source poses: the rotated and translated one, after the identity when B = 2."""
-    rng = np.random.RandomState(100 * s + b)
-    x = dict(s=s, b=b)
-    x["bw"] = rng.uniform(0.0, 1.0, size=(6 * b, LOW, LOW, D)).astype(F)
-    on = rng.uniform(size=(6 * b, LOW // 2, -(-LOW // 3), D)) < 0.25
-    x["al"] = (rng.uniform(0.05, 0.95, size=(6 * b, LOW, LOW, D)) * np.repeat(np.repeat(on, 2, axis=1), 3, axis=2)[:, :LOW, :LOW]).astype(F)
+def _case(s, b, d=D, planes=PLANES, on=0.25, seed=None):
+    """Low-res blend weights and alphas [6B,8,8,D] (alphas zero outside random 2 x 3-texel blocks, each on with probability `on`, so that the sparse
+    build drops tiles), a pair of raw panoramas in [0, 1], and the source poses: the rotated and translated one, after the identity when B = 2."""
+    rng = np.random.RandomState(100 * s + b if seed is None else seed)
+    x = dict(s=s, b=b, d=d, planes=planes)
+    x["bw"] = rng.uniform(0.0, 1.0, size=(6 * b, LOW, LOW, d)).astype(F)
+    on = rng.uniform(size=(6 * b, LOW // 2, -(-LOW // 3), d)) < on
+    x["al"] = (rng.uniform(0.05, 0.95, size=(6 * b, LOW, LOW, d)) * np.repeat(np.repeat(on, 2, axis=1), 3, axis=2)[:, :LOW, :LOW]).astype(F)
     x["raw_src"], x["raw_ref"] = smooth_noise(rng, b, 24, 50, factor=4), smooth_noise(rng, b, 24, 50, factor=4)
     x["src_pose"] = cases.source_poses()[2 - b:]
     for v in x.values():
@@ -57,12 +60,14 @@ def _same_bits(a, b):
 _YARDSTICK = {}
 
 
-def _three_launches(m, s, b):
-    """The native fp32 stack [6B,D,S,S,4] of the three launches, on the inputs hres_cube_layers prepares; run once per shape and shared."""
+def _three_launches(m, s, b, **case):
+    """The native fp32 stack [6B,D,S,S,4] of the three launches, on the inputs hres_cube_layers prepares; run once per case and shared."""
     import torch
     from matryodshka_amd import _native as N, cubemap
-    if (s, b) not in _YARDSTICK:
-        x = _case(s, b)
+    key = (s, b) + tuple(sorted(case.items()))
+    if key not in _YARDSTICK:
+        x = _case(s, b, **case)
+        D, PLANES = x["d"], x["planes"]
         k = cubemap.default_face_intrinsics(s)
         ref_faces = m.preprocess_image(m.equirect_to_cube(m._f32(x["raw_ref"]), s, k).reshape(6 * b, s, s, 3))
         pano = m.preprocess_image(m._f32(x["raw_src"]))
@@ -75,8 +80,8 @@ def _three_launches(m, s, b):
         N.check(N.lib.msi_resize_bilinear_f32(low.data_ptr(), up.data_ptr(), 6 * b, LOW, LOW, 2 * D, s, s, st), "resize")
         rgba = torch.empty((6 * b, D, s, s, 4), dtype=torch.float32, device=m.device)
         N.check(N.lib.msi_assemble_rgba_scaled_f32(psv.data_ptr(), up.data_ptr(), rgba.data_ptr(), 6 * b, s, s, D, st), "assemble")
-        _YARDSTICK[(s, b)] = rgba
-    return _YARDSTICK[(s, b)]
+        _YARDSTICK[key] = rgba
+    return _YARDSTICK[key]
 
 
 def _pack(m, rgba, fmt):
@@ -87,9 +92,9 @@ def _pack(m, rgba, fmt):
     return codes
 
 
-def _new(m, s, b, **kw):
-    x = _case(s, b)
-    return m.hres_cube_layers(x["bw"], x["al"], x["raw_src"], x["raw_ref"], x["src_pose"], s, PLANES, src_sampling='panorama', **kw)
+def _new(m, s, b, case=None, **kw):
+    x = _case(s, b, **(case or {}))
+    return m.hres_cube_layers(x["bw"], x["al"], x["raw_src"], x["raw_ref"], x["src_pose"], s, x["planes"], src_sampling='panorama', **kw)
 
 
 @pytest.mark.parametrize("layer_format", FORMATS, ids=lambda f: f if isinstance(f, str) else "+".join(f))
@@ -155,3 +160,26 @@ def test_3_the_result_goes_into_the_cube_viewer(model):
     rgb_s, dep_s = m.cube_render_views(sparse, pose, pos, size=(24, 48))
     assert bool((rgb_s == rgb_d).all()) and bool((dep_s == dep_d).all())
     assert bool(torch.isfinite(rgb_d).all()) and float(rgb_d.abs().max()) > 0
+
+
+def test_4_two_layer_groups_with_a_whole_group_dropped(model):
+    """Face 16, one cube, D = 8: the dense builder steps from one group's texels to the next, and the sparse builder meets a tile whose whole second
+    group is dropped (it skips the group) next to tiles where that group is partly kept.  Same yardsticks as tests 1 and 2."""
+    import torch
+    m = model
+    case = dict(TWO_GROUPS)
+    s, b = case.pop("s"), case.pop("b")
+    want = _three_launches(m, s, b, **case)
+    assert bool(torch.isfinite(want).all()) and float(want[..., :3].abs().max()) > 0.1
+    got = _new(m, s, b, case, layer_format=("f32", "rgba8"))
+    assert _same_bits(got["rgba_layers"], want.permute(0, 2, 3, 1, 4))
+    assert _same_bits(got["packed_layers"].data, _pack(m, want, "rgba8"))
+    sparse = _new(m, s, b, case, layer_format="rgba8", sparse=True)["sparse_layers"]
+    ref = m.sparsify_layers(got["packed_layers"], border='edge')
+    for name in ("table", "layer_start", "pool"):
+        assert torch.equal(getattr(sparse, name), getattr(ref, name)) and getattr(sparse, name).dtype == getattr(ref, name).dtype, name
+    kept = (sparse.table >= 0).cpu().numpy()                 # [6, 8, S / 4, S / 16]
+    assert kept.shape == (6, 8, s // 4, s // 16) and kept[:, 0].all()
+    group1 = kept[:, 4:8].sum(axis=1)                          # kept layers of the second group, per tile
+    assert (group1 == 0).any(), "no tile has its whole second group dropped"
+    assert ((group1 > 0) & (group1 < 4)).any(), "no tile has its second group partly kept"

@@ -60,17 +60,33 @@ def test_defined_once_in_a_geometry_unit():
 
 
 def test_the_texel_and_the_tile_are_each_defined_once():
-    """One definition of the high-res texel, in the header both kernels' units include, and one of the tile and of the scan."""
+    """One definition of the high-res texel, of the ODS source and of the two launchers, in the headers the kernels' units include, and one of the
+    tile and of the scan.  (The builders' group loops are written per kernel: as shared bodies they missed the timing margin,
+    profiles/hres_bodies_isa.txt.)"""
     from matryodshka_amd import build
     texts = {u: open(os.path.join(build.CSRC, u)).read() for u in os.listdir(build.CSRC) if u.endswith((".hip", ".h", ".cpp", ".inc"))}
-    for pattern, where in ((r"float4 hres_texel\(", "geometry_device.h"), (r"HresTaps hres_taps\(", "geometry_device.h"),
+    for pattern, where in ((r"float4 hres_texel\(", "geometry_device.h"), (r"struct OdsHres \{", "geometry_device.h"),
+                           (r"void hres_dense_launch\(", "geometry_device.h"), (r"int hres_sparse_launch\(", "geo_sparse.h"),
                            (r"constexpr int TILE_H = ", "geo_sparse.h"), (r"\nsparse_scan_kernel\(", "geo_sparse.hip"),
                            (r"\nint sparse_dims\(", "geo_sparse.hip")):
         assert {u: len(re.findall(pattern, t)) for u, t in texts.items() if re.search(pattern, t)} == {where: 1}, pattern
-    for unit, kernel in (("geo_layers.hip", "hres_layers_kernel"), ("geo_sparse_hres.hip", "hres_layers_sparse_kernel")):
+    # the dense kernel calls the one texel, the sparse kernel the texel's steps, both on the ODS source; the source's taps is where the sweep's
+    # functions are called
+    for unit, kernel, body_name in (("geo_layers.hip", "hres_layers_kernel", "hres_texel(px, "),
+                                    ("geo_sparse_hres.hip", "hres_layers_sparse_kernel", "px.taps(")):
         body = texts[unit][texts[unit].index("\n%s(" % kernel):]
         body = body[:body.index("\n}\n")]
-        assert re.search(r"hres_texel\(|hres_taps\(", body) and "ods_quad" not in body and "gather3(" not in body, unit
+        assert body_name in body and "OdsHres" in body and "ods_quad" not in body and "gather3(" not in body, unit
+    header = texts["geometry_device.h"]
+    source = header[header.index("struct OdsHres {"):]
+    source = source[:source.index("\n};\n")]
+    assert "HresTaps taps(" in source and "ods_quad(" in source and "HresRgb fetch(" in source
+    texel = header[header.index("float4 hres_texel("):]
+    texel = texel[:texel.index("\n}\n")]
+    assert "src.taps(" in texel and "src.fetch(" in texel and "hres_blend(" in texel
+    sparse = texts["geo_sparse_hres.hip"][texts["geo_sparse_hres.hip"].index("\nhres_layers_sparse_kernel("):]
+    sparse = sparse[:sparse.index("\n}\n")]
+    assert "px.taps(" in sparse and "px.fetch(" in sparse and "hres_blend(" in sparse
 
 
 # ------------------------------------------------------------------------------------------------ the argument checks

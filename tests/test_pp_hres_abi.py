@@ -55,13 +55,20 @@ def test_each_is_defined_once_in_its_geometry_unit():
 def test_the_pp_texel_is_defined_once_and_both_kernels_call_it():
     from matryodshka_amd import build
     texts = {u: open(os.path.join(build.CSRC, u)).read() for u in os.listdir(build.CSRC) if u.endswith((".hip", ".h", ".cpp", ".inc"))}
-    for pattern in (r"float4 pp_hres_texel\(", r"HresTaps pp_hres_taps\(", r"PpHresPixel pp_hres_pixel\("):
+    # the PP source, its pixel state, and where a plane point lands in one source image: one definition each
+    for pattern in (r"struct PpHres : ", r"PpHres pp_hres\(", r"TapsB pp_hres_source_taps\("):
         assert {u: len(re.findall(pattern, t)) for u, t in texts.items() if re.search(pattern, t)} == {"geometry_device.h": 1}, pattern
+    # the dense kernel calls the one texel, the sparse kernel the texel's steps, both on the PP source; the source's taps calls the one definition
+    # (the group loops are written in these kernels: as the shared bodies they missed the timing margin, profiles/hres_bodies_isa.txt)
     unit = texts["geo_planar_hres.hip"]
-    for kernel in ("pp_hres_layers_kernel", "pp_hres_layers_sparse_kernel"):
+    for kernel, body_name in (("pp_hres_layers_kernel", "hres_texel(px, "), ("pp_hres_layers_sparse_kernel", "px.taps(")):
         body = unit[unit.index("\n%s(" % kernel):]
         body = body[:body.index("\n}\n")]
-        assert re.search(r"pp_hres_texel\(|pp_hres_taps\(", body) and "pp_hres_pixel(" in body and "make_taps" not in body, kernel
+        assert body_name in body and "PpHres" in body and "pp_hres(" in body and "make_taps" not in body, kernel
+    header = texts["geometry_device.h"]
+    source = header[header.index("struct PpHres : "):]
+    source = source[:source.index("\n};\n")]
+    assert "HresTaps taps(" in source and "pp_hres_source_taps(" in source and "HresRgb fetch(" in source
 
 
 # ------------------------------------------------------------------------------------------------ the argument checks
