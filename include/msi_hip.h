@@ -68,7 +68,8 @@ const char *msi_version(void);
  *      msi_equirect_to_cube_f32; msi_sparse_index_tiles, msi_sparse_gather_tiles, msi_sparse_expand, msi_render_views_sparse;
  *      msi_hres_index_tiles, msi_hres_layers_sparse; msi_sparse_index_tiles_edge, msi_mpi_render_views_sparse,
  *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse;
- *      msi_cube_plane_sweep_f32, msi_cube_sweep_volume_bf16, msi_cube_hres_layers, msi_cube_hres_layers_sparse) */
+ *      msi_cube_plane_sweep_f32, msi_cube_sweep_volume_bf16, msi_cube_hres_layers, msi_cube_hres_layers_sparse;
+ *      msi_cube_render_views_seamless, MSI_RENDER_STATUS_NOT_CUBE_CAMERA) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -230,6 +231,8 @@ int msi_hres_layers(const float *ref_image, const float *src_image, const float 
  * not reference-defined) and reports it here instead of failing silently.  The caller zeroes the word and reads it back
  * when it wants to know (the MSI class checks host-side inputs before the launch and device-side ones through this). */
 #define MSI_RENDER_STATUS_ORIGIN_OUTSIDE 1
+/* msi_cube_render_views_seamless only: a sample's stack camera is not fx = fy = cx = cy = S/2; it was rendered with the clamp rule. */
+#define MSI_RENDER_STATUS_NOT_CUBE_CAMERA 2
 int msi_render_equirect_f32(const float *rgba_native, const float *tgt_pose_rt,
                             const float *tgt_pos, const float *depths, const float *trig,
                             int32_t batch, int32_t height, int32_t width, int32_t num_planes,
@@ -583,6 +586,38 @@ int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_p
                           int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
                           int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
                           msi_stream_t stream);
+/* msi_cube_render_views with the SEAMLESS filter (MSI.cube_render_views(filtering='seamless')): the same arguments, checks, codes,
+ * cameras, outputs and composite; only the taps differ.  With the cube camera fx = fy = cx = cy = S/2 a face stores tan = -1 ..
+ * 1 - 2/S and nothing on its +x and +y edges, so the clamp rule repeats the last texel over a one-texel band along cube edges;
+ * the neighbouring face usually stores a sample at exactly the missing point (its column 0 or row 0 lies on the shared edge).
+ * The rule is defined for that camera only (the cube point of lattice point (x, y), 0 <= x, y <= S, of a face is then a lattice
+ * point of every other face containing it).  Ray, shell hit, face choice and p = R_f^T P are msi_cube_render_views', op for op.
+ *   1. u and v are clamped to [0, S] instead of [0, S-1] (fmaxf first: a NaN still becomes 0).
+ *   2. x0 = min(floor(u), S-1), x1 = x0 + 1 <= S, du = u - x0 in [0, 1]; y0, y1, dv likewise.
+ *   3. The four taps are bilinear with msi_cube_render_views' weights and summation order.
+ *   4. A tap with x < S and y < S is the face's own texel.
+ *   5. A tap with x = S or y = S is a VIRTUAL texel at the cube point P of that lattice point (an edge point; a cube corner when
+ *      the other coordinate is 0 or S).  The other faces that contain P -- one for an edge point, two for a corner -- are taken
+ *      in ascending face index; the first whose lattice coordinates of P lie in [0, S-1]^2 supplies its texel (one fetch).  When
+ *      no face stores P the virtual texel is the mean of the clamped texels (each face's coordinates of P clamped to [0, S-1])
+ *      of all faces meeting at P, own face first, then the others in ascending face index: (a + b) * 0.5f for two faces,
+ *      ((a + b) + c) * (1.0f / 3.0f) for three; per channel, alpha included, on decoded fp32 values (a packed render keeps the
+ *      bits of the render of the unpacked stack).
+ * The three classes of the 12 cube edges under this rule:
+ *   8 are stored by ONE face (the ring front -> right -> back -> left -> front; front/up, front/down, up/right, down/left): the
+ *     filter is continuous across them;
+ *   2 have NO stored sample (right/down, back/down): the mean rule makes the filter continuous over a two-texel span;
+ *   2 are stored TWICE (up/back, up/left: row 0 of both faces): each face keeps its own texel, so a step in the CONTENT of the
+ *     two faces remains there.  That is not a filtering artefact; in-range texels are never overridden.
+ * The +x/+y corner square of a face reaches a cube corner: the three-face rule makes every face that sees it agree on its value.
+ * A sample whose stack_intrinsics are not exactly (S/2, S/2, S/2, S/2) is rendered with the clamp rule, the bits of
+ * msi_cube_render_views, and MSI_RENDER_STATUS_NOT_CUBE_CAMERA is ORed into *status_device.  Every texel address is in range by
+ * construction for any input.  Not supported: sparse stacks (msi_cube_render_views_sparse has no seamless twin). */
+int msi_cube_render_views_seamless(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                                   const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
+                                   int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
+                                   int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                                   msi_stream_t stream);
 /* Panorama -> six face images: image [B,H,W,C] fp32 (C in 1..4) -> out [B,6,S,S,C].  Texel (ix, iy) of face f looks along
  * R_f K^-1 (ix, iy, 1) with intrinsics [B,3,3]; with x and z swapped that is a direction of the render frame, sampled at
  * u = (atan2(z, x) + pi) / 2pi W - 0.5, v = (asin(y / |dir|) + pi/2) / pi H - 0.5 (the inverse of the lat-long grid of

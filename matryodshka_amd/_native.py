@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libmsi_hip.so")
 MSI_OK = 0
 MSI_NET_NUM_LAYERS = 18
 RENDER_STATUS_ORIGIN_OUTSIDE = 1
+RENDER_STATUS_NOT_CUBE_CAMERA = 2       # msi_cube_render_views_seamless: a stack camera other than S/2, rendered with the clamp rule
 MSI_CAMERA_EQUIRECT, MSI_CAMERA_PINHOLE = 0, 1   # msi_render_views_f32's camera models
 MSI_LAYERS_F32, MSI_LAYERS_RGBA8, MSI_LAYERS_RGBA16F = 0, 1, 2   # texel formats of msi_pack_layers / msi_render_views_packed
 MSI_SCORE_F32, MSI_SCORE_U8 = 0, 1                             # msi_score_images: dtype
@@ -105,6 +106,7 @@ SIGNATURES = {
     "msi_mpi_render_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "msi_mpi_render_views": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_cube_render_views": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "msi_cube_render_views_seamless": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_equirect_to_cube_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "msi_cube_plane_sweep_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "msi_cube_sweep_volume_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

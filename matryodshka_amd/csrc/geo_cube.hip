@@ -9,6 +9,31 @@
 //   z      (0,0,1)   (1,0,0)    (0,0,-1)   (-1,0,0)   (0,-1,0)   (0,1,0)
 // Texel (ix, iy) of layer d of face f is the cube-frame point R_f planes[d] K^-1 (ix, iy, 1): layer d of the six faces is a cube shell of
 // half-side planes[d].
+//
+// The SEAMLESS filter (cube_render_views_seamless_kernel, msi_cube_render_views_seamless; include/msi_hip.h and cubemap.virtual_texel state the
+// same rule).  It is defined for the cube camera fx = fy = cx = cy = S/2 only: a face then stores tan = -1 .. 1 - 2/S, nothing on its +x and +y
+// edges, and the cube point of lattice point (x, y), 0 <= x, y <= S, of a face is a lattice point of every other face that contains it.  Ray,
+// shell hit, face choice and p = R_f^T P are the clamp kernel's, op for op.  Then
+//   1. u, v are clamped to [0, S] (fmaxf first); 2. x0 = min(floor(u), S-1), x1 = x0 + 1 <= S, du = u - x0 in [0, 1], likewise y0, y1, dv;
+//   3. four bilinear taps with the clamp kernel's weights and sum order; 4. a tap with x < S and y < S is the face's own texel;
+//   5. a tap with x = S or y = S is a VIRTUAL texel at the cube point P (an edge point; a cube corner when the other coordinate is 0 or S).
+//      The other faces containing P (one on an edge, two at a corner) are tried in ascending face index: the first whose lattice coordinates
+//      of P lie in [0, S-1]^2 supplies its texel (one fetch).  When none stores P, the virtual texel is the mean of the clamped texels
+//      (coordinates clamped to [0, S-1]) of all faces meeting at P: own face first, then the others in ascending index, (a + b) * 0.5f or
+//      ((a + b) + c) * (1.0f / 3.0f), per channel (alpha included) on decoded fp32 values.
+// The neighbour across each side in closed form (t = the running coordinate; cube_side_px .. cube_corner_nx below), lattice coordinates in the
+// neighbour g:
+//   f        +x side (x = S, t = y)     +y side (y = S, t = x)     third face at corner (S, 0)     third face at corner (0, S)
+//   0 front  g 1 (0, t)                 g 5 (t, 0)                 g 4 (S, S)                      g 3 (S, S)
+//   1 right  g 2 (0, t)                 g 5 (S, t)      *          g 4 (S, 0)                      g 0 (S, S)
+//   2 back   g 3 (0, t)                 g 5 (S - t, S)  *          g 4 (0, 0)                      g 1 (S, S)
+//   3 left   g 0 (0, t)                 g 5 (0, S - t)             g 4 (0, S)                      g 2 (S, S)
+//   4 up     g 1 (S - t, 0)             g 0 (t, 0)                 g 2 (0, 0)                      g 3 (S, 0)
+//   5 down   g 1 (t, S)      *          g 2 (S - t, S)  *          g 0 (S, S)                      g 3 (0, S)
+// (* a coordinate S: the neighbour does not store the edge either.)  Of the 12 cube edges 8 are stored by one face (the ring front -> right ->
+// back -> left -> front, front/up, front/down, up/right, down/left): the filter is continuous across them.  2 have no stored sample
+// (right/down, back/down): the mean rule makes them continuous over a two-texel span.  2 are stored twice (up/back, up/left: row 0 of both
+// faces): each face keeps its own texel, so a step in CONTENT between the two faces remains there; in-range texels are never overridden.
 #include "geometry_device.h"
 
 namespace {
@@ -122,6 +147,268 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
 }
 
+// ---- the seamless filter: the neighbour tables in closed form (integer selects on the face and the side; no memory table)
+struct CubeTexel { unsigned f; int x, y; };              // lattice coordinates in [0, S] for t in [0, S]
+__device__ __forceinline__ CubeTexel cube_side_px(unsigned f, int t, int S) {      // across x = S, t = y
+  CubeTexel r;
+  r.f = f < 4u ? ((f + 1u) & 3u) : 1u;
+  r.x = f < 4u ? 0 : (f == 4u ? S - t : t);
+  r.y = f < 4u ? t : (f == 4u ? 0 : S);
+  return r;
+}
+__device__ __forceinline__ CubeTexel cube_side_py(unsigned f, int t, int S) {      // across y = S, t = x
+  const bool keep = f == 0u || f == 4u;
+  CubeTexel r;
+  r.f = f < 4u ? 5u : (f == 4u ? 0u : 2u);
+  r.x = keep ? t : (f == 1u ? S : (f == 3u ? 0 : S - t));
+  r.y = keep ? 0 : (f == 1u ? t : (f == 3u ? S - t : S));
+  return r;
+}
+__device__ __forceinline__ CubeTexel cube_corner_ny(unsigned f, int S) {           // the third face at corner (S, 0): across y = 0
+  CubeTexel r;
+  r.f = f < 4u ? 4u : (f == 4u ? 2u : 0u);
+  r.x = (f <= 1u || f == 5u) ? S : 0;
+  r.y = (f == 0u || f == 3u || f == 5u) ? S : 0;
+  return r;
+}
+__device__ __forceinline__ CubeTexel cube_corner_nx(unsigned f, int S) {           // the third face at corner (0, S): across x = 0
+  CubeTexel r;
+  r.f = f < 4u ? ((f + 3u) & 3u) : 3u;
+  r.x = f == 5u ? 0 : S;
+  r.y = f == 4u ? 0 : S;
+  return r;
+}
+// The virtual texel of lattice point (x, y) of face f with x == S or y == S (x, y in [0, S]): n = 1 -> the texel at o0 (another face's); n = 2 ->
+// (o0 + o1) * 0.5f; n = 3 -> ((o0 + o1) + o2) * (1/3), o0 the own face's clamped texel.  Offsets are texels from the sample's base; every
+// coordinate goes through min(., S-1) and every face through the selects above: in range for any f in [0, 5], x, y in [0, S].
+struct VirtualTexel { unsigned n, o0, o1, o2; };
+__device__ __forceinline__ VirtualTexel cube_virtual_texel(unsigned f, int x, int y, int S, unsigned fstride, unsigned dbase) {
+  const bool xs = x == S, ys = y == S;
+  const bool corner = (xs && ys) || (xs && y == 0) || (ys && x == 0);
+  CubeTexel a = xs ? cube_side_px(f, y, S) : cube_side_py(f, x, S);
+  CubeTexel b = (xs && ys) ? cube_side_py(f, x, S) : (xs ? cube_corner_ny(f, S) : cube_corner_nx(f, S));   // (meaningful at a corner only)
+  if (corner && b.f < a.f) { const CubeTexel c = a; a = b; b = c; }                  // ascending face index
+  const bool ia = a.x < S && a.y < S, ib = corner && b.x < S && b.y < S;
+  const int m = S - 1;
+  const auto at = [&](unsigned g, int tx, int ty) { return g * fstride + dbase + (unsigned)min(ty, m) * (unsigned)S + (unsigned)min(tx, m); };
+  const unsigned oa = at(a.f, a.x, a.y), ob = at(b.f, b.x, b.y);
+  VirtualTexel v;
+  v.n = (ia || ib) ? 1u : (corner ? 3u : 2u);
+  v.o0 = ia ? oa : (ib ? ob : at(f, x, y));
+  v.o1 = oa;
+  v.o2 = ob;
+  return v;
+}
+__device__ __forceinline__ float4 cube_select(bool c, float4 a, float4 b) {
+  float4 r;
+  r.x = c ? a.x : b.x; r.y = c ? a.y : b.y; r.z = c ? a.z : b.z; r.w = c ? a.w : b.w;
+  return r;
+}
+__device__ __forceinline__ float4 cube_mean(unsigned n, float4 a, float4 b, float4 c) {
+  float4 r;
+  if (n == 3u) {
+    const float third = 1.0f / 3.0f;
+    r.x = ((a.x + b.x) + c.x) * third; r.y = ((a.y + b.y) + c.y) * third; r.z = ((a.z + b.z) + c.z) * third; r.w = ((a.w + b.w) + c.w) * third;
+  } else {
+    r.x = (a.x + b.x) * 0.5f; r.y = (a.y + b.y) * 0.5f; r.z = (a.z + b.z) * 0.5f; r.w = (a.w + b.w) * 0.5f;
+  }
+  return r;
+}
+
+// The same table for an EDGE point (no corner), where nearly all strip lanes are: the neighbour's texel is affine in the running coordinate,
+// texel = (g D + d) S^2 + c0 + t k for t in [1, S-1] (t is clamped to that range: in the neighbour's face for any input, S >= 2).  Where the
+// neighbour does not store the edge (!stored) it is the neighbour's CLAMPED texel, the second term of the two-face mean.
+//   +x side  f < 4: g = f + 1 & 3, (0, t): c0 = 0, k = S     f = 4: g = 1, (S - t, 0): c0 = S, k = -1      f = 5: g = 1, (t, S-1): c0 = S^2 - S, k = 1, !stored
+//   +y side  f = 0, 4: g = 5, 0, (t, 0): c0 = 0, k = 1       f = 1: g = 5, (S-1, t): c0 = S - 1, k = S, !stored
+//            f = 3: g = 5, (0, S - t): c0 = S^2, k = -S      f = 2, 5: g = 5, 2, (S - t, S-1): c0 = S^2, k = -1, !stored
+struct CubeEdge { unsigned n0, n1; bool stored; };         // the neighbour's texels at t and t + 1
+__device__ __forceinline__ CubeEdge cube_edge(unsigned f, bool xside, int t, int S, unsigned ss2, unsigned fstride, unsigned dbase) {
+  const bool ring = f < 4u;
+  const unsigned gx = ring ? ((f + 1u) & 3u) : 1u, gy = ring ? 5u : (f == 4u ? 0u : 2u);
+  const int cx0 = ring ? 0 : (f == 4u ? S : (int)ss2 - S), kx = ring ? S : (f == 4u ? -1 : 1);
+  const bool keep = f == 0u || f == 4u;
+  const int cy0 = keep ? 0 : (f == 1u ? S - 1 : (int)ss2), ky = keep ? 1 : (f == 1u ? S : (f == 3u ? -S : -1));
+  const unsigned g = xside ? gx : gy;
+  const int c0 = xside ? cx0 : cy0, k = xside ? kx : ky;
+  const int ta = min(max(t, 1), S - 1), tb = min(max(t + 1, 1), S - 1);
+  const unsigned base = g * fstride + dbase;
+  CubeEdge e;
+  e.n0 = base + (unsigned)(c0 + ta * k);
+  e.n1 = base + (unsigned)(c0 + tb * k);
+  e.stored = xside ? f != 5u : (keep || f == 3u);
+  return e;
+}
+
+// cube_render_views_kernel with the seamless filter (the rule: this file's header).  Grid, rays, shell hit, face choice, blend and status are that
+// kernel's; what differs is the tap stage.
+//   camera  the rule holds for fx = fy = cx = cy = S/2 only: the sample's stack camera is compared with S/2 (scalar, uniform per workgroup).  Any
+//           other camera renders with the clamp rule (hi = S-1 below: the clamp kernel's values op for op) and ORs MSI_RENDER_STATUS_NOT_CUBE_CAMERA.
+//   taps    four unconditional loads per shell, as the clamp kernel: A is always the own texel; B, C, D are the own texel, the neighbour's texel (8 of
+//           the 12 edges: the offset is replaced, no extra fetch) or the own CLAMPED texel, the first term of a mean.  Only lanes in the strip
+//           (x1 == S or y1 == S, about 2/S of the rays) run the integer selects of cube_edge, and only lanes on the two unstored edges (the mean's
+//           second term) or in a corner square (cube_virtual_texel, the general rule) fetch again, in the blend pass;
+//           each is under a branch a wavefront with no such lane skips (s_cbranch_execz).
+//   loop    groups of four shells: first the four shells' taps are issued, then the four blends run, so up to 16 taps are in flight under the blend
+//           (the clamp kernel's unroll by 4, written out because the strip branch sits between the shells).
+//   bounds  x0, y0 in [0, S-1] by the clamps (a NaN is 0), x1, y1 in [0, S]; every fetched coordinate passes min(., S-1) (cube_edge: its running coordinate is clamped
+//           to [1, S-1], which keeps c0 + t k inside the neighbour's S^2 texels), every face is a select with values in [0, 5]: all offsets lie inside the sample's 6 D S^2 texels for any input; the descriptor's range check is a second line.
+template <int FMT> struct CubeShellTaps {
+  float4 A, B, C, D;
+  float du, dv;
+  unsigned key;            // f | x0 << 3 | again << 31 (x0 < 2^15); y0 below
+  int y0;
+};
+
+template <int MODE, int CAMERA, int FMT>
+__global__ void __launch_bounds__(256)
+cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *__restrict__ pose_rt, const float *__restrict__ tgt_pos,
+                                  const float *__restrict__ intrinsics, const float *__restrict__ stack_intrinsics,
+                                  const float *__restrict__ depths, const float *__restrict__ trig, int batch, int views, int face, int nd,
+                                  int out_h, int out_w, float *__restrict__ out_rgb, float *__restrict__ out_depth, DepthFrac F,
+                                  int *__restrict__ status) {
+  ViewBlock<4> k(out_h, out_w, views, batch);
+  if (k.past_end()) return;
+  k.decode(views);
+  const unsigned bv = k.bv;
+  const int i = k.i, j = k.j, b = k.b;
+  if (j >= out_w || i >= out_h) return;
+
+  ViewRay r = view_ray<CAMERA>(intrinsics, nullptr, trig, tgt_pos, bv, i, j, out_h, out_w);
+  apply_pose(pose_rt + (size_t)bv * 16, r);
+  const float dx = r.rz, dy = r.ry, dz = r.rx;
+  const float ox = r.cz, oy = r.cy, oz = r.cx;
+  const float inf = __builtin_inff();
+  const float ax = dx != 0.0f ? 1.0f / fabsf(dx) : inf, bx = dx != 0.0f ? ox / dx : 0.0f;
+  const float ay = dy != 0.0f ? 1.0f / fabsf(dy) : inf, by = dy != 0.0f ? oy / dy : 0.0f;
+  const float az = dz != 0.0f ? 1.0f / fabsf(dz) : inf, bz = dz != 0.0f ? oz / dz : 0.0f;
+
+  const float *Ks = stack_intrinsics + (size_t)b * 9;
+  const float kfx = Ks[0], kcx = Ks[2], kfy = Ks[4], kcy = Ks[5];
+  const float half = 0.5f * (float)face;
+  const bool cube_camera = kfx == half && kfy == half && kcx == half && kcy == half;    // (a NaN camera: false)
+  const int m = face - 1, hi = cube_camera ? face : m;
+  const float sm1 = (float)m, fhi = (float)hi;
+  const unsigned ss2 = (unsigned)face * (unsigned)face, fstride = ss2 * (unsigned)nd;
+  const size_t sample_bytes = ((size_t)6 * fstride) << StackTexel<FMT>::shift;
+  const __amdgpu_buffer_rsrc_t L =
+      __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + (size_t)b * sample_bytes), 0, (int)sample_bytes, 0x00020000);
+  float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f;
+  float hmin = inf;
+
+  const auto fetch = [&](int d, CubeShellTaps<FMT> &T) {
+    const float h = depths[d];
+    hmin = fminf(hmin, h);
+    const float t = fminf(fminf(__builtin_fmaf(h, ax, -bx), __builtin_fmaf(h, ay, -by)), __builtin_fmaf(h, az, -bz));
+    const float px = __builtin_fmaf(t, dx, ox), py = __builtin_fmaf(t, dy, oy), pz = __builtin_fmaf(t, dz, oz);
+    const float mx = fabsf(px), my = fabsf(py), mz = fabsf(pz);
+    const bool zf = mz >= mx && mz >= my;
+    const bool xf = !zf && mx >= my;
+    const bool neg = (zf ? pz : (xf ? px : py)) < 0.0f;
+    const unsigned f = zf ? (neg ? 2u : 0u) : (xf ? (neg ? 3u : 1u) : (neg ? 4u : 5u));
+    const float qx = zf ? (neg ? -px : px) : (xf ? (neg ? pz : -pz) : px);
+    const float qy = (zf || xf) ? py : (neg ? pz : -pz);
+    const float inv_h = t_div(1.0f, h);
+    const float u = fminf(fmaxf(__builtin_fmaf(qx, kfx * inv_h, kcx), 0.0f), fhi);    // fmaxf(NaN, 0) = 0
+    const float v = fminf(fmaxf(__builtin_fmaf(qy, kfy * inv_h, kcy), 0.0f), fhi);
+    const float fx0 = fminf(floorf(u), sm1), fy0 = fminf(floorf(v), sm1);
+    const int x0 = (int)fx0, y0 = (int)fy0;             // in [0, S-1]
+    const int x1 = min(x0 + 1, hi), y1 = min(y0 + 1, hi);   // in [0, S]; S only with the cube camera
+    const unsigned dbase = (unsigned)d * ss2, base = f * fstride + dbase;
+    const unsigned r0 = base + (unsigned)y0 * (unsigned)face, r1 = base + (unsigned)min(y1, m) * (unsigned)face;
+    unsigned oB = r0 + (unsigned)min(x1, m), oC = r1 + (unsigned)x0, oD = r1 + (unsigned)min(x1, m);
+    unsigned again = 0u;                                // an unstored edge or a corner square: the blend pass fetches again
+    if (x1 == face || y1 == face) {                     // the strip: B, C, D may be virtual texels
+      const bool xs = x1 == face, ys = y1 == face;
+      if (!((xs && (ys || y0 == 0)) || (ys && x0 == 0))) {   // an edge: B and D across x = S (t = y0, y0 + 1) or C and D across y = S (t = x0, x0 + 1)
+        const CubeEdge e = cube_edge(f, xs, xs ? y0 : x0, face, ss2, fstride, dbase);
+        if (e.stored) {
+          oB = xs ? e.n0 : oB; oC = xs ? oC : e.n0; oD = e.n1;
+        } else {
+          again = 1u;
+        }
+      } else {                                          // a corner square (a few lanes): the blend pass fetches its virtual texels
+        again = 1u;
+      }
+    }
+    T.A = StackTexel<FMT>::tap(L, r0 + (unsigned)x0); T.B = StackTexel<FMT>::tap(L, oB);
+    T.C = StackTexel<FMT>::tap(L, oC); T.D = StackTexel<FMT>::tap(L, oD);
+    T.du = u - fx0; T.dv = v - fy0;
+    T.key = f | ((unsigned)x0 << 3) | (again << 31);
+    T.y0 = y0;
+  };
+  const auto blend = [&](int d, CubeShellTaps<FMT> &T) {
+    if (T.key >> 31) {                                  // an unstored edge (the other face's clamped texels for the means) or a corner square
+      const unsigned f = T.key & 7u, dbase = (unsigned)d * ss2;
+      const int x0 = (int)((T.key >> 3) & 0x7fffu), y0 = T.y0, x1 = x0 + 1, y1 = y0 + 1;   // (set with the cube camera only: hi = S)
+      const bool xs = x1 == face, ys = y1 == face;
+      if (!((xs && (ys || y0 == 0)) || (ys && x0 == 0))) {   // an unstored edge: the two-face mean of both virtual texels
+        const CubeEdge e = cube_edge(f, xs, xs ? y0 : x0, face, ss2, fstride, dbase);
+        const float4 n0 = StackTexel<FMT>::tap(L, e.n0), n1 = StackTexel<FMT>::tap(L, e.n1);
+        const float4 own = cube_select(xs, T.B, T.C), m0 = cube_mean(2u, own, n0, n0);       // (selects, not two stores: the shells stay in registers)
+        T.B = cube_select(xs, m0, T.B);
+        T.C = cube_select(xs, T.C, m0);
+        T.D = cube_mean(2u, T.D, n1, n1);
+      } else {                                          // a corner square: its virtual texels through the general rule
+        const auto corner_tap = [&](int tx, int ty) {
+          const VirtualTexel vt = cube_virtual_texel(f, tx, ty, face, fstride, dbase);
+          const float4 a = StackTexel<FMT>::tap(L, vt.o0), b = StackTexel<FMT>::tap(L, vt.o1), c = StackTexel<FMT>::tap(L, vt.o2);
+          float4 r = a;
+          if (vt.n > 1u) r = cube_mean(vt.n, a, b, c);
+          return r;
+        };
+        if (xs) T.B = corner_tap(x1, y0);
+        __builtin_amdgcn_sched_barrier(0);              // (one tap's loads at a time: these few lanes must not cost every lane registers)
+        if (ys) T.C = corner_tap(x0, y1);
+        __builtin_amdgcn_sched_barrier(0);
+        T.D = corner_tap(x1, y1);
+      }
+    }
+    const float4 A = T.A, Bv = T.B, C = T.C, Dv = T.D;
+    const float dx0 = T.du, dy0 = T.dv, dx1 = 1.0f - dx0, dy1 = 1.0f - dy0;
+    const float wa = dy1 * dx1, wb = dy1 * dx0, wc = dy0 * dx1, wd = dy0 * dx0;
+    float4 c;
+    c.w = ((wa * A.w + wb * Bv.w) + wc * C.w) + wd * Dv.w;
+    c.x = ((wa * A.x + wb * Bv.x) + wc * C.x) + wd * Dv.x;
+    c.y = ((wa * A.y + wb * Bv.y) + wc * C.y) + wd * Dv.y;
+    c.z = ((wa * A.z + wb * Bv.z) + wc * C.z) + wd * Dv.z;
+    const float al = c.w;
+    if (MODE & RENDER_RGB) {
+      if (d == 0) {
+        o0 = c.x; o1 = c.y; o2 = c.z;
+      } else {
+        const float om = 1.0f - al;
+        o0 = c.x * al + o0 * om;
+        o1 = c.y * al + o1 * om;
+        o2 = c.z * al + o2 * om;
+      }
+    }
+    if (MODE & RENDER_DEPTH) {
+      if (d == 0) od = 0.0f;
+      else od = F.f[d] * al + od * (1.0f - al);
+    }
+  };
+
+  for (int d0 = 0; d0 < nd; d0 += 4) {                  // (four named shells)
+    CubeShellTaps<FMT> T0, T1, T2, T3;
+    const bool s1 = d0 + 1 < nd, s2 = d0 + 2 < nd, s3 = d0 + 3 < nd;
+    fetch(d0, T0);
+    if (s1) fetch(d0 + 1, T1);
+    if (s2) fetch(d0 + 2, T2);
+    if (s3) fetch(d0 + 3, T3);
+    blend(d0, T0);
+    if (s1) blend(d0 + 1, T1);
+    if (s2) blend(d0 + 2, T2);
+    if (s3) blend(d0 + 3, T3);
+  }
+  if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
+    const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+    int bits = cube_camera ? 0 : MSI_RENDER_STATUS_NOT_CUBE_CAMERA;
+    if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) bits |= MSI_RENDER_STATUS_ORIGIN_OUTSIDE;
+    if (bits) atomicOr(status, bits);
+  }
+  store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
+}
+
 // Panorama -> six face images: image [B,H,W,C] (C <= 4) -> out [B,6,S,S,C].  Texel (ix, iy) of face f looks along R_f K^-1 (ix, iy, 1) in the
 // cube frame; with x and z swapped that is a direction of the render frame, whose longitude atan2(z, x) and latitude asin(y / |dir|) sit at
 // u = (lon + pi) / 2pi W - 0.5, v = (lat + pi/2) / pi H - 0.5 of the lat-long grid.  Bilinear, wrapping in u and clamping in v.  One thread per
@@ -175,11 +462,12 @@ equirect_to_cube_kernel(const float *__restrict__ image, const float *__restrict
 
 extern "C" {
 
-int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
-                          const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
-                          int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
-                          int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
-                          msi_stream_t stream) {
+// the two viewers share their argument checks and grid; `seamless` picks the kernel family
+static int cube_views_launch(bool seamless, const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                             const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
+                             int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
+                             int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                             msi_stream_t stream) {
   const ViewArgs a = {"cube_render_views", out_rgb, out_depth, layers && tgt_pose_rt && tgt_pos && stack_intrinsics && depths, format, ANY_FORMAT, "",
                       &camera, trig, tgt_intrinsics, nullptr, batch >= 0 && face_size > 0 && num_planes > 0, 0, views, batch, out_height, out_width, 4};
   const auto planes = [&] {
@@ -199,11 +487,32 @@ int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_p
   const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);
   for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_camera(camera, [&](auto CAM) { for_format(format, [&](auto FMT) {
-    hipLaunchKernelGGL((cube_render_views_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>), dim3(grid), dim3(64, 4), 0, s,
-                       layers, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch, views, face_size, num_planes,
-                       out_height, out_width, out_rgb, out_depth, F, status_device);
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(64, 4), 0, s, layers, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch,
+                         views, face_size, num_planes, out_height, out_width, out_rgb, out_depth, F, status_device);
+    };
+    if (seamless) launch(cube_render_views_seamless_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
+    else launch(cube_render_views_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
   }); }); });
   return msi::check_launch("cube_render_views");
+}
+
+int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                          const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
+                          int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
+                          int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                          msi_stream_t stream) {
+  return cube_views_launch(false, layers, format, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch, views, face_size,
+                           num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
+}
+
+int msi_cube_render_views_seamless(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                                   const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
+                                   int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
+                                   int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                                   msi_stream_t stream) {
+  return cube_views_launch(true, layers, format, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch, views, face_size,
+                           num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
 }
 
 int msi_equirect_to_cube_f32(const float *image, const float *intrinsics, int32_t batch, int32_t height, int32_t width,

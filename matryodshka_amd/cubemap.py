@@ -78,6 +78,76 @@ def default_face_intrinsics(face_size):
     return np.array([[s / 2, 0, s / 2], [0, s / 2, s / 2], [0, 0, 1]], dtype=np.float32)
 
 
+# ---- the seamless filter of MSI.cube_render_views(filtering='seamless') (msi_cube_render_views_seamless) --------------------
+# Defined for default_face_intrinsics only.  A face then stores tan = -1 .. 1 - 2/S and nothing on its +x and +y edges; the cube
+# point of lattice point (x, y), 0 <= x, y <= S, of a face is a lattice point of every other face that contains it.  The rule
+# (include/msi_hip.h and csrc/geo_cube.hip state the same): u, v are clamped to [0, S]; x0 = min(floor(u), S-1), x1 = x0 + 1,
+# du = u - x0, likewise y; four bilinear taps with the clamp filter's weights and sum order; a tap with x < S and y < S is the
+# face's own texel; a tap with x = S or y = S is a VIRTUAL texel at its cube point P (an edge point, or a cube corner when the
+# other coordinate is 0 or S): the other faces containing P (one on an edge, two at a corner) are tried in ascending face index
+# and the first whose lattice coordinates of P lie in [0, S-1]^2 supplies its texel; when none stores P, the virtual texel is
+# the mean of the clamped texels (coordinates clamped to [0, S-1]) of all faces meeting at P, own face first, then the others in
+# ascending index -- (a + b) * 0.5f, ((a + b) + c) * (1.0f / 3.0f) -- per channel, alpha included.
+# Of the 12 cube edges 8 are stored by one face (the ring front -> right -> back -> left -> front, front/up, front/down,
+# up/right, down/left: continuous filter), 2 by none (right/down, back/down: the mean, continuous over two texels) and 2 by both
+# (up/back, up/left: each face keeps its own texel, a step in the CONTENT of the two faces remains; not a filtering artefact).
+def _side_px(f, t, s):
+    """Across x = S at running coordinate t = y: (neighbour, x', y') -- the kernel's cube_side_px."""
+    return ((f + 1) & 3, 0, t) if f < 4 else ((1, s - t, 0) if f == 4 else (1, t, s))
+
+
+def _side_py(f, t, s):
+    """Across y = S at running coordinate t = x -- cube_side_py."""
+    g = 5 if f < 4 else (0 if f == 4 else 2)
+    if f in (0, 4):
+        return g, t, 0
+    return (g, s, t) if f == 1 else ((g, 0, s - t) if f == 3 else (g, s - t, s))
+
+
+def _corner_ny(f, s):
+    """The third face at corner (S, 0), across y = 0 -- cube_corner_ny."""
+    return (4 if f < 4 else (2 if f == 4 else 0)), (s if f in (0, 1, 5) else 0), (s if f in (0, 3, 5) else 0)
+
+
+def _corner_nx(f, s):
+    """The third face at corner (0, S), across x = 0 -- cube_corner_nx."""
+    return ((f + 3) & 3 if f < 4 else 3), (0 if f == 5 else s), (0 if f == 4 else s)
+
+
+def virtual_texel(f, x, y, face_size):
+    """The texels behind lattice point (x, y), 0 <= x, y <= S, of face f under the seamless filter, in closed form as the
+    kernel derives them (cube_virtual_texel, csrc/geo_cube.hip): [(face, x', y', weight), ...] with every x', y' in [0, S-1]
+    and the weights summing to 1.  One entry (weight 1) for an own texel or a point another face stores; the own clamped texel
+    first and then the other faces in ascending index, weights 1/2 or 1/3, where no face stores the point."""
+    f, x, y, s = int(f), int(x), int(y), int(face_size)
+    if not (0 <= f < 6 and 0 <= x <= s and 0 <= y <= s and s >= 1):
+        raise ValueError("virtual_texel: face in [0, 5] and 0 <= x, y <= S wanted, got f = %d, (x, y) = (%d, %d), S = %d" % (f, x, y, s))
+    if x < s and y < s:
+        return [(f, x, y, 1.0)]
+    xs, ys = x == s, y == s
+    cands = [_side_px(f, y, s) if xs else _side_py(f, x, s)]
+    if xs and ys:
+        cands.append(_side_py(f, x, s))
+    elif xs and y == 0:
+        cands.append(_corner_ny(f, s))
+    elif ys and x == 0:
+        cands.append(_corner_nx(f, s))
+    cands.sort(key=lambda c: c[0])
+    for g, gx, gy in cands:
+        if gx < s and gy < s:
+            return [(g, gx, gy, 1.0)]
+    m = s - 1
+    w = 1.0 / (1 + len(cands))
+    return [(f, min(x, m), min(y, m), w)] + [(g, min(gx, m), min(gy, m), w) for g, gx, gy in cands]
+
+
+def is_default_face_intrinsics(k, face_size):
+    """True when every camera of k ([3,3] or [B,3,3]) has fx = fy = cx = cy = S/2 exactly: the camera the seamless filter needs."""
+    k = np.asarray(k, dtype=np.float64).reshape(-1, 3, 3)
+    h = face_size / 2.0
+    return bool(np.all(k[:, [0, 1, 0, 1], [0, 1, 2, 2]] == h))
+
+
 def cube_view_shapes(stack_shape, pose_shape, pos_shape, size):
     """The shape rules of MSI.cube_render_views, checked before anything touches a device: native stack [6B,D,S,S,4],
     tgt_pose_rt [B,V,4,4], tgt_pos [B,V,3] ([V,4,4] / [V,3] when B = 1), size = (h, w) required.

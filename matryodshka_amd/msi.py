@@ -1212,8 +1212,10 @@ class MSI(object):
                 "msi_equirect_to_cube_f32")
         return out
 
+    CUBE_FILTERINGS = ('clamp', 'seamless')
+
     def cube_render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, stack_intrinsics=None, camera='equirect',
-                          intrinsics=None, size=None, want_rgb=True, want_depth=True):
+                          intrinsics=None, size=None, want_rgb=True, want_depth=True, filtering='clamp'):
         """V views of each CUBE of six face stacks in ONE launch (msi_cube_render_views; no reference counterpart) ->
         (rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w]: the composited plane index / D of over_composite_depth); either is None
         when switched off.  The planar twin of render_views; works on any model (the stack is what matters).
@@ -1236,13 +1238,32 @@ class MSI(object):
         rgba_layers may be a SparseLayers of the faces made with border='edge' (sparsify_layers of the [6B,S,S,D,4] stack;
         msi_cube_render_views_sparse; whole tiles make S % 16 == 0, sparsify_layers refuses other sizes): every output element compares == to the render of the
         PackedLayers it was made from (a zero may differ in sign), provided colours are finite where alpha is zero, and the
-        status word is the same; planes=None takes the planes it carries.  A border='wrap' stack is refused (TypeError)."""
+        status word is the same; planes=None takes the planes it carries.  A border='wrap' stack is refused (TypeError).
+        filtering='clamp' (default) is the rule above.  filtering='seamless' (msi_cube_render_views_seamless; dense stacks, the
+        default stack_intrinsics only) filters ACROSS the cube's edges: with fx = cx = S/2 a face stores nothing on its +x / +y
+        edge, so clamping repeats the last texel over a one-texel band along every cube edge, while the neighbouring face
+        usually stores exactly the missing sample (its column 0 or row 0).  u, v are clamped to [0, S]; a tap at x = S or y = S
+        is a virtual texel: the texel of the first other face (ascending index) that stores that cube point, else the mean of
+        the clamped texels of the faces meeting there (cubemap.virtual_texel is the host statement of the rule, the cubemap
+        module's comment the full text).  8 of the 12 cube edges are stored by one face (continuous filter), 2 by none
+        (right/down, back/down: the mean, continuous over two texels), 2 by both (up/back, up/left: each face keeps its own
+        texel, so a step in the CONTENT of the two faces stays -- in-range texels are never overridden).  Away from the strip
+        (u, v <= S-1) the pixels are the clamp render's, bit for bit; a packed render keeps the bits of the render of the
+        unpacked stack.  A host-side stack_intrinsics other than the default raises ValueError; one given on the device is not
+        read back: such a sample is rendered with the clamp rule and render_status() returns RENDER_STATUS_NOT_CUBE_CAMERA
+        (2).  A SparseLayers raises TypeError (densify_layers it first): the edge keep rule guarantees four zero alphas only
+        for footprints inside one face."""
         from . import cubemap
         if camera not in ('equirect', 'pinhole'):
             raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
+        if filtering not in self.CUBE_FILTERINGS:
+            raise ValueError("cube_render_views: filtering must be one of %s, not %r" % (self.CUBE_FILTERINGS, filtering))
         if not (want_rgb or want_depth):
             raise ValueError("cube_render_views: want_rgb and want_depth are both False")
         lead, suffix, native_shape, planes, _keep = self._view_stack(rgba_layers, planes, "cube_render_views", 'edge')
+        if filtering == 'seamless' and suffix == "_sparse":
+            raise TypeError("cube_render_views: filtering='seamless' takes dense stacks only (a cross-edge footprint is outside the "
+                            "edge keep rule of a SparseLayers); expand it with densify_layers first")
         shape = lambda t: tuple(t.shape) if hasattr(t, "shape") else tuple(np.asarray(t).shape)
         b, v, s, d, oh, ow = cubemap.cube_view_shapes(native_shape + (4,), shape(tgt_pose_rt), shape(tgt_pos), size)
         if not any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, tgt_pose_rt, planes)):
@@ -1250,6 +1271,10 @@ class MSI(object):
                                         np.asarray(torch.as_tensor(planes)))
         pose, pos = self._f32(tgt_pose_rt).reshape(b * v, 4, 4), self._f32(tgt_pos).reshape(b * v, 3)
         depths = self._depths(planes, d)
+        if filtering == 'seamless' and stack_intrinsics is not None and not (torch.is_tensor(stack_intrinsics) and stack_intrinsics.is_cuda):
+            if not cubemap.is_default_face_intrinsics(np.asarray(torch.as_tensor(stack_intrinsics), dtype=np.float64), s):
+                raise ValueError("cube_render_views: filtering='seamless' is defined for the cube camera fx = fy = cx = cy = S/2 "
+                                 "(cubemap.default_face_intrinsics) only")
         ks = self._f32(cubemap.default_face_intrinsics(s) if stack_intrinsics is None else stack_intrinsics).reshape(-1, 3, 3)
         if ks.shape[0] == 1 and b > 1:
             ks = ks.expand(b, 3, 3)
@@ -1266,7 +1291,7 @@ class MSI(object):
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
         tail = (pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(), depths.data_ptr(), _ptr(trig), b, v, s, d,
                 self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream())
-        name = "msi_cube_render_views" + (suffix if suffix == "_sparse" else "")
+        name = "msi_cube_render_views" + ("_seamless" if filtering == 'seamless' else suffix if suffix == "_sparse" else "")
         N.check(getattr(N.lib, name)(*(lead + tail)), name)
         return rgb, dep
 
