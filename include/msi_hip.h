@@ -69,7 +69,8 @@ const char *msi_version(void);
  *      msi_hres_index_tiles, msi_hres_layers_sparse; msi_sparse_index_tiles_edge, msi_mpi_render_views_sparse,
  *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse;
  *      msi_cube_plane_sweep_f32, msi_cube_sweep_volume_bf16, msi_cube_hres_layers, msi_cube_hres_layers_sparse;
- *      msi_cube_render_views_seamless, MSI_RENDER_STATUS_NOT_CUBE_CAMERA) */
+ *      msi_cube_render_views_seamless, MSI_RENDER_STATUS_NOT_CUBE_CAMERA; msi_cube_render_ods_views,
+ *      msi_cube_render_ods_views_sparse) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -618,6 +619,49 @@ int msi_cube_render_views_seamless(const void *layers, int32_t format, const flo
                                    int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
                                    int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
                                    msi_stream_t stream);
+/* The ODS stereo camera of the cube viewer (MSI.cube_render_views(camera='ods'), MSI.cube_render_ods_pair): V eye panoramas of each
+ * cube per launch -- both eyes of a stereo 360 frame are V = 2 -- from dense stacks with either filter (msi_cube_render_ods_views:
+ * filtering 0 = the clamp taps of msi_cube_render_views, 1 = the seamless taps of msi_cube_render_views_seamless) or from an
+ * edge-rule sparse stack with the clamp taps (msi_cube_render_ods_views_sparse: (pool, table, layer_start, format) in place of
+ * the stack, msi_cube_render_views_sparse's contract).  As msi_render_ods_views beside msi_render_views_f32, they are entry
+ * points of their own, not a camera code: the codes of the *_render_views functions stay 0 and 1.  Pixel (i, j) of the lat-long
+ * grid of the OUTPUT size, before the pose:
+ *     direction  r = (cos S_j cos T_i, sin T_i, sin S_j cos T_i)                               -- the equirect camera's
+ *     origin     c = (tgt_pos[2] + sin S_j * e, tgt_pos[1], tgt_pos[0] + (-cos S_j) * e)       -- e = eye_radius[b*V + v]
+ *   then r <- pose[:3,:3] r, c <- pose (c, 1), the swap of x and z into the cube frame, and from there the arithmetic of the
+ *   entry point named above, op for op: shell hit, face choice and its tie rule, p = R_f^T P, the taps, the bilinear sum order,
+ *   the far-to-near composite.  (sin S, 0, -cos S) . r = 0: the ray is tangent to the circle of radius |e| around the head
+ *   position.  e is SIGNED as in msi_render_ods_views: e = +baseline is the left eye, e = -baseline the right eye.
+ *   eye_radius [B*V] (view v of sample b at index b*V + v), trig = the msi_build_trig_tables_host table of (out_height,
+ *   out_width); both required.  Every other argument as in msi_cube_render_views.
+ * Facts that fix the convention (tests/test_cube_ods_cpu.py holds the fp64 reference to them, tests/test_gpu_cube_ods.py the kernels):
+ *   1. e = 0 is the equirect camera: outputs and status word are bit-identical to msi_cube_render_views / _seamless / _sparse
+ *      with MSI_CAMERA_EQUIRECT for the same poses, positions and size.
+ *   2. The eye sign is the sphere camera's: for content mirror-symmetric under the render frame's right axis (z -> -z), head at
+ *      the origin and identity pose, the right-eye image is the left-eye image flipped left to right.
+ *   3. The parallax vanishes with distance: the render of a shell of half-side h converges to the equirect render as h / |e| grows.
+ * status_device (may be NULL): the origin differs from pixel to pixel here, so MSI_RENDER_STATUS_ORIGIN_OUTSIDE is set when ANY
+ * rendered pixel's origin is not strictly inside the innermost shell (max_k |o_k| >= min depths, or NaN) -- also when only a part
+ * of the circle leaves it (every lane tests its own origin; one atomic OR per wavefront that has such a lane).  Pixels stay finite
+ * for finite inputs.  MSI_RENDER_STATUS_NOT_CUBE_CAMERA (filtering 1) is msi_cube_render_views_seamless'.
+ * Argument checks before any HIP call, in this order, MSI_E_BADARG unless noted.  msi_cube_render_ods_views: both outputs NULL; a
+ * NULL input (every pointer but the outputs and status_device is required, eye_radius and trig included); unknown format; batch < 0
+ * or non-positive face_size / num_planes ("bad dims"); unknown filtering; num_planes > 128 -> MSI_E_UNSUPPORTED; views < 1; an
+ * output size below 1 x 1; a sample whose six face stacks reach 2^31 bytes; more than 2^31 - 8 workgroups.
+ * msi_cube_render_ods_views_sparse: both outputs NULL; a NULL input; unknown format (MSI_LAYERS_F32 included); bad dims; more than
+ * 128 planes, then S % 16 -> MSI_E_UNSUPPORTED; views < 1; an output size below 1 x 1; the 2^31-byte limit (of the DENSE stacks);
+ * the grid limit.  batch = 0 then returns MSI_OK without a launch. */
+int msi_cube_render_ods_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
+                              const float *eye_radius, const float *stack_intrinsics, const float *depths, const float *trig,
+                              int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t filtering,
+                              int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                              msi_stream_t stream);
+int msi_cube_render_ods_views_sparse(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format,
+                                     const float *tgt_pose_rt, const float *tgt_pos, const float *eye_radius,
+                                     const float *stack_intrinsics, const float *depths, const float *trig,
+                                     int32_t batch, int32_t views, int32_t face_size, int32_t num_planes,
+                                     int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                                     msi_stream_t stream);
 /* Panorama -> six face images: image [B,H,W,C] fp32 (C in 1..4) -> out [B,6,S,S,C].  Texel (ix, iy) of face f looks along
  * R_f K^-1 (ix, iy, 1) with intrinsics [B,3,3]; with x and z swapped that is a direction of the render frame, sampled at
  * u = (atan2(z, x) + pi) / 2pi W - 0.5, v = (asin(y / |dir|) + pi/2) / pi H - 0.5 (the inverse of the lat-long grid of

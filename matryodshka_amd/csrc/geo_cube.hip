@@ -44,7 +44,10 @@ namespace {
 //           other through the Infinity Cache and adjacent row groups share an XCD's L2.
 //   rays    render_views_kernel's (view_ray and apply_pose, geometry_device.h): (cos S cos T, sin T, sin S cos T) on the lat-long grid of the output or (1, (i + 0.5 - cy) / fy,
 //           (j + 0.5 - cx) / fx), rotated by pose[:3,:3]; origin pose @ (tgt_pos[2], tgt_pos[1], tgt_pos[0], 1).  That render frame (forward +x,
-//           down +y, right +z) becomes the cube frame by swapping x and z.  Pose, origin and both cameras are wave-uniform (scalar loads).
+//           down +y, right +z) becomes the cube frame by swapping x and z.  Pose, origin and both cameras are wave-uniform (scalar loads).  CAMERA_ODS (msi_cube_render_ods_views) is the equirect
+//           camera with view_ray's origin on the viewing circle, (tgt_pos[2] + sin S_j e, tgt_pos[1], tgt_pos[0] - cos S_j e) before the pose, e = eye_radius[bv]
+//           read through the `intrinsics` argument (the pinhole table's place: no kernel argument is added, so the other cameras' kernarg layout stands).
+//           Its origin, and with it ox, oy, oz and bx, by, bz, is per LANE (vector registers); the pose and e stay scalar.
 //   shell   For origin o, direction r and half-side h: t = min over the axes of (h sign(r_k) - o_k) / r_k, evaluated as h / |r_k| - o_k / r_k
 //           with the two quotients per pixel (IEEE divides; an axis with r_k = 0 is given +inf, and fminf drops a NaN), P = o + t r.  The face
 //           is the axis of the largest |P_k| with its sign (ties: z, x, y); p = R_f^T P is two selects; u = fx p_x / h + cx, v = fy p_y / h + cy.
@@ -57,7 +60,8 @@ namespace {
 //           unpacked stack.
 //   loop    unrolled by 4: a shell's taps do not depend on the running composite, so several shells' taps are in flight under the blend.
 //   status  a view whose origin is not strictly inside the innermost shell (max |o_k| >= min planes, or NaN) ORs MSI_RENDER_STATUS_ORIGIN_OUTSIDE
-//           into *status (one lane per workgroup); its pixels are finite for finite inputs (t may be negative, the taps are clamped).
+//           into *status (one lane per workgroup); its pixels are finite for finite inputs (t may be negative, the taps are clamped).  CAMERA_ODS: the
+//           flag is set when ANY pixel's origin fails that test -- every lane tests its own, one atomicOr per wavefront with a set lane (render_views_body's form).
 template <int MODE, int CAMERA, int FMT>
 __global__ void __launch_bounds__(256)
 cube_render_views_kernel(const void *__restrict__ layers, const float *__restrict__ pose_rt, const float *__restrict__ tgt_pos,
@@ -72,7 +76,7 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
   const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;                 // (no barrier below; lane (0, 0) of a workgroup is always inside)
 
-  ViewRay r = view_ray<CAMERA>(intrinsics, nullptr, trig, tgt_pos, bv, i, j, out_h, out_w);
+  ViewRay r = view_ray<CAMERA>(intrinsics, intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);   // (CAMERA_ODS: `intrinsics` is eye_radius)
   apply_pose(pose_rt + (size_t)bv * 16, r);
   // render frame -> cube frame: x <-> z
   const float dx = r.rz, dy = r.ry, dz = r.rx;
@@ -139,10 +143,19 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
       else od = F.f[d] * al + od * (1.0f - al);
     }
   }
-  // the origin is a property of the view: every lane agrees (fmaxf drops a NaN, so it is tested by itself)
-  if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
-    const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-    if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+  if constexpr (CAMERA == CAMERA_ODS) {
+    // the origin is a property of the lane (a point of the viewing circle): every lane tests its own, the wave votes, lane 0 issues the atomicOr
+    if (status != nullptr) {
+      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+      const bool any = __builtin_amdgcn_ballot_w64(!(omax < hmin) || ox != ox || oy != oy || oz != oz) != 0;   // (wave-uniform)
+      if (any && threadIdx.x == 0) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+    }
+  } else {
+    // the origin is a property of the view: every lane agrees (fmaxf drops a NaN, so it is tested by itself)
+    if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
+      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+      if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+    }
   }
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
 }
@@ -273,7 +286,7 @@ cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *
   const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;
 
-  ViewRay r = view_ray<CAMERA>(intrinsics, nullptr, trig, tgt_pos, bv, i, j, out_h, out_w);
+  ViewRay r = view_ray<CAMERA>(intrinsics, intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);   // (CAMERA_ODS: `intrinsics` is eye_radius)
   apply_pose(pose_rt + (size_t)bv * 16, r);
   const float dx = r.rz, dy = r.ry, dz = r.rx;
   const float ox = r.cz, oy = r.cy, oz = r.cx;
@@ -400,7 +413,14 @@ cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *
     if (s2) blend(d0 + 2, T2);
     if (s3) blend(d0 + 3, T3);
   }
-  if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
+  if constexpr (CAMERA == CAMERA_ODS) {                 // (the wave votes on its lanes' origins; the stack camera is uniform)
+    if (status != nullptr) {
+      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+      const bool any = __builtin_amdgcn_ballot_w64(!(omax < hmin) || ox != ox || oy != oy || oz != oz) != 0;
+      const int bits = (cube_camera ? 0 : MSI_RENDER_STATUS_NOT_CUBE_CAMERA) | (any ? MSI_RENDER_STATUS_ORIGIN_OUTSIDE : 0);
+      if (bits && threadIdx.x == 0) atomicOr(status, bits);
+    }
+  } else if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
     const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
     int bits = cube_camera ? 0 : MSI_RENDER_STATUS_NOT_CUBE_CAMERA;
     if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) bits |= MSI_RENDER_STATUS_ORIGIN_OUTSIDE;
@@ -462,22 +482,25 @@ equirect_to_cube_kernel(const float *__restrict__ image, const float *__restrict
 
 extern "C" {
 
-// the two viewers share their argument checks and grid; `seamless` picks the kernel family
-static int cube_views_launch(bool seamless, const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
-                             const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths, const float *trig,
+// the viewers share their argument checks and grid; `seamless` picks the kernel family.  ods: the ODS camera's entry point -- no camera code, every
+// table required, `camera_table` is eye_radius [B*V] (it travels in the kernels' `intrinsics` argument) and `filtering` is the caller's code, checked here.
+static int cube_views_launch(const char *who, bool ods, int32_t filtering, const void *layers, int32_t format, const float *tgt_pose_rt,
+                             const float *tgt_pos, const float *camera_table, const float *stack_intrinsics, const float *depths, const float *trig,
                              int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
                              int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
                              msi_stream_t stream) {
-  const ViewArgs a = {"cube_render_views", out_rgb, out_depth, layers && tgt_pose_rt && tgt_pos && stack_intrinsics && depths, format, ANY_FORMAT, "",
-                      &camera, trig, tgt_intrinsics, nullptr, batch >= 0 && face_size > 0 && num_planes > 0, 0, views, batch, out_height, out_width, 4};
+  const bool inputs = layers && tgt_pose_rt && tgt_pos && stack_intrinsics && depths && (!ods || (camera_table && trig));
+  const ViewArgs a = {who, out_rgb, out_depth, inputs, format, ANY_FORMAT, "", ods ? nullptr : &camera, trig, camera_table, nullptr,
+                      batch >= 0 && face_size > 0 && num_planes > 0, 0, views, batch, out_height, out_width, 4};
   const auto planes = [&] {
-    return num_planes <= DEPTH_FRAC_MAX ? (int)MSI_OK : msi::fail(MSI_E_UNSUPPORTED, "cube_render_views: at most %d planes", DEPTH_FRAC_MAX);
+    MSI_REQUIRE(filtering == 0 || filtering == 1, "%s: unknown filtering %d (0 clamp, 1 seamless)", who, filtering);
+    return num_planes <= DEPTH_FRAC_MAX ? (int)MSI_OK : msi::fail(MSI_E_UNSUPPORTED, "%s: at most %d planes", who, DEPTH_FRAC_MAX);
   };
   // the per-sample descriptor: the six faces' stacks are addressed with one 32-bit byte offset per lane
   const auto sample_bytes = [&] {
     const int texel_bytes = format == MSI_LAYERS_F32 ? 16 : format == MSI_LAYERS_RGBA16F ? 8 : 4;
     MSI_REQUIRE(face_size < (1 << 15) && (long)face_size * face_size * 6 * num_planes * texel_bytes < (1L << 31),   // (< 2^30 * 6 * 128 * 16)
-                "cube_render_views: a sample's six face stacks (6 x %d x %d x %d texels of %d bytes) reach 2^31 bytes (32-bit offsets)",
+                "%s: a sample's six face stacks (6 x %d x %d x %d texels of %d bytes) reach 2^31 bytes (32-bit offsets)", who,
                 num_planes, face_size, face_size, texel_bytes);
     return (int)MSI_OK;
   };
@@ -486,15 +509,19 @@ static int cube_views_launch(bool seamless, const void *layers, int32_t format, 
   if (batch == 0) return MSI_OK;
   const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);
-  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_camera(camera, [&](auto CAM) { for_format(format, [&](auto FMT) {
-    const auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(grid), dim3(64, 4), 0, s, layers, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch,
+  const auto launch = [&](auto M, auto CAM, auto FMT) {
+    const auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(64, 4), 0, s, layers, tgt_pose_rt, tgt_pos, camera_table, stack_intrinsics, depths, trig, batch,
                          views, face_size, num_planes, out_height, out_width, out_rgb, out_depth, F, status_device);
     };
-    if (seamless) launch(cube_render_views_seamless_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
-    else launch(cube_render_views_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
-  }); }); });
-  return msi::check_launch("cube_render_views");
+    if (filtering) go(cube_render_views_seamless_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
+    else go(cube_render_views_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
+  };
+  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_format(format, [&](auto FMT) {
+    if (ods) launch(M, Const<CAMERA_ODS>{}, FMT);
+    else for_camera(camera, [&](auto CAM) { launch(M, CAM, FMT); });
+  }); });
+  return msi::check_launch(who);
 }
 
 int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
@@ -502,8 +529,8 @@ int msi_cube_render_views(const void *layers, int32_t format, const float *tgt_p
                           int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
                           int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
                           msi_stream_t stream) {
-  return cube_views_launch(false, layers, format, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch, views, face_size,
-                           num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
+  return cube_views_launch("cube_render_views", false, 0, layers, format, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch,
+                           views, face_size, num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
 }
 
 int msi_cube_render_views_seamless(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos,
@@ -511,8 +538,16 @@ int msi_cube_render_views_seamless(const void *layers, int32_t format, const flo
                                    int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
                                    int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
                                    msi_stream_t stream) {
-  return cube_views_launch(true, layers, format, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch, views, face_size,
-                           num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
+  return cube_views_launch("cube_render_views", false, 1, layers, format, tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch,
+                           views, face_size, num_planes, camera, out_height, out_width, out_rgb, out_depth, status_device, stream);
+}
+
+int msi_cube_render_ods_views(const void *layers, int32_t format, const float *tgt_pose_rt, const float *tgt_pos, const float *eye_radius,
+                              const float *stack_intrinsics, const float *depths, const float *trig, int32_t batch, int32_t views,
+                              int32_t face_size, int32_t num_planes, int32_t filtering, int32_t out_height, int32_t out_width, float *out_rgb,
+                              float *out_depth, int32_t *status_device, msi_stream_t stream) {
+  return cube_views_launch("cube_render_ods_views", true, filtering, layers, format, tgt_pose_rt, tgt_pos, eye_radius, stack_intrinsics, depths, trig,
+                           batch, views, face_size, num_planes, MSI_CAMERA_EQUIRECT, out_height, out_width, out_rgb, out_depth, status_device, stream);
 }
 
 int msi_equirect_to_cube_f32(const float *image, const float *intrinsics, int32_t batch, int32_t height, int32_t width,

@@ -369,7 +369,8 @@ mpi_render_views_sparse_kernel(const void *__restrict__ pool, const int *__restr
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
 }
 
-// The cube render.  Rays, shell, face and clamped taps are cube_render_views_kernel's, op for op.  The face differs per lane, so the table, layer_start
+// The cube render.  Rays (CAMERA_ODS included: per-lane origins, eye_radius through `intrinsics`, the wave's vote on the status word), shell, face and
+// clamped taps are cube_render_views_kernel's, op for op.  The face differs per lane, so the table, layer_start
 // and the pool get one descriptor per SAMPLE -- the six faces' table rows [6 D, S/4, S/16], their 6 D + 1 entries of layer_start, and the kept tiles
 // from layer_start[6 b D] to layer_start[6 (b + 1) D] (below 2^31 bytes: the host refuses a sample whose DENSE stacks reach that) -- and the lane's
 // layer f D + d goes into the per-lane offsets.  The layer's first tile, relative to the sample's (the low words' difference: it fits 32 bits), is
@@ -390,7 +391,7 @@ cube_render_views_sparse_kernel(const void *__restrict__ pool, const int *__rest
   const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;                 // (no barrier below; lane (0, 0) of a workgroup is always inside)
 
-  ViewRay r = view_ray<CAMERA>(intrinsics, nullptr, trig, tgt_pos, bv, i, j, out_h, out_w);
+  ViewRay r = view_ray<CAMERA>(intrinsics, intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);   // (CAMERA_ODS: `intrinsics` is eye_radius)
   apply_pose(pose_rt + (size_t)bv * 16, r);
   // render frame -> cube frame: x <-> z
   const float dx = r.rz, dy = r.ry, dz = r.rx;
@@ -493,10 +494,19 @@ cube_render_views_sparse_kernel(const void *__restrict__ pool, const int *__rest
       if (ok[g]) { o0 = n.o0; o1 = n.o1; o2 = n.o2; od = n.od; }
     }
   }
-  // the origin is a property of the view: every lane agrees (fmaxf drops a NaN, so it is tested by itself)
-  if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
-    const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-    if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+  if constexpr (CAMERA == CAMERA_ODS) {
+    // the origin is a property of the lane (a point of the viewing circle): every lane tests its own, the wave votes, lane 0 issues the atomicOr
+    if (status != nullptr) {
+      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+      const bool any = __builtin_amdgcn_ballot_w64(!(omax < hmin) || ox != ox || oy != oy || oz != oz) != 0;   // (wave-uniform)
+      if (any && threadIdx.x == 0) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+    }
+  } else {
+    // the origin is a property of the view: every lane agrees (fmaxf drops a NaN, so it is tested by itself)
+    if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
+      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
+      if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+    }
   }
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
 }
@@ -562,14 +572,15 @@ int msi_mpi_render_views_sparse(const void *pool, const int32_t *table, const in
   return msi::check_launch(who);
 }
 
-int msi_cube_render_views_sparse(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format, const float *tgt_pose_rt,
-                                 const float *tgt_pos, const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths,
-                                 const float *trig, int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
-                                 int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
-                                 msi_stream_t stream) {
-  const char *who = "cube_render_views_sparse";
-  const ViewArgs a = {who, out_rgb, out_depth, pool && table && layer_start && tgt_pose_rt && tgt_pos && stack_intrinsics && depths, format,
-                      SPARSE_FORMATS, SPARSE_FORMATS_NOTE, &camera, trig, tgt_intrinsics, nullptr,
+// msi_cube_render_views_sparse and msi_cube_render_ods_views_sparse: one set of checks, one launch.  ods: no camera code, every table required,
+// `camera_table` is eye_radius [B*V] (it travels in the kernel's `intrinsics` argument).
+static int cube_views_sparse_launch(const char *who, bool ods, const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format,
+                                    const float *tgt_pose_rt, const float *tgt_pos, const float *camera_table, const float *stack_intrinsics,
+                                    const float *depths, const float *trig, int32_t batch, int32_t views, int32_t face_size, int32_t num_planes,
+                                    int32_t camera, int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth,
+                                    int32_t *status_device, msi_stream_t stream) {
+  const bool inputs = pool && table && layer_start && tgt_pose_rt && tgt_pos && stack_intrinsics && depths && (!ods || (camera_table && trig));
+  const ViewArgs a = {who, out_rgb, out_depth, inputs, format, SPARSE_FORMATS, SPARSE_FORMATS_NOTE, ods ? nullptr : &camera, trig, camera_table, nullptr,
                       batch >= 0 && face_size > 0 && num_planes > 0, 0, views, batch, out_height, out_width, 4};
   const auto unsupported = [&] {
     if (num_planes > DEPTH_FRAC_MAX) return msi::fail(MSI_E_UNSUPPORTED, "%s: at most %d planes", who, DEPTH_FRAC_MAX);
@@ -590,14 +601,38 @@ int msi_cube_render_views_sparse(const void *pool, const int32_t *table, const i
   if (batch == 0) return MSI_OK;
   const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);
-  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_camera(camera, [&](auto CAM) { for_format(format, [&](auto FMT) {
+  const auto launch = [&](auto M, auto CAM, auto FMT) {
     constexpr int fmt = decltype(FMT)::value;
     if constexpr (fmt != MSI_LAYERS_F32)
       hipLaunchKernelGGL((cube_render_views_sparse_kernel<decltype(M)::value, decltype(CAM)::value, fmt>), dim3(grid), dim3(64, 4), 0, s, pool, table,
-                         tile_starts(layer_start), tgt_pose_rt, tgt_pos, tgt_intrinsics, stack_intrinsics, depths, trig, batch, views, face_size,
+                         tile_starts(layer_start), tgt_pose_rt, tgt_pos, camera_table, stack_intrinsics, depths, trig, batch, views, face_size,
                          num_planes, out_height, out_width, out_rgb, out_depth, F, status_device);
-  }); }); });
+  };
+  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_format(format, [&](auto FMT) {
+    if (ods) launch(M, Const<CAMERA_ODS>{}, FMT);
+    else for_camera(camera, [&](auto CAM) { launch(M, CAM, FMT); });
+  }); });
   return msi::check_launch(who);
+}
+
+int msi_cube_render_views_sparse(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format, const float *tgt_pose_rt,
+                                 const float *tgt_pos, const float *tgt_intrinsics, const float *stack_intrinsics, const float *depths,
+                                 const float *trig, int32_t batch, int32_t views, int32_t face_size, int32_t num_planes, int32_t camera,
+                                 int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                                 msi_stream_t stream) {
+  return cube_views_sparse_launch("cube_render_views_sparse", false, pool, table, layer_start, format, tgt_pose_rt, tgt_pos, tgt_intrinsics,
+                                  stack_intrinsics, depths, trig, batch, views, face_size, num_planes, camera, out_height, out_width, out_rgb, out_depth,
+                                  status_device, stream);
+}
+
+int msi_cube_render_ods_views_sparse(const void *pool, const int32_t *table, const int64_t *layer_start, int32_t format, const float *tgt_pose_rt,
+                                     const float *tgt_pos, const float *eye_radius, const float *stack_intrinsics, const float *depths,
+                                     const float *trig, int32_t batch, int32_t views, int32_t face_size, int32_t num_planes,
+                                     int32_t out_height, int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device,
+                                     msi_stream_t stream) {
+  return cube_views_sparse_launch("cube_render_ods_views_sparse", true, pool, table, layer_start, format, tgt_pose_rt, tgt_pos, eye_radius,
+                                  stack_intrinsics, depths, trig, batch, views, face_size, num_planes, MSI_CAMERA_EQUIRECT, out_height, out_width,
+                                  out_rgb, out_depth, status_device, stream);
 }
 
 }  // extern "C"

@@ -187,3 +187,45 @@ def check_origin_inside(tgt_pos, pose, planes):
     hmin = float(np.min(np.asarray(planes, dtype=np.float64)))
     if not np.all(np.abs(origin).max(axis=1) < hmin):
         raise ValueError("the target ray origin (pose @ tgt_pos) must lie inside the innermost cube shell (half-side %g)" % hmin)
+
+
+def check_ods_circle_inside(tgt_pos, pose, planes, radius):
+    """check_origin_inside for MSI.cube_render_views(camera='ods'): with o the posed head position pose @ (tgt_pos[2], tgt_pos[1],
+    tgt_pos[0], 1) and e = radius [B*V] (eye * baseline, signed), max_k |o_k| + |e| < min planes must hold.  A point of the viewing
+    circle is o + R (sin S, 0, -cos S) e and every component of a rotated unit vector is at most 1, so no component of the offset
+    exceeds |e| under any rotation: the bound keeps the WHOLE circle strictly inside the innermost shell (sufficient, not necessary).
+    ValueError otherwise (NaN included).  Host arrays only."""
+    tp = np.asarray(tgt_pos, dtype=np.float64).reshape(-1, 3)
+    ps = np.asarray(pose, dtype=np.float64).reshape(-1, 4, 4)
+    e = np.abs(np.asarray(radius, dtype=np.float64).reshape(-1))
+    if ps.shape[0] != tp.shape[0] or e.shape[0] != tp.shape[0]:
+        return      # the shape checks report it
+    c = np.stack([tp[:, 2], tp[:, 1], tp[:, 0]], axis=1)
+    origin = np.einsum('bij,bj->bi', ps[:, :3, :3], c) + ps[:, :3, 3]
+    hmin = float(np.min(np.asarray(planes, dtype=np.float64)))
+    if not np.all(np.abs(origin).max(axis=1) + e < hmin):
+        raise ValueError("the ODS viewing circle (max_k |(pose @ tgt_pos)_k| + |eye * baseline|) must lie inside the innermost cube "
+                         "shell (half-side %g)" % hmin)
+
+
+CAMERAS = ('equirect', 'pinhole', 'ods')
+
+
+def check_ods_arguments(camera, eye, baseline):
+    """The rules of MSI.cube_render_views' camera, eye and baseline, checked before anything touches a device: an unknown
+    camera; eye or baseline with a camera other than 'ods'; 'ods' without eye, or without baseline (a cube stack carries no ODS
+    intrinsics to default from); a host-side baseline that is negative or not finite.  ValueError; returns camera == 'ods'."""
+    if camera not in CAMERAS:
+        raise ValueError("camera must be 'equirect', 'pinhole' or 'ods', not %r" % (camera,))
+    ods = camera == 'ods'
+    if not ods and (eye is not None or baseline is not None):
+        raise ValueError("cube_render_views: eye and baseline belong to camera='ods', not %r" % (camera,))
+    if ods and eye is None:
+        raise ValueError("cube_render_views: camera='ods' needs eye (+1 / 'left' or -1 / 'right', or an array [V] / [B,V])")
+    if ods and baseline is None:
+        raise ValueError("cube_render_views: camera='ods' needs baseline (a cube stack carries no ODS intrinsics to take it from)")
+    if ods and not (hasattr(baseline, "is_cuda") and baseline.is_cuda):
+        bl = np.asarray(baseline, dtype=np.float64)
+        if not (np.all(np.isfinite(bl)) and np.all(bl >= 0)):
+            raise ValueError("baseline must be finite and >= 0")
+    return ods

@@ -821,6 +821,40 @@ class MSI(object):
             raise ValueError("the ODS viewing circle (|pose @ tgt_pos| + |eye * baseline|) must lie inside the innermost sphere "
                              "(radius %g)" % np.abs(pl).min())
 
+    PAIR_LAYOUTS = ('views', 'top_bottom')
+
+    def _ods_pair_views(self, who, b, tgt_pose_rt, tgt_pos, baseline, layout):
+        """What render_ods_pair and cube_render_ods_pair share: one pose [B,4,4] (or [4,4]; default identity) and head position
+        [B,3] (or [3]; default 0) per sample -> the two views' (pose [B,2,4,4], pos [B,2,3], eye = left then right), with layout and
+        the baseline's shape (a float or [B]) checked."""
+        if layout not in self.PAIR_LAYOUTS:
+            raise ValueError("layout must be 'views' or 'top_bottom', not %r" % (layout,))
+
+        def per_view(x, default, tail):
+            if x is None:
+                return np.tile(default, (b, 2) + (1,) * len(tail))
+            x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+            if tuple(x.shape) == tail:
+                x = x.expand((b,) + tail)
+            if tuple(x.shape) != (b,) + tail:
+                raise ValueError("%s: expected %s or %s, got %s" % (who, (b,) + tail, tail, tuple(x.shape)))
+            return x[:, None].expand((b, 2) + tail)
+        pose = per_view(tgt_pose_rt, np.eye(4, dtype=np.float32), (4, 4))
+        pos = per_view(tgt_pos, np.zeros(3, np.float32), (3,))
+        if baseline is not None:
+            shape = tuple(baseline.shape) if hasattr(baseline, "shape") else np.shape(baseline)
+            if shape not in ((), (b,)):
+                raise ValueError("%s: baseline must be a float or [B] = %s, got %s" % (who, (b,), shape))
+        return pose, pos, np.array([1.0, -1.0], np.float32)
+
+    @staticmethod
+    def _pair_layout(rgb, dep, layout, want_rgb, want_depth):
+        """[B,2,h,w,...] as the caller asked for it: 'top_bottom' is the SAME storage as [B,2h,w,...] (a view, no copy)."""
+        if layout == 'top_bottom':
+            rgb = rgb.view(rgb.shape[0], 2 * rgb.shape[2], rgb.shape[3], 3) if rgb is not None else None
+            dep = dep.view(dep.shape[0], 2 * dep.shape[2], dep.shape[3]) if dep is not None else None
+        return (rgb, dep) if want_rgb and want_depth else rgb if want_rgb else dep
+
     def render_ods_pair(self, rgba_layers, planes=None, baseline=None, intrinsics=None, tgt_pose_rt=None, tgt_pos=None, size=None,
                         layout='views', want_depth=False):
         """Both eyes of each sample's stereo 360 frame in ONE launch (render_views(camera='ods') with V = 2: left then right,
@@ -830,31 +864,11 @@ class MSI(object):
         the input pair (ref image = left) as the MSI reproduces it.
         layout='views': rgb [B,2,h,w,3], depth [B,2,h,w].  'top_bottom': the SAME storage as [B,2h,w,3] / [B,2h,w], left eye on
         top -- the delivery format of 360 players, without a copy."""
-        if layout not in ('views', 'top_bottom'):
-            raise ValueError("layout must be 'views' or 'top_bottom', not %r" % (layout,))
         b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]     # (SparseLayers.shape is (B, H, W, D))
-
-        def per_view(x, default, tail):
-            if x is None:
-                return np.tile(default, (b, 2) + (1,) * len(tail))
-            x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))
-            if tuple(x.shape) == tail:
-                x = x.expand((b,) + tail)
-            if tuple(x.shape) != (b,) + tail:
-                raise ValueError("render_ods_pair: expected %s or %s, got %s" % ((b,) + tail, tail, tuple(x.shape)))
-            return x[:, None].expand((b, 2) + tail)
-        pose = per_view(tgt_pose_rt, np.eye(4, dtype=np.float32), (4, 4))
-        pos = per_view(tgt_pos, np.zeros(3, np.float32), (3,))
-        if baseline is not None:
-            shape = tuple(baseline.shape) if hasattr(baseline, "shape") else np.shape(baseline)
-            if shape not in ((), (b,)):
-                raise ValueError("render_ods_pair: baseline must be a float or [B] = %s, got %s" % ((b,), shape))
+        pose, pos, eye = self._ods_pair_views("render_ods_pair", b, tgt_pose_rt, tgt_pos, baseline, layout)
         rgb, dep = self.render_views(rgba_layers, pose, pos, planes, camera='ods', intrinsics=intrinsics, size=size,
-                                     want_rgb=True, want_depth=want_depth, eye=np.array([1.0, -1.0], np.float32), baseline=baseline)
-        if layout == 'top_bottom':
-            rgb = rgb.view(b, 2 * rgb.shape[2], rgb.shape[3], 3)
-            dep = dep.view(b, 2 * dep.shape[2], dep.shape[3]) if dep is not None else None
-        return (rgb, dep) if want_depth else rgb
+                                     want_rgb=True, want_depth=want_depth, eye=eye, baseline=baseline)
+        return self._pair_layout(rgb, dep, layout, True, want_depth)
 
     # ------------------------------------------------------------------ compact stacks (matryodshka_amd/packed.py)
     LAYER_FORMATS = {'rgba8': N.MSI_LAYERS_RGBA8, 'rgba16f': N.MSI_LAYERS_RGBA16F}
@@ -1215,7 +1229,7 @@ class MSI(object):
     CUBE_FILTERINGS = ('clamp', 'seamless')
 
     def cube_render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, stack_intrinsics=None, camera='equirect',
-                          intrinsics=None, size=None, want_rgb=True, want_depth=True, filtering='clamp'):
+                          intrinsics=None, size=None, want_rgb=True, want_depth=True, filtering='clamp', eye=None, baseline=None):
         """V views of each CUBE of six face stacks in ONE launch (msi_cube_render_views; no reference counterpart) ->
         (rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w]: the composited plane index / D of over_composite_depth); either is None
         when switched off.  The planar twin of render_views; works on any model (the stack is what matters).
@@ -1232,7 +1246,7 @@ class MSI(object):
         tgt_pose_rt [B,V,4,4], tgt_pos [B,V,3] ([V,4,4] / [V,3] when B = 1), camera, intrinsics: render_views' cameras and
         pose model, unchanged; its frame (forward +x, down +y, right +z) maps to the cube frame (face 0's camera frame) by
         swapping x and z, so the centre of an equirect output looks at the centre of face 0 and one set of arguments renders
-        an MSI and a cube stack of one scene.  size = (h, w) is required for both cameras.
+        an MSI and a cube stack of one scene.  size = (h, w) is required for every camera.
         Host-side poses and positions are checked before the launch (ValueError when an origin is not strictly inside the
         innermost shell: max |o_k| >= min planes); device-side ones are flagged through render_status().
         rgba_layers may be a SparseLayers of the faces made with border='edge' (sparsify_layers of the [6B,S,S,D,4] stack;
@@ -1252,10 +1266,17 @@ class MSI(object):
         unpacked stack.  A host-side stack_intrinsics other than the default raises ValueError; one given on the device is not
         read back: such a sample is rendered with the clamp rule and render_status() returns RENDER_STATUS_NOT_CUBE_CAMERA
         (2).  A SparseLayers raises TypeError (densify_layers it first): the edge keep rule guarantees four zero alphas only
-        for footprints inside one face."""
+        for footprints inside one face.
+        camera='ods' (msi_cube_render_ods_views / _sparse): the eye panoramas of a stereo 360 frame, render_views' ODS camera on a
+        cube -- the equirect camera with the ray origin on the viewing circle around the head position, (tgt_pos[2] + sin S * e,
+        tgt_pos[1], tgt_pos[0] - cos S * e) before the pose, e = eye * baseline.  eye (required): +1 / 'left' or -1 / 'right', one
+        for every view or an array [V] / [B,V]; baseline (REQUIRED here: a cube stack carries no ODS intrinsics to default from): a
+        float, [B] or [B,V], >= 0.  Both belong to this camera only.  With baseline 0 it is the equirect camera, bit for bit.
+        Works with filtering='seamless' and with a border='edge' SparseLayers (not both).  Host-side inputs must keep the whole
+        circle strictly inside the innermost shell -- max_k |o_k| + |e| < min planes, o the posed head position (ValueError;
+        cubemap.check_ods_circle_inside) --; device-side ones set RENDER_STATUS_ORIGIN_OUTSIDE when ANY pixel's origin is outside."""
         from . import cubemap
-        if camera not in ('equirect', 'pinhole'):
-            raise ValueError("camera must be 'equirect' or 'pinhole', not %r" % (camera,))
+        ods = cubemap.check_ods_arguments(camera, eye, baseline)
         if filtering not in self.CUBE_FILTERINGS:
             raise ValueError("cube_render_views: filtering must be one of %s, not %r" % (self.CUBE_FILTERINGS, filtering))
         if not (want_rgb or want_depth):
@@ -1266,9 +1287,13 @@ class MSI(object):
                             "edge keep rule of a SparseLayers); expand it with densify_layers first")
         shape = lambda t: tuple(t.shape) if hasattr(t, "shape") else tuple(np.asarray(t).shape)
         b, v, s, d, oh, ow = cubemap.cube_view_shapes(native_shape + (4,), shape(tgt_pose_rt), shape(tgt_pos), size)
-        if not any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, tgt_pose_rt, planes)):
-            cubemap.check_origin_inside(np.asarray(torch.as_tensor(tgt_pos)), np.asarray(torch.as_tensor(tgt_pose_rt)),
-                                        np.asarray(torch.as_tensor(planes)))
+        radius = self._eye_radius(eye, baseline, None, b, v) if ods else None      # ([B,V]: host values are checked there)
+        if not any(torch.is_tensor(t) and t.is_cuda for t in (tgt_pos, tgt_pose_rt, planes, radius)):
+            host = [np.asarray(torch.as_tensor(t)) for t in (tgt_pos, tgt_pose_rt, planes)]
+            if ods:
+                cubemap.check_ods_circle_inside(*(host + [radius]))
+            else:
+                cubemap.check_origin_inside(*host)
         pose, pos = self._f32(tgt_pose_rt).reshape(b * v, 4, 4), self._f32(tgt_pos).reshape(b * v, 3)
         depths = self._depths(planes, d)
         if filtering == 'seamless' and stack_intrinsics is not None and not (torch.is_tensor(stack_intrinsics) and stack_intrinsics.is_cuda):
@@ -1282,18 +1307,41 @@ class MSI(object):
             raise ValueError("stack_intrinsics must be [3,3] or [B,3,3] with B = %d" % b)
         ks = ks.contiguous()
         intr, trig = None, None
-        if camera == 'equirect':
-            trig = self._trig(oh, ow)
-        else:
+        if camera == 'pinhole':
             if intrinsics is None:
                 raise ValueError("camera='pinhole' needs intrinsics")
             intr = self._pinhole_intrinsics(intrinsics, b, v)
+        else:
+            trig = self._trig(oh, ow)
         rgb, dep = self._view_outputs(b, v, oh, ow, want_rgb, want_depth)
-        tail = (pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(), depths.data_ptr(), _ptr(trig), b, v, s, d,
-                self.CAMERAS[camera], oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream())
-        name = "msi_cube_render_views" + ("_seamless" if filtering == 'seamless' else suffix if suffix == "_sparse" else "")
-        N.check(getattr(N.lib, name)(*(lead + tail)), name)
+        out = (oh, ow, _ptr(rgb), _ptr(dep), self._render_status.data_ptr(), self._stream())
+        if ods:            # (an entry point of its own, like msi_render_ods_views: eye_radius where the pinhole table goes, a filtering code, no camera code)
+            radius = self._f32(radius).reshape(b * v)
+            name = "msi_cube_render_ods_views" + (suffix if suffix == "_sparse" else "")
+            tail = (pose.data_ptr(), pos.data_ptr(), radius.data_ptr(), ks.data_ptr(), depths.data_ptr(), trig.data_ptr(), b, v, s, d) \
+                + (() if suffix == "_sparse" else (self.CUBE_FILTERINGS.index(filtering),))
+        else:
+            name = "msi_cube_render_views" + ("_seamless" if filtering == 'seamless' else suffix if suffix == "_sparse" else "")
+            tail = (pose.data_ptr(), pos.data_ptr(), _ptr(intr), ks.data_ptr(), depths.data_ptr(), _ptr(trig), b, v, s, d, self.CAMERAS[camera])
+        N.check(getattr(N.lib, name)(*(lead + tail + out)), name)
         return rgb, dep
+
+    def cube_render_ods_pair(self, rgba_layers, planes=None, baseline=None, stack_intrinsics=None, tgt_pose_rt=None, tgt_pos=None,
+                             size=None, layout='views', filtering='clamp', want_rgb=True, want_depth=False):
+        """render_ods_pair for a cube: both eyes of each sample's stereo 360 frame in ONE launch (cube_render_views(camera='ods') with
+        V = 2: left then right, sharing one pose and head position) -> rgb, depth, or (rgb, depth) when both are wanted.
+        rgba_layers, planes, stack_intrinsics, size (required) and filtering as in cube_render_views; baseline (required) a float
+        or [B]; tgt_pose_rt [B,4,4] (or one [4,4]; default identity), tgt_pos [B,3] (or one [3]; default 0).
+        layout='views': rgb [B,2,h,w,3], depth [B,2,h,w].  'top_bottom': the SAME storage as [B,2h,w,3] / [B,2h,w], left eye on top
+        -- the delivery format of 360 players, without a copy."""
+        shape = rgba_layers.data.shape if isinstance(rgba_layers, PackedLayers) else rgba_layers.shape
+        if shape[0] == 0 or shape[0] % 6:
+            raise ValueError("cube_render_ods_pair: the leading dimension is 6 faces per sample, %d is not a multiple of 6" % shape[0])
+        b = shape[0] // 6
+        pose, pos, eye = self._ods_pair_views("cube_render_ods_pair", b, tgt_pose_rt, tgt_pos, baseline, layout)
+        rgb, dep = self.cube_render_views(rgba_layers, pose, pos, planes, stack_intrinsics=stack_intrinsics, camera='ods', size=size,
+                                          want_rgb=want_rgb, want_depth=want_depth, filtering=filtering, eye=eye, baseline=baseline)
+        return self._pair_layout(rgb, dep, layout, want_rgb, want_depth)
 
     SRC_SAMPLINGS = ('face', 'panorama')
 
