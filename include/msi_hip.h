@@ -70,7 +70,7 @@ const char *msi_version(void);
  *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse;
  *      msi_cube_plane_sweep_f32, msi_cube_sweep_volume_bf16, msi_cube_hres_layers, msi_cube_hres_layers_sparse;
  *      msi_cube_render_views_seamless, MSI_RENDER_STATUS_NOT_CUBE_CAMERA; msi_cube_render_ods_views,
- *      msi_cube_render_ods_views_sparse) */
+ *      msi_cube_render_ods_views_sparse; msi_render_views_factored) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -443,6 +443,27 @@ int msi_hres_layers_sparse(const float *ref_image, const float *src_image, const
                            const float *alphas, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
                            int32_t num_planes, const int32_t *table, const int64_t *layer_start, void *pool_out, int32_t format,
                            msi_stream_t stream);
+/* Views straight from the FACTORS of a high-res stack (MSI.hres_factors -> FactoredLayers -> MSI.render_views / render_ods_pair): the stack
+ * msi_hres_layers would build is never allocated; every tap of a render evaluates that stack's texel from msi_hres_layers' own inputs.
+ * Arguments: msi_hres_layers' inputs and sizes in its order (trig: the table of the STACK size, height x width), then the view arguments
+ * of msi_render_views_sparse: tgt_pose_rt [B*V][4][4], tgt_pos [B*V][3], view_intrinsics [B*V][3][3] (pinhole) or NULL, eye_radius
+ * [B*V] (the ODS camera; with MSI_CAMERA_EQUIRECT only) or NULL, view_trig (the table of the OUTPUT size; equirect and ODS) or NULL,
+ * views, camera, the output size, out_rgb [B,V,h,w,3] / out_depth [B,V,h,w] (either may be NULL), the status word.
+ * Every output element compares == to msi_render_views_f32 (eye_radius == NULL) / msi_render_ods_views (non-NULL) on the fp32 stack
+ * msi_hres_layers writes from the same arguments: the same bits, except that a zero may differ in sign -- where no lane of a
+ * wavefront sees a layer (blended alpha == 0, layer 0 excepted) its colour is not computed and the step adds nothing (CONTRACT as
+ * for the sparse viewer: image values are finite).  The status word is the dense kernels'.
+ * Argument checks before any HIP call, in this order, MSI_E_BADARG unless noted.  msi_hres_layers': a NULL input of the stack; bad
+ * dims; num_planes % 4 -> MSI_E_UNSUPPORTED; H * W >= 2^24 (H, B > 65535); h * w * D >= 2^31.  Then the views': both outputs NULL; a
+ * NULL pose / position; unknown camera; a NULL view_trig (equirect) / view_intrinsics (pinhole); eye_radius with the pinhole camera;
+ * views < 1; output size below 1 x 1 (2 x 2 pinhole); the grid limit of the other views renders.  batch = 0 returns MSI_OK after
+ * validation, without a launch. */
+int msi_render_views_factored(const float *ref_image, const float *src_image, const float *ref_curr_pose, const float *src_curr_pose,
+                              const float *intrinsics, const float *depths, const float *trig, const float *blend_weights,
+                              const float *alphas, int32_t batch, int32_t low_height, int32_t low_width, int32_t height, int32_t width,
+                              int32_t num_planes, const float *tgt_pose_rt, const float *tgt_pos, const float *view_intrinsics,
+                              const float *eye_radius, const float *view_trig, int32_t views, int32_t camera, int32_t out_height,
+                              int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "SparseLayers":      # (sparse.py neither)
         from .sparse import SparseLayers
         return SparseLayers
+    if name == "FactoredLayers":    # (factored.py neither)
+        from .factored import FactoredLayers
+        return FactoredLayers
     raise AttributeError(name)

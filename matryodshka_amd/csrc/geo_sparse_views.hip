@@ -30,34 +30,7 @@ __device__ __forceinline__ void tap_tiles(TapTiles &t, __amdgpu_buffer_rsrc_t T,
 }
 
 // ---- K4 from a sparse stack ---------------------------------------------------------------------------------------------------
-// make_taps_ranged (geometry_device.h) with the wrapped corner coordinates kept apart instead of folded into flat texel offsets: the same weights,
-// op for op, and the same wrapped (x, y) of every corner.
-struct TapsS {
-  unsigned x0, x1, y0, y1;
-  float wa, wb, wc, wd;
-};
-
-__device__ __forceinline__ TapsS make_taps_sparse(float x, float y, int width, int height) {
-  TapsS t;
-  const float fx0 = floorf(x), fy0 = floorf(y);
-  const float dx0 = x - fx0, dy0 = y - fy0;
-  const float dx1 = (fx0 + 1.0f) - x, dy1 = (fy0 + 1.0f) - y;
-  t.wa = dy1 * dx1;
-  t.wb = dy1 * dx0;
-  t.wc = dy0 * dx1;
-  t.wd = dy0 * dx0;
-  const int x0 = max(-1, min((int)fx0, width - 1)), y0 = max(-1, min((int)fy0, height - 1));
-  const unsigned ax = (unsigned)(x0 + width), ay = (unsigned)(y0 + height);
-  t.x0 = min(ax, ax - (unsigned)width); t.y0 = min(ay, ay - (unsigned)height);   // -1 -> n-1
-  const unsigned bx = (unsigned)(x0 + 1), by = (unsigned)(y0 + 1);
-  t.x1 = min(bx, bx - (unsigned)width); t.y1 = min(by, by - (unsigned)height);   // n -> 0
-  return t;
-}
-
-__device__ __forceinline__ float blend4(const TapsS &t, float a, float b, float c, float d) {
-  return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;
-}
-
+// (The taps are make_taps_xy's, geometry_device.h: make_taps_ranged's weights and wrapped corners, kept as coordinates.)
 // The sparse sibling of SphereStack: layer d of sample b is two buffer resources -- its row of the table ([H/4, W/16] int32) and its kept tiles in
 // the pool (pool_rsrc, geo_sparse.h).  The per-layer step is split where the memory round trips are: lookup() is SphereStack::layer up to the taps
 // (sphere_uv) plus the table loads of the tap tiles; gather() is its four taps and blends for the lanes whose tap tiles are all present.
@@ -75,14 +48,14 @@ template <int FMT> struct SparseStack {
   __device__ __forceinline__ int end(int seg) const { return ((seg + 1) * nd) / RENDER_SEGS; }
 
   struct Look : TapTiles {
-    TapsS tp;
+    TapsXY tp;
     float qc_max;
   };
   __device__ __forceinline__ Look lookup(int d, const ViewRay &r, const SphereQuad &q, const PixConsts &K, float qc_max) const {
     Look s;
     const SphereUv p = sphere_uv(depths[d], r, q, K);
     s.qc_max = fmaxf(qc_max, p.qc);
-    s.tp = make_taps_sparse(p.u, p.v, width, height);
+    s.tp = make_taps_xy(p.u, p.v, width, height);
     const size_t l = (size_t)b * nd + d;
     const __amdgpu_buffer_rsrc_t T = table_rsrc(table + l * (size_t)(table_bytes >> 2), table_bytes);
     const unsigned r0 = __umul24(s.tp.y0 >> 2, (unsigned)tx_n), r1 = __umul24(s.tp.y1 >> 2, (unsigned)tx_n);

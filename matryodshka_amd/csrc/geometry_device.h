@@ -7,6 +7,7 @@
 //   geo_sparse.hip  the sparse layer stacks' format: the tile index (both keep rules) / gather / expand kernels.  geo_sparse.h: what the three sparse units share
 //   geo_sparse_hres.hip   the high-res stack built sparse (hres_keep_kernel, hres_layers_sparse_kernel)
 //   geo_sparse_views.hip  K4 from a sparse stack: render_views_sparse_kernel (the cameras of render and ods); the planar and cube renders from one
+//   geo_factored.hip      K4 from the FACTORS of a high-res stack, no stack in memory: render_views_factored_kernel
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_planar_hres.hip   the PP high-res stack in one pass, dense or sparse: pp_hres_layers_kernel, pp_hres_layers_sparse_kernel
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
@@ -99,13 +100,16 @@ __device__ __forceinline__ Taps make_taps(float x, float y, int width, int heigh
 // a quarter of these VALU-bound kernels in 64-bit address multiplies and exec-masked division fall-backs.
 // Weights as above (unwrapped corners; (float)(int)floor(x) == floor(x) in this range); garbage inputs (NaN -> 0, inf)
 // are clamped into the image instead of taking the reference's undefined int cast.
-struct TapsR {
-  unsigned oa, ob, oc, od;   // pixel offsets of (y0,x0) (y0,x1) (y1,x0) (y1,x1)
+// The ONE definition of the clamp and the wrap is make_taps_xy: the wrapped corner COORDINATES and the weights, for the renders that address a
+// texel by (row, column) -- the sparse viewer's tiles (geo_sparse_views.hip), the factored viewer's texel function (FactoredSphereStack below);
+// make_taps_ranged folds them into flat texel offsets.
+struct TapsXY {
+  unsigned x0, x1, y0, y1;
   float wa, wb, wc, wd;
 };
 
-__device__ __forceinline__ TapsR make_taps_ranged(float x, float y, int width, int height) {
-  TapsR t;
+__device__ __forceinline__ TapsXY make_taps_xy(float x, float y, int width, int height) {
+  TapsXY t;
   const float fx0 = floorf(x), fy0 = floorf(y);
   const float dx0 = x - fx0, dy0 = y - fy0;
   const float dx1 = (fx0 + 1.0f) - x, dy1 = (fy0 + 1.0f) - y;
@@ -115,15 +119,31 @@ __device__ __forceinline__ TapsR make_taps_ranged(float x, float y, int width, i
   t.wd = dy0 * dx0;
   const int x0 = max(-1, min((int)fx0, width - 1)), y0 = max(-1, min((int)fy0, height - 1));
   const unsigned ax = (unsigned)(x0 + width), ay = (unsigned)(y0 + height);
-  const unsigned x0w = min(ax, ax - (unsigned)width), y0w = min(ay, ay - (unsigned)height);   // -1 -> n-1
+  t.x0 = min(ax, ax - (unsigned)width); t.y0 = min(ay, ay - (unsigned)height);   // -1 -> n-1
   const unsigned bx = (unsigned)(x0 + 1), by = (unsigned)(y0 + 1);
-  const unsigned x1w = min(bx, bx - (unsigned)width), y1w = min(by, by - (unsigned)height);   // n -> 0
-  const unsigned r0 = __umul24(y0w, (unsigned)width), r1 = __umul24(y1w, (unsigned)width);
-  t.oa = r0 + x0w; t.ob = r0 + x1w; t.oc = r1 + x0w; t.od = r1 + x1w;
+  t.x1 = min(bx, bx - (unsigned)width); t.y1 = min(by, by - (unsigned)height);   // n -> 0
+  return t;
+}
+
+struct TapsR {
+  unsigned oa, ob, oc, od;   // pixel offsets of (y0,x0) (y0,x1) (y1,x0) (y1,x1)
+  float wa, wb, wc, wd;
+};
+
+__device__ __forceinline__ TapsR make_taps_ranged(float x, float y, int width, int height) {
+  const TapsXY c = make_taps_xy(x, y, width, height);
+  TapsR t;
+  t.wa = c.wa; t.wb = c.wb; t.wc = c.wc; t.wd = c.wd;
+  const unsigned r0 = __umul24(c.y0, (unsigned)width), r1 = __umul24(c.y1, (unsigned)width);
+  t.oa = r0 + c.x0; t.ob = r0 + c.x1; t.oc = r1 + c.x0; t.od = r1 + c.x1;
   return t;
 }
 
 __device__ __forceinline__ float blend4(const TapsR &t, float a, float b, float c, float d) {
+  return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;
+}
+
+__device__ __forceinline__ float blend4(const TapsXY &t, float a, float b, float c, float d) {
   return ((t.wa * a + t.wb * b) + t.wc * c) + t.wd * d;
 }
 
@@ -1135,6 +1155,7 @@ template <int FMT> struct SphereStack {
   __device__ __forceinline__ SphereStack(const void *layers_, const float *depths_, int b_, int nd_, int height_, int width_)
       : layers(layers_), depths(depths_), b(b_), nd(nd_), height(height_), width(width_), hw((size_t)height_ * width_),
         layer_bytes((int)(hw << StackTexel<FMT>::shift)) {}
+  static constexpr int UNROLL = 4;   // of the layer loop of sphere_views_body
   __device__ __forceinline__ int first(int seg) const { return (seg * nd) / RENDER_SEGS; }
   __device__ __forceinline__ int end(int seg) const { return ((seg + 1) * nd) / RENDER_SEGS; }
 
@@ -1151,6 +1172,57 @@ template <int FMT> struct SphereStack {
     s.c.x = blend4(tp4, A.x, Bv.x, C.x, Dv.x);
     s.c.y = blend4(tp4, A.y, Bv.y, C.y, Dv.y);
     s.c.z = blend4(tp4, A.z, Bv.z, C.z, Dv.z);
+    return s;
+  }
+};
+
+// The sibling of SphereStack for a high-res stack that was never built (render_views_factored_kernel, geo_factored.hip): the "layers" are the
+// FACTORS of msi_hres_layers -- the two images, the two poses, the intrinsics, the stack-size trig table and the low-res blend_weights / alphas --
+// and a tap is the texel function itself, hres_texel(ods_hres(.., y, x), depth, w, a) with w, a the resize at (y, x), evaluated at the four wrapped
+// corners make_taps_xy names.  Every step is the builders' device function, in a unit compiled without contraction, so a tap has the bits
+// hres_layers_kernel stores and layer() returns what SphereStack<MSI_LAYERS_F32>::layer returns from that stack (blend4 in its order w, x, y, z).
+// Alpha first: its four taps are sixteen low-res loads and no image gather.  Where no lane of the wavefront can see the layer -- the blended alpha
+// compares == 0 and the layer is not layer 0, whose colour the composite takes whatever its alpha -- the colour is not computed and the step
+// returns colour 0: over_step is then 0 * 0 + o * 1, the dense step up to the sign of a zero (colours finite, as in the sparse viewer's contract).
+// qc_max sees every layer.  The four taps share two rows and two columns: the trig lookups and hres_axis of a row / column are common
+// subexpressions of the four ods_hres / hres_corners calls, the pose comparison (OdsHres::same) is the same for every tap of a sample.
+#ifndef MSI_FACTORED_SKIP   // (measurement: -DMSI_FACTORED_SKIP=0 computes every layer's colour, tools/hres_factored_bench.py)
+#define MSI_FACTORED_SKIP 1
+#endif
+struct FactoredSphereStack {
+  const float *image0, *image1, *pose0, *pose1, *intrinsics, *depths, *trig;   // msi_hres_layers' inputs; trig: the table of the STACK size
+  const float *bw, *al;                                                        // sample b's low-res tensors [h,w,D]
+  int b, nd, height, width, low_h, low_w;
+  float sy, sx;                                                                // hres_scale of the two axes
+  static constexpr int UNROLL = 1;   // (a layer step is ~3 500 instructions, and the wave's vote below cannot be unrolled with a remainder loop)
+  __device__ __forceinline__ int first(int seg) const { return (seg * nd) / RENDER_SEGS; }
+  __device__ __forceinline__ int end(int seg) const { return ((seg + 1) * nd) / RENDER_SEGS; }
+
+  // the resize of layer d of a low-res tensor at corners k: lerp2<float>, elementwise what hres_lerp computes for a group of layers
+  __device__ __forceinline__ float low(const float *p, int d, const HresCorners &k) const {
+    return lerp2(p[k.tl + d], p[k.tr + d], p[k.bl + d], p[k.br + d], k.xl, k.yl);
+  }
+  __device__ __forceinline__ float4 texel(int d, unsigned y, unsigned x, const HresCorners &k, float alpha, const PixConsts &K) const {
+    return hres_texel(ods_hres(image0, image1, pose0, pose1, intrinsics, trig, K, b, (int)y, (int)x, height, width), depths[d], low(bw, d, k), alpha);
+  }
+
+  struct Step { float4 c; float qc_max; };
+  __device__ __forceinline__ Step layer(int d, const ViewRay &r, const SphereQuad &q, const PixConsts &K, float qc_max) const {
+    Step s;
+    const SphereUv p = sphere_uv(depths[d], r, q, K);
+    s.qc_max = fmaxf(qc_max, p.qc);
+    const TapsXY t = make_taps_xy(p.u, p.v, width, height);
+    const HresCorners ka = hres_corners((int)t.y0, (int)t.x0, sy, sx, low_h, low_w, nd), kb = hres_corners((int)t.y0, (int)t.x1, sy, sx, low_h, low_w, nd);
+    const HresCorners kc = hres_corners((int)t.y1, (int)t.x0, sy, sx, low_h, low_w, nd), kd = hres_corners((int)t.y1, (int)t.x1, sy, sx, low_h, low_w, nd);
+    const float aa = low(al, d, ka), ab = low(al, d, kb), ac = low(al, d, kc), ad = low(al, d, kd);
+    s.c.w = blend4(t, aa, ab, ac, ad);
+    s.c.x = 0.0f; s.c.y = 0.0f; s.c.z = 0.0f;
+    if (MSI_FACTORED_SKIP && __builtin_amdgcn_ballot_w64(d == 0 || s.c.w != 0.0f) == 0) return s;   // (wave-uniform)
+    const float4 A = texel(d, t.y0, t.x0, ka, aa, K), Bv = texel(d, t.y0, t.x1, kb, ab, K);
+    const float4 C = texel(d, t.y1, t.x0, kc, ac, K), Dv = texel(d, t.y1, t.x1, kd, ad, K);
+    s.c.x = blend4(t, A.x, Bv.x, C.x, Dv.x);
+    s.c.y = blend4(t, A.y, Bv.y, C.y, Dv.y);
+    s.c.z = blend4(t, A.z, Bv.z, C.z, Dv.z);
     return s;
   }
 };
@@ -1176,11 +1248,11 @@ __device__ __forceinline__ void sphere_combine(const SphereBlock &s, float o0, f
 // Many views of one stack per launch (msi_render_views_f32 / _packed: geo_render.hip; msi_render_ods_views: geo_ods.hip): render_kernel's
 // per-layer arithmetic for V target cameras per sample, view_ray's cameras, from a stack in texel format FMT.  A workgroup is one (sample, view,
 // target row, 64-pixel block).  Outputs rgb [B,V,h,w,3] and depth [B,V,h,w].  One body, three kernel names, the ones the profiles know them by.
-template <int MODE, int CAMERA, int FMT>
-__device__ __forceinline__ void render_views_body(const void *layers, const float *pose_rt, const float *tgt_pos, const float *intrinsics,
-                                                  const float *eye_radius, const float *depths, const float *trig, int batch, int views,
-                                                  int height, int width, int nd, int out_h, int out_w, float *out_rgb, float *out_depth,
-                                                  const PixConsts &K, const DepthFrac &F, int *status) {
+// (sphere_views_body is the body for any stack type with SphereStack's first / end / layer: stack(b) makes sample b's.  K: the constants of the STACK size.)
+template <int MODE, int CAMERA, class MakeStack>
+__device__ __forceinline__ void sphere_views_body(MakeStack stack, const float *pose_rt, const float *tgt_pos, const float *intrinsics,
+                                                  const float *eye_radius, const float *trig, int batch, int views, int nd, int out_h, int out_w,
+                                                  float *out_rgb, float *out_depth, const PixConsts &K, const DepthFrac &F, int *status) {
   SphereBlock s(out_h, out_w, views, batch);
   if (s.past_end()) return;
   s.decode(views, out_w);
@@ -1188,11 +1260,11 @@ __device__ __forceinline__ void render_views_body(const void *layers, const floa
   ViewRay r = view_ray<CAMERA>(intrinsics, eye_radius, trig, tgt_pos, bv, s.i, s.j, out_h, out_w);
   apply_pose(pose_rt + (size_t)bv * 16, r);
   const SphereQuad q = sphere_quad(r);
-  const SphereStack<FMT> S(layers, depths, s.b, nd, height, width);
+  const auto S = stack(s.b);
   const size_t pix = (size_t)bv * out_h * out_w + (size_t)s.i * out_w + s.j;
   float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f, tr = 1.f;
   float qc_max = -1.0f;
-#pragma unroll 4
+#pragma unroll decltype(S)::UNROLL
   for (int d = S.first(s.seg); d < S.end(s.seg); ++d) {
     const auto t = S.layer(d, r, q, K, qc_max);
     qc_max = t.qc_max;
@@ -1209,6 +1281,15 @@ __device__ __forceinline__ void render_views_body(const void *layers, const floa
   }
   sphere_combine(s, o0, o1, o2, od, tr,
                  [&](float o0, float o1, float o2, float od) { store_pixel<MODE>(out_rgb, out_depth, pix, o0, o1, o2, od); });
+}
+
+template <int MODE, int CAMERA, int FMT>
+__device__ __forceinline__ void render_views_body(const void *layers, const float *pose_rt, const float *tgt_pos, const float *intrinsics,
+                                                  const float *eye_radius, const float *depths, const float *trig, int batch, int views,
+                                                  int height, int width, int nd, int out_h, int out_w, float *out_rgb, float *out_depth,
+                                                  const PixConsts &K, const DepthFrac &F, int *status) {
+  sphere_views_body<MODE, CAMERA>([&](int b) { return SphereStack<FMT>(layers, depths, b, nd, height, width); }, pose_rt, tgt_pos, intrinsics,
+                                  eye_radius, trig, batch, views, nd, out_h, out_w, out_rgb, out_depth, K, F, status);
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------------------------------

@@ -29,6 +29,9 @@ MSI.mpi_render_views renders with the dense render's pixels; occupancies and byt
 SparseLayers built directly (MSI.hres_layers_sparse: the kept tiles follow from the low-res alphas, only their texels are computed
 and the dense high-res stack is never allocated) and writes each sample's occupancy and bytes to <experiment>/hres_sparse.json; the
 images are the bytes of a run without the flag.
+`--hres_factored` (a high_res mode; not with --msi_format / --msi_hres_sparse) builds no high-res stack: the high-res pass renders the target view
+and depth straight from the stack's factors (MSI.hres_factors -> MSI.render_views) and saves them as `msi_hres_factors_<dir>.npz`
+(FactoredLayers.save); the images are the bytes of a run without the flag.
 `--checkpoint` reads a TF V2 checkpoint directly (tf_checkpoint.py), `--weights` an .npz of the TF variables
 (see nets.variable_shapes); without either Xavier-initialised
 weights are used (there is no network access for the pretrained checkpoint), step.txt then says 0.
@@ -327,7 +330,8 @@ def run_sample_pp(model, images, input_offset, tgt_offset, planes, num_planes, n
     return outs
 
 
-def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, dirname, msi_format=None, hres_sparse_log=None):
+def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, dirname, msi_format=None, hres_sparse_log=None,
+                    factored=False):
     """The high-res pass of test.py:283-394 for one sample: the low-res blend weights / alphas the first pass saved
     (blend_weights.npy, alphas.npy, test.py:264-271) are upsampled (align_corners), the layers re-assembled from the
     high-res sweep volume and rendered -- one fused device pass (MSI.msi_render_equirect_hres) instead of the
@@ -336,7 +340,9 @@ def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, d
     high-res stack (MSI.hres_layers) also emits it packed, saved with its planes as msi_hres_<dirname>.npz; the images are
     the same bytes either way.  hres_sparse_log (--msi_hres_sparse; a list, needs msi_format): msi_hres_<dirname>.npz is the
     SparseLayers of MSI.hres_layers_sparse instead -- the dense packed stack is never built --, the sample's occupancy and bytes
-    are appended to the list, and the images come from the fp32 stack as in a run without any of these flags."""
+    are appended to the list, and the images come from the fp32 stack as in a run without any of these flags.  factored
+    (--hres_factored; without msi_format): no high-res stack is built at all -- the sample's FactoredLayers (MSI.hres_factors) is
+    rendered directly (MSI.render_views) and saved as msi_hres_factors_<dirname>.npz; the images are the same bytes."""
     import torch
     bw_path, al_path = os.path.join(output_dir, "blend_weights.npy"), os.path.join(output_dir, "alphas.npy")
     if not (os.path.exists(bw_path) and os.path.exists(al_path)):
@@ -348,7 +354,11 @@ def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, d
     intr = np.array([[[baseline, 0, 0], [0, 1, 0], [0, 0, 1]]], dtype=np.float32)
     pos = np.asarray(tgt_pos, dtype=np.float32)[None]
     packed = None
-    if hres_sparse_log is not None:
+    if factored:
+        factors = model.hres_factors(bw, al, ref, src, eye, eye, planes, intr)
+        rgb, dep = model.render_views(factors, eye, pos)                          # [1,1,Hh,Wh,3], [1,1,Hh,Wh]
+        rgb, dep = rgb[:, 0], dep[:, 0, :, :, None].expand(-1, -1, -1, 3)         # (the depth image has three equal channels)
+    elif hres_sparse_log is not None:
         rgb, dep = model.msi_render_equirect_hres(bw, al, ref, src, eye, eye, eye, pos, planes, intr)
         packed = model.hres_layers_sparse(bw, al, ref, src, eye, eye, planes, intr, layer_format=msi_format)["sparse_layers"]
         b, hh, hw, d = packed.shape
@@ -369,6 +379,8 @@ def run_hres_sample(model, hres_images, baseline, tgt_pos, planes, output_dir, d
     write_image(os.path.join(output_dir, "output_hresdepth_%s.png" % dirname), dep[0].cpu().numpy() * 255.)
     if packed is not None:
         packed.save(os.path.join(output_dir, "msi_hres_%s.npz" % dirname))
+    if factored:
+        factors.save(os.path.join(output_dir, "msi_hres_factors_%s.npz" % dirname))
     return rgb, dep
 
 
@@ -418,6 +430,11 @@ def main(argv=None):
                          "directly from the low-res alphas and the high-res images (MSI.hres_layers_sparse: the dense high-res stack is "
                          "never allocated; --hres_height %% 4 == 0 and --hres_width %% 16 == 0) and write each sample's occupancy and bytes to "
                          "<experiment>/hres_sparse.json; the images are the bytes of a run without the flag; default: off")
+    ap.add_argument("--hres_factored", action="store_true",
+                    help="with a high_res --test_type: build NO high-res stack -- render the target view and depth straight from the stack's "
+                         "factors (MSI.hres_factors, MSI.render_views) and save them as msi_hres_factors_<dir>.npz (a FactoredLayers); the "
+                         "images are the bytes of a run without the flag; not with --msi_format or --msi_hres_sparse, which ask for a "
+                         "materialised stack; default: off")
     ap.add_argument("--hres_height", type=int, default=2048, help="loader.py:34")
     ap.add_argument("--hres_width", type=int, default=4096, help="loader.py:35")
     ap.add_argument("--num_msi_planes", type=int, default=32)
@@ -479,6 +496,10 @@ def main(argv=None):
         ap.error("--msi_hres_sparse builds the high-res stack: it needs a high_res --test_type")
     if args.msi_hres_sparse and (args.hres_height % 4 or args.hres_width % 16):
         ap.error("--msi_hres_sparse needs --hres_height % 4 == 0 and --hres_width % 16 == 0")
+    if args.hres_factored and (args.msi_format is not None or args.msi_hres_sparse):
+        ap.error("--hres_factored builds no high-res stack: --msi_format and --msi_hres_sparse ask for a materialised one")
+    if args.hres_factored and "high_res" not in args.test_type:
+        ap.error("--hres_factored renders the high-res pass: it needs a high_res --test_type")
     if args.num_psv_planes != args.num_msi_planes:
         raise SystemExit("--num_psv_planes must equal --num_msi_planes (msi.py:138 indexes the source volume with num_msi_planes)")
     if "high_res" in args.test_type and args.input_type != "ODS":
@@ -556,7 +577,7 @@ def main(argv=None):
                     for i in ids[:2]]
             dirname = sample_dirname(scene, ids, args.test_type, args.prefix)
             run_hres_sample(model, hres, cam[0], cam[1:4], planes, os.path.join(exp_dir, dirname), dirname, msi_format=args.msi_format,
-                            hres_sparse_log=hres_sparse_log)
+                            hres_sparse_log=hres_sparse_log, factored=args.hres_factored)
             n += "high_res_only" in args.test_type
     for log, name, what in ((hres_sparse_log, "hres_sparse.json", "High-res occupancies"), (pp_sparse_log, "pp_sparse.json", "PP occupancies"),
                             (sparse_log, "sparse.json", "Occupancies")):

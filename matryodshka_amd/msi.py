@@ -20,6 +20,7 @@ import torch
 
 from . import _native as N
 from . import nets
+from .factored import FactoredLayers
 from .packed import FORMATS as PACKED_FORMATS, PackedLayers
 from .sparse import BORDERS, SparseLayers, TILE_H, TILE_W
 
@@ -486,6 +487,9 @@ class MSI(object):
 
     # ------------------------------------------------------------------ msi.py:384-452
     def _native_layers(self, rgba_layers):
+        if isinstance(rgba_layers, FactoredLayers):
+            raise TypeError("this method reads layer stacks, not their factors: render a FactoredLayers with render_views or "
+                            "render_ods_pair, or build its stack with materialize_layers first")
         if isinstance(rgba_layers, SparseLayers):
             raise TypeError("this method does not read sparse stacks: render a SparseLayers with render_views or render_ods_pair "
                             "(MSI; border='wrap') or with mpi_render_views / cube_render_views (border='edge'), or expand it with "
@@ -636,7 +640,16 @@ class MSI(object):
         of its name: '_sparse', '_packed' or '_f32'; (b, d, h, w); planes; the stack on this device, which the caller holds until
         the launch).  planes=None takes the planes a PackedLayers or SparseLayers carries.  A sparse stack made for the other kind
         of surface is refused: an edge-rule stack misses tiles a sphere render reads across the border, and a sphere stack in a
-        planar viewer is almost always a mistake."""
+        planar viewer is almost always a mistake.
+        A FactoredLayers (render_views alone): the leading arguments are msi_hres_layers' inputs and sizes, the suffix is '_factored'."""
+        if isinstance(rgba_layers, FactoredLayers):
+            if who != "render_views":
+                raise TypeError("%s reads layer stacks, not their factors: build the stack of a FactoredLayers with "
+                                "materialize_layers first" % who)
+            f = rgba_layers if rgba_layers.device == self.device else rgba_layers.to(self.device)
+            planes = f.planes if planes is None else planes
+            head, keep = self._hres_head(f, planes)
+            return head, "_factored", self._factored_dims(f), planes, keep
         if isinstance(rgba_layers, SparseLayers):
             if rgba_layers.border != border:
                 raise TypeError("%s reads SparseLayers made with border=%r, not %r: expand this one with densify_layers and "
@@ -722,7 +735,11 @@ class MSI(object):
         rgba_layers may be a SparseLayers (sparsify_layers; msi_render_views_sparse), for all three cameras: every output element
         compares == to the render of the PackedLayers it was made from and of densify_layers(rgba_layers) -- the same bits, except
         that a zero may differ in sign -- provided colours are finite where alpha is zero (always so for rgba8).  planes=None
-        takes the planes it carries.  Only a stack made with border='wrap' (the default) is accepted: TypeError otherwise."""
+        takes the planes it carries.  Only a stack made with border='wrap' (the default) is accepted: TypeError otherwise.
+        rgba_layers may be a FactoredLayers (hres_factors; msi_render_views_factored), for all three cameras: no stack exists, every
+        tap evaluates the texel hres_layers would have stored, and every output element compares == to the render of
+        materialize_layers(rgba_layers)['rgba_layers'] (a zero may differ in sign; image values finite).  planes=None takes the
+        planes it carries."""
         if camera not in self.CAMERAS:
             raise ValueError("camera must be 'equirect', 'pinhole' or 'ods', not %r" % (camera,))
         if camera != 'ods' and (eye is not None or baseline is not None):
@@ -759,6 +776,8 @@ class MSI(object):
         if suffix == "_sparse":
             args = lead + views + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape \
                 + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
+        elif suffix == "_factored":               # (depths and the stack's sizes are in `lead`: msi_hres_layers' argument list)
+            args = lead + views + (_ptr(intr), _ptr(radius), _ptr(trig), v) + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
         elif camera == 'ods':
             name = "msi_render_ods_views"
             args = lead + views + (radius.data_ptr(), depths.data_ptr(), trig.data_ptr()) + shape
@@ -864,7 +883,7 @@ class MSI(object):
         the input pair (ref image = left) as the MSI reproduces it.
         layout='views': rgb [B,2,h,w,3], depth [B,2,h,w].  'top_bottom': the SAME storage as [B,2h,w,3] / [B,2h,w], left eye on
         top -- the delivery format of 360 players, without a copy."""
-        b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]     # (SparseLayers.shape is (B, H, W, D))
+        b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]     # (SparseLayers / FactoredLayers.shape: (B, H, W, D))
         pose, pos, eye = self._ods_pair_views("render_ods_pair", b, tgt_pose_rt, tgt_pos, baseline, layout)
         rgb, dep = self.render_views(rgba_layers, pose, pos, planes, camera='ods', intrinsics=intrinsics, size=size,
                                      want_rgb=True, want_depth=want_depth, eye=eye, baseline=baseline)
@@ -899,6 +918,9 @@ class MSI(object):
         data-dependent.  The result is the same bytes every time and equals sparse.sparsify_np of the codes."""
         if isinstance(layers, SparseLayers):
             raise TypeError("sparsify_layers takes an fp32 stack or a PackedLayers, not a SparseLayers")
+        if isinstance(layers, FactoredLayers):
+            raise TypeError("sparsify_layers takes an fp32 stack or a PackedLayers, not a FactoredLayers: build its sparse stack with "
+                            "materialize_layers(..., sparse=True)")
         if border not in BORDERS:
             raise ValueError("border must be one of %s, not %r" % (BORDERS, border))
         pk = layers if isinstance(layers, PackedLayers) else self.pack_layers(layers, format, planes)
@@ -940,8 +962,9 @@ class MSI(object):
     def unpack_layers(self, packed):
         """PackedLayers -> fp32 [B,H,W,D,4], a permuted view of a new native [B,D,H,W,4] stack (msi_unpack_layers)."""
         if not isinstance(packed, PackedLayers):
-            raise TypeError("unpack_layers takes a PackedLayers" + (" (expand a SparseLayers with densify_layers first)"
-                                                                    if isinstance(packed, SparseLayers) else ""))
+            raise TypeError("unpack_layers takes a PackedLayers" + (
+                " (expand a SparseLayers with densify_layers first)" if isinstance(packed, SparseLayers) else
+                " (build the fp32 stack of a FactoredLayers with materialize_layers)" if isinstance(packed, FactoredLayers) else ""))
         data = packed.data if packed.data.device == self.device else packed.data.to(self.device)
         b, d, h, w, _ = data.shape
         native = torch.empty((b, d, h, w, 4), dtype=torch.float32, device=self.device)
@@ -1005,6 +1028,51 @@ class MSI(object):
         formats = self._layer_formats(layer_format)
         return self._hres_build_sparse("hres_layers_sparse", 'ODS', blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose,
                                        planes, intrinsics, ref_pose_inv, *formats)
+
+    def hres_factors(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics,
+                     ref_pose_inv=None):
+        """The arguments of hres_layers -> the FactoredLayers (matryodshka_amd/factored.py) of the stack hres_layers would build: its
+        checks, its preprocessing of the two images and its pose composition, and no launch beyond those.  The result goes straight
+        into render_views / render_ods_pair (msi_render_views_factored: the stack is never allocated) and into save; every other
+        method wants materialize_layers of it.  ODS models only."""
+        if self.input_type != 'ODS':
+            raise ValueError("hres_factors sweeps the sphere (input_type='ODS' models); the perspective sweep has no factored stack")
+        bw, al, hres_ref, hres_src, cur, intr, _depths, _trig = self._hres_inputs(
+            "hres_factors", blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes, intrinsics, ref_pose_inv)
+        return FactoredLayers(bw, al, hres_ref, hres_src, cur[0], cur[1], intr, planes)
+
+    @staticmethod
+    def _factored_dims(f):
+        """(B, D, Hh, Wh) of the stack a FactoredLayers stands for."""
+        b, hh, hw, d = f.shape
+        return (b, d, hh, hw)
+
+    def _hres_head(self, f, planes):
+        """msi_hres_layers' inputs and sizes from a FactoredLayers on this device -> (the argument tuple, the tensors behind its pointers: `f`,
+        the planes on the device -- a NEW tensor when `planes` is a tensor that had to be moved or converted -- and the trig table; the
+        caller holds them until the launch)."""
+        b, d, hh, hw = self._factored_dims(f)
+        h, w = f.alphas.shape[1], f.alphas.shape[2]
+        depths, trig = self._depths(planes, d), self._trig(hh, hw)
+        head = (f.ref_image.data_ptr(), f.src_image.data_ptr(), f.ref_pose.data_ptr(), f.src_pose.data_ptr(), f.intrinsics.data_ptr(),
+                depths.data_ptr(), trig.data_ptr(), f.blend_weights.data_ptr(), f.alphas.data_ptr(), b, h, w, hh, hw, d)
+        return head, (f, depths, trig)
+
+    def materialize_layers(self, factors, layer_format='f32', sparse=False):
+        """FactoredLayers -> the stack it stands for: what hres_layers returns for the same request (msi_hres_layers on the stored
+        pieces: result['rgba_layers'] and / or result['packed_layers'], layer_format as there), or with sparse=True what
+        hres_layers_sparse returns ({'sparse_layers': ...}; layer_format 'rgba8' or 'rgba16f')."""
+        if not isinstance(factors, FactoredLayers):
+            raise TypeError("materialize_layers takes a FactoredLayers (hres_factors)")
+        f = factors if factors.device == self.device else factors.to(self.device)
+        want_f32, pfmt = self._layer_formats(layer_format)
+        (head, _keep), shape = self._hres_head(f, f.planes), self._factored_dims(f)     # (_keep: alive until the launch)
+        if not sparse:
+            return self._hres_dense("msi_hres_layers", head, shape, f.planes, want_f32, pfmt)
+        if want_f32 or pfmt is None:
+            raise ValueError("materialize_layers(sparse=True) takes layer_format 'rgba8' or 'rgba16f' alone (fp32 pools are not built)")
+        return self._hres_sparse("msi_hres_index_tiles", "msi_hres_layers_sparse", head, f.alphas, tuple(f.alphas.shape[1:3]), shape, f.planes,
+                                 pfmt, 'wrap')
 
     def mpi_hres_layers(self, blend_weights, alphas, raw_hres_ref_image, raw_hres_src_image, ref_pose, src_pose, planes,
                         intrinsics, ref_pose_inv=None, layer_format='f32'):
