@@ -70,7 +70,7 @@ const char *msi_version(void);
  *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse;
  *      msi_cube_plane_sweep_f32, msi_cube_sweep_volume_bf16, msi_cube_hres_layers, msi_cube_hres_layers_sparse;
  *      msi_cube_render_views_seamless, MSI_RENDER_STATUS_NOT_CUBE_CAMERA; msi_cube_render_ods_views,
- *      msi_cube_render_ods_views_sparse; msi_render_views_factored) */
+ *      msi_cube_render_ods_views_sparse; msi_render_views_factored; msi_build_mips, msi_render_views_mip) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -464,6 +464,66 @@ int msi_render_views_factored(const float *ref_image, const float *src_image, co
                               int32_t num_planes, const float *tgt_pose_rt, const float *tgt_pos, const float *view_intrinsics,
                               const float *eye_radius, const float *view_trig, int32_t views, int32_t camera, int32_t out_height,
                               int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
+/* Mip-mapped layer stacks (MSI.build_mips -> MipLayers -> MSI.render_views / render_ods_pair with lod_bias; no reference counterpart):
+ * the viewers above take four bilinear taps at the stack's own resolution, which aliases wherever an output pixel covers more than
+ * one texel (a thumbnail of a large stack, a wide field of view, the poles, the far side of a translated viewpoint).  A stack gets
+ * the levels of a pyramid, and the view kernel blends the two levels that bracket each pixel's footprint (trilinear filtering).
+ * matryodshka_amd/mips.py holds the pyramid rule in numpy (build_mips_np; the kernel is tested against it bit for bit) and
+ * tests/mip_reference.py the view rule in fp64.
+ *
+ * msi_build_mips: layers [B,D,H,W] texels of `format` (any MSI_LAYERS_*), levels = L in 1 .. MSI_MIP_MAX_LEVELS, H and W multiples
+ * of 2^(L-1), the top level (H >> (L-1)) x (W >> (L-1)) at least 2 x 2.  mips_out holds the levels 1 .. L-1, consecutive, level l
+ * [B,D,H>>l,W>>l] texels of the same format, 16-byte aligned (about a third of the base's bytes); level 0 is the base, untouched.
+ * One launch: the base is read once, a workgroup reduces 32 x 32 base texels of one (sample, layer) through every level.
+ *   THE PYRAMID RULE (fp32, one rounding per operation, no fused multiply-add), on DECODED texels (a, c_0..c_2) = (alpha, colour):
+ *     level 1   texel (y, x) owns the base block rows 2y, 2y+1 x columns 2x, 2x+1 = tl, tr, bl, br.  Its partial sums are
+ *                 A = sum a,   P_k = sum fl(a * c_k),   Q_k = sum c_k,   each summed as (tl + tr) + (bl + br).
+ *     level l   the partials of texel (y, x) are the sums of the four partials of level l-1 at (2y, 2y+1) x (2x, 2x+1), in the
+ *               same order.  Partials are never quantised: only the texel that is stored is.
+ *     texel     with n = 4^l:  alpha = A * (1/n);  colour_k = P_k / A (IEEE divide) where the layer d != 0 and A > 0, else
+ *               colour_k = Q_k * (1/n).  Layer 0 always takes the plain mean: over-compositing ignores its alpha.
+ *     store     encoded with the format's encoder above (rgba8 / rgba16f); MSI_LAYERS_F32 stores the four floats.
+ *   A transparent texel's colour therefore never bleeds into a coarser level.
+ * Argument checks before any HIP call, in this order, MSI_E_BADARG: a NULL layers (a NULL mips_out with L > 1); unknown format;
+ * non-positive dims (batch < 0); L outside 1 .. MSI_MIP_MAX_LEVELS; H or W not a multiple of 2^(L-1); a top level below 2 x 2;
+ * 2^31 or more workgroups.  batch = 0 and L = 1 (nothing to write) return MSI_OK without a launch.
+ *
+ * msi_render_views_mip: msi_render_views_packed's arguments with, after `format`, mips (msi_build_mips' buffer for the same
+ * sizes and format; may be NULL when levels = 1), levels, lod_bias, and -- as in msi_render_views_sparse -- eye_radius [B*V] after
+ * intrinsics: non-NULL (with MSI_CAMERA_EQUIRECT only) selects the ODS camera of msi_render_ods_views.  Cameras, pose, ray / sphere
+ * quadratic, pixel coordinates, over-composite, segment combine, outputs and the status word are those renders', op for op; only the
+ * blended texel (r, g, b, alpha) of a layer changes:
+ *   THE TEXEL RULE.  (u, v) is the layer's hit of pixel (i, j), in pixel coordinates of the H x W base.  (u_x, v_x) is the hit
+ *   of the column neighbour (i, j'), j' = j + 1 if j + 1 < out_width else j - 1; (u_y, v_y) that of the row neighbour (i', j), i'
+ *   chosen the same way.  A neighbour is the WHOLE ray of that pixel (for the ODS camera its origin moves too).  An axis of one
+ *   pixel has no neighbour: its differences are 0.
+ *     du_x = u_x - u, du_x -= W * rint(du_x / W)   (u wraps: the nearer way round);   dv_x = v_x - v   (v does not wrap);  same for y
+ *     rho    = max(hypot(du_x, dv_x), hypot(du_y, dv_y))                  texels per output pixel, isotropic
+ *     lambda = min(max(log2(rho) + lod_bias, 0), L - 1);  rho = 0 or a NaN gives 0
+ *     l0 = floor(lambda),  f = lambda - l0,  l1 = min(l0 + 1, L - 1)
+ *     at level l the hit is  u_l = (u + 0.5) * 2^-l - 0.5,  v_l = (v + 0.5) * 2^-l - 0.5   (l = 0: u and v themselves)
+ *     t_l    = the viewers' wrap-around bilinear lookup (four taps, both axes wrap, weights from the unwrapped corners, summed
+ *              a, b, c, d) of level l at (u_l, v_l) with the level's size (W >> l, H >> l)
+ *     texel  = t_l0 + f * (t_l1 - t_l0) per component  (f = 0: t_l0 itself; level l1 is then not read)
+ *   The kernel evaluates log2, the reciprocal of W and the hits with the continuous-tail primitives of the other renders (1 ulp);
+ *   nothing here branches on them discontinuously: the rule is continuous in the ray.
+ *   Properties: a pixel with lambda = 0 on every layer has the bits of msi_render_views_packed / msi_render_ods_views; so has the
+ *   whole image when levels = 1 or lod_bias <= -64.  lod_bias >= 64 reads the top level alone.
+ *   The footprint is isotropic: near the stack's poles, where du_x is large while dv_x is small, lambda follows du_x and the image
+ *   is blurred along v as well (anisotropic filtering is not implemented).
+ * Argument checks before any HIP call, in this order, MSI_E_BADARG: both outputs NULL; a NULL layers / pose / position / depths
+ * (a NULL mips with L > 1); unknown format; unknown camera; a NULL trig (equirect) / intrinsics (pinhole); eye_radius with the
+ * pinhole camera; bad dims; a NaN lod_bias; L outside 1 .. MSI_MIP_MAX_LEVELS; H or W not a multiple of 2^(L-1); a top level below
+ * 2 x 2; views < 1; output size below 1 x 1 (2 x 2 pinhole); H * W >= 2^24; the grid limit of the other views renders.  batch = 0
+ * returns MSI_OK after validation, without a launch. */
+#define MSI_MIP_MAX_LEVELS 6
+int msi_build_mips(const void *layers, int32_t format, int32_t batch, int32_t num_planes, int32_t height, int32_t width,
+                   int32_t levels, void *mips_out, msi_stream_t stream);
+int msi_render_views_mip(const void *layers, int32_t format, const void *mips, int32_t levels, float lod_bias,
+                         const float *tgt_pose_rt, const float *tgt_pos, const float *intrinsics, const float *eye_radius,
+                         const float *depths, const float *trig, int32_t batch, int32_t views, int32_t height, int32_t width,
+                         int32_t num_planes, int32_t camera, int32_t out_height, int32_t out_width, float *out_rgb,
+                         float *out_depth, int32_t *status_device, msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -22,4 +22,7 @@ def __getattr__(name):
     if name == "FactoredLayers":    # (factored.py neither)
         from .factored import FactoredLayers
         return FactoredLayers
+    if name == "MipLayers":         # (mips.py neither)
+        from .mips import MipLayers
+        return MipLayers
     raise AttributeError(name)

@@ -92,6 +92,8 @@ SIGNATURES = {
     "msi_render_views_sparse": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_hres_index_tiles": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_render_views_factored": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "msi_build_mips": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "msi_render_views_mip": (_I, [_P, _I, _P, _I, c_float, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_hres_layers_sparse": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "msi_sparse_index_tiles_edge": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_pp_hres_layers": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),

@@ -29,7 +29,7 @@ SOURCES = [
 # the geometry side: one translation unit per kernel family (csrc/geometry_device.h holds what they share and says why none of them may contract
 # a*b+c into fma), compiled in parallel.  The flags are attached here, to the whole list: a unit cannot join without them.
 GEO_UNITS = ["geo_prep.hip", "geo_sweep.hip", "geo_layers.hip", "geo_render.hip", "geo_planar.hip", "geo_planar_hres.hip", "geo_cube.hip", "geo_cube_sweep.hip", "geo_ods.hip",
-             "geo_sparse.hip", "geo_sparse_hres.hip", "geo_sparse_views.hip", "geo_factored.hip"]
+             "geo_sparse.hip", "geo_sparse_hres.hip", "geo_sparse_views.hip", "geo_factored.hip", "geo_mip.hip"]
 SOURCES += [(u, ["-ffp-contract=off"] + NO_SLP + os.environ.get("MSI_GEO_DEFINES", "").split()) for u in GEO_UNITS]   # e.g. MSI_GEO_DEFINES="-DMSI_SWEEP_WAVES=5" (tuning)
 # the K2 convolution path: one translation unit per kernel family (r05; cnn_device.h holds what they share), compiled in parallel
 CNN_UNITS = ["cnn.hip", "cnn_net.hip", "cnn_plan.hip", "cnn_igemm.hip", "cnn_halo.hip", "cnn_x3.hip", "cnn_bf16.hip", "cnn_tail.hip"]

@@ -8,6 +8,7 @@
 //   geo_sparse_hres.hip   the high-res stack built sparse (hres_keep_kernel, hres_layers_sparse_kernel)
 //   geo_sparse_views.hip  K4 from a sparse stack: render_views_sparse_kernel (the cameras of render and ods); the planar and cube renders from one
 //   geo_factored.hip      K4 from the FACTORS of a high-res stack, no stack in memory: render_views_factored_kernel
+//   geo_mip.hip           mip-mapped stacks: build_mips_kernel (the pyramid of a stack in one launch) and K4 with a trilinear texel, render_views_mip_kernel
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_planar_hres.hip   the PP high-res stack in one pass, dense or sparse: pp_hres_layers_kernel, pp_hres_layers_sparse_kernel
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel

@@ -21,6 +21,7 @@ import torch
 from . import _native as N
 from . import nets
 from .factored import FactoredLayers
+from .mips import MipLayers, check_levels as check_mip_levels, level_shapes as mip_level_shapes, max_levels as max_mip_levels
 from .packed import FORMATS as PACKED_FORMATS, PackedLayers
 from .sparse import BORDERS, SparseLayers, TILE_H, TILE_W
 
@@ -487,6 +488,9 @@ class MSI(object):
 
     # ------------------------------------------------------------------ msi.py:384-452
     def _native_layers(self, rgba_layers):
+        if isinstance(rgba_layers, MipLayers):
+            raise TypeError("this method does not read mip-mapped stacks: render a MipLayers with render_views or render_ods_pair, or "
+                            "pass its level 0, .base")
         if isinstance(rgba_layers, FactoredLayers):
             raise TypeError("this method reads layer stacks, not their factors: render a FactoredLayers with render_views or "
                             "render_ods_pair, or build its stack with materialize_layers first")
@@ -641,7 +645,17 @@ class MSI(object):
         the launch).  planes=None takes the planes a PackedLayers or SparseLayers carries.  A sparse stack made for the other kind
         of surface is refused: an edge-rule stack misses tiles a sphere render reads across the border, and a sphere stack in a
         planar viewer is almost always a mistake.
-        A FactoredLayers (render_views alone): the leading arguments are msi_hres_layers' inputs and sizes, the suffix is '_factored'."""
+        A FactoredLayers (render_views alone): the leading arguments are msi_hres_layers' inputs and sizes, the suffix is '_factored'.
+        A MipLayers (render_views alone): (layers, format, mips, levels), the suffix is '_mip'."""
+        if isinstance(rgba_layers, MipLayers):
+            if who != "render_views":
+                raise TypeError("%s does not read mip-mapped stacks: pass the MipLayers' level 0, .base" % who)
+            mip = rgba_layers if rgba_layers.data.device == self.device else rgba_layers.to(self.device)
+            planes = mip.planes if planes is None else planes
+            if planes is None:
+                raise ValueError("%s: planes is required (this MipLayers carries none)" % who)
+            fmt = N.MSI_LAYERS_F32 if mip.format == 'f32' else self.LAYER_FORMATS[mip.format]
+            return (mip.data.data_ptr(), fmt, mip.mips.data_ptr(), mip.levels), "_mip", tuple(mip.data.shape[:4]), planes, mip
         if isinstance(rgba_layers, FactoredLayers):
             if who != "render_views":
                 raise TypeError("%s reads layer stacks, not their factors: build the stack of a FactoredLayers with "
@@ -702,7 +716,7 @@ class MSI(object):
         return rgb, dep
 
     def render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, camera='equirect', intrinsics=None, size=None,
-                     want_rgb=True, want_depth=True, eye=None, baseline=None):
+                     want_rgb=True, want_depth=True, eye=None, baseline=None, lod_bias=0.0):
         """V views of each MSI in ONE launch (msi_render_views_f32; no reference counterpart) -> (rgb, depth):
         rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w] (one channel: msi_render_equirect_depth(...)[..., 0]); either is None
         when switched off.
@@ -739,7 +753,14 @@ class MSI(object):
         rgba_layers may be a FactoredLayers (hres_factors; msi_render_views_factored), for all three cameras: no stack exists, every
         tap evaluates the texel hres_layers would have stored, and every output element compares == to the render of
         materialize_layers(rgba_layers)['rgba_layers'] (a zero may differ in sign; image values finite).  planes=None takes the
-        planes it carries."""
+        planes it carries.
+        rgba_layers may be a MipLayers (build_mips; msi_render_views_mip), for all three cameras: every layer's texel is blended from
+        the two pyramid levels that bracket the pixel's footprint on that layer (trilinear filtering; the rule is in msi_hip.h), so
+        a view SMALLER than the stack -- a thumbnail, a wide field of view, the poles, the far side of a translated viewpoint --
+        does not alias.  lod_bias is added to the level of detail: > 0 blurs, < 0 sharpens, <= -64 is the plain render of .base bit
+        for bit (so is a pixel whose footprint is at most one texel on every layer, and a MipLayers of one level).  The filter is
+        isotropic: near the stack's poles it blurs along latitude too.  planes=None takes the planes it carries.  lod_bias belongs
+        to a MipLayers: anything but 0 with another kind of stack is a ValueError."""
         if camera not in self.CAMERAS:
             raise ValueError("camera must be 'equirect', 'pinhole' or 'ods', not %r" % (camera,))
         if camera != 'ods' and (eye is not None or baseline is not None):
@@ -748,6 +769,11 @@ class MSI(object):
             raise ValueError("render_views: camera='ods' needs eye (+1 / 'left' or -1 / 'right', or an array [V] / [B,V])")
         if not (want_rgb or want_depth):
             raise ValueError("render_views: want_rgb and want_depth are both False")
+        lod_bias = float(lod_bias)
+        if lod_bias != lod_bias:
+            raise ValueError("render_views: lod_bias is NaN")
+        if lod_bias != 0.0 and not isinstance(rgba_layers, MipLayers):
+            raise ValueError("render_views: lod_bias belongs to a MipLayers (build_mips), this stack has one level")
         lead, suffix, (b, d, h, w), planes, _keep = self._view_stack(rgba_layers, planes, "render_views", 'wrap')   # (_keep: alive until the launch)
         if camera != 'ods':
             self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
@@ -775,6 +801,9 @@ class MSI(object):
         name = "msi_render_views" + suffix
         if suffix == "_sparse":
             args = lead + views + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape \
+                + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
+        elif suffix == "_mip":                    # (msi_render_views_sparse's list behind the stack and lod_bias)
+            args = lead + (lod_bias,) + views + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape \
                 + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
         elif suffix == "_factored":               # (depths and the stack's sizes are in `lead`: msi_hres_layers' argument list)
             args = lead + views + (_ptr(intr), _ptr(radius), _ptr(trig), v) + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
@@ -875,22 +904,47 @@ class MSI(object):
         return (rgb, dep) if want_rgb and want_depth else rgb if want_rgb else dep
 
     def render_ods_pair(self, rgba_layers, planes=None, baseline=None, intrinsics=None, tgt_pose_rt=None, tgt_pos=None, size=None,
-                        layout='views', want_depth=False):
+                        layout='views', want_depth=False, lod_bias=0.0):
         """Both eyes of each sample's stereo 360 frame in ONE launch (render_views(camera='ods') with V = 2: left then right,
         sharing one pose and head position) -> rgb, or (rgb, depth) with want_depth.
         tgt_pose_rt [B,4,4] (or one [4,4]; default identity), tgt_pos [B,3] (or one [3]; default 0); planes, baseline,
         intrinsics and size as in render_views -- with the sample's own baseline, identity pose and position 0 the two views are
         the input pair (ref image = left) as the MSI reproduces it.
         layout='views': rgb [B,2,h,w,3], depth [B,2,h,w].  'top_bottom': the SAME storage as [B,2h,w,3] / [B,2h,w], left eye on
-        top -- the delivery format of 360 players, without a copy."""
-        b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]     # (SparseLayers / FactoredLayers.shape: (B, H, W, D))
+        top -- the delivery format of 360 players, without a copy.  lod_bias: render_views', for a MipLayers."""
+        b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]     # (SparseLayers / FactoredLayers / MipLayers.shape: (B, H, W, D))
         pose, pos, eye = self._ods_pair_views("render_ods_pair", b, tgt_pose_rt, tgt_pos, baseline, layout)
         rgb, dep = self.render_views(rgba_layers, pose, pos, planes, camera='ods', intrinsics=intrinsics, size=size,
-                                     want_rgb=True, want_depth=want_depth, eye=eye, baseline=baseline)
+                                     want_rgb=True, want_depth=want_depth, eye=eye, baseline=baseline, lod_bias=lod_bias)
         return self._pair_layout(rgb, dep, layout, True, want_depth)
 
     # ------------------------------------------------------------------ compact stacks (matryodshka_amd/packed.py)
     LAYER_FORMATS = {'rgba8': N.MSI_LAYERS_RGBA8, 'rgba16f': N.MSI_LAYERS_RGBA16F}
+
+    def build_mips(self, layers, levels=None, planes=None):
+        """A stack -> MipLayers (matryodshka_amd/mips.py): the stack as level 0 plus the levels 1 .. L-1 of its pyramid in one buffer,
+        about a third of the stack's bytes, one launch that reads the stack once (msi_build_mips; the rule is in msi_hip.h and, in
+        numpy, mips.build_mips_np).  `layers` is an fp32 stack [B,H,W,D,4] (a permuted view of the native stack goes through without a
+        copy) or a PackedLayers, whose format the levels keep.  levels: L in 1..6 with H and W multiples of 2^(L-1) and a top level of
+        at least 2 x 2 (ValueError); None takes the largest L the sizes allow.  `planes`, or else the planes a PackedLayers carries,
+        travel with the result, which goes into render_views / render_ods_pair."""
+        if isinstance(layers, (MipLayers, SparseLayers, FactoredLayers)):
+            raise TypeError("build_mips takes an fp32 stack or a PackedLayers, not a %s%s" % (
+                type(layers).__name__, ": pass its level 0, .base" if isinstance(layers, MipLayers) else ""))
+        if isinstance(layers, PackedLayers):
+            data = layers.data if layers.data.device == self.device else layers.data.to(self.device)
+            planes = layers.planes if planes is None else planes
+            base, fmt = PackedLayers(data, layers.format, planes), self.LAYER_FORMATS[layers.format]
+        else:
+            base = data = self._native_layers(layers)
+            fmt = N.MSI_LAYERS_F32
+        b, d, h, w, _ = data.shape
+        if planes is not None and len(planes) != d:
+            raise ValueError("len(planes) != number of layers")
+        levels = max_mip_levels(h, w) if levels is None else check_mip_levels(h, w, levels)
+        mips = torch.empty((sum(int(np.prod(s)) for s in mip_level_shapes(data.shape, levels)),), dtype=data.dtype, device=self.device)
+        N.check(N.lib.msi_build_mips(data.data_ptr(), fmt, b, d, h, w, levels, mips.data_ptr(), self._stream()), "msi_build_mips")
+        return MipLayers(base, mips, levels, planes)
 
     def pack_layers(self, rgba_layers, format='rgba8', planes=None):
         """fp32 stack [B,H,W,D,4] -> PackedLayers in `format` ('rgba8': 4 bytes per texel, 'rgba16f': 8; the rule is in
@@ -918,6 +972,8 @@ class MSI(object):
         data-dependent.  The result is the same bytes every time and equals sparse.sparsify_np of the codes."""
         if isinstance(layers, SparseLayers):
             raise TypeError("sparsify_layers takes an fp32 stack or a PackedLayers, not a SparseLayers")
+        if isinstance(layers, MipLayers):
+            raise TypeError("sparsify_layers takes an fp32 stack or a PackedLayers, not a MipLayers: pass its level 0, .base")
         if isinstance(layers, FactoredLayers):
             raise TypeError("sparsify_layers takes an fp32 stack or a PackedLayers, not a FactoredLayers: build its sparse stack with "
                             "materialize_layers(..., sparse=True)")
@@ -964,7 +1020,8 @@ class MSI(object):
         if not isinstance(packed, PackedLayers):
             raise TypeError("unpack_layers takes a PackedLayers" + (
                 " (expand a SparseLayers with densify_layers first)" if isinstance(packed, SparseLayers) else
-                " (build the fp32 stack of a FactoredLayers with materialize_layers)" if isinstance(packed, FactoredLayers) else ""))
+                " (build the fp32 stack of a FactoredLayers with materialize_layers)" if isinstance(packed, FactoredLayers) else
+                " (pass a MipLayers' level 0, .base)" if isinstance(packed, MipLayers) else ""))
         data = packed.data if packed.data.device == self.device else packed.data.to(self.device)
         b, d, h, w, _ = data.shape
         native = torch.empty((b, d, h, w, 4), dtype=torch.float32, device=self.device)
@@ -1402,6 +1459,8 @@ class MSI(object):
         or [B]; tgt_pose_rt [B,4,4] (or one [4,4]; default identity), tgt_pos [B,3] (or one [3]; default 0).
         layout='views': rgb [B,2,h,w,3], depth [B,2,h,w].  'top_bottom': the SAME storage as [B,2h,w,3] / [B,2h,w], left eye on top
         -- the delivery format of 360 players, without a copy."""
+        if isinstance(rgba_layers, MipLayers):
+            raise TypeError("cube_render_ods_pair does not read mip-mapped stacks: pass the MipLayers' level 0, .base")
         shape = rgba_layers.data.shape if isinstance(rgba_layers, PackedLayers) else rgba_layers.shape
         if shape[0] == 0 or shape[0] % 6:
             raise ValueError("cube_render_ods_pair: the leading dimension is 6 faces per sample, %d is not a multiple of 6" % shape[0])
