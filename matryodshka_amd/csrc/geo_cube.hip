@@ -1,19 +1,11 @@
 // The cube-map viewer of the PP path (no reference counterpart): cube_render_views_kernel renders V views per sample from SIX face stacks in one
 // launch, equirect_to_cube_kernel cuts a panorama into the six face images the PP network takes; kernels first, their C ABI entry points below.
-//
-// Conventions (include/msi_hip.h states them for callers).  The cube frame is the camera frame of face 0 (x right, y down, z forward).  Face f of
-// sample b is entry 6 b + f of the native [6B,D,S,S] stack; its camera axes in the cube frame are the columns of R_f:
-//   f      0 front   1 right    2 back     3 left     4 up       5 down
-//   x      (1,0,0)   (0,0,-1)   (-1,0,0)   (0,0,1)    (1,0,0)    (1,0,0)
-//   y      (0,1,0)   (0,1,0)    (0,1,0)    (0,1,0)    (0,0,1)    (0,0,-1)
-//   z      (0,0,1)   (1,0,0)    (0,0,-1)   (-1,0,0)   (0,-1,0)   (0,1,0)
-// Texel (ix, iy) of layer d of face f is the cube-frame point R_f planes[d] K^-1 (ix, iy, 1): layer d of the six faces is a cube shell of
-// half-side planes[d].
+// The cube conventions and the pixel's pieces (ray, shell hit, blend, origin test) are geo_cube.h's.
 //
 // The SEAMLESS filter (cube_render_views_seamless_kernel, msi_cube_render_views_seamless; include/msi_hip.h and cubemap.virtual_texel state the
 // same rule).  It is defined for the cube camera fx = fy = cx = cy = S/2 only: a face then stores tan = -1 .. 1 - 2/S, nothing on its +x and +y
 // edges, and the cube point of lattice point (x, y), 0 <= x, y <= S, of a face is a lattice point of every other face that contains it.  Ray,
-// shell hit, face choice and p = R_f^T P are the clamp kernel's, op for op.  Then
+// shell hit, face choice and p = R_f^T P are geo_cube.h's pieces, the clamp kernel's too.  Then
 //   1. u, v are clamped to [0, S] (fmaxf first); 2. x0 = min(floor(u), S-1), x1 = x0 + 1 <= S, du = u - x0 in [0, 1], likewise y0, y1, dv;
 //   3. four bilinear taps with the clamp kernel's weights and sum order; 4. a tap with x < S and y < S is the face's own texel;
 //   5. a tap with x = S or y = S is a VIRTUAL texel at the cube point P (an edge point; a cube corner when the other coordinate is 0 or S).
@@ -35,6 +27,7 @@
 // (right/down, back/down): the mean rule makes them continuous over a two-texel span.  2 are stored twice (up/back, up/left: row 0 of both
 // faces): each face keeps its own texel, so a step in CONTENT between the two faces remains there; in-range texels are never overridden.
 #include "geometry_device.h"
+#include "geo_cube.h"
 
 namespace {
 
@@ -42,26 +35,18 @@ namespace {
 // replaces, then c a + acc (1 - a)); a workgroup is 64 x 4 pixels of one (sample, view), a wave one row.
 //   grid    1-D, sample -> view -> 4-row group -> 64-pixel block with the XCD-aware mapping of every many-views render (ViewBlock, geometry_device.h): the views of one cube follow each
 //           other through the Infinity Cache and adjacent row groups share an XCD's L2.
-//   rays    render_views_kernel's (view_ray and apply_pose, geometry_device.h): (cos S cos T, sin T, sin S cos T) on the lat-long grid of the output or (1, (i + 0.5 - cy) / fy,
-//           (j + 0.5 - cx) / fx), rotated by pose[:3,:3]; origin pose @ (tgt_pos[2], tgt_pos[1], tgt_pos[0], 1).  That render frame (forward +x,
-//           down +y, right +z) becomes the cube frame by swapping x and z.  Pose, origin and both cameras are wave-uniform (scalar loads).  CAMERA_ODS (msi_cube_render_ods_views) is the equirect
-//           camera with view_ray's origin on the viewing circle, (tgt_pos[2] + sin S_j e, tgt_pos[1], tgt_pos[0] - cos S_j e) before the pose, e = eye_radius[bv]
-//           read through the `intrinsics` argument (the pinhole table's place: no kernel argument is added, so the other cameras' kernarg layout stands).
-//           Its origin, and with it ox, oy, oz and bx, by, bz, is per LANE (vector registers); the pose and e stay scalar.
-//   shell   For origin o, direction r and half-side h: t = min over the axes of (h sign(r_k) - o_k) / r_k, evaluated as h / |r_k| - o_k / r_k
-//           with the two quotients per pixel (IEEE divides; an axis with r_k = 0 is given +inf, and fminf drops a NaN), P = o + t r.  The face
-//           is the axis of the largest |P_k| with its sign (ties: z, x, y); p = R_f^T P is two selects; u = fx p_x / h + cx, v = fy p_y / h + cy.
-//   taps    u, v are clamped to [0, S-1] (fmaxf first: a NaN becomes 0 BEFORE the float -> int conversion), then bilinear over (x0, y0) ..
-//           (min(x0+1, S-1), min(y0+1, S-1)): clamp to the edge of the chosen face, no zero padding, no fetch from the neighbouring face.
+//   pixel   ray, shell hit, blend and origin test are geo_cube.h's pieces (cube_ray, cube_hit with hi = S-1, cube_blend, cube_origin_outside);
+//           CAMERA_ODS is msi_cube_render_ods_views.
+//   taps    bilinear over (x0, y0) .. (min(x0+1, S-1), min(y0+1, S-1)) of u, v in [0, S-1]: clamp to the edge of the chosen face, no zero padding,
+//           no fetch from the neighbouring face.
 //           The face index differs per lane, so the descriptor is per SAMPLE (scalar: the six faces' 6 D S^2 texels) and the face and layer
 //           are in the 32-bit per-lane offset ((f D + d) S^2 + y S + x) << log2(texel bytes); the host refuses a sample of 2^31 bytes or more.
 //           Every index is in [0, S-1] and f in [0, 5] by construction, whatever the inputs; the descriptor's range check is a second line.
 //           One 16-, 8- or 4-byte load per tap, decoded by geometry_device.h's decoders: a packed render has the bits of the render of the
 //           unpacked stack.
-//   loop    unrolled by 4: a shell's taps do not depend on the running composite, so several shells' taps are in flight under the blend.
-//   status  a view whose origin is not strictly inside the innermost shell (max |o_k| >= min planes, or NaN) ORs MSI_RENDER_STATUS_ORIGIN_OUTSIDE
-//           into *status (one lane per workgroup); its pixels are finite for finite inputs (t may be negative, the taps are clamped).  CAMERA_ODS: the
-//           flag is set when ANY pixel's origin fails that test -- every lane tests its own, one atomicOr per wavefront with a set lane (render_views_body's form).
+//   loop    unrolled by 4: a shell's taps do not depend on the running composite, so several shells' taps are in flight under the blend.  The
+//           composite is this kernel's own text (over_step grows its depth-only instantiations: profiles/shared_render_pieces_isa.txt).
+//   status  one lane per workgroup; CAMERA_ODS: every lane tests its own origin, one atomicOr per wavefront with a set lane.
 template <int MODE, int CAMERA, int FMT>
 __global__ void __launch_bounds__(256)
 cube_render_views_kernel(const void *__restrict__ layers, const float *__restrict__ pose_rt, const float *__restrict__ tgt_pos,
@@ -76,48 +61,26 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
   const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;                 // (no barrier below; lane (0, 0) of a workgroup is always inside)
 
-  ViewRay r = view_ray<CAMERA>(intrinsics, intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);   // (CAMERA_ODS: `intrinsics` is eye_radius)
-  apply_pose(pose_rt + (size_t)bv * 16, r);
-  // render frame -> cube frame: x <-> z
-  const float dx = r.rz, dy = r.ry, dz = r.rx;
-  const float ox = r.cz, oy = r.cy, oz = r.cx;
-  // t_k = h / |r_k| - o_k / r_k
-  const float inf = __builtin_inff();
-  const float ax = dx != 0.0f ? 1.0f / fabsf(dx) : inf, bx = dx != 0.0f ? ox / dx : 0.0f;
-  const float ay = dy != 0.0f ? 1.0f / fabsf(dy) : inf, by = dy != 0.0f ? oy / dy : 0.0f;
-  const float az = dz != 0.0f ? 1.0f / fabsf(dz) : inf, bz = dz != 0.0f ? oz / dz : 0.0f;
-
-  const float *Ks = stack_intrinsics + (size_t)b * 9;   // the six faces' camera: fx . cx / . fy cy
-  const float kfx = Ks[0], kcx = Ks[2], kfy = Ks[4], kcy = Ks[5];
+  const CubeRay r = cube_ray<CAMERA>(intrinsics, trig, tgt_pos, pose_rt, bv, i, j, out_h, out_w);
+  const CubeCamera cam = cube_stack_camera(stack_intrinsics, b);
   const float sm1 = (float)(face - 1);
   const unsigned ss2 = (unsigned)face * (unsigned)face, fstride = ss2 * (unsigned)nd;     // texels of a layer / of a face's stack
   const size_t sample_bytes = ((size_t)6 * fstride) << StackTexel<FMT>::shift;          // (< 2^31, checked on the host)
   const __amdgpu_buffer_rsrc_t L =
       __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + (size_t)b * sample_bytes), 0, (int)sample_bytes, 0x00020000);
   float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f;
-  float hmin = inf;
+  float hmin = __builtin_inff();
 
 #pragma unroll 4
   for (int d = 0; d < nd; ++d) {
     const float h = depths[d];
     hmin = fminf(hmin, h);
-    const float t = fminf(fminf(__builtin_fmaf(h, ax, -bx), __builtin_fmaf(h, ay, -by)), __builtin_fmaf(h, az, -bz));
-    const float px = __builtin_fmaf(t, dx, ox), py = __builtin_fmaf(t, dy, oy), pz = __builtin_fmaf(t, dz, oz);
-    const float mx = fabsf(px), my = fabsf(py), mz = fabsf(pz);
-    const bool zf = mz >= mx && mz >= my;               // ties: z, x, y (a NaN point compares false everywhere: a y face, clamped taps)
-    const bool xf = !zf && mx >= my;
-    const bool neg = (zf ? pz : (xf ? px : py)) < 0.0f;
-    const unsigned f = zf ? (neg ? 2u : 0u) : (xf ? (neg ? 3u : 1u) : (neg ? 4u : 5u));
-    const float qx = zf ? (neg ? -px : px) : (xf ? (neg ? pz : -pz) : px);   // p = R_f^T P
-    const float qy = (zf || xf) ? py : (neg ? pz : -pz);
-    const float inv_h = t_div(1.0f, h);
-    const float u = fminf(fmaxf(__builtin_fmaf(qx, kfx * inv_h, kcx), 0.0f), sm1);   // fmaxf(NaN, 0) = 0
-    const float v = fminf(fmaxf(__builtin_fmaf(qy, kfy * inv_h, kcy), 0.0f), sm1);
-    const float fx0 = floorf(u), fy0 = floorf(v);
-    const float dx0 = u - fx0, dy0 = v - fy0, dx1 = 1.0f - dx0, dy1 = 1.0f - dy0;
+    const CubeHit p = cube_hit(r, cam, h, sm1);
+    const float fx0 = floorf(p.u), fy0 = floorf(p.v);
+    const float dx0 = p.u - fx0, dy0 = p.v - fy0, dx1 = 1.0f - dx0, dy1 = 1.0f - dy0;
     const int x0 = (int)fx0, y0 = (int)fy0;             // in [0, S-1]
     const int x1 = min(x0 + 1, face - 1), y1 = min(y0 + 1, face - 1);
-    const unsigned base = f * fstride + (unsigned)d * ss2;
+    const unsigned base = p.f * fstride + (unsigned)d * ss2;
     const unsigned r0 = base + (unsigned)y0 * (unsigned)face, r1 = base + (unsigned)y1 * (unsigned)face;
     const float4 A = StackTexel<FMT>::tap(L, r0 + (unsigned)x0), Bv = StackTexel<FMT>::tap(L, r0 + (unsigned)x1);
     const float4 C = StackTexel<FMT>::tap(L, r1 + (unsigned)x0), Dv = StackTexel<FMT>::tap(L, r1 + (unsigned)x1);
@@ -143,18 +106,14 @@ cube_render_views_kernel(const void *__restrict__ layers, const float *__restric
       else od = F.f[d] * al + od * (1.0f - al);
     }
   }
-  if constexpr (CAMERA == CAMERA_ODS) {
-    // the origin is a property of the lane (a point of the viewing circle): every lane tests its own, the wave votes, lane 0 issues the atomicOr
+  if constexpr (CAMERA == CAMERA_ODS) {                 // (every lane tests its own origin, the wave votes, lane 0 issues the atomicOr)
     if (status != nullptr) {
-      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-      const bool any = __builtin_amdgcn_ballot_w64(!(omax < hmin) || ox != ox || oy != oy || oz != oz) != 0;   // (wave-uniform)
+      const bool any = __builtin_amdgcn_ballot_w64(cube_origin_outside(r, hmin)) != 0;   // (wave-uniform)
       if (any && threadIdx.x == 0) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
     }
-  } else {
-    // the origin is a property of the view: every lane agrees (fmaxf drops a NaN, so it is tested by itself)
+  } else {                                              // (the origin is a property of the view: every lane agrees)
     if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
-      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-      if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+      if (cube_origin_outside(r, hmin)) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
     }
   }
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
@@ -252,8 +211,8 @@ __device__ __forceinline__ CubeEdge cube_edge(unsigned f, bool xside, int t, int
   return e;
 }
 
-// cube_render_views_kernel with the seamless filter (the rule: this file's header).  Grid, rays, shell hit, face choice, blend and status are that
-// kernel's; what differs is the tap stage.
+// cube_render_views_kernel with the seamless filter (the rule: this file's header).  Grid and composite are that kernel's, the pixel's pieces
+// geo_cube.h's (cube_hit with hi = S for the cube camera); what differs is the tap stage.
 //   camera  the rule holds for fx = fy = cx = cy = S/2 only: the sample's stack camera is compared with S/2 (scalar, uniform per workgroup).  Any
 //           other camera renders with the clamp rule (hi = S-1 below: the clamp kernel's values op for op) and ORs MSI_RENDER_STATUS_NOT_CUBE_CAMERA.
 //   taps    four unconditional loads per shell, as the clamp kernel: A is always the own texel; B, C, D are the own texel, the neighbour's texel (8 of
@@ -286,19 +245,10 @@ cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *
   const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;
 
-  ViewRay r = view_ray<CAMERA>(intrinsics, intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);   // (CAMERA_ODS: `intrinsics` is eye_radius)
-  apply_pose(pose_rt + (size_t)bv * 16, r);
-  const float dx = r.rz, dy = r.ry, dz = r.rx;
-  const float ox = r.cz, oy = r.cy, oz = r.cx;
-  const float inf = __builtin_inff();
-  const float ax = dx != 0.0f ? 1.0f / fabsf(dx) : inf, bx = dx != 0.0f ? ox / dx : 0.0f;
-  const float ay = dy != 0.0f ? 1.0f / fabsf(dy) : inf, by = dy != 0.0f ? oy / dy : 0.0f;
-  const float az = dz != 0.0f ? 1.0f / fabsf(dz) : inf, bz = dz != 0.0f ? oz / dz : 0.0f;
-
-  const float *Ks = stack_intrinsics + (size_t)b * 9;
-  const float kfx = Ks[0], kcx = Ks[2], kfy = Ks[4], kcy = Ks[5];
+  const CubeRay r = cube_ray<CAMERA>(intrinsics, trig, tgt_pos, pose_rt, bv, i, j, out_h, out_w);
+  const CubeCamera cam = cube_stack_camera(stack_intrinsics, b);
   const float half = 0.5f * (float)face;
-  const bool cube_camera = kfx == half && kfy == half && kcx == half && kcy == half;    // (a NaN camera: false)
+  const bool cube_camera = cam.fx == half && cam.fy == half && cam.cx == half && cam.cy == half;    // (a NaN camera: false)
   const int m = face - 1, hi = cube_camera ? face : m;
   const float sm1 = (float)m, fhi = (float)hi;
   const unsigned ss2 = (unsigned)face * (unsigned)face, fstride = ss2 * (unsigned)nd;
@@ -306,24 +256,14 @@ cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *
   const __amdgpu_buffer_rsrc_t L =
       __builtin_amdgcn_make_buffer_rsrc((void *)(static_cast<const char *>(layers) + (size_t)b * sample_bytes), 0, (int)sample_bytes, 0x00020000);
   float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f;
-  float hmin = inf;
+  float hmin = __builtin_inff();
 
   const auto fetch = [&](int d, CubeShellTaps<FMT> &T) {
     const float h = depths[d];
     hmin = fminf(hmin, h);
-    const float t = fminf(fminf(__builtin_fmaf(h, ax, -bx), __builtin_fmaf(h, ay, -by)), __builtin_fmaf(h, az, -bz));
-    const float px = __builtin_fmaf(t, dx, ox), py = __builtin_fmaf(t, dy, oy), pz = __builtin_fmaf(t, dz, oz);
-    const float mx = fabsf(px), my = fabsf(py), mz = fabsf(pz);
-    const bool zf = mz >= mx && mz >= my;
-    const bool xf = !zf && mx >= my;
-    const bool neg = (zf ? pz : (xf ? px : py)) < 0.0f;
-    const unsigned f = zf ? (neg ? 2u : 0u) : (xf ? (neg ? 3u : 1u) : (neg ? 4u : 5u));
-    const float qx = zf ? (neg ? -px : px) : (xf ? (neg ? pz : -pz) : px);
-    const float qy = (zf || xf) ? py : (neg ? pz : -pz);
-    const float inv_h = t_div(1.0f, h);
-    const float u = fminf(fmaxf(__builtin_fmaf(qx, kfx * inv_h, kcx), 0.0f), fhi);    // fmaxf(NaN, 0) = 0
-    const float v = fminf(fmaxf(__builtin_fmaf(qy, kfy * inv_h, kcy), 0.0f), fhi);
-    const float fx0 = fminf(floorf(u), sm1), fy0 = fminf(floorf(v), sm1);
+    const CubeHit p = cube_hit(r, cam, h, fhi);
+    const unsigned f = p.f;
+    const float fx0 = fminf(floorf(p.u), sm1), fy0 = fminf(floorf(p.v), sm1);
     const int x0 = (int)fx0, y0 = (int)fy0;             // in [0, S-1]
     const int x1 = min(x0 + 1, hi), y1 = min(y0 + 1, hi);   // in [0, S]; S only with the cube camera
     const unsigned dbase = (unsigned)d * ss2, base = f * fstride + dbase;
@@ -345,7 +285,7 @@ cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *
     }
     T.A = StackTexel<FMT>::tap(L, r0 + (unsigned)x0); T.B = StackTexel<FMT>::tap(L, oB);
     T.C = StackTexel<FMT>::tap(L, oC); T.D = StackTexel<FMT>::tap(L, oD);
-    T.du = u - fx0; T.dv = v - fy0;
+    T.du = p.u - fx0; T.dv = p.v - fy0;
     T.key = f | ((unsigned)x0 << 3) | (again << 31);
     T.y0 = y0;
   };
@@ -376,14 +316,7 @@ cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *
         T.D = corner_tap(x1, y1);
       }
     }
-    const float4 A = T.A, Bv = T.B, C = T.C, Dv = T.D;
-    const float dx0 = T.du, dy0 = T.dv, dx1 = 1.0f - dx0, dy1 = 1.0f - dy0;
-    const float wa = dy1 * dx1, wb = dy1 * dx0, wc = dy0 * dx1, wd = dy0 * dx0;
-    float4 c;
-    c.w = ((wa * A.w + wb * Bv.w) + wc * C.w) + wd * Dv.w;
-    c.x = ((wa * A.x + wb * Bv.x) + wc * C.x) + wd * Dv.x;
-    c.y = ((wa * A.y + wb * Bv.y) + wc * C.y) + wd * Dv.y;
-    c.z = ((wa * A.z + wb * Bv.z) + wc * C.z) + wd * Dv.z;
+    const float4 c = cube_blend(T.du, T.dv, T.A, T.B, T.C, T.D);
     const float al = c.w;
     if (MODE & RENDER_RGB) {
       if (d == 0) {
@@ -415,15 +348,13 @@ cube_render_views_seamless_kernel(const void *__restrict__ layers, const float *
   }
   if constexpr (CAMERA == CAMERA_ODS) {                 // (the wave votes on its lanes' origins; the stack camera is uniform)
     if (status != nullptr) {
-      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-      const bool any = __builtin_amdgcn_ballot_w64(!(omax < hmin) || ox != ox || oy != oy || oz != oz) != 0;
+      const bool any = __builtin_amdgcn_ballot_w64(cube_origin_outside(r, hmin)) != 0;
       const int bits = (cube_camera ? 0 : MSI_RENDER_STATUS_NOT_CUBE_CAMERA) | (any ? MSI_RENDER_STATUS_ORIGIN_OUTSIDE : 0);
       if (bits && threadIdx.x == 0) atomicOr(status, bits);
     }
   } else if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
-    const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
     int bits = cube_camera ? 0 : MSI_RENDER_STATUS_NOT_CUBE_CAMERA;
-    if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) bits |= MSI_RENDER_STATUS_ORIGIN_OUTSIDE;
+    if (cube_origin_outside(r, hmin)) bits |= MSI_RENDER_STATUS_ORIGIN_OUTSIDE;
     if (bits) atomicOr(status, bits);
   }
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
@@ -496,14 +427,7 @@ static int cube_views_launch(const char *who, bool ods, int32_t filtering, const
     MSI_REQUIRE(filtering == 0 || filtering == 1, "%s: unknown filtering %d (0 clamp, 1 seamless)", who, filtering);
     return num_planes <= DEPTH_FRAC_MAX ? (int)MSI_OK : msi::fail(MSI_E_UNSUPPORTED, "%s: at most %d planes", who, DEPTH_FRAC_MAX);
   };
-  // the per-sample descriptor: the six faces' stacks are addressed with one 32-bit byte offset per lane
-  const auto sample_bytes = [&] {
-    const int texel_bytes = format == MSI_LAYERS_F32 ? 16 : format == MSI_LAYERS_RGBA16F ? 8 : 4;
-    MSI_REQUIRE(face_size < (1 << 15) && (long)face_size * face_size * 6 * num_planes * texel_bytes < (1L << 31),   // (< 2^30 * 6 * 128 * 16)
-                "%s: a sample's six face stacks (6 x %d x %d x %d texels of %d bytes) reach 2^31 bytes (32-bit offsets)", who,
-                num_planes, face_size, face_size, texel_bytes);
-    return (int)MSI_OK;
-  };
+  const auto sample_bytes = [&] { return cube_sample_bytes_check(who, format, face_size, num_planes); };
   unsigned grid;
   if (const int e = check_views(a, planes, sample_bytes, &grid)) return e;
   if (batch == 0) return MSI_OK;
@@ -517,10 +441,7 @@ static int cube_views_launch(const char *who, bool ods, int32_t filtering, const
     if (filtering) go(cube_render_views_seamless_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
     else go(cube_render_views_kernel<decltype(M)::value, decltype(CAM)::value, decltype(FMT)::value>);
   };
-  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_format(format, [&](auto FMT) {
-    if (ods) launch(M, Const<CAMERA_ODS>{}, FMT);
-    else for_camera(camera, [&](auto CAM) { launch(M, CAM, FMT); });
-  }); });
+  for_view_kernel(render_mode(out_rgb, out_depth), format, ods, camera, launch);
   return msi::check_launch(who);
 }
 

@@ -60,16 +60,13 @@ int msi_render_views_factored(const float *ref_image, const float *src_image, co
   const PixConsts K = make_consts(height, width);
   const DepthFrac F = depth_fractions(num_planes);
   hipStream_t s = msi::as_stream(stream);
-  const auto launch = [&](auto M, auto CAM) {
+  const auto launch = [&](auto M, auto CAM, auto) {   // (no texel format: the factors are fp32)
     hipLaunchKernelGGL((render_views_factored_kernel<decltype(M)::value, decltype(CAM)::value>), dim3(grid), dim3(64, RENDER_SEGS), 0, s, ref_image,
                        src_image, ref_curr_pose, src_curr_pose, intrinsics, depths, trig, blend_weights, alphas, low_height, low_width, sy, sx,
                        tgt_pose_rt, tgt_pos, view_intrinsics, eye_radius, view_trig, batch, views, height, width, num_planes, out_height, out_width,
                        out_rgb, out_depth, K, F, status_device);
   };
-  for_mode(render_mode(out_rgb, out_depth), [&](auto M) {
-    if (eye_radius) launch(M, Const<CAMERA_ODS>{});
-    else for_camera(camera, [&](auto CAM) { launch(M, CAM); });
-  });
+  for_view_kernel(render_mode(out_rgb, out_depth), MSI_LAYERS_F32, eye_radius != nullptr, camera, launch);
   return msi::check_launch(who);
 }
 

@@ -286,10 +286,7 @@ int msi_render_views_mip(const void *layers, int32_t format, const void *mips, i
                        lod_bias, tgt_pose_rt, tgt_pos, intrinsics, eye_radius, depths, trig, batch, views, height, width, num_planes, out_height, out_width,
                        out_rgb, out_depth, K, F, status_device);
   };
-  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_format(format, [&](auto FMT) {
-    if (eye_radius) launch(M, Const<CAMERA_ODS>{}, FMT);
-    else for_camera(camera, [&](auto CAM) { launch(M, CAM, FMT); });
-  }); });
+  for_view_kernel(render_mode(out_rgb, out_depth), format, eye_radius != nullptr, camera, launch);
   return msi::check_launch(who);
 }
 

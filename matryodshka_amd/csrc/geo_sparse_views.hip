@@ -4,6 +4,7 @@
 // kernel's pixel with one table lookup per tap tile in front of the gathers; kernels first, the C ABI entry points below.
 #include "geometry_device.h"
 #include "geo_sparse.h"
+#include "geo_cube.h"
 
 namespace {
 
@@ -342,8 +343,8 @@ mpi_render_views_sparse_kernel(const void *__restrict__ pool, const int *__restr
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
 }
 
-// The cube render.  Rays (CAMERA_ODS included: per-lane origins, eye_radius through `intrinsics`, the wave's vote on the status word), shell, face and
-// clamped taps are cube_render_views_kernel's, op for op.  The face differs per lane, so the table, layer_start
+// The cube render.  Ray (CAMERA_ODS included), shell hit with hi = S-1, blend and origin test are geo_cube.h's pieces, as in cube_render_views_kernel;
+// the clamped tap coordinates are that kernel's.  The face differs per lane, so the table, layer_start
 // and the pool get one descriptor per SAMPLE -- the six faces' table rows [6 D, S/4, S/16], their 6 D + 1 entries of layer_start, and the kept tiles
 // from layer_start[6 b D] to layer_start[6 (b + 1) D] (below 2^31 bytes: the host refuses a sample whose DENSE stacks reach that) -- and the lane's
 // layer f D + d goes into the per-lane offsets.  The layer's first tile, relative to the sample's (the low words' difference: it fits 32 bits), is
@@ -364,19 +365,8 @@ cube_render_views_sparse_kernel(const void *__restrict__ pool, const int *__rest
   const int i = k.i, j = k.j, b = k.b;
   if (j >= out_w || i >= out_h) return;                 // (no barrier below; lane (0, 0) of a workgroup is always inside)
 
-  ViewRay r = view_ray<CAMERA>(intrinsics, intrinsics, trig, tgt_pos, bv, i, j, out_h, out_w);   // (CAMERA_ODS: `intrinsics` is eye_radius)
-  apply_pose(pose_rt + (size_t)bv * 16, r);
-  // render frame -> cube frame: x <-> z
-  const float dx = r.rz, dy = r.ry, dz = r.rx;
-  const float ox = r.cz, oy = r.cy, oz = r.cx;
-  // t_k = h / |r_k| - o_k / r_k
-  const float inf = __builtin_inff();
-  const float ax = dx != 0.0f ? 1.0f / fabsf(dx) : inf, bx = dx != 0.0f ? ox / dx : 0.0f;
-  const float ay = dy != 0.0f ? 1.0f / fabsf(dy) : inf, by = dy != 0.0f ? oy / dy : 0.0f;
-  const float az = dz != 0.0f ? 1.0f / fabsf(dz) : inf, bz = dz != 0.0f ? oz / dz : 0.0f;
-
-  const float *Ks = stack_intrinsics + (size_t)b * 9;   // the six faces' camera: fx . cx / . fy cy
-  const float kfx = Ks[0], kcx = Ks[2], kfy = Ks[4], kcy = Ks[5];
+  const CubeRay r = cube_ray<CAMERA>(intrinsics, trig, tgt_pos, pose_rt, bv, i, j, out_h, out_w);
+  const CubeCamera cam = cube_stack_camera(stack_intrinsics, b);
   const float sm1 = (float)(face - 1);
   const unsigned tx_n = (unsigned)face / TILE_W, ty_n = (unsigned)face / TILE_H;
   const size_t layer0 = (size_t)6 * b * nd;             // the sample's first layer
@@ -387,7 +377,7 @@ cube_render_views_sparse_kernel(const void *__restrict__ pool, const int *__rest
   const __amdgpu_buffer_rsrc_t L = pool_rsrc<FMT>(static_cast<const char *>(pool), first, layer_start[layer0 + layers_n] - first);
   const unsigned first_lo = (unsigned)first;
   float o0 = 0.f, o1 = 0.f, o2 = 0.f, od = 0.f;
-  float hmin = inf;
+  float hmin = __builtin_inff();
 
   struct Look : TapTiles {
     float dx0, dy0;
@@ -398,23 +388,12 @@ cube_render_views_sparse_kernel(const void *__restrict__ pool, const int *__rest
     Look s;
     const float h = depths[d];
     hmin = fminf(hmin, h);
-    const float t = fminf(fminf(__builtin_fmaf(h, ax, -bx), __builtin_fmaf(h, ay, -by)), __builtin_fmaf(h, az, -bz));
-    const float px = __builtin_fmaf(t, dx, ox), py = __builtin_fmaf(t, dy, oy), pz = __builtin_fmaf(t, dz, oz);
-    const float mx = fabsf(px), my = fabsf(py), mz = fabsf(pz);
-    const bool zf = mz >= mx && mz >= my;               // ties: z, x, y (a NaN point compares false everywhere: a y face, clamped taps)
-    const bool xf = !zf && mx >= my;
-    const bool neg = (zf ? pz : (xf ? px : py)) < 0.0f;
-    const unsigned f = zf ? (neg ? 2u : 0u) : (xf ? (neg ? 3u : 1u) : (neg ? 4u : 5u));
-    const float qx = zf ? (neg ? -px : px) : (xf ? (neg ? pz : -pz) : px);   // p = R_f^T P
-    const float qy = (zf || xf) ? py : (neg ? pz : -pz);
-    const float inv_h = t_div(1.0f, h);
-    const float u = fminf(fmaxf(__builtin_fmaf(qx, kfx * inv_h, kcx), 0.0f), sm1);   // fmaxf(NaN, 0) = 0
-    const float v = fminf(fmaxf(__builtin_fmaf(qy, kfy * inv_h, kcy), 0.0f), sm1);
-    const float fx0 = floorf(u), fy0 = floorf(v);
-    s.dx0 = u - fx0; s.dy0 = v - fy0;
+    const CubeHit p = cube_hit(r, cam, h, sm1);
+    const float fx0 = floorf(p.u), fy0 = floorf(p.v);
+    s.dx0 = p.u - fx0; s.dy0 = p.v - fy0;
     const int x0 = (int)fx0, y0 = (int)fy0;             // in [0, S-1]
     const int x1 = min(x0 + 1, face - 1), y1 = min(y0 + 1, face - 1);
-    const unsigned lr = f * (unsigned)nd + (unsigned)d; // the lane's layer within the sample: below 6 D
+    const unsigned lr = p.f * (unsigned)nd + (unsigned)d; // the lane's layer within the sample: below 6 D
     const unsigned ty0 = (unsigned)y0 >> 2, ty1 = (unsigned)y1 >> 2;
     const unsigned r0 = (lr * ty_n + ty0) * tx_n, r1 = (lr * ty_n + ty1) * tx_n;
     const unsigned c0 = (unsigned)x0 >> 4, c1 = (unsigned)x1 >> 4;
@@ -433,17 +412,8 @@ cube_render_views_sparse_kernel(const void *__restrict__ pool, const int *__rest
     q.d = raw_tap<FMT>(L, at(s.id, s.in_d));
     return q;
   };
-  // cube_render_views_kernel's blend: wa A + wb B + wc C + wd D
   const auto blend = [&](const Look &s, const RawTaps<FMT> &q) {
-    const float4 A = decode_tap<FMT>(q.a), Bv = decode_tap<FMT>(q.b), C = decode_tap<FMT>(q.c), Dv = decode_tap<FMT>(q.d);
-    const float dx0 = s.dx0, dy0 = s.dy0, dx1 = 1.0f - dx0, dy1 = 1.0f - dy0;
-    const float wa = dy1 * dx1, wb = dy1 * dx0, wc = dy0 * dx1, wd = dy0 * dx0;
-    float4 c;
-    c.w = ((wa * A.w + wb * Bv.w) + wc * C.w) + wd * Dv.w;
-    c.x = ((wa * A.x + wb * Bv.x) + wc * C.x) + wd * Dv.x;
-    c.y = ((wa * A.y + wb * Bv.y) + wc * C.y) + wd * Dv.y;
-    c.z = ((wa * A.z + wb * Bv.z) + wc * C.z) + wd * Dv.z;
-    return c;
+    return cube_blend(s.dx0, s.dy0, decode_tap<FMT>(q.a), decode_tap<FMT>(q.b), decode_tap<FMT>(q.c), decode_tap<FMT>(q.d));
   };
   for (int d0 = 0; d0 < nd; d0 += PLANAR_GROUP) {
     Look look[PLANAR_GROUP];
@@ -467,18 +437,14 @@ cube_render_views_sparse_kernel(const void *__restrict__ pool, const int *__rest
       if (ok[g]) { o0 = n.o0; o1 = n.o1; o2 = n.o2; od = n.od; }
     }
   }
-  if constexpr (CAMERA == CAMERA_ODS) {
-    // the origin is a property of the lane (a point of the viewing circle): every lane tests its own, the wave votes, lane 0 issues the atomicOr
+  if constexpr (CAMERA == CAMERA_ODS) {                 // (every lane tests its own origin, the wave votes, lane 0 issues the atomicOr)
     if (status != nullptr) {
-      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-      const bool any = __builtin_amdgcn_ballot_w64(!(omax < hmin) || ox != ox || oy != oy || oz != oz) != 0;   // (wave-uniform)
+      const bool any = __builtin_amdgcn_ballot_w64(cube_origin_outside(r, hmin)) != 0;   // (wave-uniform)
       if (any && threadIdx.x == 0) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
     }
-  } else {
-    // the origin is a property of the view: every lane agrees (fmaxf drops a NaN, so it is tested by itself)
+  } else {                                              // (the origin is a property of the view: every lane agrees)
     if (status != nullptr && threadIdx.x == 0 && threadIdx.y == 0) {
-      const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-      if (!(omax < hmin) || ox != ox || oy != oy || oz != oz) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
+      if (cube_origin_outside(r, hmin)) atomicOr(status, MSI_RENDER_STATUS_ORIGIN_OUTSIDE);
     }
   }
   store_pixel<MODE>(out_rgb, out_depth, ((size_t)bv * out_h + i) * out_w + j, o0, o1, o2, od);
@@ -511,10 +477,7 @@ int msi_render_views_sparse(const void *pool, const int32_t *table, const int64_
                          tile_starts(layer_start), tgt_pose_rt, tgt_pos, intrinsics, eye_radius, depths, trig, batch, views, height, width, num_planes,
                          out_height, out_width, out_rgb, out_depth, K, F, status_device);
   };
-  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_format(format, [&](auto FMT) {
-    if (eye_radius) launch(M, Const<CAMERA_ODS>{}, FMT);
-    else for_camera(camera, [&](auto CAM) { launch(M, CAM, FMT); });
-  }); });
+  for_view_kernel(render_mode(out_rgb, out_depth), format, eye_radius != nullptr, camera, launch);
   return msi::check_launch(who);
 }
 
@@ -560,15 +523,7 @@ static int cube_views_sparse_launch(const char *who, bool ods, const void *pool,
     if (face_size % TILE_W == 0) return (int)MSI_OK;        // (and with it S % 4 == 0)
     return msi::fail(MSI_E_UNSUPPORTED, "%s: a sparse cube needs S %% %d == 0 (got %d)", who, TILE_W, face_size);
   };
-  // the per-sample descriptor of the pool: a sample's kept tiles are addressed with one 32-bit byte offset per lane; they are no more than its dense
-  // stacks, which msi_cube_render_views holds to the same bound
-  const auto sample_bytes = [&] {
-    const int texel_bytes = format == MSI_LAYERS_RGBA16F ? 8 : 4;
-    MSI_REQUIRE(face_size < (1 << 15) && (long)face_size * face_size * 6 * num_planes * texel_bytes < (1L << 31),
-                "%s: a sample's six face stacks (6 x %d x %d x %d texels of %d bytes) reach 2^31 bytes (32-bit offsets)", who, num_planes,
-                face_size, face_size, texel_bytes);
-    return (int)MSI_OK;
-  };
+  const auto sample_bytes = [&] { return cube_sample_bytes_check(who, format, face_size, num_planes); };   // (the DENSE stacks' bound)
   unsigned grid;
   if (const int e = check_views(a, unsupported, sample_bytes, &grid)) return e;
   if (batch == 0) return MSI_OK;
@@ -581,10 +536,7 @@ static int cube_views_sparse_launch(const char *who, bool ods, const void *pool,
                          tile_starts(layer_start), tgt_pose_rt, tgt_pos, camera_table, stack_intrinsics, depths, trig, batch, views, face_size,
                          num_planes, out_height, out_width, out_rgb, out_depth, F, status_device);
   };
-  for_mode(render_mode(out_rgb, out_depth), [&](auto M) { for_format(format, [&](auto FMT) {
-    if (ods) launch(M, Const<CAMERA_ODS>{}, FMT);
-    else for_camera(camera, [&](auto CAM) { launch(M, CAM, FMT); });
-  }); });
+  for_view_kernel(render_mode(out_rgb, out_depth), format, ods, camera, launch);
   return msi::check_launch(who);
 }
 

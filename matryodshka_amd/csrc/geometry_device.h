@@ -12,6 +12,7 @@
 //   geo_planar.hip  the PP path: perspective plane sweeps, the MPI render and its many-views form (fp32 or packed stacks)
 //   geo_planar_hres.hip   the PP high-res stack in one pass, dense or sparse: pp_hres_layers_kernel, pp_hres_layers_sparse_kernel
 //   geo_cube.hip    the cube-map viewer of the PP path: cube_render_views_kernel (six face stacks as one panorama or headset view), equirect_to_cube_kernel
+//                   (geo_cube.h: the cube conventions and the pieces of the cube pixel, for this unit and geo_sparse_views.hip's cube kernel)
 //   geo_cube_sweep.hip    the cube path's source half sampled from the source PANORAMA, across face edges: cube_sweep_kernel, cube_sweep_volume_bf16_kernel,
 //                         cube_hres_layers_kernel, cube_hres_layers_sparse_kernel
 // Here: ONLY what more than one family uses (anonymous namespace: every unit inlines its own copy); each block says who shares it and why the
@@ -1412,6 +1413,13 @@ template <class F> void for_format(int format, F f) {
 template <class F> void for_camera(int camera, F f) {
   if (camera == MSI_CAMERA_PINHOLE) f(Const<MSI_CAMERA_PINHOLE>{});
   else f(Const<MSI_CAMERA_EQUIRECT>{});
+}
+// the table of a viewer with view_ray's three cameras: f(M, CAM, FMT) once; ods: CAMERA_ODS, whatever the (equirect) camera code
+template <class F> void for_view_kernel(int mode, int format, bool ods, int camera, F f) {
+  for_mode(mode, [&](auto M) { for_format(format, [&](auto FMT) {
+    if (ods) f(M, Const<CAMERA_ODS>{}, FMT);
+    else for_camera(camera, [&](auto CAM) { f(M, CAM, FMT); });
+  }); });
 }
 
 // layers, planar-hres, cube-sweep (msi_hres_layers, msi_pp_hres_layers, msi_cube_hres_layers): ONE store policy and ONE table of instantiations for the

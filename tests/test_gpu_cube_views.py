@@ -356,3 +356,94 @@ def test_from_a_panorama_pair_to_the_viewer(gpu):
     assert tuple(scores['psnr'].shape) == (b, V) and torch.isfinite(scores['ssim']).all() and float(scores['psnr'].min()) >= 38.6
     torch.cuda.synchronize()
     assert m.render_status() == 0
+
+
+# ------------------------------------------------------------------------------- 7. every kernel form at the smallest shapes
+# Every instantiation of the three cube viewer kernels (mode x camera x format; clamp, seamless, sparse) at the smallest shapes that take
+# every branch: output 5 x 70 (two 64-pixel blocks, the second partial; a row group of four and one of one row), B = 2, V = 2, D = 3 and
+# D = 6 (an odd sparse group of two; a remainder of the seamless group of four), S = 8 dense and S = 16 sparse (whole tiles).  The forms
+# are held to each other with the viewer's identities, all bit for bit: a single output is that half of the double render, a packed render
+# is the render of the unpacked stack, the ODS camera with baseline 0 is the equirect camera, the seamless filter with another stack camera
+# is the clamp render (and says so in the status word), a sparse render == the render of the packed stack it was made from.
+SMALL_PLANES = {3: [50.0, 5.0, 1.0], 6: [100.0, 30.0, 10.0, 3.0, 1.5, 1.0]}
+SMALL_SIZE = (5, 70)
+MODES = [(True, True), (True, False), (False, True)]
+
+
+def _small_cameras(torch, m, layers, s, planes, ks=None, **kw):
+    """{camera: {mode: (rgb, depth)}} of one stack for the three cameras and the three output modes, the status word checked after each."""
+    pose, pos = _poses(2)
+    out = {}
+    for camera, extra in (("equirect", {}), ("pinhole", dict(intrinsics=_k_target(SMALL_SIZE))), ("ods", dict(eye=[1, -1], baseline=0.06)),
+                          ("ods0", dict(eye=[1, -1], baseline=0.0))):
+        out[camera] = {}
+        for mode in MODES:
+            out[camera][mode] = m.cube_render_views(layers, pose, pos, planes=planes, stack_intrinsics=_k_stack(s) if ks is None else ks,
+                                                    camera=camera.rstrip("0"), size=SMALL_SIZE, want_rgb=mode[0], want_depth=mode[1],
+                                                    **extra, **kw)
+            torch.cuda.synchronize()
+            assert m.render_status() == (0 if ks is None or kw.get("filtering", "clamp") == "clamp" else 2), (camera, mode)
+    return out
+
+
+def _assert_modes_and_cameras(torch, r, what):
+    for camera in r:
+        rgb, dep = r[camera][(True, True)]
+        assert tuple(rgb.shape) == (B, 2) + SMALL_SIZE + (3,) and tuple(dep.shape) == (B, 2) + SMALL_SIZE
+        assert torch.isfinite(rgb).all() and torch.isfinite(dep).all()
+        only_rgb, only_dep = r[camera][(True, False)], r[camera][(False, True)]
+        assert only_rgb[1] is None and torch.equal(only_rgb[0], rgb), (what, camera)
+        assert only_dep[0] is None and torch.equal(only_dep[1], dep), (what, camera)
+    assert all(torch.equal(a, b) for a, b in zip(r["ods0"][(True, True)], r["equirect"][(True, True)])), what
+    assert not torch.equal(r["ods"][(True, True)][0], r["equirect"][(True, True)][0]), what        # (the baseline is in the pixels)
+    assert not torch.equal(r["pinhole"][(True, True)][0], r["equirect"][(True, True)][0]), what
+
+
+def _same_bits(torch, a, b):
+    return all(torch.equal(a[c][mode][i], b[c][mode][i]) for c in a for mode in MODES for i in (0, 1) if a[c][mode][i] is not None)
+
+
+@gpu_test
+@pytest.mark.parametrize("d", sorted(SMALL_PLANES))
+def test_every_dense_kernel_form_at_the_smallest_shapes(gpu, d):
+    torch, m = gpu
+    s, planes = 8, SMALL_PLANES[d]
+    x = _dev(torch, _cube(s, d))
+    other = _dev(torch, np.array([[3.5, 0, 3.5], [0, 3.5, 3.5], [0, 0, 1]], F))     # (S-1)/2, handed over on the device: not the cube camera
+    m.render_status()
+    for fmt in ("f32", "rgba8", "rgba16f"):
+        layers = x if fmt == "f32" else m.pack_layers(x, fmt, planes)
+        clamp = _small_cameras(torch, m, layers, s, planes)
+        seamless = _small_cameras(torch, m, layers, s, planes, filtering="seamless")
+        for r, what in ((clamp, (fmt, "clamp")), (seamless, (fmt, "seamless"))):
+            _assert_modes_and_cameras(torch, r, what)
+        assert not _same_bits(torch, clamp, seamless), fmt                             # (S = 8: a quarter of the rays are in the strip)
+        assert _same_bits(torch, _small_cameras(torch, m, layers, s, planes, ks=other, filtering="seamless"),
+                          _small_cameras(torch, m, layers, s, planes, ks=other)), fmt
+        if fmt != "f32":
+            unpacked = m.unpack_layers(layers)
+            assert _same_bits(torch, clamp, _small_cameras(torch, m, unpacked, s, planes)), fmt
+            assert _same_bits(torch, seamless, _small_cameras(torch, m, unpacked, s, planes, filtering="seamless")), fmt
+
+
+@gpu_test
+@pytest.mark.parametrize("d", sorted(SMALL_PLANES))
+def test_every_sparse_kernel_form_at_the_smallest_shapes(gpu, d):
+    torch, m = gpu
+    s, planes = 16, SMALL_PLANES[d]
+    x = np.array(_cube(s, d))
+    x[:, 8:, :, 1, 3] = 0.0                                  # layer 1 is empty in the lower half of every face ...
+    x[0::2, :, :, d - 1, 3] = 0.0                            # ... and the nearest layer on the even faces: tiles to drop
+    x = _dev(torch, x)
+    m.render_status()
+    for fmt in ("rgba8", "rgba16f"):
+        packed = m.pack_layers(x, fmt, planes)
+        sparse = m.sparsify_layers(packed, border="edge")
+        assert 0 < sparse.occupancy < 1
+        from_sparse, dense = _small_cameras(torch, m, sparse, s, None), _small_cameras(torch, m, packed, s, None)
+        _assert_modes_and_cameras(torch, from_sparse, (fmt, "sparse"))
+        for camera in dense:
+            for mode in MODES:
+                for g, w in zip(from_sparse[camera][mode], dense[camera][mode]):
+                    assert (g is None) == (w is None)
+                    assert g is None or bool((g == w).all()), (fmt, camera, mode)          # == : a zero may differ in sign
