@@ -70,7 +70,7 @@ const char *msi_version(void);
  *      msi_cube_render_views_sparse; msi_pp_hres_layers, msi_hres_index_tiles_edge, msi_pp_hres_layers_sparse;
  *      msi_cube_plane_sweep_f32, msi_cube_sweep_volume_bf16, msi_cube_hres_layers, msi_cube_hres_layers_sparse;
  *      msi_cube_render_views_seamless, MSI_RENDER_STATUS_NOT_CUBE_CAMERA; msi_cube_render_ods_views,
- *      msi_cube_render_ods_views_sparse; msi_render_views_factored; msi_build_mips, msi_render_views_mip) */
+ *      msi_cube_render_ods_views_sparse; msi_render_views_factored; msi_build_mips, msi_render_views_mip; msi_render_views_aniso) */
 #define MSI_ABI_VERSION 9
 int32_t msi_abi_version(void);
 const char *msi_last_error_string(void);
@@ -510,13 +510,54 @@ int msi_render_views_factored(const float *ref_image, const float *src_image, co
  *   Properties: a pixel with lambda = 0 on every layer has the bits of msi_render_views_packed / msi_render_ods_views; so has the
  *   whole image when levels = 1 or lod_bias <= -64.  lod_bias >= 64 reads the top level alone.
  *   The footprint is isotropic: near the stack's poles, where du_x is large while dv_x is small, lambda follows du_x and the image
- *   is blurred along v as well (anisotropic filtering is not implemented).
+ *   is blurred along v as well (msi_render_views_aniso below filters along the footprint's major axis instead).
  * Argument checks before any HIP call, in this order, MSI_E_BADARG: both outputs NULL; a NULL layers / pose / position / depths
  * (a NULL mips with L > 1); unknown format; unknown camera; a NULL trig (equirect) / intrinsics (pinhole); eye_radius with the
  * pinhole camera; bad dims; a NaN lod_bias; L outside 1 .. MSI_MIP_MAX_LEVELS; H or W not a multiple of 2^(L-1); a top level below
  * 2 x 2; views < 1; output size below 1 x 1 (2 x 2 pinhole); H * W >= 2^24; the grid limit of the other views renders.  batch = 0
- * returns MSI_OK after validation, without a launch. */
+ * returns MSI_OK after validation, without a launch.
+ *
+ * msi_render_views_aniso (MSI.render_views / render_ods_pair with max_anisotropy > 1): msi_render_views_mip's arguments with
+ * max_anisotropy = A in [1, MSI_ANISO_MAX] after lod_bias.  An equirect stack's texel rows near a pole span the whole circle: a view
+ * that does not share the stack's poles (an eye looking up or down, a tilted head, a translated viewpoint) has footprints there that
+ * are many texels long and about one wide, which the isotropic rule above answers with a coarse level, smeared both ways.  Here the
+ * level follows the MINOR axis of the footprint and several trilinear samples are taken along the MAJOR axis.  Everything but the
+ * blended texel of a layer is msi_render_views_mip's, op for op; tests/aniso_reference.py holds the rule in fp64.
+ *   THE ANISOTROPIC TEXEL RULE.  (u, v), the two neighbours (their choice at the image border included) and du_x, dv_x, du_y, dv_y
+ *   as in THE TEXEL RULE above (du wrapped the nearer way round, dv not wrapped).  Per layer, in this fp32 operation order (one
+ *   rounding per operation, no fused multiply-add; sqrt, the quotients marked /~, the reciprocal square root and log2 are the
+ *   1-ulp continuous-tail primitives of the other renders):
+ *     E = du_x du_x + du_y du_y,   G = dv_x dv_x + dv_y dv_y,   Fm = du_x dv_x + du_y dv_y        (J J^T of the 2 x 2 footprint Jacobian)
+ *     h = 0.5 (E - G),   R = sqrt(h h + Fm Fm)
+ *     s_max = sqrt(0.5 (E + G) + R)                  texels per pixel along the major axis of the footprint ellipse
+ *     s_min = |du_x dv_y - du_y dv_x| /~ s_max       ... along the minor axis
+ *     ratio = 1 unless s_max > 1 (so also for s_max = 0 or a NaN), else min(max(s_max /~ max(s_min, 1), 1), A)
+ *             (the inner max(., 1) only absorbs the rounding of the quotients: the exact value is >= 1 already)
+ *     step  = s_max /~ ratio                         base texels between samples
+ *     lambda = min(max(log2(step) + lod_bias, 0), L - 1);  step = 0 or a NaN gives 0;   l0, f, l1 as above
+ *     axis  (a_u, a_v) = (h + R, Fm) if h >= 0 else (Fm, R - h);  n2 = a_u a_u + a_v a_v;
+ *           (mu_u, mu_v) = (a_u, a_v) * rsqrt(n2) if n2 > 0 else (1, 0)        unit major axis, texel space
+ *     s_u = step * mu_u,  s_v = step * mu_v
+ *     M = ceil(0.5 (ratio - 1));   samples m = -M .. M at (u + m s_u, v + m s_v); for m != 0 each coordinate is then wrapped by whole
+ *           sizes, u -= W floor((u + 0.5) (1 / W)), v -= H floor((v + 0.5) (1 / H)), the sample of m = 0 is the hit itself
+ *     w_m = min(max(0.5 ratio - (|m| - 0.5), 0), 1) * (1 / ratio)   (IEEE reciprocal)   a box of length `ratio` cut into unit cells
+ *           around the samples: the cells of |m| < M are whole, the outermost two are what is left; sum of w_m = 1
+ *     t_m = the trilinear texel of THE TEXEL RULE at sample m (per-level hit transform, wrap-around bilinear lookup, lerp by f)
+ *     texel = w_0 t_0, then + w_1 t_1, + w_1 t_-1, + w_2 t_2, + w_2 t_-2, ..  in this order, per component
+ *   Properties: the outermost weights go to 0 exactly where M changes (ratio = 2M + 1), the axis only matters where ratio > 1 and
+ *   its sign not at all (the samples are symmetric), so nothing is discontinuous in the ray.  ratio = 1 gives ONE trilinear sample
+ *   with weight 1 -- its own bits -- whose lambda comes from s_max: that is not rho of THE TEXEL RULE (the longer COLUMN of the
+ *   Jacobian, where s_max is its larger singular value), so A = 1 is not bit-identical to msi_render_views_mip (MSI.render_views
+ *   calls that entry point for max_anisotropy = 1).  A pixel with s_max <= 1 on every layer has the bits of the plain render
+ *   (msi_render_views_packed / msi_render_ods_views), and lod_bias <= -64 is the plain render bit for bit: that shortcut alone
+ *   skips the filter.  A stack of one level (mips NULL) is still filtered along the major axis at level 0 -- a view magnified in
+ *   v and minified in u.  At most 2 ceil((A - 1) / 2) + 1 samples per layer: 17 at A = 16.  The samples wrap on BOTH axes, as the
+ *   viewers' lookup does: a sample that leaves the stack over a pole comes back in at the opposite pole (near a pole the major
+ *   axis runs along u, where wrapping is the geometry; the wrap in v is the lookup's, not the sphere's).
+ * Argument checks: msi_render_views_mip's, in its order, with one more after the NaN lod_bias: max_anisotropy NaN or outside
+ * [1, MSI_ANISO_MAX].  batch = 0 returns MSI_OK after validation, without a launch. */
 #define MSI_MIP_MAX_LEVELS 6
+#define MSI_ANISO_MAX 16
 int msi_build_mips(const void *layers, int32_t format, int32_t batch, int32_t num_planes, int32_t height, int32_t width,
                    int32_t levels, void *mips_out, msi_stream_t stream);
 int msi_render_views_mip(const void *layers, int32_t format, const void *mips, int32_t levels, float lod_bias,
@@ -524,6 +565,11 @@ int msi_render_views_mip(const void *layers, int32_t format, const void *mips, i
                          const float *depths, const float *trig, int32_t batch, int32_t views, int32_t height, int32_t width,
                          int32_t num_planes, int32_t camera, int32_t out_height, int32_t out_width, float *out_rgb,
                          float *out_depth, int32_t *status_device, msi_stream_t stream);
+int msi_render_views_aniso(const void *layers, int32_t format, const void *mips, int32_t levels, float lod_bias,
+                           float max_anisotropy, const float *tgt_pose_rt, const float *tgt_pos, const float *intrinsics,
+                           const float *eye_radius, const float *depths, const float *trig, int32_t batch, int32_t views,
+                           int32_t height, int32_t width, int32_t num_planes, int32_t camera, int32_t out_height,
+                           int32_t out_width, float *out_rgb, float *out_depth, int32_t *status_device, msi_stream_t stream);
 /* MSI.msi_render_equirect_view_single (msi.py:431-452): the warped, un-composited
  * layers, out_layers [D,B,H,W,4]. */
 int msi_project_layers_f32(const float *rgba_native, const float *tgt_pose_rt,

@@ -17,6 +17,7 @@ RENDER_STATUS_ORIGIN_OUTSIDE = 1
 RENDER_STATUS_NOT_CUBE_CAMERA = 2       # msi_cube_render_views_seamless: a stack camera other than S/2, rendered with the clamp rule
 MSI_CAMERA_EQUIRECT, MSI_CAMERA_PINHOLE = 0, 1   # msi_render_views_f32's camera models
 MSI_LAYERS_F32, MSI_LAYERS_RGBA8, MSI_LAYERS_RGBA16F = 0, 1, 2   # texel formats of msi_pack_layers / msi_render_views_packed
+MSI_ANISO_MAX = 16                                             # msi_render_views_aniso: the largest max_anisotropy
 MSI_SCORE_F32, MSI_SCORE_U8 = 0, 1                             # msi_score_images: dtype
 MSI_SCORE_RAW, MSI_SCORE_IMAGE, MSI_SCORE_DEPTH = 0, 1, 2      # ... transform
 MSI_SCORE_MSE, MSI_SCORE_MAE, MSI_SCORE_SSIM = 1, 2, 4         # ... metrics mask (PSNR comes with MSE)
@@ -94,6 +95,7 @@ SIGNATURES = {
     "msi_render_views_factored": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_build_mips": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "msi_render_views_mip": (_I, [_P, _I, _P, _I, c_float, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "msi_render_views_aniso": (_I, [_P, _I, _P, _I, c_float, c_float, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "msi_hres_layers_sparse": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "msi_sparse_index_tiles_edge": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "msi_pp_hres_layers": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),

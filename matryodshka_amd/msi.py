@@ -716,7 +716,7 @@ class MSI(object):
         return rgb, dep
 
     def render_views(self, rgba_layers, tgt_pose_rt, tgt_pos, planes=None, camera='equirect', intrinsics=None, size=None,
-                     want_rgb=True, want_depth=True, eye=None, baseline=None, lod_bias=0.0):
+                     want_rgb=True, want_depth=True, eye=None, baseline=None, lod_bias=0.0, max_anisotropy=1.0):
         """V views of each MSI in ONE launch (msi_render_views_f32; no reference counterpart) -> (rgb, depth):
         rgb [B,V,h,w,3] in [-1,1], depth [B,V,h,w] (one channel: msi_render_equirect_depth(...)[..., 0]); either is None
         when switched off.
@@ -758,9 +758,13 @@ class MSI(object):
         the two pyramid levels that bracket the pixel's footprint on that layer (trilinear filtering; the rule is in msi_hip.h), so
         a view SMALLER than the stack -- a thumbnail, a wide field of view, the poles, the far side of a translated viewpoint --
         does not alias.  lod_bias is added to the level of detail: > 0 blurs, < 0 sharpens, <= -64 is the plain render of .base bit
-        for bit (so is a pixel whose footprint is at most one texel on every layer, and a MipLayers of one level).  The filter is
-        isotropic: near the stack's poles it blurs along latitude too.  planes=None takes the planes it carries.  lod_bias belongs
-        to a MipLayers: anything but 0 with another kind of stack is a ValueError."""
+        for bit (so is a pixel whose footprint is at most one texel on every layer, and a MipLayers of one level).  With
+        max_anisotropy = 1 (the default) the filter is isotropic: near the stack's poles, where a footprint is many texels long and
+        one wide, it blurs along latitude too.  max_anisotropy = A in (1, 16] (msi_render_views_aniso) takes the level from the
+        footprint's minor axis and up to 2 ceil((A - 1) / 2) + 1 trilinear samples along its major axis (the rule is in msi_hip.h):
+        the ceiling and the floor of a tilted, rolled or translated view stay sharp without aliasing; away from the poles it is the
+        trilinear render.  It costs time where footprints are long and is opt-in.  planes=None takes the planes it carries.
+        lod_bias and max_anisotropy belong to a MipLayers: anything but 0 / 1 with another kind of stack is a ValueError."""
         if camera not in self.CAMERAS:
             raise ValueError("camera must be 'equirect', 'pinhole' or 'ods', not %r" % (camera,))
         if camera != 'ods' and (eye is not None or baseline is not None):
@@ -774,6 +778,11 @@ class MSI(object):
             raise ValueError("render_views: lod_bias is NaN")
         if lod_bias != 0.0 and not isinstance(rgba_layers, MipLayers):
             raise ValueError("render_views: lod_bias belongs to a MipLayers (build_mips), this stack has one level")
+        max_anisotropy = float(max_anisotropy)
+        if not 1.0 <= max_anisotropy <= N.MSI_ANISO_MAX:                   # (a NaN fails the comparison)
+            raise ValueError("render_views: max_anisotropy must be in [1, %d], not %r" % (N.MSI_ANISO_MAX, max_anisotropy))
+        if max_anisotropy != 1.0 and not isinstance(rgba_layers, MipLayers):
+            raise ValueError("render_views: max_anisotropy belongs to a MipLayers (build_mips), this stack is filtered isotropically")
         lead, suffix, (b, d, h, w), planes, _keep = self._view_stack(rgba_layers, planes, "render_views", 'wrap')   # (_keep: alive until the launch)
         if camera != 'ods':
             self._domain_guard(tgt_pos, tgt_pose_rt, planes, swap_xz=True)
@@ -802,8 +811,10 @@ class MSI(object):
         if suffix == "_sparse":
             args = lead + views + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape \
                 + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
-        elif suffix == "_mip":                    # (msi_render_views_sparse's list behind the stack and lod_bias)
-            args = lead + (lod_bias,) + views + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape \
+        elif suffix == "_mip":                    # (msi_render_views_sparse's list behind the stack and lod_bias; max_anisotropy > 1: the anisotropic twin)
+            if max_anisotropy != 1.0:
+                name = "msi_render_views_aniso"
+            args = lead + ((lod_bias,) if max_anisotropy == 1.0 else (lod_bias, max_anisotropy)) + views + (_ptr(intr), _ptr(radius), depths.data_ptr(), _ptr(trig)) + shape \
                 + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
         elif suffix == "_factored":               # (depths and the stack's sizes are in `lead`: msi_hres_layers' argument list)
             args = lead + views + (_ptr(intr), _ptr(radius), _ptr(trig), v) + ((N.MSI_CAMERA_EQUIRECT,) if camera == 'ods' else code)
@@ -904,18 +915,19 @@ class MSI(object):
         return (rgb, dep) if want_rgb and want_depth else rgb if want_rgb else dep
 
     def render_ods_pair(self, rgba_layers, planes=None, baseline=None, intrinsics=None, tgt_pose_rt=None, tgt_pos=None, size=None,
-                        layout='views', want_depth=False, lod_bias=0.0):
+                        layout='views', want_depth=False, lod_bias=0.0, max_anisotropy=1.0):
         """Both eyes of each sample's stereo 360 frame in ONE launch (render_views(camera='ods') with V = 2: left then right,
         sharing one pose and head position) -> rgb, or (rgb, depth) with want_depth.
         tgt_pose_rt [B,4,4] (or one [4,4]; default identity), tgt_pos [B,3] (or one [3]; default 0); planes, baseline,
         intrinsics and size as in render_views -- with the sample's own baseline, identity pose and position 0 the two views are
         the input pair (ref image = left) as the MSI reproduces it.
         layout='views': rgb [B,2,h,w,3], depth [B,2,h,w].  'top_bottom': the SAME storage as [B,2h,w,3] / [B,2h,w], left eye on
-        top -- the delivery format of 360 players, without a copy.  lod_bias: render_views', for a MipLayers."""
+        top -- the delivery format of 360 players, without a copy.  lod_bias and max_anisotropy: render_views', for a MipLayers."""
         b = (rgba_layers.data if isinstance(rgba_layers, PackedLayers) else rgba_layers).shape[0]     # (SparseLayers / FactoredLayers / MipLayers.shape: (B, H, W, D))
         pose, pos, eye = self._ods_pair_views("render_ods_pair", b, tgt_pose_rt, tgt_pos, baseline, layout)
         rgb, dep = self.render_views(rgba_layers, pose, pos, planes, camera='ods', intrinsics=intrinsics, size=size,
-                                     want_rgb=True, want_depth=want_depth, eye=eye, baseline=baseline, lod_bias=lod_bias)
+                                     want_rgb=True, want_depth=want_depth, eye=eye, baseline=baseline, lod_bias=lod_bias,
+                                     max_anisotropy=max_anisotropy)
         return self._pair_layout(rgb, dep, layout, True, want_depth)
 
     # ------------------------------------------------------------------ compact stacks (matryodshka_amd/packed.py)
